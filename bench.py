@@ -21,7 +21,12 @@ queues, streams that share a queue run one after the other.  bench.py asks for 8
 N > 1 is launched by torch.distributed.run, one rank per GPU; the path shards by image (independent
 units, no data-path collective), so every rank runs the same per-GPU workload: weak scaling.
 
-Prints ONE JSON line on rank 0 (see the contract in the task statement) with extra objects:
+A plain run sets up, warms up, times the K steps and prints the result line (`ms_per_step` = milliseconds of one timed step).
+--dump-outputs DIR: after the timed steps, rank 0 writes what the last timed step returned as DIR/<name>.npy (float32 / float64;
+inference: `x_out` and `bpp`, training: the step's loss scalars), at most 64 MB in all -- a larger output is stored as a fixed, seeded
+sample of its elements.  Inputs and weights are seeded, so two builds run with the same arguments can be compared output for output.
+
+--full: everything else the benchmark measures, each with runs of its own (rank 0, after the timed steps), as extra objects:
   roofline               -- the dominant kernel (3x3 128->128 conv on the fp32 matrix cores), timed IN-STEP: HIP events around
                             the 32-layer residual stack of the encoder / of the decoder on the step's own activations, n stacks
                             in flight like the step, / launches.  `achieved` = FLOPs the matrix pipe executes (Winograd:
@@ -32,6 +37,7 @@ Prints ONE JSON line on rank 0 (see the contract in the task statement) with ext
   shapes                 -- the north_star's 256x256 shape (batch 1 and 8) through the same step
   cpu_baseline           -- the CPU oracle (torch fp32 restatement of the reference) timed on a bounded sample of the same
                             workload (rank 0, N = 1 only)
+  (also: one_image_at_a_time, the stage split, other_branch_sharing, cfg5_4k, train; --mode train: the step's roofline)
 """
 import argparse
 import ctypes
@@ -245,8 +251,12 @@ def main():
     p.add_argument('--share', default='auto', choices=['auto', 'cu_range', 'full_chip', 'serial'],
                    help='how decoder and context model share the chip (imgcomp_cvpr_amd/streams.py); auto = the package default')
     p.add_argument('--idle_layers', type=int, default=None, help="cu_range sharing: 3x3 launches of the decoder that leave the side stream's CUs idle (0 = all; default: sized from the context model's work)")
-    p.add_argument('--no_cpu_baseline', action='store_true')
-    p.add_argument('--no_extras', action='store_true', help='headline only: no stage split, roofline, extra shapes (rocprofv3 runs)')
+    p.add_argument('--full', action='store_true',
+                   help='after the headline: stage split, roofline, other shapes and configurations, training step, CPU baseline')
+    p.add_argument('--dump-outputs', dest='dump_outputs', default=None, metavar='DIR',
+                   help="write the last timed step's outputs as DIR/<name>.npy (rank 0)")
+    p.add_argument('--no_cpu_baseline', action='store_true', help='--full without the CPU baseline')
+    p.add_argument('--no_extras', action='store_true', help='headline only, even with --full (rocprofv3 runs)')
     p.add_argument('--pipelined', action='store_true', help='also run the informational three-pipelines-in-flight section')
     p.add_argument('--in_flight', type=int, default=4,
                    help='independent batch-1 images in flight on their own streams (serial arrangement only); 1 = one image at a time')
@@ -318,6 +328,8 @@ def main():
     elapsed = max_over_ranks(torch, dist, elapsed, dev, world, a.backend)
     ranks_seen = ranks_report(torch, dist, dev, rank, world, a.backend)
     value = N * H * Wd * world * a.steps / elapsed / 1e6
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(a.dump_outputs, {'x_out': x_out, 'bpp': bpp})
     if a.calib_copy:
         src = torch.randn(64 * 1024 * 1024, device=dev)
         dst = torch.empty_like(src)
@@ -330,7 +342,8 @@ def main():
     extra = {'branch_sharing': share, 'context_model_stream_cus': cus, 'bpp_synthetic': round(float(bpp), 5),
              'images_in_flight': n_flight}
     roofline = roofline_pc = None
-    if rank == 0 and not a.no_extras:
+    extras = a.full and not a.no_extras
+    if rank == 0 and extras:
         st = _lib.current_stream(dev)
         ev = [ctypes.c_void_p() for _ in range(2)]
         for e in ev:
@@ -565,7 +578,7 @@ def main():
 
     # ---- CPU baseline: the oracle on the host cores (rank 0, N == 1 only) ----
     cpu = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline and not a.no_extras:
+    if rank == 0 and world == 1 and not a.no_cpu_baseline and extras:
         from oracle import oracle as O
         # torch's CPU conv kernels oversubscribe badly beyond a few dozen threads on the 256-core host
         # (16 threads is the fastest setting measured on the MI355X box)
@@ -628,6 +641,30 @@ def main():
     if world > 1:
         dist.barrier()                 # rank 0 is still timing the stage split / dominant kernel: leave together
         dist.destroy_process_group()
+
+
+DUMP_LIMIT_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: name -> tensor / number of the last timed step, written as out_dir/<name>.npy (float64 stays float64, everything
+    else float32).  Over DUMP_LIMIT_BYTES in all, every array keeps the same share of its elements: a fixed, seeded, sorted sample of
+    its flattened values (the same elements for the same shapes, run after run)."""
+    import numpy as np
+    import torch
+    host = {}
+    for name, v in arrays.items():
+        t = torch.as_tensor(v).detach()
+        t = t.double() if t.dtype == torch.float64 else t.float()
+        host[name] = t.cpu().numpy()
+    total = sum(h.nbytes for h in host.values())
+    os.makedirs(out_dir, exist_ok=True)
+    for name, h in host.items():
+        if total > DUMP_LIMIT_BYTES and h.size > 1:
+            keep = max(1, int(h.size * (DUMP_LIMIT_BYTES - 4096 * len(host)) // total))
+            idx = np.sort(np.random.RandomState(0).choice(h.size, keep, replace=False))
+            h = h.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + '.npy'), h)
 
 
 def self_launch(n):
@@ -863,11 +900,15 @@ def train_main(a, dev, rank, world):
     elapsed, out, tr = train_steps_timed(torch, dist, dev, rank, world, N, H, Wd, a.steps, a.warmup, a.backend)
     ranks_seen = ranks_report(torch, dist, dev, rank, world, a.backend)
     if rank == 0:
+        if a.dump_outputs:
+            dump_outputs(a.dump_outputs, {k: torch.as_tensor(float(v), dtype=torch.float64) for k, v in out.items()})
         from imgcomp_cvpr_amd import _lib, weights as W
-        try:
-            roof = train_roofline(torch, _lib.lib, _lib, W, tr, dev, N, H, Wd, elapsed / a.steps * 1e3)
-        except Exception as ex:                                    # informational
-            roof = {'error': str(ex)[:300]}
+        roof = None
+        if a.full and not a.no_extras:
+            try:
+                roof = train_roofline(torch, _lib.lib, _lib, W, tr, dev, N, H, Wd, elapsed / a.steps * 1e3)
+            except Exception as ex:                                # informational
+                roof = {'error': str(ex)[:300]}
         print(json.dumps({
             'metric': 'training images/s (cfg3: cvpr/med + res_shallow, 128x128 crops, {})'.format(
                 'batch 32 per GPU' if a.scaling == 'weak' else 'global batch 32 split over the GPUs'),

@@ -978,6 +978,26 @@ def test_bench_training_flop_count_matches_the_survey_figures():
     assert abs(ex4 - (rest + c3 * (0.25 + 0.25 + 16.0 / 36.0) + 3 * bench.FLOP_PER_SYMBOL_PC_LIVE * sym)) < 1e-6 * ex4
 
 
+def test_bench_dump_outputs_formats_and_bounded_sample(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: one .npy per output, float32 (float64 kept), whole when the outputs fit the budget; over it, a fixed,
+    seeded, sorted sample of every output's elements, the same from call to call"""
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    x = torch.arange(2 * 3 * 40 * 50, dtype=torch.float32).reshape(2, 3, 40, 50)
+    bench.dump_outputs(str(tmp_path / 'a'), {'x_out': x, 'bpp': torch.tensor(1.25, dtype=torch.float64), 'n': 3})
+    got = {n: np.load(str(tmp_path / 'a' / (n + '.npy'))) for n in ('x_out', 'bpp', 'n')}
+    assert got['x_out'].dtype == np.float32 and np.array_equal(got['x_out'], x.numpy())
+    assert got['bpp'].dtype == np.float64 and float(got['bpp']) == 1.25 and got['n'].dtype == np.float32
+    monkeypatch.setattr(bench, 'DUMP_LIMIT_BYTES', 20000)
+    for d in ('b', 'c'):
+        bench.dump_outputs(str(tmp_path / d), {'x_out': x, 'bpp': torch.tensor(1.25, dtype=torch.float64)})
+    b, c = (np.load(str(tmp_path / d / 'x_out.npy')) for d in ('b', 'c'))
+    assert b.ndim == 1 and 0 < b.nbytes <= 20000 and np.array_equal(b, c)
+    assert np.all(np.diff(b) > 0) and np.all(np.isin(b, x.numpy()))      # distinct elements of x in their order
+    assert float(np.load(str(tmp_path / 'b' / 'bpp.npy'))) == 1.25
+
+
 def test_profile_evidence_is_self_consistent():
     """the committed evidence files of the newest round agree with themselves (a digest whose sums and step count described
     different windows): profiles/rNN_counters.json -- concurrency = kernel time / span of the SAME window, kernel time per step = the

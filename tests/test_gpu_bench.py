@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 import torch
 
@@ -30,7 +31,7 @@ def _launch(nproc, port, extra, timeout=600):
 def test_bench_two_ranks_inference(cuda):
     """`bench.py --gpus 2`: returns, rank 0 prints one line, the rank-0-only extras (stage split, roofline, other shapes) run
     without any process-group call while rank 1 waits at the final barrier."""
-    out = _launch(2, 29561, ['--steps', '3', '--warmup', '1', '--height', '128', '--width', '192'])
+    out = _launch(2, 29561, ['--steps', '3', '--warmup', '1', '--height', '128', '--width', '192', '--full'])
     assert out['n_gpus'] == 2 and out['steps'] == 3 and out['scaling'] == 'weak' and out['value'] > 0
     assert out['roofline'] is not None and 0 < out['roofline']['frac'] <= 1
     assert out['cpu_baseline'] is None                              # N = 1 only
@@ -66,8 +67,8 @@ def test_bench_launches_itself_for_more_than_one_gpu(cuda):
 
 
 def test_bench_single_rank_contract(cuda):
-    """the default launch: one JSON line carrying the contract's keys plus roofline / cpu_baseline"""
-    out = _launch(1, 0, ['--steps', '3', '--warmup', '1', '--height', '128', '--width', '192'])
+    """the --full launch: one JSON line carrying the contract's keys plus roofline / cpu_baseline"""
+    out = _launch(1, 0, ['--steps', '3', '--warmup', '1', '--height', '128', '--width', '192', '--full'])
     for k in ('metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'higher_is_better', 'scaling', 'vs_baseline',
               'dtype', 'data', 'config', 'roofline', 'cpu_baseline'):
         assert k in out, k
@@ -77,6 +78,23 @@ def test_bench_single_rank_contract(cuda):
     tr = out['train']
     assert 'error' not in tr, tr
     assert tr['value'] > 0 and tr['checks']['ms_ssim_in_unit_interval'] and tr['checks']['d_loss_is_K_times_one_minus_ms_ssim']
+
+
+def test_bench_plain_run_is_lean_and_dumps_its_outputs(cuda, tmp_path):
+    """the default launch times its steps and prints the contract's keys, nothing measured beside them; --dump-outputs writes the last
+    timed step's x_out / bpp, the same from run to run (seeded inputs and weights)"""
+    args = ['--steps', '4', '--warmup', '1', '--height', '128', '--width', '192']
+    outs = []
+    for k in range(2):
+        out = _launch(1, 0, args + ['--dump-outputs', str(tmp_path / str(k))])
+        assert out['steps'] == 4 and out['warmup'] == 1 and out['ms_per_step'] > 0
+        assert abs(out['ms_per_step'] - 1e3 * 128 * 192 / 1e6 / out['value']) < 1e-3 * out['ms_per_step'] + 1e-3
+        assert out['roofline'] is None and out['cpu_baseline'] is None and 'train' not in out and 'shapes' not in out
+        outs.append({n: np.load(str(tmp_path / str(k) / (n + '.npy'))) for n in ('x_out', 'bpp')})
+    assert outs[0]['x_out'].shape == (1, 3, 128, 192) and outs[0]['x_out'].dtype == np.float32
+    assert outs[0]['bpp'].dtype in (np.float32, np.float64) and float(outs[0]['bpp']) > 0
+    for n in ('x_out', 'bpp'):
+        assert np.array_equal(outs[0][n], outs[1][n]), n
 
 
 @pytest.mark.parametrize('n_flight,rounds', [(4, 16), (8, 26)])

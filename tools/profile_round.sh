@@ -21,8 +21,8 @@ timeout 320 $t pmc b_write "WRITE_SIZE" $STEP
 timeout 320 $t pmc b_l2 "TCP_TCC_READ_REQ_sum TCC_HIT_sum TCC_MISS_sum" $STEP
 # the context model standalone, on the REAL encoder output of the bench image (what bench.py's roofline_context_model times)
 timeout 320 $t trace pc python tools/run_pc.py 40
-# the training step (BASELINE configs[2])
-timeout 320 $t trace train python bench.py --mode train --steps 6 --warmup 2
+# the training step (BASELINE configs[2]), with its roofline object (--full: the filter-gradient timing loop is in the trace too)
+timeout 320 $t trace train python bench.py --mode train --steps 6 --warmup 2 --full
 # the in-flight schedule WITHOUT a tracer: in-kernel launch stamps (needs the -DW4_LAUNCH_STAMPS build, made in the build container:
 #   tools/build_variants.sh conv3x3_wino4.hip ls="-fno-slp-vectorize -DW4_LAUNCH_STAMPS")
 if [ -f imgcomp_cvpr_amd/csrc/variants/lib_ls.so ]; then
