@@ -160,8 +160,12 @@ def train_loss(x_uint8, weights, ae_cfg, pc_cfg, dtype=torch.float64):
     net = _cba(net, p, O.ENC + '/h2', 2, True)
     net = _res_stack(net, p, O.ENC, 'enc', B)
     net = _cba(net, p, O.ENC + '/to_bn', 2, False)
-    hm = torch.clamp(torch.clamp(torch.sigmoid(net[:, 0:1]) * C - torch.arange(C, dtype=dtype).view(1, C, 1, 1), max=1.0), min=0.0)
-    z = hm * net[:, 1:]
+    if ae_cfg.get('heatmap', True):
+        hm = torch.clamp(torch.clamp(torch.sigmoid(net[:, 0:1]) * C - torch.arange(C, dtype=dtype).view(1, C, 1, 1), max=1.0), min=0.0)
+        z = hm * net[:, 1:]
+    else:
+        # autoencoder.py:236-242: to_bn emits C channels, z is its output, no mask
+        hm, z = None, net
     c = p[O.ENC + '/centers']
     dist = (z.unsqueeze(-1) - c) ** 2
     qsoft = (torch.softmax(-dist, -1) * c).sum(-1)
@@ -189,7 +193,7 @@ def train_loss(x_uint8, weights, ae_cfg, pc_cfg, dtype=torch.float64):
     else:
         raise ValueError('Invalid: {}'.format(kind))
     H_real = bc.mean()
-    H_mask = (bc * hm).mean()
+    H_mask = (bc * hm).mean() if hm is not None else H_real          # train.py:306-309: bc_mask = bc without a heatmap
     H_soft = 0.5 * (H_mask + H_real)
     pc_loss = ae_cfg['beta'] * torch.clamp(H_soft - ae_cfg['H_target'], min=0.0)
     f = ae_cfg['regularization_factor']

@@ -222,11 +222,14 @@ def test_conv3x3_c128_winograd(cuda, shape, N, H, W):
 W4_RTOL = 2e-5
 
 
-@pytest.mark.parametrize('N,H,W', [(1, 16, 64), (2, 13, 20), (1, 7, 4), (1, 40, 72), (3, 10, 36), (1, 128, 192), (4, 32, 32), (2, 21, 28)])
+@pytest.mark.parametrize('N,H,W', [(1, 16, 64), (2, 13, 20), (1, 7, 4), (1, 40, 72), (3, 10, 36), (1, 128, 192), (4, 32, 32), (2, 21, 28),
+                                   (30, 40, 40)])
 def test_conv3x3_c128_winograd_f4(cuda, N, H, W):
     """Winograd F(4x4,3x3) (csrc/conv3x3_wino4.hip) against the float64 conv: interior and border segments, heights that are
-    not multiples of 4, widths with tiles beyond the map, ReLU / one / two residuals, the adjoint packing; odd widths refuse."""
+    not multiples of 4, widths with tiles beyond the map, ReLU / one / two residuals, the adjoint packing; odd widths refuse.
+    (30, 40, 40) is the reference's training crop geometry (30 x 160 x 160 crops -> 40 x 40 maps)."""
     L = _lib()
+    torch.set_num_threads(16)
     assert L.lib.ic_wino4_3x3_c128_supported(N, H, W) == 1 and L.lib.ic_wino4_3x3_c128_supported(N, H, W + 1) == 0
     rs = np.random.RandomState(400 + H)
     x = rs.normal(0, 1, (N, 128, H, W)).astype(np.float32)

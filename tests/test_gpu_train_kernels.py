@@ -1,0 +1,285 @@
+"""-m gpu: the training-side backward kernels through the C ABI, each against a float64 evaluation on the CPU -- every plan form
+of the 2-D filter gradient, the context model's 3-D filter gradient in its four layer roles (k = 24 and 64), the logits'
+cross-entropy gradient, the bias sums and the quantiser / importance-map backward at training size.  Every case runs twice and
+must give the same bits: each reduction here claims a fixed order."""
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+from tests.util import assert_close, dev
+
+pytestmark = pytest.mark.gpu
+
+
+def _L():
+    from imgcomp_cvpr_amd import _lib
+    return _lib
+
+
+def _cdiv(a, b):
+    return -(-a // b)
+
+
+def _wg_plan(A, B, P, KH, KW):
+    """csrc/conv_wgrad.hip wg_plan restated: -> ((TA, TB, WA, WB), slices S, positions per slice PS)"""
+    ta, tb = _cdiv(A, 32), _cdiv(B, 32)
+    TA, WA = (2 if ta >= 2 else 1), (2 if ta > 2 else 1)
+    TB, WB = (2 if tb >= 2 else 1), (2 if tb > 2 else 1)
+    groups = _cdiv(A, 32 * TA * WA) * _cdiv(B, 32 * TB * WB)
+    lds_bytes = 2 * 32 * (TA * WA + TB * WB) * 36 * 4
+    per_cu = max(1, min(160 * 1024 // lds_bytes, 16 // (WA * WB)))
+    want = max(1, min(256 * per_cu // (KH * KW * groups), _cdiv(P, 128)))
+    ps = _cdiv(_cdiv(P, want), 32) * 32
+    return (TA, TB, WA, WB), _cdiv(P, ps), ps
+
+
+def _twice(launch):
+    """two launches into NaN-filled outputs -> the first result; asserts the second is bit-identical"""
+    a, b = launch(), launch()
+    torch.cuda.synchronize()
+    for u, v in zip(a, b):
+        assert torch.equal(u, v), 'a second launch gives other bits'
+    return a
+
+
+# ---- ic_conv2d_wgrad_f32: the nine <TA,TB,WA,WB> forms --------------------------------------------------------------------
+
+# (name, A, B, N, H, W, K, stride, kind, weight decay); conv: U = x (N,A,H,W); deconv: x (N,B,H,W), U = dy on the 2H x 2W grid
+WG_CASES = [
+    ('1111_tiny', 3, 3, 1, 5, 6, 3, 1, 'conv', 0.25),
+    ('1211', 3, 33, 2, 23, 33, 5, 2, 'conv', 0.0),
+    ('1212', 3, 100, 2, 19, 21, 3, 1, 'conv', 0.25),
+    ('2111', 33, 3, 2, 26, 34, 5, 2, 'conv', 0.25),
+    ('2211', 33, 33, 3, 29, 23, 3, 1, 'conv', None),
+    ('2212_deconv', 33, 100, 2, 15, 11, 5, 2, 'deconv', 0.25),
+    ('2121', 100, 3, 2, 20, 23, 3, 1, 'conv', 0.25),
+    ('2221', 100, 33, 1, 33, 41, 5, 2, 'conv', 0.25),
+    ('2222_s1', 100, 100, 2, 17, 15, 3, 1, 'conv', 0.25),
+    ('2222_s2_k5', 100, 100, 2, 90, 86, 5, 2, 'conv', 0.25),
+]
+
+
+@pytest.mark.parametrize('name,A,B,N,H,W,K,stride,kind,wd', WG_CASES, ids=[c[0] for c in WG_CASES])
+def test_conv2d_filter_gradient_plan_forms(cuda, name, A, B, N, H, W, K, stride, kind, wd):
+    """ic_conv2d_wgrad_f32 on every plan form (channel counts 3 / 33 / 100: one tile, two tiles, four partial tiles), stride 1
+    and 2, K = 3 and 5, the transposed conv, the weight-decay term; the K-split into S >= 3 slices with a ragged last slice (and
+    S == 1 on the tiny case) against float64 autograd of the oracle's conv / transposed conv."""
+    from oracle import train_oracle as T
+    L = _L()
+    rs = np.random.RandomState(sum(map(ord, name)))
+    if kind == 'conv':
+        x = rs.normal(0, 1, (N, A, H, W)).astype(np.float32)
+        w = rs.normal(0, 0.1, (K, K, A, B)).astype(np.float32)
+    else:
+        x = rs.normal(0, 1, (N, B, H, W)).astype(np.float32)
+        w = rs.normal(0, 0.1, (K, K, A, B)).astype(np.float32)           # TF transposed layout [kh][kw][out = A][in = B]
+    wt = torch.tensor(w, dtype=torch.float64, requires_grad=True)
+    xt = torch.tensor(x, dtype=torch.float64)
+    y = T._conv(xt, wt, stride) if kind == 'conv' else T._deconv(xt, wt)
+    dy = rs.normal(0, 1, tuple(y.shape)).astype(np.float32)
+    y.backward(torch.tensor(dy, dtype=torch.float64))
+    ref = wt.grad + (wd * wt.detach() if wd is not None else 0.0)
+    d = lambda a: dev(a, cuda)
+    if kind == 'conv':
+        U, V, UH, UW = d(x), d(dy), H, W
+    else:
+        U, V, UH, UW = d(dy), d(x), 2 * H, 2 * W
+    VH, VW = _cdiv(UH, stride), _cdiv(UW, stride)
+    P = N * VH * VW
+    key, S_plan, PS = _wg_plan(A, B, P, K, K)
+    assert '{}{}{}{}'.format(*key) == name[:4]
+    need = L.lib.ic_conv2d_wgrad_workspace_bytes(N, A, B, VH, VW, K, K)
+    S = need // (K * K * A * B * 4)
+    assert need == S * K * K * A * B * 4 and S == S_plan
+    if name.endswith('_tiny'):
+        assert S == 1
+    else:
+        assert S >= 3 and P % PS != 0, (S, P, PS)
+    wd_ = d(w)
+    ws = torch.empty(need, dtype=torch.uint8, device=cuda)
+
+    def launch():
+        dw = torch.full((K, K, A, B), float('nan'), device=cuda)
+        L.check(L.lib.ic_conv2d_wgrad_f32(L.ptr(U), L.ptr(V), L.ptr(dw), N, A, UH, UW, B, K, K, stride,
+                                          L.ptr(wd_) if wd is not None else None, wd or 0.0, L.ptr(ws), need, L.current_stream()))
+        return (dw,)
+    dw, = _twice(launch)
+    assert_close(dw, ref, 'conv2d wgrad plan {} ({}, S {})'.format(name[:4], name, S), 1e-5)
+
+
+# ---- ic_pc_wgrad_f32: the context model's masked (2,3,3) conv3d ----------------------------------------------------------
+
+def _pc_layers(N, C, h, w, k, L):
+    """the four ic_pc_wgrad_f32 calls of TrainGraph._pc_backward: (role, A, B, VD, VH, VW, first_mask)"""
+    return [('k->L', k, L, C, h, w, 0),
+            ('k->k conv2', k, k, C + 1, h + 2, w + 2, 0),
+            ('k->k conv1', k, k, C + 2, h + 4, w + 4, 0),
+            ('first', 1, k, C + 3, h + 6, w + 6, 1)]
+
+
+PC_CASES = [(24, 6, 1, 1, 2, 2), (64, 6, 1, 1, 2, 2), (24, 16, 1, 1, 2, 2), (24, 6, 2, 32, 16, 16), (64, 6, 2, 32, 16, 16),
+            (64, 16, 1, 5, 6, 9)]
+
+
+@pytest.mark.parametrize('k,L,N,C,h,w', PC_CASES)
+def test_pc_filter_gradient_layer_roles(cuda, k, L, N, C, h, w):
+    """ic_pc_wgrad_f32 as TrainGraph._pc_backward calls it: the k -> L layer, the two k -> k "other"-mask layers and the first
+    layer, whose input is the symbol volume padded on load with pad_value = centers[0] != 0 under the "first" mask.  Against
+    float64 autograd of F.conv3d(U, W * mask) with respect to W; the dead taps come out exactly 0; S >= 2 slices on the cfg3-like
+    volume."""
+    from oracle import oracle as O
+    Lb = _L()
+    rs = np.random.RandomState(k * 1000 + L * 10 + C)
+    first, other = O.pc_masks(3)
+    centers = np.linspace(-2, 2, 6).astype(np.float32)
+    pad_value = float(centers[0])
+    q = centers[rs.randint(0, 6, (N, C, h, w))]
+    for role, A, B, VD, VH, VW, fm in _pc_layers(N, C, h, w, k, L):
+        P = N * VD * VH * VW
+        V = rs.normal(0, 1, (N, B, VD, VH, VW)).astype(np.float32)
+        mask = torch.as_tensor(first if fm else other, dtype=torch.float64)[..., None, None]
+        wt = torch.zeros((2, 3, 3, A, B), dtype=torch.float64, requires_grad=True)
+        if fm:
+            Ut = O.pad_for_probclass3d(torch.as_tensor(q, dtype=torch.float64), 9, pad_value).unsqueeze(1)
+            Ud = None
+        else:
+            U = np.maximum(rs.normal(0, 1, (N, A, VD + 1, VH + 2, VW + 2)), 0).astype(np.float32)    # post-ReLU activations
+            Ut = torch.as_tensor(U, dtype=torch.float64)
+            Ud = dev(U, cuda)
+        assert tuple(Ut.shape) == (N, A, VD + 1, VH + 2, VW + 2)
+        y = F.conv3d(Ut, (wt * mask).permute(4, 3, 0, 1, 2))
+        y.backward(torch.as_tensor(V, dtype=torch.float64))
+        need = Lb.lib.ic_pc_wgrad_workspace_bytes(N, A, B, VD, VH, VW)
+        S = need // (14 * A * B * 4)
+        assert need == S * 14 * A * B * 4
+        if C >= 32:
+            assert S >= 2, (role, S)
+        qd, Vd = dev(q, cuda), dev(V, cuda)
+        ws = torch.empty(need, dtype=torch.uint8, device=cuda)
+
+        def launch():
+            dw = torch.full((2, 3, 3, A, B), float('nan'), device=cuda)
+            Lb.check(Lb.lib.ic_pc_wgrad_f32(Lb.ptr(Ud), Lb.ptr(qd) if fm else None, pad_value, Lb.ptr(Vd), Lb.ptr(dw), N, A, B,
+                                            VD, VH, VW, fm, Lb.ptr(ws), need, Lb.current_stream()))
+            return (dw,)
+        dw, = _twice(launch)
+        dead = (mask[..., 0, 0] == 0)
+        assert int(dead.sum()) == (5 if fm else 4)
+        assert bool((dw.cpu()[dead] == 0).all()), '{}: a dead tap has a nonzero gradient'.format(role)
+        assert_close(dw, wt.grad, 'pc wgrad k={} L={} {} (P {}, S {})'.format(k, L, role, P, S), 1e-5)
+
+
+# ---- ic_pc_dlogits_f32 ---------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize('L', [3, 6, 8, 16])
+def test_pc_dlogits(cuda, L):
+    """g = d(-log2 softmax(logits)[sym] * d_bits) / d(pre-ReLU logits): zero where the ReLU clipped the logit to 0, with exact
+    zeros next to positive values in every row; planar (N, L, vol) output.  L = 17 is refused before any launch."""
+    Lb = _L()
+    rs = np.random.RandomState(L)
+    N, vol = 3, 1000
+    pre = rs.normal(0.3, 1.5, (N, vol, L)).astype(np.float32)
+    pre[:, :, 0] = -1.0                                     # every row has an exact zero after the ReLU...
+    pre[:, :, L - 1] = np.abs(pre[:, :, L - 1]) + 0.1       # ...next to a positive value
+    logits = np.maximum(pre, 0).astype(np.float32)
+    sym = rs.randint(0, L, (N, vol)).astype(np.int64)
+    sym[:, ::7] = 0                                         # the symbol sits on a clipped logit
+    dbits = rs.normal(0, 1, (N, vol)).astype(np.float32)
+    pt = torch.tensor(pre, dtype=torch.float64, requires_grad=True)
+    lg = torch.log_softmax(torch.relu(pt), -1)
+    nll = -torch.gather(lg, -1, torch.as_tensor(sym).unsqueeze(-1)).squeeze(-1) * float(np.log2(np.e))
+    (nll * torch.as_tensor(dbits, dtype=torch.float64)).sum().backward()
+    ref = pt.grad.permute(0, 2, 1)
+    ld, sd, bd = dev(logits, cuda), torch.as_tensor(sym).to(cuda), dev(dbits, cuda)
+
+    def launch():
+        g = torch.full((N, L, vol), float('nan'), device=cuda)
+        Lb.check(Lb.lib.ic_pc_dlogits_f32(Lb.ptr(ld), Lb.ptr(sd), Lb.ptr(bd), Lb.ptr(g), N, vol, L, Lb.current_stream()))
+        return (g,)
+    g, = _twice(launch)
+    clipped = torch.as_tensor(logits).permute(0, 2, 1) == 0
+    assert bool((g.cpu()[clipped] == 0).all())
+    assert_close(g, ref, 'pc dlogits L={}'.format(L), 1e-5)
+    g17 = torch.empty((1, 17, 4), device=cuda)
+    assert Lb.lib.ic_pc_dlogits_f32(Lb.ptr(ld), Lb.ptr(sd), Lb.ptr(bd), Lb.ptr(g17), 1, 4, 17, Lb.current_stream()) != 0
+
+
+# ---- ic_channel_sum_f32 --------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize('N,C,M', [(1, 5, 1), (2, 64, 7), (4, 6, 8), (32, 3, 1), (3, 24, 12345), (2, 65, 4096)])
+def test_channel_sum(cuda, N, C, M):
+    """per-channel sums of an (N, C, M) tensor (the context model's bias gradients): N * M below, at and far above the 32-chunk
+    split, M = 1 and odd M, against a float64 sum."""
+    Lb = _L()
+    rs = np.random.RandomState(N * 7 + M)
+    x = rs.normal(0.5, 1, (N, C, M)).astype(np.float32)
+    xd = dev(x, cuda)
+    ws = torch.empty(Lb.lib.ic_channel_sum_workspace_bytes(C), dtype=torch.uint8, device=cuda)
+
+    def launch():
+        out = torch.full((C,), float('nan'), device=cuda)
+        Lb.check(Lb.lib.ic_channel_sum_f32(Lb.ptr(xd), Lb.ptr(out), N, C, M, Lb.ptr(ws), Lb.current_stream()))
+        return (out,)
+    out, = _twice(launch)
+    assert_close(out, torch.as_tensor(x, dtype=torch.float64).sum(dim=(0, 2)), 'channel sum N*M={}'.format(N * M), 1e-6)
+
+
+# ---- ic_heatmap_quantize_bwd_f32 at training size ------------------------------------------------------------------------
+
+QB_CASES = [(1, 32, 6, True), (1, 64, 16, True), (1, 32, 16, False), (1, 64, 6, False), (0, 32, 6, False), (0, 64, 16, False)]
+
+
+@pytest.mark.parametrize('heatmap,C,L,with_dhm', QB_CASES)
+def test_quantizer_backward_training_size(cuda, heatmap, C, L, with_dhm):
+    """the quantiser (+ importance map) backward on N * h * w = 133120 > 512 * 256 pixels: the 512-block grid-stride loop runs
+    a second round and the centre gradient is the stage-2 sum over 512 block partials.  Heatmap on (d_heatmap given and NULL)
+    and off, C = 32 / 64, L = 6 / 16, against float64 autograd (evaluated image by image)."""
+    Lb = _L()
+    N, h, w = 4, 160, 208
+    assert N * h * w > 512 * 256
+    rs = np.random.RandomState(C + L + 100 * heatmap)
+    CB = C + heatmap
+    bott = rs.normal(0, 1.5, (N, CB, h, w)).astype(np.float32)
+    if heatmap:
+        # sigmoid(z0) * C within the fp32 band of an integer puts u = sigmoid(z0) C - c on a clip edge, where fp32 (the device,
+        # as TF) and float64 may take different sides and the d z0 sum gains or loses a whole channel: keep z0 out of that band
+        while True:
+            s = torch.sigmoid(torch.as_tensor(bott[:, 0], dtype=torch.float64)).numpy() * C
+            near = np.abs(s - np.round(s)) < 1e-4
+            if not near.any():
+                break
+            bott[:, 0][near] += np.float32(1e-2)
+    centers = np.linspace(-2, 2, L).astype(np.float32)
+    gq = rs.normal(0, 1, (N, C, h, w)).astype(np.float32)
+    gh = rs.normal(0, 1, (N, C, h, w)).astype(np.float32) if (heatmap and with_dhm) else None
+    ct = torch.tensor(centers, dtype=torch.float64, requires_grad=True)
+    ar = torch.arange(C, dtype=torch.float64).view(1, C, 1, 1)
+    ref_db = torch.empty((N, CB, h, w), dtype=torch.float64)
+    for n in range(N):
+        bt = torch.tensor(bott[n:n + 1], dtype=torch.float64, requires_grad=True)
+        if heatmap:
+            hm = torch.clamp(torch.clamp(torch.sigmoid(bt[:, 0:1]) * C - ar, max=1.0), min=0.0)
+            z = hm * bt[:, 1:]
+        else:
+            z = bt
+        qsoft = (torch.softmax(-(z.unsqueeze(-1) - ct) ** 2, -1) * ct).sum(-1)
+        loss = (qsoft * torch.as_tensor(gq[n:n + 1], dtype=torch.float64)).sum()
+        if gh is not None:
+            loss = loss + (hm * torch.as_tensor(gh[n:n + 1], dtype=torch.float64)).sum()
+        loss.backward()
+        ref_db[n] = bt.grad[0]
+    d = lambda a: dev(a, cuda)
+    bd, cd, gqd = d(bott), d(centers), d(gq)
+    ghd = d(gh) if gh is not None else None
+    ws = torch.empty(Lb.lib.ic_heatmap_quantize_bwd_workspace_bytes(L), dtype=torch.uint8, device=cuda)
+
+    def launch():
+        db, dc = torch.full((N, CB, h, w), float('nan'), device=cuda), torch.full((L,), float('nan'), device=cuda)
+        Lb.check(Lb.lib.ic_heatmap_quantize_bwd_f32(Lb.ptr(bd), Lb.ptr(cd), L, 1.0, Lb.ptr(gqd), Lb.ptr(ghd), Lb.ptr(db), Lb.ptr(dc),
+                                                    N, C, h, w, heatmap, Lb.ptr(ws), Lb.current_stream()))
+        return db, dc
+    db, dc = _twice(launch)
+    tag = 'quantiser bwd {} C={} L={}{}'.format('heatmap' if heatmap else 'no heatmap', C, L, ' d_heatmap' if gh is not None else '')
+    assert_close(db, ref_db, tag + ': d bottleneck', 1e-5)
+    assert_close(dc, ct.grad, tag + ': d centers', 1e-5)

@@ -61,7 +61,7 @@ def test_bn_train_forward_backward(cuda):
         assert_close(dx, xt.grad, 'bn dx', 1e-5)
 
 
-@pytest.mark.parametrize('N,H,W', [(32, 32, 32), (2, 37, 68), (1, 128, 192), (3, 30, 44)])
+@pytest.mark.parametrize('N,H,W', [(32, 32, 32), (2, 37, 68), (1, 128, 192), (3, 30, 44), (30, 40, 40)])
 def test_conv3x3_epilogue_batchnorm_sums(cuda, N, H, W):
     """Round 6: the training step's forward 3x3 convolution leaves the per-segment channel sums of its RAW output
     behind (ic_wino4_3x3_c128_raw_stats_f32: both segment shapes, ragged maps -- rows and tiles beyond the map must not count), and
@@ -147,7 +147,7 @@ def test_fused_adam_matches_the_multi_tensor_form(cuda):
     assert float(fp[offs[1] + 33:offs[2]].abs().max()) == 0.0          # the padding between tensors stays zero
 
 
-@pytest.mark.parametrize('N,H,W', [(2, 16, 16), (1, 12, 20), (1, 7, 8), (3, 9, 34), (32, 32, 32)])
+@pytest.mark.parametrize('N,H,W', [(2, 16, 16), (1, 12, 20), (1, 7, 8), (3, 9, 34), (32, 32, 32), (30, 40, 40)])
 def test_winograd_filter_gradient(cuda, N, H, W):
     """ic_conv3x3_c128_wgrad_f32 (Winograd-domain GEMMs over all 2x2 tiles) against autograd in float64 on the small shapes and
     against the direct-form kernel everywhere: ragged chunks of tiles (W = 20: 10 tiles = 8 + 2), odd heights, several slices."""
@@ -172,7 +172,8 @@ def test_winograd_filter_gradient(cuda, N, H, W):
                                       L.ptr(ws2), need2, L.current_stream()))
     torch.cuda.synchronize()
     assert_close(dw, dw2.double(), 'dW winograd vs direct {}x{}x{}'.format(N, H, W), 2e-5)
-    if N * H * W <= 2048:
+    if N * H * W <= 2048 or (N, H, W) == (30, 40, 40):          # and the reference's 160 x 160 training crops at full size
+        torch.set_num_threads(16)
         wt = torch.tensor(w, dtype=torch.float64, requires_grad=True)
         y = T._conv(torch.tensor(x, dtype=torch.float64), wt, 1)
         y.backward(torch.tensor(dy, dtype=torch.float64))
@@ -292,6 +293,53 @@ def test_training_step_matches_oracle(cuda):
         assert e <= GTOL, 'gradient of {}: relative error {:.3e}'.format(name, e)
     assert len([n for n in p if p[n].grad is not None]) == len(g.grads) == 219
     print('worst gradient error', worst)
+
+
+@pytest.mark.parametrize('label,ae_name,pc_name,heatmap,seed', [
+    ('hi training step', 'hi', 'res_shallow_64', True, 3),
+    ('no-heatmap training step', 'med', 'res_shallow', False, 2),
+])
+def test_training_step_untested_configs_match_oracle(cuda, label, ae_name, pc_name, heatmap, seed):
+    """one step (batch 2, 32x32, MSE distortion, rate term active) of the two configurations no other training test builds:
+    the high-rate pair cvpr/hi + res_shallow_64 (C = 64, to_bn emits 65 channels, k = 64 context model) and cvpr/med without the
+    importance map (autoencoder.py:236-242: z = to_bn's output; train.py:306-309: H_mask = H_real).  Symbols equal to the float64
+    oracle's (the seeds keep every z >= 1.5e-4 away from a decision midpoint in the oracle), z / bit cost / x_out, the scalar
+    losses and EVERY parameter gradient against its autograd."""
+    from imgcomp_cvpr_amd import training, config_parser as cp, weights as W
+    from oracle import train_oracle as T
+    ae, _ = cp.parse(cp.builtin_config_path('ae_configs', 'cvpr', ae_name))
+    pc, _ = cp.parse(cp.builtin_config_path('pc_configs', 'cvpr', pc_name))
+    ae.distortion_to_minimize = 'mse'
+    ae.H_target = 0.5                                     # keep the rate term active
+    ae.heatmap = heatmap
+    wts = W.synthetic_weights(ae, pc)
+    assert np.asarray(wts['autoencoder/encoder/to_bn/weights']).shape[-1] == int(ae.num_chan_bn) + int(heatmap)
+    x = W.synthetic_image((2, 3, 32, 32), 'natural', seed)
+    total, comps, p = T.train_loss(x, wts, ae.as_dict(), pc.as_dict(), torch.float64)
+    total.backward()
+    assert (comps['heatmap'] is None) == (not heatmap)
+    g = training.TrainGraph(ae, pc, wts, cuda)
+    out = g.forward_backward(dev(x, cuda))
+    torch.cuda.synchronize()
+    assert (g.last['heatmap'] is None) == (not heatmap)
+    assert torch.equal(g.last['symbols'].cpu(), comps['symbols']), 'symbol flip between fp32 and fp64: pick another seed'
+    assert_close(g.last['z'], comps['z'].detach(), label + ': z', 1e-4)
+    assert_close(g.last['bc'], comps['bc'].detach(), label + ': bit cost', 1e-4)
+    assert_close(g.last['x_out'], comps['x_out'].detach(), label + ': x_out', 1e-4)
+    assert abs(out['d_loss_scaled'] - float(comps['d_loss_scaled'])) < 1e-3 * abs(float(comps['d_loss_scaled']))
+    assert abs(out['pc_loss'] - float(comps['pc_loss'])) < 1e-3 * abs(float(comps['pc_loss'])) and out['pc_loss'] > 0
+    assert abs(out['H_real'] - float(comps['H_real'])) < 1e-4 * abs(float(comps['H_real']))
+    assert abs(out['H_mask'] - float(comps['H_mask'])) < 1e-4 * abs(float(comps['H_mask']))
+    if not heatmap:
+        assert out['H_mask'] == out['H_real']
+    assert abs(g.regularization_loss() - float(comps['reg'])) < 1e-4 * float(comps['reg'])
+    n_ref = 0
+    for name, ref in p.items():
+        if ref.grad is None:
+            continue
+        n_ref += 1
+        assert_close(g.grads[name], ref.grad, label + ': every gradient', GTOL)
+    assert n_ref == len(g.grads)
 
 
 def test_ms_ssim_loss_module(cuda):
