@@ -7,7 +7,9 @@ Differences from the reference, all on the speed side, none in the stream:
   * decode stays sequential by nature (a table depends on the symbols decoded so far); by default the whole loop
     runs on the device without host round trips (PredictionNetwork.decode_stream -> ic_pc_decode_f32); with
     device_decode=False it asks the prediction network one context at a time from Python, exactly like
-    bit_counter.py:137-164 (both are tested to return the same symbols).
+    bit_counter.py:137-164 (both are tested to return the same symbols);
+  * with device_encode=True the coding side runs on the device too (PredictionNetwork.encode_stream -> ic_pc_encode_f32): the
+    same bytes, without the (n, L) tables ever leaving the device.
 Raster order C -> H -> W, the first symbol is not coded (only its -log2 p enters the theoretical cost),
 and the three run-time checks of the reference are kept (bit_counter.py:51,56,68).
 """
@@ -21,11 +23,18 @@ from . import arithmetic_coding as ac
 from . import probclass
 
 
-def encode_decode_to_file_ctx(syms, prediction_net, syms_format='HWC', verbose=False, device_decode=True):
-    """:return: number of bits needed to encode all symbols in `syms` (HWC / CHW, or a batch of them)."""
+def encode_decode_to_file_ctx(syms, prediction_net, syms_format='HWC', verbose=False, device_decode=True, device_encode=False,
+                              theoretical_bit_cost=None):
+    """:return: number of bits needed to encode all symbols in `syms` (HWC / CHW, or a batch of them).
+    device_encode=True: the stream comes from the device encoder.  The host path takes the theoretical cost of the first run-time
+    check from the probabilities it has on the host anyway; here it comes from one bitcost call of the context model, or from the
+    caller who already has it -- `theoretical_bit_cost`: a number, or a callable symbols_chw -> bits such as
+    ProbclassNetworkTesting.get_total_bit_cost."""
     _print = print if verbose else (lambda *a, **k: None)
     if len(syms.shape) == 4:
-        return int(np.sum([encode_decode_to_file_ctx(syms[b, ...], prediction_net, syms_format, verbose, device_decode)
+        assert theoretical_bit_cost is None or callable(theoretical_bit_cost), 'a batch needs the cost of each volume: pass a callable'
+        return int(np.sum([encode_decode_to_file_ctx(syms[b, ...], prediction_net, syms_format, verbose, device_decode,
+                                                     device_encode, theoretical_bit_cost)
                            for b in range(syms.shape[0])]))
     assert len(syms.shape) == 3, 'Expected HWC or CHW'
     assert syms_format in ('HWC', 'CHW')
@@ -39,7 +48,10 @@ def encode_decode_to_file_ctx(syms, prediction_net, syms_format='HWC', verbose=F
         _print('Encoding symbols of shape {} ({} symbols) with context shape {}...'.format(
             syms.shape, int(np.prod(syms.shape)), ctx_shape))
         syms_padded = prediction_net.pad_symbols_volume(syms)
-        virtual_num_bits, first_sym, theoretical_bit_cost = _encode(fd, syms_padded, syms, prediction_net)
+        if device_encode:
+            virtual_num_bits, first_sym, theoretical_bit_cost = _encode_on_device(fd, syms, prediction_net, theoretical_bit_cost)
+        else:
+            virtual_num_bits, first_sym, theoretical_bit_cost = _encode(fd, syms_padded, syms, prediction_net)
         assert abs(virtual_num_bits - theoretical_bit_cost) < 50, 'Virtual: {} -- Theoretical: {}'.format(
             virtual_num_bits, theoretical_bit_cost)
         actual_num_bits = os.path.getsize(fout_p) * 8
@@ -77,6 +89,22 @@ def _encode(fd, syms_padded, syms, prediction_net):
     with open(fd, 'wb') as fout:
         num_bits = ac.encode_sequence(flat[1:], freqs[1:], fout)
     return num_bits, first_sym, theoretical_bit_cost
+
+
+def _encode_on_device(fd, syms, prediction_net, theoretical_bit_cost):
+    """the stream of PredictionNetwork.encode_stream, written to the file the decoder reads."""
+    stream, first_sym = prediction_net.encode_stream(syms)
+    if theoretical_bit_cost is None:
+        import torch
+        centers = prediction_net.centers
+        sym = torch.as_tensor(np.ascontiguousarray(syms)).to(centers.device).long()[None]
+        # pad value centers[0]: the coder's tables see the symbol volume padded with symbol 0 (pad_symbols_volume)
+        bc = prediction_net.pc.bitcost(centers[sym].contiguous(), sym, is_training=False, pad_value=float(centers[0]))
+        theoretical_bit_cost = float(bc.double().sum())
+    with open(fd, 'wb') as fout:
+        fout.write(stream)
+    cost = theoretical_bit_cost(syms) if callable(theoretical_bit_cost) else theoretical_bit_cost
+    return 8 * len(stream), first_sym, float(cost)
 
 
 def _decode(fout_p, symbols_shape_padded, ctx_shape, first_sym, get_freqs):

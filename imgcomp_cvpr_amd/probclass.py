@@ -345,6 +345,43 @@ class PredictionNetwork(object):
         """(pr, freqs), each (num_contexts, L), contexts in the order of iter_over_blocks."""
         return self._tables(symbols_padded)
 
+    def encode_stream(self, symbols, capacity=None):
+        """The mirror of decode_stream: the whole coding side on the device (ic_pc_encode_f32).  symbols: un-padded (C,h,w) numpy /
+        tensor -> (stream_bytes, first_sym); a batch (N,C,h,w) -> a list of N such pairs, coded concurrently by ONE launch.
+        The tables are bit for bit those of get_all(pad_symbols_volume(symbols)) -- the symbol volume padded with symbol 0, the
+        centres gathered, pc.logits on the padded volume, as _tables does -- but they never exist in memory: the kernel takes
+        (cum_lo, cum_hi, total) of each symbol from a table row held in registers, and only the stream comes back to the host.
+        capacity: bytes reserved per stream (tests); default ic_pc_encode_capacity_bytes, which always suffices."""
+        dev = self.centers.device
+        sym = symbols if torch.is_tensor(symbols) else torch.as_tensor(np.ascontiguousarray(symbols))
+        batched = sym.dim() == 4
+        if not batched:
+            sym = sym[None]
+        assert sym.dim() == 4, 'Expected CHW or NCHW symbols'
+        sym = sym.to(dev).long().contiguous()
+        N, C, h, w = (int(v) for v in sym.shape)
+        pad = self.pc_class.get_context_size(self.config) // 2
+        q = self.centers[torch.nn.functional.pad(sym, (pad, pad, pad, pad, pad, 0))].contiguous()    # (N,C+4,h+8,w+8), symbol 0 around
+        logits = self.pc.logits(q, is_training=False)                  # (N,C,h,w,L)
+        count = C * h * w
+        cap = int(lib.ic_pc_encode_capacity_bytes(count)) if capacity is None else int(capacity)
+        out = torch.empty((N, max(cap, 1)), dtype=torch.uint8, device=dev)
+        info = torch.zeros((2, N), dtype=torch.int64, device=dev)       # row 0: nbytes; row 1: status (int32 in the low words)
+        status = info[1].view(torch.int32)[:N]
+        check(lib.ic_pc_encode_f32(ptr(logits), ptr(sym), N, count, self.pc.L, self.freqs_resolution, ptr(out), cap,
+                                   ptr(info[0]), ptr(status), _lib.current_stream(dev)), 'ic_pc_encode_f32')
+        nbytes = info[0].tolist()
+        status = status.tolist()
+        res = []
+        for n in range(N):
+            if status[n] == 1:
+                raise ValueError('Cannot code symbol because total is too large')
+            if status[n] != 0:
+                raise ValueError('device range encoder: {} (status {})'.format(
+                    {2: 'stream capacity too small', 3: 'symbol outside [0, L)'}.get(status[n], 'error'), status[n]))
+            res.append((bytes(out[n, :nbytes[n]].cpu().numpy()), int(sym[n, 0, 0, 0])))
+        return res if batched else res[0]
+
     def decode_stream(self, stream_bytes, symbols_shape, first_sym, flags=0):
         """Row N3: the whole sequential decode on the device (ic_pc_decode_f32) -- per symbol the same context-model
         kernels as get_freqs, the table, the arithmetic-decoder step and the gather of the next context are enqueued

@@ -278,6 +278,22 @@ size_t ic_pc_decode_workspace_bytes(int C, int h, int w, int k);
 int ic_pc_decode_f32(const uint8_t* bitstream, long long nbytes, int first_sym, const float* const* wtab_host,
                      const float* centers, int k, int L, float resolution, int64_t* symbols, int* status,
                      int C, int h, int w, void* workspace, size_t workspace_bytes, int flags, ic_stream_t stream);
+/* The encoder side of the real-bpp path on the device: the mirror image of ic_pc_decode_f32.  Codes N symbol volumes in one
+ * launch (one work-group per volume) with the 32-bit range coder of arithmetic_coding.py; the stream of each volume is byte
+ * for byte arithmetic_coding.encode_sequence(symbols[1:], freqs[1:]) over the tables ic_pc_logits_to_freqs_f32 derives from
+ * the same logits -- but no (count, L) table is written anywhere: a table row lives in registers until (cum_lo, cum_hi,
+ * total) of the symbol that occurred are taken from it.  Symbol 0 of a volume is not coded (count == 1 gives the one byte 0x80).
+ *   logits: device (N, count, L), raster C,H,W, as ic_pc_logits_f32 writes them;  symbols: device int64 (N, count)
+ *   resolution: 1e9 (probclass.py:443);  L <= 16
+ *   bitstream: out, device (N, capacity);  nothing is ever stored at or beyond `capacity` of a volume
+ *   nbytes: out, device (N): bytes written, the zero-padded last byte included
+ *   status: out, device (N): 0 ok, 1 = a table's total exceeded 2^30 + 2, 2 = capacity too small (the stream is cut off),
+ *           3 = a symbol outside [0, L)
+ * ic_pc_encode_capacity_bytes(count) = 4 count + 16 always suffices (a coder step commits at most 32 bits; measured worst case
+ * 30.5 bits per symbol: frequency 1 of a total of 2^30 + 2, repeated). */
+size_t ic_pc_encode_capacity_bytes(long long count);
+int ic_pc_encode_f32(const float* logits, const int64_t* symbols, int N, long long count, int L, float resolution,
+                     uint8_t* bitstream, long long capacity, long long* nbytes, int* status, ic_stream_t stream);
 /* bits -> sum(bits) (bits.py:4-14 numerator); deterministic two-stage reduction.
  * partial: >= 1024 floats of scratch.  out_sum: 1 float. */
 int ic_sum_f32(const float* v, long long count, float* partial, float* out_sum, ic_stream_t stream);
