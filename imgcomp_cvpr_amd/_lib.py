@@ -54,6 +54,20 @@ def edge_tiles_per_wg(n):
     return n & 0xff
 
 
+class PcTile(ctypes.Structure):
+    """ic_pc_tile_t: one tile of ic_pc_decode_tiles_f32 (a host array of these is passed by pointer)."""
+    _fields_ = [('y0', c_int), ('x0', c_int), ('th', c_int), ('tw', c_int), ('stream_off', c_longlong), ('stream_bytes', c_longlong),
+                ('first_sym', c_int), ('reserved', c_int)]
+
+
+def tile_table(tiles):
+    """[(y0, x0, th, tw, stream_off, stream_bytes, first_sym)] -> host array of ic_pc_tile_t."""
+    arr = (PcTile * len(tiles))()
+    for i, t in enumerate(tiles):
+        arr[i] = PcTile(*[int(v) for v in t], 0)
+    return arr
+
+
 # name -> (restype, argtypes); mirrors include/imgcomp_hip.h one-to-one (tests/test_abi.py checks
 # that every ic_* prototype of the header is listed here and exported by the .so).
 PROTOTYPES = {
@@ -98,6 +112,9 @@ PROTOTYPES = {
     'ic_pc_decode_workspace_bytes': (c_size_t, [c_int] * 4),
     'ic_pc_decode_f32': (c_int, [c_void_p, c_longlong, c_int, POINTER(c_void_p), c_void_p, c_int, c_int, c_float,
                                  c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_int, c_void_p]),
+    'ic_pc_decode_tiles_workspace_bytes': (c_size_t, [c_int] * 5),
+    'ic_pc_decode_tiles_f32': (c_int, [c_void_p, c_longlong, c_void_p, c_int, POINTER(c_void_p), c_void_p, c_int, c_int, c_float,
+                                       c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_int, c_void_p]),
     'ic_sum_f32': (c_int, [c_void_p, c_longlong, c_void_p, c_void_p, c_void_p]),
     'ic_mean_f32': (c_int, [c_void_p, c_longlong, c_float, c_void_p, c_void_p, c_void_p]),
     'ic_mean_rows_f32': (c_int, [c_void_p, c_int, c_longlong, c_float, c_void_p, c_void_p, c_void_p]),

@@ -1,6 +1,7 @@
 """Image codec: an image to a self-describing file and back.
 
     python -m imgcomp_cvpr_amd.codec compress   IN.png  OUT.icf [--ae_config cvpr/low] [--pc_config cvpr/res_shallow] [--weights synthetic|FILE.npz|CKPT]
+                                                                [--tile PIXELS]
     python -m imgcomp_cvpr_amd.codec decompress IN.icf  OUT.png [same options]
 
 compress:   pad to a multiple of the subsampling factor (val.add_padding) -> ae.encode -> PredictionNetwork.encode_stream (the
@@ -24,6 +25,19 @@ Container (little-endian; INTEGRATION.md has the same table):
     ..      8     payload length n (u64)
     ..      n     payload
     ..      4     CRC-32 (zlib.crc32) of every byte before it (u32)
+--tile (Codec(tile=(th, tw))): format 2.  The autoencoder still sees the whole image; the symbol volume is cut into tiles of th x tw
+latent positions (all channels), each coded as a volume of its own -- own padding, own stream, first symbol uncoded -- so all tiles
+decode concurrently (ic_pc_decode_tiles_f32, one work-group per tile) and damage stays inside a tile.  The price is the context lost
+at tile borders and one stream termination per tile.  Without --tile every byte is format 1 as above; decompress reads both.
+    0       4     magic  b'ICVF'
+    4       2     format version (u16) = 2
+    ..            ae name, pc name, H, W, C, h, w, L (u16), resolution (f64), fingerprint (u32): as version 1, without first_sym
+    ..      2+2   th, tw (u16, u16): tile extent in symbol-volume units
+    ..      4     ntiles (u32) = ceil(h / th) * ceil(w / tw)
+    ..      6*nt  per tile, raster order: first_sym (u16), stream length in bytes (u32)
+    ..      8     payload length n (u64) = the sum of the stream lengths
+    ..      n     payload: the tiles' streams back to back, in table order
+    ..      4     CRC-32 of every byte before it (u32)
 Every failure of parse / decompress is a ValueError that names the cause; nothing of a refused file reaches the device.
 """
 import argparse
@@ -42,6 +56,37 @@ _MIN_SIZE = 4 + 2 + 2 + 2 + 8 + 10 + 2 + 2 + 8 + 4 + 8 + 4        # both names e
 
 Container = namedtuple('Container', ['version', 'ae_name', 'pc_name', 'H', 'W', 'C', 'h', 'w', 'L', 'first_sym',
                                      'resolution', 'fingerprint', 'payload'])
+
+
+FORMAT_VERSION_TILED = 2
+TiledContainer = namedtuple('TiledContainer', ['version', 'ae_name', 'pc_name', 'H', 'W', 'C', 'h', 'w', 'L', 'resolution', 'fingerprint',
+                                               'th', 'tw', 'first_syms', 'streams', 'payload'])
+
+
+def tile_grid(h, w, th, tw):
+    """the tiles of an (h, w) latent plane cut into th x tw blocks: [(y0, x0, th', tw')] in raster order, ceil(h / th) * ceil(w / tw)
+    of them, the last row / column smaller where th / tw does not divide; every position is in exactly one tile."""
+    h, w, th, tw = int(h), int(w), int(th), int(tw)
+    if h < 1 or w < 1 or th < 1 or tw < 1:
+        raise ValueError('tile grid: plane {} x {} and tile {} x {} must all be at least 1'.format(h, w, th, tw))
+    return [(y0, x0, min(th, h - y0), min(tw, w - x0)) for y0 in range(0, h, th) for x0 in range(0, w, tw)]
+
+
+def build_tiled_container(ae_name, pc_name, H, W, C, h, w, L, resolution, fingerprint, th, tw, first_syms, streams):
+    """format 2: first_syms / streams per tile in the order of tile_grid(h, w, th, tw)."""
+    a, p = ae_name.encode('utf-8'), pc_name.encode('utf-8')
+    streams = [bytes(b) for b in streams]
+    assert len(first_syms) == len(streams)
+    head = b''.join([
+        MAGIC, struct.pack('<H', FORMAT_VERSION_TILED),
+        struct.pack('<H', len(a)), a, struct.pack('<H', len(p)), p,
+        struct.pack('<II', H, W), struct.pack('<HII', C, h, w), struct.pack('<H', L),
+        struct.pack('<d', float(resolution)), struct.pack('<I', fingerprint & 0xffffffff),
+        struct.pack('<HH', th, tw), struct.pack('<I', len(streams))] +
+        [struct.pack('<HI', f, len(b)) for f, b in zip(first_syms, streams)] +
+        [struct.pack('<Q', sum(len(b) for b in streams))])
+    body = head + b''.join(streams)
+    return body + struct.pack('<I', zlib.crc32(body) & 0xffffffff)
 
 
 def build_container(ae_name, pc_name, H, W, C, h, w, L, first_sym, resolution, fingerprint, payload):
@@ -75,16 +120,18 @@ class _Reader(object):
 
 
 def parse_container(data):
-    """bytes -> Container.  Order: size, magic, version, CRC over the whole file -- only then are the header's lengths read, each
-    against the bytes that remain; the payload length must equal exactly what is left before the CRC."""
+    """bytes -> Container (version 1) or TiledContainer (version 2).  Order: size, magic, version, CRC over the whole file -- only
+    then are the header's lengths read, each against the bytes that remain; the payload length must equal exactly what is left
+    before the CRC."""
     data = bytes(data)
     if len(data) < _MIN_SIZE:
         raise ValueError('truncated file: {} bytes, the smallest container has {}'.format(len(data), _MIN_SIZE))
     if data[:4] != MAGIC:
         raise ValueError('wrong magic {!r}: not a codec file (expected {!r})'.format(data[:4], MAGIC))
     version, = struct.unpack('<H', data[4:6])
-    if version != FORMAT_VERSION:
-        raise ValueError('unsupported format version {} (this codec reads version {})'.format(version, FORMAT_VERSION))
+    if version not in (FORMAT_VERSION, FORMAT_VERSION_TILED):
+        raise ValueError('unsupported format version {} (this codec reads versions {} and {})'.format(
+            version, FORMAT_VERSION, FORMAT_VERSION_TILED))
     stored, = struct.unpack('<I', data[-4:])
     actual = zlib.crc32(data[:-4]) & 0xffffffff
     if stored != actual:
@@ -99,6 +146,8 @@ def parse_container(data):
         raise ValueError('config name is not UTF-8')
     H, W = r.unpack('<II', 'image size')
     C, h, w = r.unpack('<HII', 'symbol volume shape')
+    if version == FORMAT_VERSION_TILED:
+        return _parse_tiled(r, version, ae_name, pc_name, H, W, C, h, w)
     L, first_sym = r.unpack('<HH', 'L and first symbol')
     resolution, = r.unpack('<d', 'frequency resolution')
     fingerprint, = r.unpack('<I', 'model fingerprint')
@@ -107,6 +156,43 @@ def parse_container(data):
     if n != left:
         raise ValueError('payload length {} does not equal the {} bytes that remain in the file'.format(n, left))
     return Container(version, ae_name, pc_name, H, W, C, h, w, L, first_sym, resolution, fingerprint, r.take(n, 'payload'))
+
+
+def _parse_tiled(r, version, ae_name, pc_name, H, W, C, h, w):
+    """the rest of a format-2 file after the symbol volume shape (the CRC has been checked)."""
+    L, = r.unpack('<H', 'L')
+    resolution, = r.unpack('<d', 'frequency resolution')
+    fingerprint, = r.unpack('<I', 'model fingerprint')
+    th, tw = r.unpack('<HH', 'tile extent')
+    ntiles, = r.unpack('<I', 'tile count')
+    if th == 0 or tw == 0:
+        raise ValueError('tile extent {} x {}: a tile has at least one row and one column'.format(th, tw))
+    if h < 1 or w < 1:
+        raise ValueError('symbol volume {} x {} cannot be tiled'.format(h, w))
+    expected = ((h + th - 1) // th) * ((w + tw - 1) // tw)
+    if ntiles != expected:
+        raise ValueError('tile count {} does not equal the {} tiles of a {} x {} volume cut into {} x {}'.format(
+            ntiles, expected, h, w, th, tw))
+    table = r.take(6 * ntiles, 'tile table')              # against the bytes that remain, before anything of its size is built
+    first_syms, lengths = [], []
+    for t in range(ntiles):
+        f, n_t = struct.unpack_from('<HI', table, 6 * t)
+        if f >= L:
+            raise ValueError('first symbol {} of tile {} is not below L = {}'.format(f, t, L))
+        first_syms.append(f)
+        lengths.append(n_t)
+    n, = r.unpack('<Q', 'payload length')
+    if sum(lengths) != n:
+        raise ValueError('stream lengths of the {} tiles sum to {}, the payload length is {}'.format(ntiles, sum(lengths), n))
+    left = len(r.data) - r.pos
+    if n != left:
+        raise ValueError('payload length {} does not equal the {} bytes that remain in the file'.format(n, left))
+    payload = r.take(n, 'payload')
+    streams, pos = [], 0
+    for n_t in lengths:
+        streams.append(payload[pos:pos + n_t])
+        pos += n_t
+    return TiledContainer(version, ae_name, pc_name, H, W, C, h, w, L, resolution, fingerprint, th, tw, first_syms, streams, payload)
 
 
 def model_fingerprint(centers, pc_params):
@@ -131,9 +217,16 @@ def config_name(config):
 class Codec(object):
     """builds the networks once (as val.Fetcher does); compress / decompress map HWC uint8 images to container bytes and back.
     device_encode: which range encoder writes the payload -- the bytes are the same either way (tests/test_gpu_codec.py); the
-    default is the one that measured faster end to end on a Kodak volume."""
+    default is the one that measured faster end to end on a Kodak volume.
+    tile: None writes format 1; (th, tw) in symbol-volume units writes format 2, one stream per tile.  Reading needs no option:
+    the file's version decides."""
 
-    def __init__(self, ae_config, pc_config, weights, device='cuda', plan_flags=0, device_encode=True):
+    def __init__(self, ae_config, pc_config, weights, device='cuda', plan_flags=0, device_encode=True, tile=None):
+        if tile is not None:
+            tile = (int(tile[0]), int(tile[1]))
+            if not (1 <= tile[0] <= 0xffff and 1 <= tile[1] <= 0xffff):
+                raise ValueError('tile extent {} x {} is outside 1 .. 65535'.format(*tile))
+        self.tile = tile
         import torch
         from . import autoencoder, probclass
         self.device = torch.device(device)
@@ -181,11 +274,16 @@ class Codec(object):
     def compress(self, img_hwc_uint8):
         enc, (H, W) = self.encode_symbols(img_hwc_uint8)
         sym = enc.symbols[0]
+        C, h, w = (int(v) for v in sym.shape)
+        if self.tile is not None:
+            th, tw = self.tile
+            coded = self.pred.encode_tiles(sym, th, tw)
+            return build_tiled_container(self.ae_name, self.pc_name, H, W, C, h, w, self.L, self.pred.freqs_resolution,
+                                         self.fingerprint, th, tw, [f for _, f in coded], [b for b, _ in coded])
         if self.device_encode:
             payload, first_sym = self.pred.encode_stream(sym)
         else:
             payload, first_sym = self._host_encode_stream(sym.cpu().numpy())
-        C, h, w = (int(v) for v in sym.shape)
         return build_container(self.ae_name, self.pc_name, H, W, C, h, w, self.L, first_sym, self.pred.freqs_resolution,
                                self.fingerprint, payload)
 
@@ -207,18 +305,22 @@ class Codec(object):
         if (c.h, c.w) != (eh, ew):
             raise ValueError('header mismatch: symbol volume {} x {} does not belong to a {} x {} image (expected {} x {})'.format(
                 c.h, c.w, c.H, c.W, eh, ew))
-        if c.first_sym >= c.L:
-            raise ValueError('header mismatch: first symbol {} is not below L = {}'.format(c.first_sym, c.L))
+        for first_sym in (c.first_syms if isinstance(c, TiledContainer) else [c.first_sym]):
+            if first_sym >= c.L:
+                raise ValueError('header mismatch: first symbol {} is not below L = {}'.format(first_sym, c.L))
         if c.resolution != self.pred.freqs_resolution:
             raise ValueError('header mismatch: frequency resolution {} in the file, {} in the model'.format(
                 c.resolution, self.pred.freqs_resolution))
 
     def decode_symbols(self, data):
-        """container bytes -> (symbols (C,h,w) int64 numpy, Container)."""
+        """container bytes of either format -> (symbols (C,h,w) int64 numpy, Container or TiledContainer)."""
         c = parse_container(data)
         self.check_container(c)
         try:
-            sym = self.pred.decode_stream(c.payload, (c.C, c.h, c.w), c.first_sym)
+            if isinstance(c, TiledContainer):
+                sym = self.pred.decode_tiles(c.streams, c.first_syms, (c.C, c.h, c.w), c.th, c.tw)
+            else:
+                sym = self.pred.decode_stream(c.payload, (c.C, c.h, c.w), c.first_sym)
         except ValueError as e:
             raise ValueError('decoder status is not 0: {}'.format(e))
         return sym, c
@@ -273,6 +375,9 @@ def main(argv=None):
                                                           "ckpts dir (as val.py)")
     p.add_argument('--synthetic_seed', type=int, default=1234, help='seed of --weights synthetic')
     p.add_argument('--device', default='cuda:0')
+    p.add_argument('--tile', type=int, default=None, metavar='PIXELS',
+                   help='compress: square tiles of this many image pixels (a positive multiple of the subsampling factor), one stream '
+                        'per tile, decoded concurrently (format 2); default: one stream (format 1)')
     flags = p.parse_args(argv)
     from . import config_parser, val, weights as _weights
     try:
@@ -284,10 +389,16 @@ def main(argv=None):
             wts = val.load_weights_for_job(None, flags.weights, ae_config, pc_config)
         codec = Codec(ae_config, pc_config, wts, flags.device)
         if flags.command == 'compress':
+            if flags.tile is not None:
+                if flags.tile <= 0 or flags.tile % codec.factor != 0:
+                    raise ValueError('--tile {} is not a positive multiple of the subsampling factor {}'.format(flags.tile, codec.factor))
+                codec.tile = (flags.tile // codec.factor, flags.tile // codec.factor)
             data, pixels = codec.compress_file(flags.input, flags.output)
-            payload = len(parse_container(data).payload)
-            print('{}: {} bytes, payload {} bytes = {:.4f} bpp, file {:.4f} bpp'.format(
-                flags.output, len(data), payload, 8.0 * payload / pixels, 8.0 * len(data) / pixels))
+            c = parse_container(data)
+            payload = len(c.payload)
+            tiles = ', {} tiles'.format(len(c.streams)) if isinstance(c, TiledContainer) else ''
+            print('{}: {} bytes, payload {} bytes = {:.4f} bpp, file {:.4f} bpp{}'.format(
+                flags.output, len(data), payload, 8.0 * payload / pixels, 8.0 * len(data) / pixels, tiles))
         else:
             img = codec.decompress_file(flags.input, flags.output)
             size = os.path.getsize(flags.input)

@@ -938,17 +938,18 @@ struct PcDecArgs {
     float resolution;
 };
 
-__device__ __forceinline__ int pc_dec_bit(const PcDecArgs& a, PcDecState& s) {
+__device__ __forceinline__ int pc_dec_bit(const unsigned char* bits, long long nbytes, PcDecState& s) {
     if (s.bit_left == 0) {
         s.cur_byte = s.nxt_byte;
         s.byte_pos += 1;
         const long long np = s.byte_pos + 1;
-        s.nxt_byte = np < a.nbytes ? a.bits[np] : 0;   // past the end the stream reads as zeros (arithmetic_coding.py)
+        s.nxt_byte = np < nbytes ? bits[np] : 0;       // past the end the stream reads as zeros (arithmetic_coding.py)
         s.bit_left = 8;
     }
     --s.bit_left;
     return (s.cur_byte >> s.bit_left) & 1;
 }
+__device__ __forceinline__ int pc_dec_bit(const PcDecArgs& a, PcDecState& s) { return pc_dec_bit(a.bits, a.nbytes, s); }
 
 __device__ void pc_dec_gather(const PcDecArgs& a, long long idx) {
     // context of symbol idx = padded block [c, c+5) x [y, y+9) x [x, x+9)
@@ -1026,10 +1027,10 @@ __device__ __forceinline__ unsigned long long pc_udiv(unsigned long long n, unsi
 // pc_table_row with its L exponentials, divisions and conversions spread over L lanes; the sum runs over readlane values in
 // j order (0 + e0 + e1 + ...: the same fp32 sequence).  Returns the symbol (uniform).
 template <int LC>       // LC = number of centres when known at compile time (the loops over readlane unroll), 0 = a.L
-__device__ __forceinline__ int pc_dec_symbol_wave(const PcDecArgs& a, PcDecState& s, float logit) {
+__device__ __forceinline__ int pc_dec_symbol_wave(const unsigned char* bits, long long nbytes, int L_rt, float resolution, PcDecState& s, float logit) {
     const unsigned long long MASK = (1ull << PC_AC_BITS) - 1, TOP = 1ull << (PC_AC_BITS - 1), SECOND = TOP >> 1;
     const unsigned long long MAX_TOTAL = (1ull << (PC_AC_BITS - 2)) + 2;
-    const int L = LC ? LC : a.L, lane = threadIdx.x & 63;
+    const int L = LC ? LC : L_rt, lane = threadIdx.x & 63;
     auto bcast = [](float v, int src) -> float { return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), src)); };
     float m = bcast(logit, 48);
 #pragma unroll
@@ -1039,7 +1040,7 @@ __device__ __forceinline__ int pc_dec_symbol_wave(const PcDecArgs& a, PcDecState
 #pragma unroll
     for (int j = 0; j < L; ++j) sum += bcast(e, 48 + j);
     const float pr = e / sum;
-    long long fl = (long long)__fmul_rn(pr, a.resolution);
+    long long fl = (long long)__fmul_rn(pr, resolution);
     fl = fl < 1 ? 1 : fl;
     const unsigned f32 = (unsigned)fl;                   // <= resolution < 2^31 (total is checked against 2^30 + 2 below)
     unsigned long long total = 0;
@@ -1056,12 +1057,12 @@ __device__ __forceinline__ int pc_dec_symbol_wave(const PcDecArgs& a, PcDecState
     s.high = s.low + pc_udiv(cum_hi * r, total) - 1;
     s.low = s.low + pc_udiv(cum_lo * r, total);
     while (((s.low ^ s.high) & TOP) == 0) {
-        s.code = ((s.code << 1) & MASK) | (unsigned)pc_dec_bit(a, s);
+        s.code = ((s.code << 1) & MASK) | (unsigned)pc_dec_bit(bits, nbytes, s);
         s.low = (s.low << 1) & MASK;
         s.high = ((s.high << 1) & MASK) | 1;
     }
     while ((s.low & ~s.high & SECOND) != 0) {
-        s.code = (s.code & TOP) | ((s.code << 1) & (MASK >> 1)) | (unsigned)pc_dec_bit(a, s);
+        s.code = (s.code & TOP) | ((s.code << 1) & (MASK >> 1)) | (unsigned)pc_dec_bit(bits, nbytes, s);
         s.low = (s.low << 1) & (MASK >> 1);
         s.high = ((s.high << 1) & (MASK >> 1)) | TOP | 1;
     }
@@ -1337,13 +1338,21 @@ struct PcCachedArgs {
 // chain position of (tap t, channel ci) in the K sequence of pc_mfma_kernel<24, ...>: 2 * (4 * ((ci / 8) * 14 + t) + (ci % 8) / 2) + ci % 2
 __device__ __forceinline__ int pc_chain_idx(int t, int ci) { return 8 * ((ci >> 3) * PC_NT + t) + (ci & 7); }
 
-__global__ __launch_bounds__(256) void pc_dec_cached_kernel(const PcCachedArgs f) {
+// The decoder of ONE volume by ONE work-group: the body of pc_dec_cached_kernel (a whole volume) and of pc_dec_tiles_kernel (one
+// tile of a volume per work-group).  f holds what all volumes of a launch share (weights, centres, C, L, resolution); the volume
+// being decoded -- stream, extents, first symbol, padded volume, caches, status -- comes as plain values, so that a kernel can
+// take them from a table without a private copy of the struct (which would live in scratch).  Symbol (c, y, x) is stored at
+// out[c * out_cs + y * out_rs + x]: out_cs = h * w, out_rs = w for a whole volume; the strides of the full volume, and out
+// moved to the tile's corner, for a tile.
+__device__ __forceinline__ void pc_dec_cached_body(const PcCachedArgs& f, const unsigned char* bits, long long nbytes, int h, int w, int first_sym,
+                                                   float* vol, float* c0, float* c1, float* c2, int* status,
+                                                   long long* __restrict__ out, long long out_cs, int out_rs) {
     constexpr int K = 24, KT = PC_NT * K;                 // 336 inputs per output
     __shared__ __attribute__((aligned(16))) float s_in[3][KT];          // inputs of conv1 / conv2 / conv3 in chain order
     __shared__ __attribute__((aligned(16))) float s_v[16];              // the 13 live taps of conv0
     __shared__ float s_part[2][4][64];
     __shared__ float s_centers[16];
-    const PcDecArgs& a = f.d;
+    const PcDecArgs& a = f.d;                             // centres, C, L, resolution: what all volumes of a launch share
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int L = a.L;
     // ---- per-lane constants ----
@@ -1369,14 +1378,14 @@ __global__ __launch_bounds__(256) void pc_dec_cached_kernel(const PcCachedArgs f
     const int pl = tid / 84, pe = tid - pl * 84, pt = pe / 6, pq = pe - pt * 6;
     const bool pf_on = tid < 252 && pt < 12;
     const int pkd = pt < 9 ? 0 : 1, pkh = pt < 9 ? pt / 3 : 0, pkw = pt < 9 ? pt % 3 : pt - 9;
-    const int ni = a.h + 6 - 2 * pl, nj = a.w + 6 - 2 * pl;
-    const float* cpl = pl == 0 ? f.c0 : (pl == 1 ? f.c1 : f.c2);
+    const int ni = h + 6 - 2 * pl, nj = w + 6 - 2 * pl;
+    const float* cpl = pl == 0 ? c0 : (pl == 1 ? c1 : c2);
     const int pdst = 8 * ((pq >> 1) * PC_NT + pt) + 4 * (pq & 1);      // chain position of channels 4 pq .. 4 pq + 3 of tap pt
     const int vkd = tid < 9 ? 0 : 1, vkh = tid < 9 ? tid / 3 : 0, vkw = tid < 9 ? tid % 3 : tid - 9;
-    const int PH = a.h + 8, PW = a.w + 8, HW = a.h * a.w;
-    const int D1 = a.C + 3, I1 = a.h + 6, J1 = a.w + 5;   // last D, I, J of the sweep
+    const int PH = h + 8, PW = w + 8;
+    const int D1 = a.C + 3, I1 = h + 6, J1 = w + 5;       // last D, I, J of the sweep
     auto layer_valid = [&](int l, int D, int I, int J) -> bool {     // does step (D, I, J) produce a voxel of layer l + 1?
-        return D >= 2 + l && I >= 2 + l && J >= 1 + l && I <= a.h + 5 - l && J <= a.w + 4 - l;
+        return D >= 2 + l && I >= 2 + l && J >= 1 + l && I <= h + 5 - l && J <= w + 4 - l;
     };
     pc_f32x4 pf = {0.f, 0.f, 0.f, 0.f};
     float pv = pad;
@@ -1385,13 +1394,13 @@ __global__ __launch_bounds__(256) void pc_dec_cached_kernel(const PcCachedArgs f
             const int off = (((D - 2 - pl + pkd) * ni + (I - 2 - pl + pkh)) * nj + (J - 1 - pl + pkw)) * K + 4 * pq;
             pf = *reinterpret_cast<const pc_f32x4*>(cpl + off);
         }
-        if (tid < 12) pv = a.vol[((size_t)(D - 1 + vkd) * PH + (I - 1 + vkh)) * PW + J + vkw];
+        if (tid < 12) pv = vol[((size_t)(D - 1 + vkd) * PH + (I - 1 + vkh)) * PW + J + vkw];
     };
     PcDecState s;                                         // wave 0 keeps the coder state, identical in all its lanes
     s.low = 0; s.high = (1ull << PC_AC_BITS) - 1; s.code = 0;
-    s.byte_pos = -1; s.bit_left = 0; s.cur_byte = 0; s.nxt_byte = a.nbytes > 0 ? a.bits[0] : 0; s.error = 0; s.next = 1;
+    s.byte_pos = -1; s.bit_left = 0; s.cur_byte = 0; s.nxt_byte = nbytes > 0 ? bits[0] : 0; s.error = 0; s.next = 1;
     if (wave == 0)
-        for (int i = 0; i < PC_AC_BITS; ++i) s.code = (s.code << 1) | (unsigned)pc_dec_bit(a, s);
+        for (int i = 0; i < PC_AC_BITS; ++i) s.code = (s.code << 1) | (unsigned)pc_dec_bit(bits, nbytes, s);
     if (tid == 0) s_v[12] = pad;                          // V[1][1][0]
     // LDS hand-over between the waves: wait for this wave's LDS operations only.  (__syncthreads() also waits for the global
     // stores of the cache voxels to be acknowledged; their readers are a row of steps away and every wave drains its
@@ -1434,7 +1443,7 @@ __global__ __launch_bounds__(256) void pc_dec_cached_kernel(const PcCachedArgs f
         a0 = fmaxf(a0 + bias0, 0.f);
         if (lane < K) {
             s_in[0][pc_chain_idx(13, lane)] = a0;         // every wave writes the same value: no barrier before its own reads
-            if (wave == 0) f.c0[(((size_t)(D - 1) * (a.h + 6) + (I - 1)) * (a.w + 6) + J) * K + lane] = a0;
+            if (wave == 0) c0[(((size_t)(D - 1) * (h + 6) + (I - 1)) * (w + 6) + J) * K + lane] = a0;
         }
         PC_PH(1);
         // ---- conv1 ----
@@ -1444,7 +1453,7 @@ __global__ __launch_bounds__(256) void pc_dec_cached_kernel(const PcCachedArgs f
             const float v = (s_part[0][0][lane] + s_part[0][1][lane]) + (s_part[0][2][lane] + s_part[0][3][lane]);
             const float a1 = fmaxf(v + bias_l, 0.f);
             s_in[1][pc_chain_idx(13, co)] = a1;
-            if (wave == 0 && v1) f.c1[(((size_t)(D - 2) * (a.h + 4) + (I - 2)) * (a.w + 4) + (J - 1)) * K + co] = a1;
+            if (wave == 0 && v1) c1[(((size_t)(D - 2) * (h + 4) + (I - 2)) * (w + 4) + (J - 1)) * K + co] = a1;
         }
         PC_PH(2);
         // ---- conv2 + skip ----
@@ -1455,7 +1464,7 @@ __global__ __launch_bounds__(256) void pc_dec_cached_kernel(const PcCachedArgs f
             float a2 = v + bias_l;
             a2 += a0;
             s_in[2][pc_chain_idx(13, co)] = a2;
-            if (wave == 0 && v2) f.c2[(((size_t)(D - 3) * (a.h + 2) + (I - 3)) * (a.w + 2) + (J - 2)) * K + co] = a2;
+            if (wave == 0 && v2) c2[(((size_t)(D - 3) * (h + 2) + (I - 3)) * (w + 2) + (J - 2)) * K + co] = a2;
         }
         PC_PH(3);
         // ---- conv3 -> logits of the symbol at V[D][I][J + 1] ----
@@ -1473,12 +1482,12 @@ __global__ __launch_bounds__(256) void pc_dec_cached_kernel(const PcCachedArgs f
         if (wave == 0) {
             float vnext = pad;
             if (v3) {
-                const long long idx = ((long long)(D - 4) * a.h + (I - 4)) * a.w + (J - 3);
-                const int sym = idx == 0 ? a.first_sym : (L == 6 ? pc_dec_symbol_wave<6>(a, s, logit) : pc_dec_symbol_wave<0>(a, s, logit));
+                const bool first = D == 4 && I == 4 && J == 3;                  // the first symbol is not coded
+                const int sym = first ? first_sym : (L == 6 ? pc_dec_symbol_wave<6>(bits, nbytes, L, a.resolution, s, logit) : pc_dec_symbol_wave<0>(bits, nbytes, L, a.resolution, s, logit));
                 vnext = s_centers[sym];
                 if (lane == 0) {
-                    a.symbols[idx] = sym;
-                    a.vol[((size_t)D * PH + I) * PW + J + 1] = vnext;
+                    out[(long long)(D - 4) * out_cs + (long long)(I - 4) * out_rs + (J - 3)] = sym;
+                    vol[((size_t)D * PH + I) * PW + J + 1] = vnext;
                 }
             }
             if (lane == 0) s_v[12] = vnext;               // V at the next step's position (pad outside the symbol volume)
@@ -1493,11 +1502,55 @@ __global__ __launch_bounds__(256) void pc_dec_cached_kernel(const PcCachedArgs f
         D = Dn; I = In; J = Jn;
         prefetch(D, I, J);
     }
-    if (tid == 0) *f.status = s.error;
+    if (tid == 0) *status = s.error;
 #ifdef PC_DEC_PROF
     if (tid == 0) printf("pc_dec_cached phases (clocks, thread 0): wait+stage %llu | conv0 %llu | conv1 %llu | conv2 %llu | conv3 %llu | decode %llu | tail+prefetch issue %llu\n",
                          ph[0], ph[1], ph[2], ph[3], ph[4], ph[5], ph[6]);
 #endif
+}
+
+__global__ __launch_bounds__(256) void pc_dec_cached_kernel(const PcCachedArgs f) {
+    pc_dec_cached_body(f, f.d.bits, f.d.nbytes, f.d.h, f.d.w, f.d.first_sym, f.d.vol, f.c0, f.c1, f.c2, f.status,
+                       f.d.symbols, (long long)f.d.h * f.d.w, f.d.w);
+}
+
+// ---- tiles: one work-group per tile, all tiles of a volume in one launch -----------------------------------------------------
+// A tile is a (C, th, tw) block of the symbol volume that was coded as a volume of its own (own padding, own stream, first
+// symbol uncoded).  Work-group t decodes tiles[t] with pc_dec_cached_body in slot t of the workspace (padded volume + three
+// caches, laid out for the largest tile; a smaller tile uses a prefix of each part with its own strides) and stores its symbols
+// straight into the full volume.  A work-group reads only what it wrote itself or what an earlier launch wrote (weights,
+// centres, streams, the table, the filled volumes): nothing passes between work-groups, nothing depends on co-residency.
+struct PcTilesArgs {
+    PcCachedArgs f;                   // weights, centres, C, L, resolution only: the rest comes from tiles[blockIdx.x]
+    const unsigned char* bits;        // all streams
+    const ic_pc_tile_t* tiles;        // device copy of the table
+    char* slots; size_t slot_bytes, off_c0, off_c1, off_c2;
+    long long* symbols; int* status;
+    int h, w;                         // the full volume
+};
+
+__global__ __launch_bounds__(256) void pc_dec_tiles_kernel(const PcTilesArgs t) {
+    const ic_pc_tile_t tl = t.tiles[blockIdx.x];
+    char* slot = t.slots + (size_t)blockIdx.x * t.slot_bytes;
+    pc_dec_cached_body(t.f, t.bits + tl.stream_off, tl.stream_bytes, tl.th, tl.tw, tl.first_sym, (float*)slot,
+                       (float*)(slot + t.off_c0), (float*)(slot + t.off_c1), (float*)(slot + t.off_c2), t.status + blockIdx.x,
+                       t.symbols + (long long)tl.y0 * t.w + tl.x0, (long long)t.h * t.w, t.w);
+}
+
+// symbol 0 in every tile's padded volume: grid (ceil(n / 256), ntiles)
+__global__ __launch_bounds__(256) void pc_dec_fill_slots_kernel(char* __restrict__ slots, size_t slot_bytes, long long n,
+                                                                const float* __restrict__ centers) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) ((float*)(slots + (size_t)blockIdx.y * slot_bytes))[i] = centers[0];
+}
+
+// slow path of ic_pc_decode_tiles_f32: a tile decoded into a buffer of its own -> its place in the full volume
+__global__ __launch_bounds__(256) void pc_tile_place_kernel(const long long* __restrict__ src, long long* __restrict__ dst,
+                                                            int C, int th, int tw, int h, int w, int y0, int x0) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long long)C * th * tw) return;
+    const int x = (int)(i % tw), y = (int)((i / tw) % th), c = (int)(i / ((long long)tw * th));
+    dst[((long long)c * h + y0 + y) * w + x0 + x] = src[i];
 }
 
 static size_t pc_dec_align(size_t b) { return (b + 255) & ~(size_t)255; }
@@ -1644,6 +1697,78 @@ extern "C" int ic_pc_decode_f32(const uint8_t* bitstream, long long nbytes, int 
     }
     IC_LAUNCH_CHECK();
     if (hipMemcpyAsync(status, &a.st->error, sizeof(int), hipMemcpyDeviceToDevice, st) != hipSuccess) return IC_ERR_ARG;
+    return IC_OK;
+}
+
+// workspace of ic_pc_decode_tiles_f32: the table, then either one slot per tile (k = 24, flags 0) or what the single-volume
+// paths need for the largest tile plus that tile's symbols
+static size_t pc_dec_tile_slot_bytes(int C, int th, int tw, int k) {
+    return pc_dec_align((size_t)(C + 4) * (th + 8) * (tw + 8) * sizeof(float)) + pc_dec_cache_bytes(C, th, tw, k);
+}
+
+extern "C" size_t ic_pc_decode_tiles_workspace_bytes(int C, int th_max, int tw_max, int ntiles, int k) {
+    if (C <= 0 || th_max <= 0 || tw_max <= 0 || ntiles <= 0 || k <= 0) return 0;
+    const size_t slots = k == 24 ? (size_t)ntiles * pc_dec_tile_slot_bytes(C, th_max, tw_max, k) : 0;
+    const size_t loop = ic_pc_decode_workspace_bytes(C, th_max, tw_max, k) + pc_dec_align((size_t)C * th_max * tw_max * sizeof(int64_t));
+    return pc_dec_align((size_t)ntiles * sizeof(ic_pc_tile_t)) + (slots > loop ? slots : loop);
+}
+
+extern "C" int ic_pc_decode_tiles_f32(const uint8_t* bitstreams, long long total_bytes, const ic_pc_tile_t* tiles_host, int ntiles,
+                                      const float* const* wtab_host, const float* centers, int k, int L, float resolution,
+                                      int64_t* symbols, int* status, int C, int h, int w, void* workspace,
+                                      size_t workspace_bytes, int flags, ic_stream_t stream) {
+    // everything about the descriptors is decided here, on the host, before the first HIP call
+    IC_CHECK_ARG(bitstreams && tiles_host && wtab_host && centers && symbols && status && workspace);
+    IC_CHECK_ARG(total_bytes >= 0 && ntiles > 0 && C > 0 && h > 0 && w > 0 && k > 0 && L > 0);
+    int th_max = 0, tw_max = 0;
+    for (int t = 0; t < ntiles; ++t) {
+        const ic_pc_tile_t& d = tiles_host[t];
+        IC_CHECK_ARG(d.th >= 1 && d.tw >= 1 && d.y0 >= 0 && d.x0 >= 0 && d.th <= h - d.y0 && d.tw <= w - d.x0);
+        IC_CHECK_ARG(d.stream_off >= 0 && d.stream_bytes >= 0 && d.stream_off <= total_bytes && d.stream_bytes <= total_bytes - d.stream_off);
+        IC_CHECK_ARG(d.first_sym >= 0 && d.first_sym < L);
+        th_max = d.th > th_max ? d.th : th_max;
+        tw_max = d.tw > tw_max ? d.tw : tw_max;
+    }
+    if (L > 16) return IC_ERR_UNSUPPORTED;
+    if (workspace_bytes < ic_pc_decode_tiles_workspace_bytes(C, th_max, tw_max, ntiles, k)) return IC_ERR_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    char* p = (char*)workspace;
+    const size_t table_bytes = pc_dec_align((size_t)ntiles * sizeof(ic_pc_tile_t));
+    if (k == 24 && flags == 0) {
+        ic_pc_tile_t* tiles_dev = (ic_pc_tile_t*)p; p += table_bytes;
+        // tiles_host is pageable host memory: the runtime has taken its copy of it when this returns
+        if (hipMemcpyAsync(tiles_dev, tiles_host, (size_t)ntiles * sizeof(ic_pc_tile_t), hipMemcpyHostToDevice, st) != hipSuccess) return IC_ERR_ARG;
+        PcTilesArgs a{};
+        a.f.d.centers = centers; a.f.d.C = C; a.f.d.L = L; a.f.d.resolution = resolution;
+        a.f.w0 = wtab_host[0]; a.f.b0 = wtab_host[1]; a.f.w1 = wtab_host[2]; a.f.b1 = wtab_host[3];
+        a.f.w2 = wtab_host[4]; a.f.b2 = wtab_host[5]; a.f.w3 = wtab_host[6]; a.f.b3 = wtab_host[7];
+        a.bits = bitstreams; a.tiles = tiles_dev; a.slots = p;
+        a.slot_bytes = pc_dec_tile_slot_bytes(C, th_max, tw_max, k);
+        a.off_c0 = pc_dec_align((size_t)(C + 4) * (th_max + 8) * (tw_max + 8) * sizeof(float));
+        a.off_c1 = a.off_c0 + pc_dec_align(pc_dec_cache_floats(C, th_max, tw_max, k, 0) * sizeof(float));
+        a.off_c2 = a.off_c1 + pc_dec_align(pc_dec_cache_floats(C, th_max, tw_max, k, 1) * sizeof(float));
+        a.symbols = (long long*)symbols; a.status = status; a.h = h; a.w = w;
+        const long long nvol = (long long)(C + 4) * (th_max + 8) * (tw_max + 8);
+        hipLaunchKernelGGL(pc_dec_fill_slots_kernel, dim3((unsigned)((nvol + 255) / 256), (unsigned)ntiles), dim3(256), 0, st,
+                           a.slots, a.slot_bytes, nvol, centers);
+        hipLaunchKernelGGL(pc_dec_tiles_kernel, dim3((unsigned)ntiles), dim3(256), 0, st, a);
+        IC_LAUNCH_CHECK();
+        return IC_OK;
+    }
+    // the slow path (other k, or one of the test flags): tile after tile through the single-volume decoder, then into place
+    p += table_bytes;
+    const size_t loop_ws = ic_pc_decode_workspace_bytes(C, th_max, tw_max, k);
+    int64_t* tile_syms = (int64_t*)(p + loop_ws);
+    for (int t = 0; t < ntiles; ++t) {
+        const ic_pc_tile_t& d = tiles_host[t];
+        const int rc = ic_pc_decode_f32(bitstreams + d.stream_off, d.stream_bytes, d.first_sym, wtab_host, centers, k, L, resolution,
+                                        tile_syms, status + t, C, d.th, d.tw, p, loop_ws, flags, stream);
+        if (rc) return rc;
+        const long long n = (long long)C * d.th * d.tw;
+        hipLaunchKernelGGL(pc_tile_place_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const long long*)tile_syms,
+                           (long long*)symbols, C, d.th, d.tw, h, w, d.y0, d.x0);
+    }
+    IC_LAUNCH_CHECK();
     return IC_OK;
 }
 

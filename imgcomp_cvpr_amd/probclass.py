@@ -402,6 +402,51 @@ class PredictionNetwork(object):
             raise ValueError('Cannot decode symbol because total is too large')
         return out.cpu().numpy()
 
+    def encode_tiles(self, symbols, th, tw):
+        """symbols: un-padded (C,h,w) -> [(stream_bytes, first_sym)] for the tiles of codec.tile_grid(h, w, th, tw), in grid order.
+        Every tile is coded as a volume of its own: its stream is encode_stream(symbols[:, y0:y0+th', x0:x0+tw']) byte for byte.
+        Tiles of one shape (at most four: interior, right column, bottom row, corner) are one encode_stream batch, one launch."""
+        from .codec import tile_grid
+        sym = symbols if torch.is_tensor(symbols) else torch.as_tensor(np.ascontiguousarray(symbols))
+        assert sym.dim() == 3, 'Expected CHW symbols'
+        sym = sym.to(self.centers.device).long()
+        grid = tile_grid(int(sym.shape[1]), int(sym.shape[2]), th, tw)
+        by_shape = OrderedDict()
+        for t, (y0, x0, a, b) in enumerate(grid):
+            by_shape.setdefault((a, b), []).append(t)
+        res = [None] * len(grid)
+        for (a, b), members in by_shape.items():
+            batch = torch.stack([sym[:, grid[t][0]:grid[t][0] + a, grid[t][1]:grid[t][1] + b] for t in members])
+            for t, r in zip(members, self.encode_stream(batch)):
+                res[t] = r
+        return res
+
+    def decode_tiles(self, streams, first_syms, symbols_shape, th, tw, flags=0):
+        """The mirror of encode_tiles: all tiles of a volume decoded by ONE launch, one work-group per tile
+        (ic_pc_decode_tiles_f32; other k than 24 or non-zero flags: tile after tile, the slow path).  streams / first_syms in the
+        order of codec.tile_grid(h, w, th, tw); symbols_shape: un-padded (C,h,w).  -> (C,h,w) int64 numpy."""
+        from .codec import tile_grid
+        C, h, w = (int(v) for v in symbols_shape)
+        grid = tile_grid(h, w, th, tw)
+        if len(streams) != len(grid) or len(first_syms) != len(grid):
+            raise ValueError('{} streams and {} first symbols for a grid of {} tiles'.format(len(streams), len(first_syms), len(grid)))
+        dev = self.centers.device
+        offs = np.concatenate([[0], np.cumsum([len(b) for b in streams])]).astype(np.int64)
+        table = _lib.tile_table([(y0, x0, a, b, offs[t], len(streams[t]), first_syms[t]) for t, (y0, x0, a, b) in enumerate(grid)])
+        data = torch.frombuffer(bytearray(b''.join(streams)) or bytearray(1), dtype=torch.uint8).to(dev)
+        out = torch.empty((C, h, w), dtype=torch.int64, device=dev)
+        status = torch.zeros(len(grid), dtype=torch.int32, device=dev)
+        need = lib.ic_pc_decode_tiles_workspace_bytes(C, min(th, h), min(tw, w), len(grid), self.pc._k)
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        centers = self.centers.contiguous().float()
+        check(lib.ic_pc_decode_tiles_f32(ptr(data), int(offs[-1]), table, len(grid), self.pc._tab, ptr(centers), self.pc._k, self.pc.L,
+                                         self.freqs_resolution, ptr(out), ptr(status), C, h, w, ptr(ws), need, int(flags),
+                                         _lib.current_stream(dev)), 'ic_pc_decode_tiles_f32')
+        for t, st in enumerate(status.tolist()):            # (the host waits here: the table and the streams are done with)
+            if st != 0:
+                raise ValueError('Cannot decode symbol because total is too large (tile {} at ({}, {}))'.format(t, grid[t][0], grid[t][1]))
+        return out.cpu().numpy()
+
     def get_pr(self, input_ctx):
         """:param input_ctx: symbols of ONE context, CHW = input_ctx_shape -> (L,) float32."""
         assert tuple(input_ctx.shape) == tuple(self.input_ctx_shape), '{} != {}'.format(

@@ -278,6 +278,26 @@ size_t ic_pc_decode_workspace_bytes(int C, int h, int w, int k);
 int ic_pc_decode_f32(const uint8_t* bitstream, long long nbytes, int first_sym, const float* const* wtab_host,
                      const float* centers, int k, int L, float resolution, int64_t* symbols, int* status,
                      int C, int h, int w, void* workspace, size_t workspace_bytes, int flags, ic_stream_t stream);
+/* Tiles: several streams per volume, all decoded by one launch.  A tile is the block [y0, y0 + th) x [x0, x0 + tw) of the latent
+ * plane with all C channels, coded as a volume of its own: padded by itself, first symbol uncoded, its own stream of
+ * stream_bytes bytes at bitstreams + stream_off (past its end a stream reads as zeros, never as the next tile's bytes).
+ *   tiles_host: HOST array of ntiles descriptors (as wtab_host is a host array); it is read before the call returns.  Every
+ *     descriptor is checked on the host before any device call: th, tw >= 1, y0, x0 >= 0, y0 + th <= h, x0 + tw <= w,
+ *     0 <= stream_off, stream_off + stream_bytes <= total_bytes, 0 <= first_sym < L (IC_ERR_ARG), and the workspace against the
+ *     largest tile (IC_ERR_WORKSPACE).  Tiles need not form a grid; overlapping tiles are the caller's business (not checked).
+ *   symbols: out, device int64 (C,h,w): every tile's symbols at their place;  status: out, device int (ntiles), as above per tile
+ *   k = 24, flags = 0: ONE launch of ntiles work-groups, each the activation-cache decoder of ic_pc_decode_f32 on its own tile;
+ *     work-groups share nothing and do not wait for each other, so ntiles may exceed what the device holds at once.
+ *   other k, or IC_PC_DECODE_PER_LAYER / IC_PC_DECODE_RECOMPUTE: the slow path -- tile after tile through ic_pc_decode_f32
+ *     into a buffer, then copied into place (correctness only).
+ *   workspace: ic_pc_decode_tiles_workspace_bytes(C, largest th, largest tw, ntiles, k) -- ONE SLOT PER TILE (padded volume and
+ *     three activation caches: about 4 MB for a (32, 16, 16) tile, 24 of them for a 512 x 768 image); it grows with ntiles. */
+typedef struct { int y0, x0, th, tw; long long stream_off, stream_bytes; int first_sym, reserved; } ic_pc_tile_t;
+size_t ic_pc_decode_tiles_workspace_bytes(int C, int th_max, int tw_max, int ntiles, int k);
+int ic_pc_decode_tiles_f32(const uint8_t* bitstreams, long long total_bytes, const ic_pc_tile_t* tiles_host, int ntiles,
+                           const float* const* wtab_host, const float* centers, int k, int L, float resolution,
+                           int64_t* symbols, int* status, int C, int h, int w, void* workspace, size_t workspace_bytes,
+                           int flags, ic_stream_t stream);
 /* The encoder side of the real-bpp path on the device: the mirror image of ic_pc_decode_f32.  Codes N symbol volumes in one
  * launch (one work-group per volume) with the 32-bit range coder of arithmetic_coding.py; the stream of each volume is byte
  * for byte arithmetic_coding.encode_sequence(symbols[1:], freqs[1:]) over the tables ic_pc_logits_to_freqs_f32 derives from
