@@ -55,17 +55,42 @@ def edge_tiles_per_wg(n):
 
 
 class PcTile(ctypes.Structure):
-    """ic_pc_tile_t: one tile of ic_pc_decode_tiles_f32 (a host array of these is passed by pointer)."""
+    """ic_pc_tile_t: one tile of ic_pc_decode_tiles_f32 / ic_pc_decode_tiles_batch_f32 (a host array of these is passed by pointer).
+    volume: the tile's entry in the batch call's volume table; 0 for the single-volume call, which does not read it."""
     _fields_ = [('y0', c_int), ('x0', c_int), ('th', c_int), ('tw', c_int), ('stream_off', c_longlong), ('stream_bytes', c_longlong),
-                ('first_sym', c_int), ('reserved', c_int)]
+                ('first_sym', c_int), ('volume', c_int)]
+
+
+class PcVolume(ctypes.Structure):
+    """ic_pc_volume_t: one volume of ic_pc_decode_tiles_batch_f32; the offsets count elements of `symbols` / `q`."""
+    _fields_ = [('h', c_int), ('w', c_int), ('symbols_off', c_longlong), ('q_off', c_longlong)]
 
 
 def tile_table(tiles):
-    """[(y0, x0, th, tw, stream_off, stream_bytes, first_sym)] -> host array of ic_pc_tile_t."""
+    """[(y0, x0, th, tw, stream_off, stream_bytes, first_sym[, volume])] -> host array of ic_pc_tile_t (volume 0 where not given)."""
     arr = (PcTile * len(tiles))()
     for i, t in enumerate(tiles):
-        arr[i] = PcTile(*[int(v) for v in t], 0)
+        t = [int(v) for v in t]
+        arr[i] = PcTile(*(t if len(t) == 8 else t + [0]))
     return arr
+
+
+def volume_table(volumes):
+    """[(h, w, symbols_off, q_off)] -> host array of ic_pc_volume_t."""
+    arr = (PcVolume * len(volumes))()
+    for i, v in enumerate(volumes):
+        arr[i] = PcVolume(*[int(x) for x in v])
+    return arr
+
+
+def packed_volume_table(shapes):
+    """[(C, h, w)] of one C -> (host array of ic_pc_volume_t, [element offset of each volume], total elements): the volumes back
+    to back in one buffer, the same layout for `symbols` and `q`."""
+    offs, total = [], 0
+    for C, h, w in shapes:
+        offs.append(total)
+        total += int(C) * int(h) * int(w)
+    return volume_table([(h, w, o, o) for (C, h, w), o in zip(shapes, offs)]), offs, total
 
 
 # name -> (restype, argtypes); mirrors include/imgcomp_hip.h one-to-one (tests/test_abi.py checks
@@ -115,6 +140,9 @@ PROTOTYPES = {
     'ic_pc_decode_tiles_workspace_bytes': (c_size_t, [c_int] * 5),
     'ic_pc_decode_tiles_f32': (c_int, [c_void_p, c_longlong, c_void_p, c_int, POINTER(c_void_p), c_void_p, c_int, c_int, c_float,
                                        c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_int, c_void_p]),
+    'ic_pc_decode_tiles_batch_workspace_bytes': (c_size_t, [c_int] * 6),
+    'ic_pc_decode_tiles_batch_f32': (c_int, [c_void_p, c_longlong, c_void_p, c_int, c_void_p, c_int, POINTER(c_void_p), c_void_p, c_int,
+                                             c_int, c_float, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_int, c_void_p]),
     'ic_sum_f32': (c_int, [c_void_p, c_longlong, c_void_p, c_void_p, c_void_p]),
     'ic_mean_f32': (c_int, [c_void_p, c_longlong, c_float, c_void_p, c_void_p, c_void_p]),
     'ic_mean_rows_f32': (c_int, [c_void_p, c_int, c_longlong, c_float, c_void_p, c_void_p, c_void_p]),

@@ -3,6 +3,8 @@
     python -m imgcomp_cvpr_amd.codec compress   IN.png  OUT.icf [--ae_config cvpr/low] [--pc_config cvpr/res_shallow] [--weights synthetic|FILE.npz|CKPT]
                                                                 [--tile PIXELS]
     python -m imgcomp_cvpr_amd.codec decompress IN.icf  OUT.png [same options]
+    python -m imgcomp_cvpr_amd.codec compress-dir   IN_DIR OUT_DIR [--tile PIXELS] [--batch N]     every *.png / *.jpg -> OUT_DIR/<stem>.icf
+    python -m imgcomp_cvpr_amd.codec decompress-dir IN_DIR OUT_DIR [--batch N]                     every *.icf -> OUT_DIR/<stem>.png
 
 compress:   pad to a multiple of the subsampling factor (val.add_padding) -> ae.encode -> PredictionNetwork.encode_stream (the
             range coder on the device, ic_pc_encode_f32) -> container.
@@ -39,10 +41,14 @@ at tile borders and one stream termination per tile.  Without --tile every byte 
     ..      n     payload: the tiles' streams back to back, in table order
     ..      4     CRC-32 of every byte before it (u32)
 Every failure of parse / decompress is a ValueError that names the cause; nothing of a refused file reaches the device.
+The -dir commands and Codec.compress_many / decompress_many work on a list of images at once: the same bytes and the same pixels as
+the single-image calls, file by file, but the tiles of all files are coded by one launch each way (ic_pc_decode_tiles_batch_f32: one
+work-group per tile, whichever file it belongs to) and up to four autoencoder passes are in flight.  The file formats are unchanged.
 """
 import argparse
 import io
 import os
+import re
 import struct
 import sys
 import zlib
@@ -70,6 +76,48 @@ def tile_grid(h, w, th, tw):
     if h < 1 or w < 1 or th < 1 or tw < 1:
         raise ValueError('tile grid: plane {} x {} and tile {} x {} must all be at least 1'.format(h, w, th, tw))
     return [(y0, x0, min(th, h - y0), min(tw, w - x0)) for y0 in range(0, h, th) for x0 in range(0, w, tw)]
+
+
+def chunk_tiles(tile_shapes, need, budget):
+    """cut a list of tiles [(th, tw)] into consecutive chunks [(start, stop)] for a decoder whose workspace grows with the number of
+    tiles of a call: need(th_max, tw_max, ntiles) -> bytes for a chunk of ntiles tiles, the largest th x tw.  Greedy, order kept:
+    every tile is in exactly one chunk and need(chunk) <= budget for every chunk; a tile that does not fit alone is a ValueError."""
+    chunks, start = [], 0
+    while start < len(tile_shapes):
+        th_max, tw_max = int(tile_shapes[start][0]), int(tile_shapes[start][1])
+        if need(th_max, tw_max, 1) > budget:
+            raise ValueError('tile {} of {} x {} needs a workspace of {} bytes, the budget is {}'.format(
+                start, th_max, tw_max, need(th_max, tw_max, 1), budget))
+        stop = start + 1
+        while stop < len(tile_shapes):
+            a, b = max(th_max, int(tile_shapes[stop][0])), max(tw_max, int(tile_shapes[stop][1]))
+            if need(a, b, stop + 1 - start) > budget:
+                break
+            th_max, tw_max, stop = a, b, stop + 1
+        chunks.append((start, stop))
+        start = stop
+    return chunks
+
+
+def list_dir_jobs(in_dir, out_dir, command):
+    """the files a -dir command works on: [(input path, output path)] sorted by file name.  compress-dir: every *.png / *.jpg of
+    in_dir -> out_dir/<stem>.icf; decompress-dir: every *.icf -> out_dir/<stem>.png.  Two inputs with one stem (a.png, a.jpg) would
+    write one output: a ValueError, as is a missing directory or one without such files."""
+    exts, out_ext = {'compress-dir': (('.png', '.jpg'), '.icf'), 'decompress-dir': (('.icf',), '.png')}[command]
+    if not os.path.isdir(in_dir):
+        raise ValueError('{}: {!r} is not a directory'.format(command, in_dir))
+    names = sorted(n for n in os.listdir(in_dir)
+                   if os.path.splitext(n)[1].lower() in exts and os.path.isfile(os.path.join(in_dir, n)))
+    if not names:
+        raise ValueError('{}: no {} file in {!r}'.format(command, ' / '.join('*' + e for e in exts), in_dir))
+    jobs, seen = [], {}
+    for n in names:
+        stem = os.path.splitext(n)[0]
+        if stem in seen:
+            raise ValueError('{}: {} and {} would both be written to {}{}'.format(command, seen[stem], n, stem, out_ext))
+        seen[stem] = n
+        jobs.append((os.path.join(in_dir, n), os.path.join(out_dir, stem + out_ext)))
+    return jobs
 
 
 def build_tiled_container(ae_name, pc_name, H, W, C, h, w, L, resolution, fingerprint, th, tw, first_syms, streams):
@@ -336,6 +384,123 @@ class Codec(object):
         t, l = ((-c.H) % f) // 2, ((-c.W) % f) // 2                               # val.add_padding's offsets
         return np.ascontiguousarray(img[t:t + c.H, l:l + c.W, :])
 
+    # -- a list of images per call: the same bytes / pixels as the calls above, file by file --
+
+    IN_FLIGHT = 4
+
+    def _lanes(self, n):
+        """up to IN_FLIGHT (stream, autoencoder) pairs: objects over the SAME device weights with their own workspaces
+        (sharing_weights, as val.validate keeps its fetchers), so that independent batch-1 passes overlap on the device."""
+        import torch
+        lanes = getattr(self, '_lane_cache', None)
+        if lanes is None:
+            lanes = self._lane_cache = []
+        while len(lanes) < min(max(int(n), 1), self.IN_FLIGHT):
+            ae = self.ae.sharing_weights()
+            ae.plan_flags = self.ae.plan_flags
+            lanes.append((torch.cuda.Stream(device=self.device), ae))
+        return lanes[:min(max(int(n), 1), self.IN_FLIGHT)]
+
+    def _in_flight(self, items, fn):
+        """fn(ae, item) -> device tensor for every item, item i on lane i % IN_FLIGHT; the current stream waits for all lanes."""
+        import torch
+        cur = torch.cuda.current_stream(self.device)
+        lanes = self._lanes(len(items))
+        for st, _ in lanes:
+            st.wait_stream(cur)
+        outs = []
+        for i, item in enumerate(items):
+            st, ae = lanes[i % len(lanes)]
+            with torch.cuda.stream(st):
+                out = fn(ae, item)
+            out.record_stream(cur)                        # allocated on the lane's stream, consumed on the caller's
+            outs.append(out)
+        for st, _ in lanes:
+            cur.wait_stream(st)
+        return outs
+
+    def compress_many(self, images):
+        """[HWC uint8] of any mix of shapes -> [container bytes], element i byte for byte compress(images[i]).  Every image goes
+        through the encoder on its own (batch 1, the plan flags of compress: the kernel form of a layer depends on the batch size,
+        the bytes must not), up to IN_FLIGHT at a time; then the tiles of all images are coded by one launch per tile shape."""
+        import torch
+        from . import val
+        if not self.device_encode:
+            return [self.compress(img) for img in images]
+        xs, sizes = [], []
+        for i, img in enumerate(images):
+            img = np.asarray(img)
+            if img.ndim != 3 or img.shape[2] not in (3, 4) or img.dtype != np.uint8:
+                raise ValueError('image {}: expected an HWC uint8 image with 3 channels, got {} {}'.format(i, img.shape, img.dtype))
+            img = img[:, :, :3]
+            sizes.append((int(img.shape[0]), int(img.shape[1])))
+            padded, _ = val.add_padding(img, self.factor)
+            xs.append(torch.as_tensor(np.ascontiguousarray(np.transpose(padded, (2, 0, 1)))[None]).to(self.device).float())
+        syms = self._in_flight(xs, lambda ae, x: ae.encode(x, is_training=False).symbols[0])
+        out = [None] * len(syms)
+        if self.tile is not None:
+            th, tw = self.tile
+            for i, coded in enumerate(self.pred.encode_tiles_batch(syms, th, tw)):
+                C, h, w = (int(v) for v in syms[i].shape)
+                out[i] = build_tiled_container(self.ae_name, self.pc_name, sizes[i][0], sizes[i][1], C, h, w, self.L,
+                                               self.pred.freqs_resolution, self.fingerprint, th, tw,
+                                               [f for _, f in coded], [b for b, _ in coded])
+            return out
+        by_shape = {}
+        for i, sym in enumerate(syms):
+            by_shape.setdefault(tuple(sym.shape), []).append(i)
+        for shape, members in by_shape.items():          # format 1: volumes of one shape are one encode_stream batch
+            C, h, w = (int(v) for v in shape)
+            for i, (payload, first_sym) in zip(members, self.pred.encode_stream(torch.stack([syms[i] for i in members]))):
+                out[i] = build_container(self.ae_name, self.pc_name, sizes[i][0], sizes[i][1], C, h, w, self.L, first_sym,
+                                         self.pred.freqs_resolution, self.fingerprint, payload)
+        return out
+
+    def _crop(self, x_out_chw, c):
+        img = np.transpose(x_out_chw.cpu().numpy(), (1, 2, 0))
+        f = self.factor
+        t, l = ((-c.H) % f) // 2, ((-c.W) % f) // 2                               # val.add_padding's offsets
+        return np.ascontiguousarray(img[t:t + c.H, l:l + c.W, :])
+
+    def decompress_many(self, datas, max_workspace_bytes=1 << 31):
+        """[container bytes] of either format, any mix of shapes -> [HWC uint8], element i equal to decompress(datas[i]).
+        Every file is parsed and checked first; the first refusal raises its ValueError with the index of the file in front and
+        nothing has reached the device.  The format-2 files of the most frequent tile extent are decoded together
+        (decode_tiles_batch: the tiles of all of them in one launch per workspace chunk, the centres q staying on the device) and
+        go through the decoder up to IN_FLIGHT at a time; format-1 files and other tile extents take the single-file path."""
+        import torch
+        heads = []
+        for i, data in enumerate(datas):
+            try:
+                c = parse_container(data)
+                self.check_container(c)
+            except ValueError as e:
+                raise ValueError('file {}: {}'.format(i, e))
+            heads.append(c)
+        extents = [(c.th, c.tw) for c in heads if isinstance(c, TiledContainer)]
+        major = max(sorted(set(extents)), key=extents.count) if extents else None
+        together = [i for i, c in enumerate(heads) if isinstance(c, TiledContainer) and (c.th, c.tw) == major]
+        out = [None] * len(datas)
+        if together:
+            try:
+                qs = self.pred.decode_tiles_batch([(heads[i].streams, heads[i].first_syms, (heads[i].C, heads[i].h, heads[i].w))
+                                                   for i in together], major[0], major[1], want='q',
+                                                  max_workspace_bytes=max_workspace_bytes)
+            except ValueError as e:
+                m = re.search(r'volume (\d+)', str(e))
+                where = 'file {}: '.format(together[int(m.group(1))]) if m else ''
+                raise ValueError('{}decoder status is not 0: {}'.format(where, e))
+            imgs = self._in_flight(qs, lambda ae, q: ae.decode(q[None], is_training=False).to(torch.uint8)[0])    # tf.cast truncates (val.py)
+            for i, x in zip(together, imgs):
+                out[i] = self._crop(x, heads[i])
+        for i, data in enumerate(datas):
+            if out[i] is None:
+                try:
+                    out[i] = self.decompress(data)
+                except ValueError as e:
+                    raise ValueError('file {}: {}'.format(i, e))
+        return out
+
     def compress_file(self, image_path, out_path):
         from PIL import Image
         img = np.asarray(Image.open(image_path).convert('RGB'), dtype=np.uint8)     # as val.load_image_chw reads it
@@ -364,9 +529,81 @@ def _resolve_config(arg, tree, env):
     return p
 
 
+def _compress_line(path, data, pixels):
+    c = parse_container(data)
+    payload = len(c.payload)
+    tiles = ', {} tiles'.format(len(c.streams)) if isinstance(c, TiledContainer) else ''
+    return '{}: {} bytes, payload {} bytes = {:.4f} bpp, file {:.4f} bpp{}'.format(
+        path, len(data), payload, 8.0 * payload / pixels, 8.0 * len(data) / pixels, tiles)
+
+
+def _decompress_line(path, img, size):
+    return '{}: {} x {} from {} bytes = {:.4f} bpp'.format(path, img.shape[0], img.shape[1], size, 8.0 * size / (img.shape[0] * img.shape[1]))
+
+
+def check_dir_args(flags, factor):
+    """everything about a -dir command line that can be refused without a device -> (jobs, tile or None)"""
+    if flags.batch < 1:
+        raise ValueError('--batch {} is not at least 1'.format(flags.batch))
+    tile = None
+    if flags.tile is not None:
+        if flags.command != 'compress-dir':
+            raise ValueError('--tile belongs to compress / compress-dir: a file says by itself how it is tiled')
+        if flags.tile <= 0 or flags.tile % factor != 0:
+            raise ValueError('--tile {} is not a positive multiple of the subsampling factor {}'.format(flags.tile, factor))
+        tile = (flags.tile // factor, flags.tile // factor)
+    jobs = list_dir_jobs(flags.input, flags.output, flags.command)
+    if os.path.exists(flags.output) and not os.path.isdir(flags.output):
+        raise ValueError('{}: output {!r} exists and is not a directory'.format(flags.command, flags.output))
+    return jobs, tile
+
+
+def _main_dir(flags, ae_config, pc_config):
+    """compress-dir / decompress-dir: one model build, --batch files per compress_many / decompress_many call"""
+    from PIL import Image
+    from . import autoencoder, val, weights as _weights
+    jobs, tile = check_dir_args(flags, int(autoencoder.get_network_cls(ae_config).get_subsampling_factor()))
+    if flags.weights == 'synthetic':
+        wts = _weights.synthetic_weights(ae_config, pc_config, seed=flags.synthetic_seed)
+    else:
+        wts = val.load_weights_for_job(None, flags.weights, ae_config, pc_config)
+    codec = Codec(ae_config, pc_config, wts, flags.device, tile=tile)
+    os.makedirs(flags.output, exist_ok=True)
+    total_in = total_out = total_pixels = 0
+    for start in range(0, len(jobs), flags.batch):
+        part = jobs[start:start + flags.batch]
+        if flags.command == 'compress-dir':
+            imgs = [np.asarray(Image.open(src).convert('RGB'), dtype=np.uint8) for src, _ in part]     # as compress_file reads them
+            for (src, dst), img, data in zip(part, imgs, codec.compress_many(imgs)):
+                with open(dst, 'wb') as f:
+                    f.write(data)
+                print(_compress_line(dst, data, img.shape[0] * img.shape[1]))
+                total_in, total_out, total_pixels = total_in + os.path.getsize(src), total_out + len(data), total_pixels + img.shape[0] * img.shape[1]
+        else:
+            datas = []
+            for src, _ in part:
+                with open(src, 'rb') as f:
+                    datas.append(f.read())
+            try:
+                imgs = codec.decompress_many(datas)
+            except ValueError as e:
+                m = re.match(r'file (\d+): ', str(e))
+                raise ValueError('{}: {}'.format(part[int(m.group(1))][0], str(e)[m.end():]) if m else str(e))
+            for (src, dst), data, img in zip(part, datas, imgs):
+                Image.fromarray(img).save(dst)
+                print(_decompress_line(dst, img, len(data)))
+                total_in, total_out, total_pixels = total_in + len(data), total_out + os.path.getsize(dst), total_pixels + img.shape[0] * img.shape[1]
+    if flags.command == 'compress-dir':
+        print('total: {} files, {} pixels, {} bytes = {:.4f} bpp'.format(len(jobs), total_pixels, total_out, 8.0 * total_out / total_pixels))
+    else:
+        print('total: {} files, {} pixels from {} bytes = {:.4f} bpp'.format(len(jobs), total_pixels, total_in, 8.0 * total_in / total_pixels))
+    return 0
+
+
 def main(argv=None):
-    p = argparse.ArgumentParser(description='compress an image to a codec file, or a codec file back to an image')
-    p.add_argument('command', choices=['compress', 'decompress'])
+    p = argparse.ArgumentParser(description='compress an image to a codec file, or a codec file back to an image; '
+                                            'the -dir commands do so for every file of a directory, --batch files per call')
+    p.add_argument('command', choices=['compress', 'decompress', 'compress-dir', 'decompress-dir'])
     p.add_argument('input')
     p.add_argument('output')
     p.add_argument('--ae_config', default='cvpr/low', help='a config file, or a name below $CONFIG_BASE_AE / the package\'s ae_configs')
@@ -378,11 +615,14 @@ def main(argv=None):
     p.add_argument('--tile', type=int, default=None, metavar='PIXELS',
                    help='compress: square tiles of this many image pixels (a positive multiple of the subsampling factor), one stream '
                         'per tile, decoded concurrently (format 2); default: one stream (format 1)')
+    p.add_argument('--batch', type=int, default=8, metavar='N', help='compress-dir / decompress-dir: files per call (default 8)')
     flags = p.parse_args(argv)
     from . import config_parser, val, weights as _weights
     try:
         ae_config, _ = config_parser.parse(_resolve_config(flags.ae_config, 'ae_configs', 'CONFIG_BASE_AE'))
         pc_config, _ = config_parser.parse(_resolve_config(flags.pc_config, 'pc_configs', 'CONFIG_BASE_PC'))
+        if flags.command.endswith('-dir'):
+            return _main_dir(flags, ae_config, pc_config)
         if flags.weights == 'synthetic':
             wts = _weights.synthetic_weights(ae_config, pc_config, seed=flags.synthetic_seed)
         else:
@@ -394,16 +634,10 @@ def main(argv=None):
                     raise ValueError('--tile {} is not a positive multiple of the subsampling factor {}'.format(flags.tile, codec.factor))
                 codec.tile = (flags.tile // codec.factor, flags.tile // codec.factor)
             data, pixels = codec.compress_file(flags.input, flags.output)
-            c = parse_container(data)
-            payload = len(c.payload)
-            tiles = ', {} tiles'.format(len(c.streams)) if isinstance(c, TiledContainer) else ''
-            print('{}: {} bytes, payload {} bytes = {:.4f} bpp, file {:.4f} bpp{}'.format(
-                flags.output, len(data), payload, 8.0 * payload / pixels, 8.0 * len(data) / pixels, tiles))
+            print(_compress_line(flags.output, data, pixels))
         else:
             img = codec.decompress_file(flags.input, flags.output)
-            size = os.path.getsize(flags.input)
-            print('{}: {} x {} from {} bytes = {:.4f} bpp'.format(flags.output, img.shape[0], img.shape[1], size,
-                                                                 8.0 * size / (img.shape[0] * img.shape[1])))
+            print(_decompress_line(flags.output, img, os.path.getsize(flags.input)))
     except ValueError as e:
         print('error: {}'.format(e), file=sys.stderr)
         return 2

@@ -1344,6 +1344,9 @@ __device__ __forceinline__ int pc_chain_idx(int t, int ci) { return 8 * ((ci >> 
 // take them from a table without a private copy of the struct (which would live in scratch).  Symbol (c, y, x) is stored at
 // out[c * out_cs + y * out_rs + x]: out_cs = h * w, out_rs = w for a whole volume; the strides of the full volume, and out
 // moved to the tile's corner, for a tile.
+// SYMS = false (ic_pc_decode_tiles_batch_f32 with symbols == NULL): nothing is stored through out; the padded volume still
+// receives every symbol's centre, which is what that caller copies out.
+template <bool SYMS = true>
 __device__ __forceinline__ void pc_dec_cached_body(const PcCachedArgs& f, const unsigned char* bits, long long nbytes, int h, int w, int first_sym,
                                                    float* vol, float* c0, float* c1, float* c2, int* status,
                                                    long long* __restrict__ out, long long out_cs, int out_rs) {
@@ -1486,7 +1489,7 @@ __device__ __forceinline__ void pc_dec_cached_body(const PcCachedArgs& f, const 
                 const int sym = first ? first_sym : (L == 6 ? pc_dec_symbol_wave<6>(bits, nbytes, L, a.resolution, s, logit) : pc_dec_symbol_wave<0>(bits, nbytes, L, a.resolution, s, logit));
                 vnext = s_centers[sym];
                 if (lane == 0) {
-                    out[(long long)(D - 4) * out_cs + (long long)(I - 4) * out_rs + (J - 3)] = sym;
+                    if (SYMS) out[(long long)(D - 4) * out_cs + (long long)(I - 4) * out_rs + (J - 3)] = sym;
                     vol[((size_t)D * PH + I) * PW + J + 1] = vnext;
                 }
             }
@@ -1551,6 +1554,53 @@ __global__ __launch_bounds__(256) void pc_tile_place_kernel(const long long* __r
     if (i >= (long long)C * th * tw) return;
     const int x = (int)(i % tw), y = (int)((i / tw) % th), c = (int)(i / ((long long)tw * th));
     dst[((long long)c * h + y0 + y) * w + x0 + x] = src[i];
+}
+
+// ---- tiles of several volumes in one launch (ic_pc_decode_tiles_batch_f32) ---------------------------------------------------
+// As pc_dec_tiles_kernel, with the volume of a tile taken from a second table: own (h, w), own place in `symbols` and `q`.
+// q = centers[symbols] is what the decoder's padded volume holds at the end of the sweep (every decoded symbol's centre was
+// stored there for the context gathers), so after the body the work-group copies its tile's interior out: all 256 threads,
+// consecutive x on consecutive lanes, once per tile -- nothing is added to the per-symbol path of pc_dec_cached_body.
+struct PcTilesBatchArgs {
+    PcCachedArgs f;                   // weights, centres, C, L, resolution only
+    const unsigned char* bits;
+    const ic_pc_tile_t* tiles;        // device copies of the two tables
+    const ic_pc_volume_t* volumes;
+    char* slots; size_t slot_bytes, off_c0, off_c1, off_c2;
+    long long* symbols; float* q; int* status;
+};
+
+template <bool SYMS>
+__global__ __launch_bounds__(256) void pc_dec_tiles_batch_kernel(const PcTilesBatchArgs t) {
+    const ic_pc_tile_t tl = t.tiles[blockIdx.x];
+    const ic_pc_volume_t v = t.volumes[tl.volume];
+    char* slot = t.slots + (size_t)blockIdx.x * t.slot_bytes;
+    const long long corner = (long long)tl.y0 * v.w + tl.x0, plane = (long long)v.h * v.w;
+    pc_dec_cached_body<SYMS>(t.f, t.bits + tl.stream_off, tl.stream_bytes, tl.th, tl.tw, tl.first_sym, (float*)slot,
+                             (float*)(slot + t.off_c0), (float*)(slot + t.off_c1), (float*)(slot + t.off_c2), t.status + blockIdx.x,
+                             SYMS ? t.symbols + v.symbols_off + corner : nullptr, plane, v.w);
+    if (t.q == nullptr) return;
+    __syncthreads();                  // the volume's last stores (lane 0 of wave 0) are visible to the whole work-group
+    const float* vol = (const float*)slot;
+    float* q = t.q + v.q_off + corner;
+    const int PH = tl.th + 8, PW = tl.tw + 8, n = t.f.d.C * tl.th * tl.tw;
+    for (int i = threadIdx.x; i < n; i += 256) {
+        const int x = i % tl.tw, y = (i / tl.tw) % tl.th, c = i / (tl.tw * tl.th);
+        q[(long long)c * plane + (long long)y * v.w + x] = vol[((size_t)(c + 4) * PH + y + 4) * PW + x + 4];
+    }
+}
+
+// slow path of ic_pc_decode_tiles_batch_f32: a tile decoded into a buffer of its own -> its place in its volume, as symbols
+// and / or centres
+__global__ __launch_bounds__(256) void pc_tile_place_batch_kernel(const long long* __restrict__ src, long long* __restrict__ dst,
+                                                                  float* __restrict__ q, const float* __restrict__ centers,
+                                                                  int C, int th, int tw, int h, int w, int y0, int x0) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long long)C * th * tw) return;
+    const int x = (int)(i % tw), y = (int)((i / tw) % th), c = (int)(i / ((long long)tw * th));
+    const long long o = ((long long)c * h + y0 + y) * w + x0 + x, sym = src[i];
+    if (dst) dst[o] = sym;
+    if (q) q[o] = centers[sym];
 }
 
 static size_t pc_dec_align(size_t b) { return (b + 255) & ~(size_t)255; }
@@ -1767,6 +1817,85 @@ extern "C" int ic_pc_decode_tiles_f32(const uint8_t* bitstreams, long long total
         const long long n = (long long)C * d.th * d.tw;
         hipLaunchKernelGGL(pc_tile_place_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const long long*)tile_syms,
                            (long long*)symbols, C, d.th, d.tw, h, w, d.y0, d.x0);
+    }
+    IC_LAUNCH_CHECK();
+    return IC_OK;
+}
+
+// workspace of ic_pc_decode_tiles_batch_f32: the tile table, the volume table, then as ic_pc_decode_tiles_f32
+extern "C" size_t ic_pc_decode_tiles_batch_workspace_bytes(int C, int th_max, int tw_max, int ntiles, int nvolumes, int k) {
+    if (nvolumes <= 0) return 0;
+    const size_t base = ic_pc_decode_tiles_workspace_bytes(C, th_max, tw_max, ntiles, k);
+    return base ? base + pc_dec_align((size_t)nvolumes * sizeof(ic_pc_volume_t)) : 0;
+}
+
+extern "C" int ic_pc_decode_tiles_batch_f32(const uint8_t* bitstreams, long long total_bytes, const ic_pc_tile_t* tiles_host, int ntiles,
+                                            const ic_pc_volume_t* volumes_host, int nvolumes, const float* const* wtab_host,
+                                            const float* centers, int k, int L, float resolution, int64_t* symbols, float* q,
+                                            int* status, int C, void* workspace, size_t workspace_bytes, int flags,
+                                            ic_stream_t stream) {
+    // everything about the two tables is decided here, on the host, before the first HIP call
+    IC_CHECK_ARG(bitstreams && tiles_host && volumes_host && wtab_host && centers && (symbols || q) && status && workspace);
+    IC_CHECK_ARG(total_bytes >= 0 && ntiles > 0 && nvolumes > 0 && C > 0 && k > 0 && L > 0);
+    for (int n = 0; n < nvolumes; ++n) {
+        const ic_pc_volume_t& v = volumes_host[n];
+        IC_CHECK_ARG(v.h >= 1 && v.w >= 1 && v.symbols_off >= 0 && v.q_off >= 0);
+    }
+    int th_max = 0, tw_max = 0;
+    for (int t = 0; t < ntiles; ++t) {
+        const ic_pc_tile_t& d = tiles_host[t];
+        IC_CHECK_ARG(d.volume >= 0 && d.volume < nvolumes);
+        const ic_pc_volume_t& v = volumes_host[d.volume];
+        IC_CHECK_ARG(d.th >= 1 && d.tw >= 1 && d.y0 >= 0 && d.x0 >= 0 && d.y0 <= v.h && d.x0 <= v.w && d.th <= v.h - d.y0 && d.tw <= v.w - d.x0);
+        IC_CHECK_ARG(d.stream_off >= 0 && d.stream_bytes >= 0 && d.stream_off <= total_bytes && d.stream_bytes <= total_bytes - d.stream_off);
+        IC_CHECK_ARG(d.first_sym >= 0 && d.first_sym < L);
+        th_max = d.th > th_max ? d.th : th_max;
+        tw_max = d.tw > tw_max ? d.tw : tw_max;
+    }
+    if (L > 16) return IC_ERR_UNSUPPORTED;
+    if (workspace_bytes < ic_pc_decode_tiles_batch_workspace_bytes(C, th_max, tw_max, ntiles, nvolumes, k)) return IC_ERR_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    char* p = (char*)workspace;
+    const size_t table_bytes = pc_dec_align((size_t)ntiles * sizeof(ic_pc_tile_t));
+    const size_t vtable_bytes = pc_dec_align((size_t)nvolumes * sizeof(ic_pc_volume_t));
+    if (k == 24 && flags == 0) {
+        ic_pc_tile_t* tiles_dev = (ic_pc_tile_t*)p; p += table_bytes;
+        ic_pc_volume_t* volumes_dev = (ic_pc_volume_t*)p; p += vtable_bytes;
+        // both tables are pageable host memory: the runtime has taken its copy of them when these return
+        if (hipMemcpyAsync(tiles_dev, tiles_host, (size_t)ntiles * sizeof(ic_pc_tile_t), hipMemcpyHostToDevice, st) != hipSuccess) return IC_ERR_ARG;
+        if (hipMemcpyAsync(volumes_dev, volumes_host, (size_t)nvolumes * sizeof(ic_pc_volume_t), hipMemcpyHostToDevice, st) != hipSuccess) return IC_ERR_ARG;
+        PcTilesBatchArgs a{};
+        a.f.d.centers = centers; a.f.d.C = C; a.f.d.L = L; a.f.d.resolution = resolution;
+        a.f.w0 = wtab_host[0]; a.f.b0 = wtab_host[1]; a.f.w1 = wtab_host[2]; a.f.b1 = wtab_host[3];
+        a.f.w2 = wtab_host[4]; a.f.b2 = wtab_host[5]; a.f.w3 = wtab_host[6]; a.f.b3 = wtab_host[7];
+        a.bits = bitstreams; a.tiles = tiles_dev; a.volumes = volumes_dev; a.slots = p;
+        a.slot_bytes = pc_dec_tile_slot_bytes(C, th_max, tw_max, k);
+        a.off_c0 = pc_dec_align((size_t)(C + 4) * (th_max + 8) * (tw_max + 8) * sizeof(float));
+        a.off_c1 = a.off_c0 + pc_dec_align(pc_dec_cache_floats(C, th_max, tw_max, k, 0) * sizeof(float));
+        a.off_c2 = a.off_c1 + pc_dec_align(pc_dec_cache_floats(C, th_max, tw_max, k, 1) * sizeof(float));
+        a.symbols = (long long*)symbols; a.q = q; a.status = status;
+        const long long nvol = (long long)(C + 4) * (th_max + 8) * (tw_max + 8);
+        hipLaunchKernelGGL(pc_dec_fill_slots_kernel, dim3((unsigned)((nvol + 255) / 256), (unsigned)ntiles), dim3(256), 0, st,
+                           a.slots, a.slot_bytes, nvol, centers);
+        if (symbols) hipLaunchKernelGGL(pc_dec_tiles_batch_kernel<true>, dim3((unsigned)ntiles), dim3(256), 0, st, a);
+        else hipLaunchKernelGGL(pc_dec_tiles_batch_kernel<false>, dim3((unsigned)ntiles), dim3(256), 0, st, a);
+        IC_LAUNCH_CHECK();
+        return IC_OK;
+    }
+    // the slow path (other k, or one of the test flags): tile after tile through the single-volume decoder, then into place
+    p += table_bytes + vtable_bytes;
+    const size_t loop_ws = ic_pc_decode_workspace_bytes(C, th_max, tw_max, k);
+    int64_t* tile_syms = (int64_t*)(p + loop_ws);
+    for (int t = 0; t < ntiles; ++t) {
+        const ic_pc_tile_t& d = tiles_host[t];
+        const ic_pc_volume_t& v = volumes_host[d.volume];
+        const int rc = ic_pc_decode_f32(bitstreams + d.stream_off, d.stream_bytes, d.first_sym, wtab_host, centers, k, L, resolution,
+                                        tile_syms, status + t, C, d.th, d.tw, p, loop_ws, flags, stream);
+        if (rc) return rc;
+        const long long n = (long long)C * d.th * d.tw;
+        hipLaunchKernelGGL(pc_tile_place_batch_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const long long*)tile_syms,
+                           symbols ? (long long*)symbols + v.symbols_off : nullptr, q ? q + v.q_off : nullptr, centers,
+                           C, d.th, d.tw, v.h, v.w, d.y0, d.x0);
     }
     IC_LAUNCH_CHECK();
     return IC_OK;

@@ -9,6 +9,7 @@ All positions are evaluated in parallel by libimgcomp_hip.so (csrc/probclass.hip
 padded on load, never materialised.  Weights come from ``load_weights(dict)`` in the reference's
 variable names/layouts (unmasked conv3d filters [2,3,3,cin,cout] + biases).
 """
+import ctypes
 import itertools
 from collections import OrderedDict
 
@@ -446,6 +447,89 @@ class PredictionNetwork(object):
             if st != 0:
                 raise ValueError('Cannot decode symbol because total is too large (tile {} at ({}, {}))'.format(t, grid[t][0], grid[t][1]))
         return out.cpu().numpy()
+
+    def encode_tiles_batch(self, volumes, th, tw):
+        """encode_tiles for a list of un-padded (C,h,w) symbol volumes of any mix of (h, w): -> per volume the list encode_tiles
+        gives for it, byte for byte.  The tiles of ALL volumes are grouped by tile shape -- for a folder of equal-sized images the
+        same four shapes as for one -- and each group is one encode_stream batch, one ic_pc_encode_f32 launch."""
+        from .codec import tile_grid
+        dev = self.centers.device
+        syms, grids = [], []
+        for v in volumes:
+            sym = v if torch.is_tensor(v) else torch.as_tensor(np.ascontiguousarray(v))
+            assert sym.dim() == 3, 'Expected CHW symbols'
+            syms.append(sym.to(dev).long())
+            grids.append(tile_grid(int(sym.shape[1]), int(sym.shape[2]), th, tw))
+        by_shape = OrderedDict()
+        for n, grid in enumerate(grids):
+            for t, (y0, x0, a, b) in enumerate(grid):
+                by_shape.setdefault((int(syms[n].shape[0]), a, b), []).append((n, t))
+        res = [[None] * len(grid) for grid in grids]
+        for (_, a, b), members in by_shape.items():
+            batch = torch.stack([syms[n][:, grids[n][t][0]:grids[n][t][0] + a, grids[n][t][1]:grids[n][t][1] + b] for n, t in members])
+            for (n, t), r in zip(members, self.encode_stream(batch)):
+                res[n][t] = r
+        return res
+
+    def decode_tiles_batch(self, volumes, th, tw, want='q', max_workspace_bytes=1 << 31, flags=0):
+        """The mirror of encode_tiles_batch: the tiles of ALL volumes decoded by one launch per chunk (ic_pc_decode_tiles_batch_f32,
+        one work-group per tile).  volumes: [(streams, first_syms, (C,h,w))], each as decode_tiles takes them, one C throughout.
+        want: 'q' -> per volume the (C,h,w) float32 DEVICE tensor centers[symbols] (what ae.decode consumes: the symbols never
+        visit the host), 'symbols' -> the (C,h,w) int64 device tensor, 'both' -> (q, symbols) pairs.
+        The workspace is one slot per tile, so the tile list is cut into chunks whose workspace stays within max_workspace_bytes
+        (chunk_tiles; a cut may fall inside a volume); the chunks run one after the other on the current stream."""
+        from .codec import tile_grid, chunk_tiles
+        if want not in ('q', 'symbols', 'both'):
+            raise ValueError("want is 'q', 'symbols' or 'both', got {!r}".format(want))
+        if not volumes:
+            return []
+        dev = self.centers.device
+        shapes, tiles, where, blobs, pos = [], [], [], [], 0
+        for n, (streams, first_syms, shape) in enumerate(volumes):
+            C, h, w = (int(v) for v in shape)
+            if C != int(volumes[0][2][0]):
+                raise ValueError('volume {} has {} channels, volume 0 has {}'.format(n, C, int(volumes[0][2][0])))
+            grid = tile_grid(h, w, th, tw)
+            if len(streams) != len(grid) or len(first_syms) != len(grid):
+                raise ValueError('volume {}: {} streams and {} first symbols for a grid of {} tiles'.format(
+                    n, len(streams), len(first_syms), len(grid)))
+            shapes.append((C, h, w))
+            for t, (y0, x0, a, b) in enumerate(grid):
+                tiles.append((y0, x0, a, b, pos, len(streams[t]), first_syms[t], n))
+                where.append((n, t, y0, x0))
+                blobs.append(bytes(streams[t]))
+                pos += len(streams[t])
+        C, k = shapes[0][0], self.pc._k
+        vtable, offs, total = _lib.packed_volume_table(shapes)
+
+        def need(th_max, tw_max, ntiles):
+            return int(lib.ic_pc_decode_tiles_batch_workspace_bytes(C, th_max, tw_max, ntiles, len(shapes), k))
+
+        chunks = chunk_tiles([(a, b) for _, _, a, b, _, _, _, _ in tiles], need, int(max_workspace_bytes))
+        table = _lib.tile_table(tiles)
+        data = torch.frombuffer(bytearray(b''.join(blobs)) or bytearray(1), dtype=torch.uint8).to(dev)
+        q = torch.empty(total, dtype=torch.float32, device=dev) if want in ('q', 'both') else None
+        sym = torch.empty(total, dtype=torch.int64, device=dev) if want in ('symbols', 'both') else None
+        status = torch.zeros(len(tiles), dtype=torch.int32, device=dev)
+        ws_bytes = max(need(max(tiles[i][2] for i in range(a, b)), max(tiles[i][3] for i in range(a, b)), b - a) for a, b in chunks)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        centers = self.centers.contiguous().float()
+        step = ctypes.sizeof(_lib.PcTile)
+        for a, b in chunks:
+            check(lib.ic_pc_decode_tiles_batch_f32(ptr(data), pos, ctypes.c_void_p(ctypes.addressof(table) + a * step), b - a,
+                                                   vtable, len(shapes), self.pc._tab, ptr(centers), k, self.pc.L,
+                                                   self.freqs_resolution, ptr(sym), ptr(q), ptr(status[a:b]), C, ptr(ws), ws_bytes,
+                                                   int(flags), _lib.current_stream(dev)), 'ic_pc_decode_tiles_batch_f32')
+        for i, st in enumerate(status.tolist()):            # (the host waits here: the tables and the streams are done with)
+            if st != 0:
+                n, t, y0, x0 = where[i]
+                raise ValueError('Cannot decode symbol because total is too large (volume {}, tile {} at ({}, {}))'.format(n, t, y0, x0))
+        cut = lambda buf: [buf[o:o + c * h * w].view(c, h, w) for (c, h, w), o in zip(shapes, offs)]
+        if want == 'q':
+            return cut(q)
+        if want == 'symbols':
+            return cut(sym)
+        return list(zip(cut(q), cut(sym)))
 
     def get_pr(self, input_ctx):
         """:param input_ctx: symbols of ONE context, CHW = input_ctx_shape -> (L,) float32."""

@@ -292,12 +292,29 @@ int ic_pc_decode_f32(const uint8_t* bitstream, long long nbytes, int first_sym, 
  *     into a buffer, then copied into place (correctness only).
  *   workspace: ic_pc_decode_tiles_workspace_bytes(C, largest th, largest tw, ntiles, k) -- ONE SLOT PER TILE (padded volume and
  *     three activation caches: about 4 MB for a (32, 16, 16) tile, 24 of them for a 512 x 768 image); it grows with ntiles. */
-typedef struct { int y0, x0, th, tw; long long stream_off, stream_bytes; int first_sym, reserved; } ic_pc_tile_t;
+typedef struct { int y0, x0, th, tw; long long stream_off, stream_bytes; int first_sym, volume; } ic_pc_tile_t;
 size_t ic_pc_decode_tiles_workspace_bytes(int C, int th_max, int tw_max, int ntiles, int k);
 int ic_pc_decode_tiles_f32(const uint8_t* bitstreams, long long total_bytes, const ic_pc_tile_t* tiles_host, int ntiles,
                            const float* const* wtab_host, const float* centers, int k, int L, float resolution,
                            int64_t* symbols, int* status, int C, int h, int w, void* workspace, size_t workspace_bytes,
                            int flags, ic_stream_t stream);
+/* Tiles of SEVERAL volumes in one launch (a folder of files): as above, with a table of volumes beside the table of tiles.
+ *   volumes_host: HOST array of nvolumes descriptors, read before the call returns.  All volumes have C channels; volume n is
+ *     (C, h, w) int64 at symbols + symbols_off and (C, h, w) float32 at q + q_off (offsets in elements, the caller lays the
+ *     volumes out without overlap).  A tile names its volume in the descriptor's last field (`volume`; 0 for every caller of
+ *     ic_pc_decode_tiles_f32, which ignores it) and its y0, x0, th, tw are checked against THAT volume's h, w; in addition
+ *     0 <= volume < nvolumes, h, w >= 1, offsets >= 0 -- all IC_ERR_ARG on the host, before any device call.
+ *   symbols: out, may be NULL;  q: out, may be NULL: q[c,y,x] = centers[symbols[c,y,x]], the tensor ic_ae_decode_f32 consumes,
+ *     written by the tile's work-group when its tile is done.  Not both NULL (IC_ERR_ARG).  status: out, device int (ntiles).
+ *   k = 24, flags = 0: ONE launch of ntiles work-groups over all volumes; other k or the slow-path flags: tile after tile.
+ *   workspace: ic_pc_decode_tiles_batch_workspace_bytes(C, largest th, largest tw, ntiles, nvolumes, k), one slot per tile as
+ *     above: a caller with many files cuts the tile list into several calls (any cut will do, also inside a volume). */
+typedef struct { int h, w; long long symbols_off, q_off; } ic_pc_volume_t;
+size_t ic_pc_decode_tiles_batch_workspace_bytes(int C, int th_max, int tw_max, int ntiles, int nvolumes, int k);
+int ic_pc_decode_tiles_batch_f32(const uint8_t* bitstreams, long long total_bytes, const ic_pc_tile_t* tiles_host, int ntiles,
+                                 const ic_pc_volume_t* volumes_host, int nvolumes, const float* const* wtab_host,
+                                 const float* centers, int k, int L, float resolution, int64_t* symbols, float* q, int* status,
+                                 int C, void* workspace, size_t workspace_bytes, int flags, ic_stream_t stream);
 /* The encoder side of the real-bpp path on the device: the mirror image of ic_pc_decode_f32.  Codes N symbol volumes in one
  * launch (one work-group per volume) with the 32-bit range coder of arithmetic_coding.py; the stream of each volume is byte
  * for byte arithmetic_coding.encode_sequence(symbols[1:], freqs[1:]) over the tables ic_pc_logits_to_freqs_f32 derives from
