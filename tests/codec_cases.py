@@ -1,6 +1,8 @@
-"""Shared by tests/test_cpu_codec.py and tests/test_gpu_codec.py: a word-level model of the device range encoder
+"""Shared by tests/test_cpu_codec*.py and tests/test_gpu_codec*.py: a word-level model of the device range encoder
 (csrc/pc_encode.hip) in plain Python, the host coder wrapped so that its pending-underflow count can be observed, and the
-constructed sequences (long pending runs, worst-case cost) as logits whose softmax tables give them."""
+constructed sequences (long pending runs, worst-case cost) as logits whose softmax tables give them.  For the decoders: a
+word-level model of pc_dec_symbol_wave (csrc/probclass.hip), the host decoder as a function of (bytes, tables), context-model
+weights whose table is one chosen row at every position, and the byte strings no encoder wrote."""
 import io
 
 import numpy as np
@@ -192,3 +194,148 @@ def worst_case_logits(n=200):
     """the symbol of frequency 1 (p = e^-40 truncates to 0, floor 1) against one of frequency `resolution`, repeated:
     about log2(1e9 + 1) = 29.9 bits per symbol, the most a softmax table can cost."""
     return np.tile(np.array([[0.0, 40.0]], np.float32), (n, 1)), np.zeros(n, np.int64)
+
+
+# ---- the decode side ----------------------------------------------------------------------------------------------------------
+
+LAST_LAYER = 'probclass3d/logits/conv3d_conv2_mask'
+
+
+def constant_table_weights(ae_cfg, pc_cfg, bias, seed=1234):
+    """weights.synthetic_weights with the filter of the last context-model layer zeroed and its bias set to `bias`.  The logits of
+    a position are relu(conv(activations, filter) + bias); every product with a zero filter tap is +-0 (the activations are
+    finite), their sum is +-0, +-0 + bias is bias exactly and bias >= 0 passes the ReLU unchanged: the logits are exactly `bias`
+    at every position, whatever the symbols around it and whichever kernel computes them (parallel pass, encoder, every decoder).
+    The frequency table is then one row, chosen by the test."""
+    from imgcomp_cvpr_amd import weights as W
+    bias = np.asarray(bias, np.float32)
+    assert bias.shape == (ae_cfg.num_centers,) and (bias >= 0).all(), 'one bias per centre, none below 0 (the final ReLU)'
+    w = W.synthetic_weights(ae_cfg, pc_cfg, seed=seed)
+    w[LAST_LAYER + '/weights'] = np.zeros_like(w[LAST_LAYER + '/weights'])
+    w[LAST_LAYER + '/biases'] = bias.copy()
+    return w
+
+
+def straddle_symbols(table, steps, prefix=()):
+    """one fixed integer table: after coding `prefix`, follow the host encoder's state and always code the symbol whose interval
+    contains 2^31 (lo < 2^31 <= hi) -- its top bits differ, nothing is shifted out, so the pending count only grows.
+    -> (the `steps` symbols, the pending count reached).  A table without such a symbol at some step (a cumulative boundary
+    exactly at half the range) is refused."""
+    table = [int(v) for v in table]
+    cum = [0]
+    for v in table:
+        cum.append(cum[-1] + v)
+    tot = cum[-1]
+    enc = ac.ArithmeticEncoder(ac.CountingBitOutputStream(ac.BitOutputStream(_Keep())))
+    for k in prefix:
+        enc.write_cum(cum[k], cum[k + 1], tot)
+    half, symbols = 1 << 31, []
+    for step in range(steps):
+        r = enc.high - enc.low + 1
+        hit = [k for k in range(len(table))
+               if enc.low + cum[k] * r // tot < half <= enc.low + cum[k + 1] * r // tot - 1]
+        assert len(hit) == 1, 'table {}: no symbol straddles 2^31 at step {} (low {:#x}, high {:#x})'.format(table, step, enc.low, enc.high)
+        before = enc._pending
+        enc.write_cum(cum[hit[0]], cum[hit[0] + 1], tot)
+        assert enc._pending >= before
+        symbols.append(hit[0])
+    return symbols, enc._pending
+
+
+def _freq_tables(freq_rows):
+    """one SimpleFrequencyTable per row; a row that is the same object as the one before it (a constant table repeated) shares it"""
+    last, table = None, None
+    for row in freq_rows:
+        if table is None or row is not last:
+            last, table = row, ac.SimpleFrequencyTable(row)
+        yield table
+
+
+def host_decode(data, freq_rows):
+    """arithmetic_coding's decoder over the bytes `data`, one table per symbol -> list of symbols.  It reads zeros past the end
+    and never refuses a byte string: a total reference for streams that no encoder wrote."""
+    dec = ac.ArithmeticDecoder(ac.BitInputStream(io.BytesIO(bytes(data))))
+    return [dec.read(t) for t in _freq_tables(freq_rows)]
+
+
+def model_udiv(n, d):
+    """pc_udiv: the double-precision quotient, then one exact correction step.  Its documented precondition: n < 2^63,
+    d < 2^34, n / d < 2^34."""
+    assert 0 <= n < (1 << 63) and 0 < d < (1 << 34) and n // d < (1 << 34)
+    q = int(float(n) / float(d))
+    rem = n - q * d
+    if rem < 0:
+        q -= 1
+    elif rem >= d:
+        q += 1
+    return q
+
+
+class ModelBits(object):
+    """pc_dec_bit: most significant bit first, zeros past the end"""
+
+    def __init__(self, data):
+        self.data, self.pos, self.left, self.cur = bytes(data), -1, 0, 0
+
+    def bit(self):
+        if self.left == 0:
+            self.pos += 1
+            self.cur = self.data[self.pos] if self.pos < len(self.data) else 0
+            self.left = 8
+        self.left -= 1
+        return (self.cur >> self.left) & 1
+
+
+def model_decode(data, freq_rows):
+    """pc_dec_symbol_wave's serial loop over the tables -> (symbols, status): the 32 priming bits, value by pc_udiv, the linear
+    search over the cumulative sums, both renormalisation loops.  status 1 (and the symbols before) at the first table whose
+    total exceeds 2^30 + 2."""
+    TOP, SECOND = 1 << 31, 1 << 30
+    inp = ModelBits(data)
+    low, high, code = 0, M32, 0
+    for _ in range(32):
+        code = (code << 1) | inp.bit()
+    symbols = []
+    for row in freq_rows:
+        fr = [int(v) for v in row]
+        L, total = len(fr), sum(fr)
+        if total > ac.MAX_TOTAL:
+            return symbols, 1
+        assert low <= code <= high
+        r = high - low + 1
+        value = model_udiv((code - low + 1) * total - 1, r)
+        assert value == ((code - low + 1) * total - 1) // r
+        sym, cum = 0, 0
+        while sym + 1 < L and cum + fr[sym] <= value:
+            cum += fr[sym]
+            sym += 1
+        qh, ql = model_udiv((cum + fr[sym]) * r, total), model_udiv(cum * r, total)
+        assert qh == (cum + fr[sym]) * r // total and ql == cum * r // total
+        high = low + qh - 1
+        low = low + ql
+        while ((low ^ high) & TOP) == 0:
+            code = ((code << 1) & M32) | inp.bit()
+            low = (low << 1) & M32
+            high = ((high << 1) & M32) | 1
+        while (low & ~high & SECOND) != 0:
+            code = (code & TOP) | ((code << 1) & (M32 >> 1)) | inp.bit()
+            low = (low << 1) & (M32 >> 1)
+            high = ((high << 1) & (M32 >> 1)) | TOP | 1
+        symbols.append(sym)
+    return symbols, 0
+
+
+def garbage_strings(valid, seed, lengths=(1, 7, 64, 200)):
+    """byte strings that no encoder wrote, for a decoder that must still agree with the host decoder on them:
+    [(name, bytes)] -- empty, all ones, all zeros, zeros then ones, seeded random strings of `lengths`, and the valid stream
+    `valid` cut at each of its first 16 byte positions, cut in half, and with one bit flipped (early, in the middle, at the end)."""
+    rs = np.random.RandomState(seed)
+    out = [('empty', b''), ('ones', b'\xff' * 64), ('zeros', b'\x00' * 64), ('zeros then ones', b'\x00' * 4 + b'\xff' * 60)]
+    out += [('random {}'.format(n), rs.randint(0, 256, size=n).astype(np.uint8).tobytes()) for n in lengths]
+    out += [('cut at {}'.format(n), valid[:n]) for n in range(min(16, len(valid)))]
+    out.append(('first half', valid[:len(valid) // 2]))
+    for bit in sorted(set([3, 4 * len(valid), 8 * len(valid) - 1, int(rs.randint(0, 8 * len(valid)))])) if valid else []:
+        flipped = bytearray(valid)
+        flipped[bit >> 3] ^= 0x80 >> (bit & 7)
+        out.append(('bit {} flipped'.format(bit), bytes(flipped)))
+    return out

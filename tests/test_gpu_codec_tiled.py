@@ -116,7 +116,7 @@ def test_decode_tiles_returns_the_symbols(cuda, plain, shape, tile):
 
 
 @pytest.mark.parametrize('shape,tile,victim', [((61, 93), (3, 5), 4), ((512, 768), (16, 16), 9)])
-def test_a_damaged_tile_stays_alone(plain, shape, tile, victim):
+def test_a_damaged_tile_stays_alone(plain, shape, tile, victim, tmp_path):
     """the truncated-stream case of test_device_decoder_stream on one tile: its stream cut to the first half (zeros past the end,
     never the next tile's bytes) still decodes to symbols in [0, L); every other tile is exact."""
     from imgcomp_cvpr_amd import codec
@@ -136,6 +136,12 @@ def test_a_damaged_tile_stays_alone(plain, shape, tile, victim):
     g = grid[victim]
     assert np.array_equal(_sub(out, g), pred.decode_stream(streams[victim], (sym.shape[0], g[2], g[3]), firsts[victim]))
     assert not np.array_equal(_sub(out, g), _sub(sym, g))
+    if shape == (61, 93):                                # ... and what the host loop makes of it (480 symbols: cheap on the host)
+        from imgcomp_cvpr_amd import bit_counter
+        path = str(tmp_path / 'cut.bin')
+        open(path, 'wb').write(streams[victim])
+        ref = bit_counter._decode(path, (sym.shape[0] + 4, g[2] + 8, g[3] + 8), pred.input_ctx_shape, firsts[victim], pred.get_freqs)
+        assert np.array_equal(_sub(out, g), pred.undo_pad_symbols_volume(ref))
 
 
 def test_one_tile_is_the_format_1_payload(cuda, configs, syn_weights, plain):

@@ -251,6 +251,10 @@ def test_device_decoder_stream(cuda, configs, syn_weights, nets, tmp_path):
     assert np.array_equal(ref, sym)
     cut = pred.decode_stream(data[:len(data) // 2], sym.shape, first)
     assert cut.shape == sym.shape and cut.min() >= 0 and cut.max() < 6 and not np.array_equal(cut, sym)
+    cut_path = str(tmp_path / 'cut.bin')                                 # ... and it is what the host loop makes of the same cut stream
+    open(cut_path, 'wb').write(data[:len(data) // 2])
+    cut_ref = pred.undo_pad_symbols_volume(bit_counter._decode(cut_path, padded.shape, pred.input_ctx_shape, first, pred.get_freqs))
+    assert np.array_equal(cut, cut_ref)
     n_same = int(np.argmax(cut.reshape(-1) != sym.reshape(-1)))
     assert n_same > sym.size // 4                                        # everything before the cut is still right
     one = pred.decode_stream(b'', (1, 1, 1), 4)
