@@ -1,10 +1,11 @@
 """Image codec: an image to a self-describing file and back.
 
     python -m imgcomp_cvpr_amd.codec compress   IN.png  OUT.icf [--ae_config cvpr/low] [--pc_config cvpr/res_shallow] [--weights synthetic|FILE.npz|CKPT]
-                                                                [--tile PIXELS]
-    python -m imgcomp_cvpr_amd.codec decompress IN.icf  OUT.png [same options]
-    python -m imgcomp_cvpr_amd.codec compress-dir   IN_DIR OUT_DIR [--tile PIXELS] [--batch N]     every *.png / *.jpg -> OUT_DIR/<stem>.icf
-    python -m imgcomp_cvpr_amd.codec decompress-dir IN_DIR OUT_DIR [--batch N]                     every *.icf -> OUT_DIR/<stem>.png
+                                                                [--tile PIXELS [--checked]]
+    python -m imgcomp_cvpr_amd.codec decompress IN.icf  OUT.png [same options] [--salvage]
+    python -m imgcomp_cvpr_amd.codec compress-dir   IN_DIR OUT_DIR [--tile PIXELS [--checked]] [--batch N]   every *.png / *.jpg -> OUT_DIR/<stem>.icf
+    python -m imgcomp_cvpr_amd.codec decompress-dir IN_DIR OUT_DIR [--batch N] [--salvage]                   every *.icf -> OUT_DIR/<stem>.png
+    python -m imgcomp_cvpr_amd.codec verify PATH [PATH ...]         files or directories of *.icf: the checksums, without model or device
 
 compress:   pad to a multiple of the subsampling factor (val.add_padding) -> ae.encode -> PredictionNetwork.encode_stream (the
             range coder on the device, ic_pc_encode_f32) -> container.
@@ -40,6 +41,19 @@ at tile borders and one stream termination per tile.  Without --tile every byte 
     ..      8     payload length n (u64) = the sum of the stream lengths
     ..      n     payload: the tiles' streams back to back, in table order
     ..      4     CRC-32 of every byte before it (u32)
+--tile --checked (Codec(tile=(th, tw), checked=True)): format 4, "checked tiles" -- format 2 with a CRC-32 per tile stream and one
+over the header, 4 * ntiles + 4 bytes more, the streams the same bytes.  decompress reads it with the strictness of format 2 (any
+flipped bit, any truncation is refused).  salvage (Codec.salvage / salvage_many, --salvage) reads what a damaged format-4 file still
+holds: after a header that passes its own CRC, every tile whose bytes are there and match their CRC is decoded, the others are
+filled on the device from their intact neighbours (ic_pc_conceal_tiles) and named in the report.  verify checks files on the host.
+    0       4     magic  b'ICVF'
+    4       2     format version (u16) = 4        (3 is not used and is refused)
+    ..            ae name, pc name, H, W, C, h, w, L, resolution, fingerprint, th, tw, ntiles: as version 2
+    ..      10*nt per tile, raster order: first_sym (u16), stream length in bytes (u32), CRC-32 of that tile's stream bytes (u32)
+    ..      8     payload length n (u64) = the sum of the stream lengths
+    ..      4     header CRC-32: of every byte before it (magic up to and including the payload length)
+    ..      n     payload: the tiles' streams back to back, in table order
+    ..      4     CRC-32 of every byte before it (u32)
 Every failure of parse / decompress is a ValueError that names the cause; nothing of a refused file reaches the device.
 The -dir commands and Codec.compress_many / decompress_many work on a list of images at once: the same bytes and the same pixels as
 the single-image calls, file by file, but the tiles of all files are coded by one launch each way (ic_pc_decode_tiles_batch_f32: one
@@ -67,6 +81,16 @@ Container = namedtuple('Container', ['version', 'ae_name', 'pc_name', 'H', 'W', 
 FORMAT_VERSION_TILED = 2
 TiledContainer = namedtuple('TiledContainer', ['version', 'ae_name', 'pc_name', 'H', 'W', 'C', 'h', 'w', 'L', 'resolution', 'fingerprint',
                                                'th', 'tw', 'first_syms', 'streams', 'payload'])
+
+
+FORMAT_VERSION_CHECKED = 4                                           # 3 is not used: it stays "unsupported"
+CheckedContainer = namedtuple('CheckedContainer', TiledContainer._fields + ('stream_crcs',))
+_TILED = (TiledContainer, CheckedContainer)
+
+# what salvage tells about a file: damaged is [DamagedTile] in tile order; latent = (y0, x0, th, tw) in the symbol volume, pixels =
+# (y0, x0, height, width) in the returned image, clipped to it (height or width 0: the tile lies in the padding)
+DamagedTile = namedtuple('DamagedTile', ['index', 'reason', 'latent', 'pixels'])
+SalvageReport = namedtuple('SalvageReport', ['ntiles', 'file_crc_ok', 'damaged'])
 
 
 def tile_grid(h, w, th, tw):
@@ -120,20 +144,34 @@ def list_dir_jobs(in_dir, out_dir, command):
     return jobs
 
 
-def build_tiled_container(ae_name, pc_name, H, W, C, h, w, L, resolution, fingerprint, th, tw, first_syms, streams):
-    """format 2: first_syms / streams per tile in the order of tile_grid(h, w, th, tw)."""
+def _tiled_head(version, ae_name, pc_name, H, W, C, h, w, L, resolution, fingerprint, th, tw, rows, n):
     a, p = ae_name.encode('utf-8'), pc_name.encode('utf-8')
-    streams = [bytes(b) for b in streams]
-    assert len(first_syms) == len(streams)
-    head = b''.join([
-        MAGIC, struct.pack('<H', FORMAT_VERSION_TILED),
+    return b''.join([
+        MAGIC, struct.pack('<H', version),
         struct.pack('<H', len(a)), a, struct.pack('<H', len(p)), p,
         struct.pack('<II', H, W), struct.pack('<HII', C, h, w), struct.pack('<H', L),
         struct.pack('<d', float(resolution)), struct.pack('<I', fingerprint & 0xffffffff),
-        struct.pack('<HH', th, tw), struct.pack('<I', len(streams))] +
-        [struct.pack('<HI', f, len(b)) for f, b in zip(first_syms, streams)] +
-        [struct.pack('<Q', sum(len(b) for b in streams))])
+        struct.pack('<HH', th, tw), struct.pack('<I', len(rows))] + rows + [struct.pack('<Q', n)])
+
+
+def build_tiled_container(ae_name, pc_name, H, W, C, h, w, L, resolution, fingerprint, th, tw, first_syms, streams):
+    """format 2: first_syms / streams per tile in the order of tile_grid(h, w, th, tw)."""
+    streams = [bytes(b) for b in streams]
+    assert len(first_syms) == len(streams)
+    head = _tiled_head(FORMAT_VERSION_TILED, ae_name, pc_name, H, W, C, h, w, L, resolution, fingerprint, th, tw,
+                       [struct.pack('<HI', f, len(b)) for f, b in zip(first_syms, streams)], sum(len(b) for b in streams))
     body = head + b''.join(streams)
+    return body + struct.pack('<I', zlib.crc32(body) & 0xffffffff)
+
+
+def build_checked_container(ae_name, pc_name, H, W, C, h, w, L, resolution, fingerprint, th, tw, first_syms, streams):
+    """format 4: format 2 with a CRC-32 per stream in the tile table and a CRC-32 over the header behind the payload length."""
+    streams = [bytes(b) for b in streams]
+    assert len(first_syms) == len(streams)
+    head = _tiled_head(FORMAT_VERSION_CHECKED, ae_name, pc_name, H, W, C, h, w, L, resolution, fingerprint, th, tw,
+                       [struct.pack('<HII', f, len(b), zlib.crc32(b) & 0xffffffff) for f, b in zip(first_syms, streams)],
+                       sum(len(b) for b in streams))
+    body = head + struct.pack('<I', zlib.crc32(head) & 0xffffffff) + b''.join(streams)
     return body + struct.pack('<I', zlib.crc32(body) & 0xffffffff)
 
 
@@ -168,33 +206,25 @@ class _Reader(object):
 
 
 def parse_container(data):
-    """bytes -> Container (version 1) or TiledContainer (version 2).  Order: size, magic, version, CRC over the whole file -- only
-    then are the header's lengths read, each against the bytes that remain; the payload length must equal exactly what is left
-    before the CRC."""
+    """bytes -> Container (version 1), TiledContainer (version 2) or CheckedContainer (version 4).  Order: size, magic, version, CRC
+    over the whole file -- only then are the header's lengths read, each against the bytes that remain; the payload length must
+    equal exactly what is left before the CRC.  Version 4 in addition: its header CRC and every tile's stream CRC."""
     data = bytes(data)
     if len(data) < _MIN_SIZE:
         raise ValueError('truncated file: {} bytes, the smallest container has {}'.format(len(data), _MIN_SIZE))
     if data[:4] != MAGIC:
         raise ValueError('wrong magic {!r}: not a codec file (expected {!r})'.format(data[:4], MAGIC))
     version, = struct.unpack('<H', data[4:6])
-    if version not in (FORMAT_VERSION, FORMAT_VERSION_TILED):
-        raise ValueError('unsupported format version {} (this codec reads versions {} and {})'.format(
-            version, FORMAT_VERSION, FORMAT_VERSION_TILED))
+    if version not in (FORMAT_VERSION, FORMAT_VERSION_TILED, FORMAT_VERSION_CHECKED):
+        raise ValueError('unsupported format version {} (this codec reads versions {}, {} and {})'.format(
+            version, FORMAT_VERSION, FORMAT_VERSION_TILED, FORMAT_VERSION_CHECKED))
     stored, = struct.unpack('<I', data[-4:])
     actual = zlib.crc32(data[:-4]) & 0xffffffff
     if stored != actual:
         raise ValueError('CRC mismatch: file says {:08x}, content gives {:08x} (corrupt or truncated file)'.format(stored, actual))
     r = _Reader(data[:-4])
-    r.take(6, 'magic and version')
-    ae_name = r.take(r.unpack('<H', 'ae config name length')[0], 'ae config name')
-    pc_name = r.take(r.unpack('<H', 'pc config name length')[0], 'pc config name')
-    try:
-        ae_name, pc_name = ae_name.decode('utf-8'), pc_name.decode('utf-8')
-    except UnicodeDecodeError:
-        raise ValueError('config name is not UTF-8')
-    H, W = r.unpack('<II', 'image size')
-    C, h, w = r.unpack('<HII', 'symbol volume shape')
-    if version == FORMAT_VERSION_TILED:
+    ae_name, pc_name, H, W, C, h, w = _parse_front(r)
+    if version != FORMAT_VERSION:
         return _parse_tiled(r, version, ae_name, pc_name, H, W, C, h, w)
     L, first_sym = r.unpack('<HH', 'L and first symbol')
     resolution, = r.unpack('<d', 'frequency resolution')
@@ -206,8 +236,23 @@ def parse_container(data):
     return Container(version, ae_name, pc_name, H, W, C, h, w, L, first_sym, resolution, fingerprint, r.take(n, 'payload'))
 
 
-def _parse_tiled(r, version, ae_name, pc_name, H, W, C, h, w):
-    """the rest of a format-2 file after the symbol volume shape (the CRC has been checked)."""
+def _parse_front(r):
+    """what every format begins with: magic and version (checked by the caller), the two names, the image and volume shapes"""
+    r.take(6, 'magic and version')
+    ae_name = r.take(r.unpack('<H', 'ae config name length')[0], 'ae config name')
+    pc_name = r.take(r.unpack('<H', 'pc config name length')[0], 'pc config name')
+    try:
+        ae_name, pc_name = ae_name.decode('utf-8'), pc_name.decode('utf-8')
+    except UnicodeDecodeError:
+        raise ValueError('config name is not UTF-8')
+    H, W = r.unpack('<II', 'image size')
+    C, h, w = r.unpack('<HII', 'symbol volume shape')
+    return ae_name, pc_name, H, W, C, h, w
+
+
+def _parse_tile_table(r, version, h, w):
+    """L .. payload length of a format-2 / format-4 header, every length against the bytes that remain -> (L, resolution,
+    fingerprint, th, tw, first_syms, lengths, crcs or None, n)"""
     L, = r.unpack('<H', 'L')
     resolution, = r.unpack('<d', 'frequency resolution')
     fingerprint, = r.unpack('<I', 'model fingerprint')
@@ -221,10 +266,16 @@ def _parse_tiled(r, version, ae_name, pc_name, H, W, C, h, w):
     if ntiles != expected:
         raise ValueError('tile count {} does not equal the {} tiles of a {} x {} volume cut into {} x {}'.format(
             ntiles, expected, h, w, th, tw))
-    table = r.take(6 * ntiles, 'tile table')              # against the bytes that remain, before anything of its size is built
-    first_syms, lengths = [], []
+    checked = version == FORMAT_VERSION_CHECKED
+    row = 10 if checked else 6
+    table = r.take(row * ntiles, 'tile table')            # against the bytes that remain, before anything of its size is built
+    first_syms, lengths, crcs = [], [], [] if checked else None
     for t in range(ntiles):
-        f, n_t = struct.unpack_from('<HI', table, 6 * t)
+        if checked:
+            f, n_t, crc = struct.unpack_from('<HII', table, row * t)
+            crcs.append(crc)
+        else:
+            f, n_t = struct.unpack_from('<HI', table, row * t)
         if f >= L:
             raise ValueError('first symbol {} of tile {} is not below L = {}'.format(f, t, L))
         first_syms.append(f)
@@ -232,6 +283,18 @@ def _parse_tiled(r, version, ae_name, pc_name, H, W, C, h, w):
     n, = r.unpack('<Q', 'payload length')
     if sum(lengths) != n:
         raise ValueError('stream lengths of the {} tiles sum to {}, the payload length is {}'.format(ntiles, sum(lengths), n))
+    return L, resolution, fingerprint, th, tw, first_syms, lengths, crcs, n
+
+
+def _parse_tiled(r, version, ae_name, pc_name, H, W, C, h, w):
+    """the rest of a format-2 / format-4 file after the symbol volume shape (the CRC over the file has been checked)."""
+    L, resolution, fingerprint, th, tw, first_syms, lengths, crcs, n = _parse_tile_table(r, version, h, w)
+    if crcs is not None:
+        end = r.pos
+        stored, = r.unpack('<I', 'header CRC')
+        actual = zlib.crc32(r.data[:end]) & 0xffffffff
+        if stored != actual:
+            raise ValueError('header CRC mismatch: file says {:08x}, the header gives {:08x}'.format(stored, actual))
     left = len(r.data) - r.pos
     if n != left:
         raise ValueError('payload length {} does not equal the {} bytes that remain in the file'.format(n, left))
@@ -240,7 +303,63 @@ def _parse_tiled(r, version, ae_name, pc_name, H, W, C, h, w):
     for n_t in lengths:
         streams.append(payload[pos:pos + n_t])
         pos += n_t
-    return TiledContainer(version, ae_name, pc_name, H, W, C, h, w, L, resolution, fingerprint, th, tw, first_syms, streams, payload)
+    if crcs is None:
+        return TiledContainer(version, ae_name, pc_name, H, W, C, h, w, L, resolution, fingerprint, th, tw, first_syms, streams, payload)
+    for t, (b, crc) in enumerate(zip(streams, crcs)):
+        actual = zlib.crc32(b) & 0xffffffff
+        if actual != crc:
+            raise ValueError('stream CRC mismatch in tile {}: the table says {:08x}, the stream gives {:08x}'.format(t, crc, actual))
+    return CheckedContainer(version, ae_name, pc_name, H, W, C, h, w, L, resolution, fingerprint, th, tw, first_syms, streams, payload, crcs)
+
+
+def parse_salvage(data):
+    """what a possibly damaged format-4 file still holds -> (CheckedContainer, damage, file_crc_ok).  damage: [(tile, reason)] in
+    tile order, reason 'crc' (the bytes are there, their CRC differs) or 'truncated' (the tile's byte range is not complete);
+    streams[t] of such a tile is None.  Order: size, magic, version, then the header up to its own CRC, every length against the
+    bytes that are there; a header that fails its CRC is a ValueError, nothing of it is believed.  Behind a good header the
+    payload is what follows, at most the declared n bytes; the CRC over the file is not required, file_crc_ok says whether it is
+    there and right; bytes behind the declared end are ignored."""
+    data = bytes(data)
+    if len(data) < _MIN_SIZE:
+        raise ValueError('truncated file: {} bytes, the smallest container has {}'.format(len(data), _MIN_SIZE))
+    if data[:4] != MAGIC:
+        raise ValueError('wrong magic {!r}: not a codec file (expected {!r})'.format(data[:4], MAGIC))
+    version, = struct.unpack('<H', data[4:6])
+    if version in (FORMAT_VERSION, FORMAT_VERSION_TILED):
+        raise ValueError('format version {} has nothing to salvage with: one CRC over the whole file, none per tile (only version {}, '
+                         'written with --tile --checked, can be salvaged)'.format(version, FORMAT_VERSION_CHECKED))
+    if version != FORMAT_VERSION_CHECKED:
+        raise ValueError('unsupported format version {} (only version {} can be salvaged)'.format(version, FORMAT_VERSION_CHECKED))
+    r = _Reader(data)
+    try:
+        ae_name, pc_name, H, W, C, h, w = _parse_front(r)
+        L, resolution, fingerprint, th, tw, first_syms, lengths, crcs, n = _parse_tile_table(r, version, h, w)
+        end = r.pos
+        stored, = r.unpack('<I', 'header CRC')
+    except ValueError as e:
+        # the header's own words cannot be told from damage before its CRC has been seen
+        raise ValueError('header damaged: nothing can be recovered ({})'.format(e))
+    actual = zlib.crc32(data[:end]) & 0xffffffff
+    if stored != actual:
+        raise ValueError('header damaged: nothing can be recovered (header CRC mismatch: file says {:08x}, the header gives {:08x})'.format(
+            stored, actual))
+    start = r.pos
+    payload = data[start:start + n]                        # what arrived of it
+    streams, damage, pos = [], [], 0
+    for t, (n_t, crc) in enumerate(zip(lengths, crcs)):
+        if n_t and pos + n_t > len(payload):           # (an empty stream is complete wherever the file ends)
+            streams.append(None)
+            damage.append((t, 'truncated'))
+        elif zlib.crc32(payload[pos:pos + n_t]) & 0xffffffff != crc:
+            streams.append(None)
+            damage.append((t, 'crc'))
+        else:
+            streams.append(payload[pos:pos + n_t])
+        pos += n_t
+    tail = data[start + n:start + n + 4]
+    file_crc_ok = len(payload) == n and len(tail) == 4 and struct.unpack('<I', tail)[0] == zlib.crc32(data[:start + n]) & 0xffffffff
+    return (CheckedContainer(version, ae_name, pc_name, H, W, C, h, w, L, resolution, fingerprint, th, tw, first_syms, streams, payload,
+                             crcs), damage, file_crc_ok)
 
 
 def model_fingerprint(centers, pc_params):
@@ -266,15 +385,18 @@ class Codec(object):
     """builds the networks once (as val.Fetcher does); compress / decompress map HWC uint8 images to container bytes and back.
     device_encode: which range encoder writes the payload -- the bytes are the same either way (tests/test_gpu_codec.py); the
     default is the one that measured faster end to end on a Kodak volume.
-    tile: None writes format 1; (th, tw) in symbol-volume units writes format 2, one stream per tile.  Reading needs no option:
-    the file's version decides."""
+    tile: None writes format 1; (th, tw) in symbol-volume units writes format 2, one stream per tile; with checked=True format 4,
+    the same streams with a CRC each (salvage reads what a damaged one still holds).  Reading needs no option: the file's version
+    decides."""
 
-    def __init__(self, ae_config, pc_config, weights, device='cuda', plan_flags=0, device_encode=True, tile=None):
+    def __init__(self, ae_config, pc_config, weights, device='cuda', plan_flags=0, device_encode=True, tile=None, checked=False):
         if tile is not None:
             tile = (int(tile[0]), int(tile[1]))
             if not (1 <= tile[0] <= 0xffff and 1 <= tile[1] <= 0xffff):
                 raise ValueError('tile extent {} x {} is outside 1 .. 65535'.format(*tile))
-        self.tile = tile
+        if checked and tile is None:
+            raise ValueError('checked=True needs a tile extent: the checksums of format 4 are per tile')
+        self.tile, self.checked = tile, bool(checked)
         import torch
         from . import autoencoder, probclass
         self.device = torch.device(device)
@@ -326,7 +448,7 @@ class Codec(object):
         if self.tile is not None:
             th, tw = self.tile
             coded = self.pred.encode_tiles(sym, th, tw)
-            return build_tiled_container(self.ae_name, self.pc_name, H, W, C, h, w, self.L, self.pred.freqs_resolution,
+            return self._build_tiled(self.ae_name, self.pc_name, H, W, C, h, w, self.L, self.pred.freqs_resolution,
                                          self.fingerprint, th, tw, [f for _, f in coded], [b for b, _ in coded])
         if self.device_encode:
             payload, first_sym = self.pred.encode_stream(sym)
@@ -334,6 +456,12 @@ class Codec(object):
             payload, first_sym = self._host_encode_stream(sym.cpu().numpy())
         return build_container(self.ae_name, self.pc_name, H, W, C, h, w, self.L, first_sym, self.pred.freqs_resolution,
                                self.fingerprint, payload)
+
+    @property
+    def _build_tiled(self):
+        if self.checked and self.tile is None:
+            raise ValueError('checked=True needs a tile extent: the checksums of format 4 are per tile')
+        return build_checked_container if self.checked else build_tiled_container
 
     def check_container(self, c):
         """the header against the loaded model and against itself; the volume is bounded by the header's own image size only (a
@@ -353,7 +481,7 @@ class Codec(object):
         if (c.h, c.w) != (eh, ew):
             raise ValueError('header mismatch: symbol volume {} x {} does not belong to a {} x {} image (expected {} x {})'.format(
                 c.h, c.w, c.H, c.W, eh, ew))
-        for first_sym in (c.first_syms if isinstance(c, TiledContainer) else [c.first_sym]):
+        for first_sym in (c.first_syms if isinstance(c, _TILED) else [c.first_sym]):
             if first_sym >= c.L:
                 raise ValueError('header mismatch: first symbol {} is not below L = {}'.format(first_sym, c.L))
         if c.resolution != self.pred.freqs_resolution:
@@ -365,7 +493,7 @@ class Codec(object):
         c = parse_container(data)
         self.check_container(c)
         try:
-            if isinstance(c, TiledContainer):
+            if isinstance(c, _TILED):
                 sym = self.pred.decode_tiles(c.streams, c.first_syms, (c.C, c.h, c.w), c.th, c.tw)
             else:
                 sym = self.pred.decode_stream(c.payload, (c.C, c.h, c.w), c.first_sym)
@@ -442,7 +570,7 @@ class Codec(object):
             th, tw = self.tile
             for i, coded in enumerate(self.pred.encode_tiles_batch(syms, th, tw)):
                 C, h, w = (int(v) for v in syms[i].shape)
-                out[i] = build_tiled_container(self.ae_name, self.pc_name, sizes[i][0], sizes[i][1], C, h, w, self.L,
+                out[i] = self._build_tiled(self.ae_name, self.pc_name, sizes[i][0], sizes[i][1], C, h, w, self.L,
                                                self.pred.freqs_resolution, self.fingerprint, th, tw,
                                                [f for _, f in coded], [b for b, _ in coded])
             return out
@@ -465,7 +593,7 @@ class Codec(object):
     def decompress_many(self, datas, max_workspace_bytes=1 << 31):
         """[container bytes] of either format, any mix of shapes -> [HWC uint8], element i equal to decompress(datas[i]).
         Every file is parsed and checked first; the first refusal raises its ValueError with the index of the file in front and
-        nothing has reached the device.  The format-2 files of the most frequent tile extent are decoded together
+        nothing has reached the device.  The format-2 / format-4 files of the most frequent tile extent are decoded together
         (decode_tiles_batch: the tiles of all of them in one launch per workspace chunk, the centres q staying on the device) and
         go through the decoder up to IN_FLIGHT at a time; format-1 files and other tile extents take the single-file path."""
         import torch
@@ -477,9 +605,9 @@ class Codec(object):
             except ValueError as e:
                 raise ValueError('file {}: {}'.format(i, e))
             heads.append(c)
-        extents = [(c.th, c.tw) for c in heads if isinstance(c, TiledContainer)]
+        extents = [(c.th, c.tw) for c in heads if isinstance(c, _TILED)]
         major = max(sorted(set(extents)), key=extents.count) if extents else None
-        together = [i for i, c in enumerate(heads) if isinstance(c, TiledContainer) and (c.th, c.tw) == major]
+        together = [i for i, c in enumerate(heads) if isinstance(c, _TILED) and (c.th, c.tw) == major]
         out = [None] * len(datas)
         if together:
             try:
@@ -499,6 +627,61 @@ class Codec(object):
                     out[i] = self.decompress(data)
                 except ValueError as e:
                     raise ValueError('file {}: {}'.format(i, e))
+        return out
+
+    # -- what a damaged format-4 file still holds --
+
+    def _salvage_head(self, data):
+        """parse_salvage + the model checks -> (CheckedContainer, {tile: reason}, file_crc_ok); nothing on the device"""
+        c, damage, file_crc_ok = parse_salvage(data)
+        self.check_container(c)
+        return c, dict(damage), file_crc_ok
+
+    def _report(self, c, reasons, decoded, file_crc_ok):
+        """reasons: {tile: 'crc' | 'truncated'} of the reader; decoded: [(tile, reason)] of decode_tiles_batch(conceal=True)"""
+        f = self.factor
+        top, left = ((-c.H) % f) // 2, ((-c.W) % f) // 2                         # val.add_padding's offsets
+        grid, damaged = tile_grid(c.h, c.w, c.th, c.tw), []
+        for t, why in decoded:
+            y0, x0, a, b = grid[t]
+            py0, py1 = min(max(y0 * f - top, 0), c.H), min(max((y0 + a) * f - top, 0), c.H)
+            px0, px1 = min(max(x0 * f - left, 0), c.W), min(max((x0 + b) * f - left, 0), c.W)
+            damaged.append(DamagedTile(t, reasons.get(t, why), (y0, x0, a, b), (py0, px0, py1 - py0, px1 - px0)))
+        return SalvageReport(len(grid), bool(file_crc_ok), damaged)
+
+    def salvage(self, data):
+        """container bytes of format 4, possibly damaged -> (HWC uint8 image, SalvageReport).  Tiles whose bytes are there and match
+        their CRC are decoded; the others -- and any whose decoder status is not 0 -- are filled on the device from their intact
+        neighbours (ic_pc_conceal_tiles) and listed in report.damaged.  An intact file gives decompress(data) and an empty list.
+        A ValueError where nothing can be recovered: another format, a damaged header, another model."""
+        import torch
+        c, reasons, file_crc_ok = self._salvage_head(data)
+        qs, damage = self.pred.decode_tiles_batch([(c.streams, c.first_syms, (c.C, c.h, c.w))], c.th, c.tw, want='q', conceal=True)
+        x_out = self.ae.decode(qs[0][None], is_training=False).to(torch.uint8)   # tf.cast truncates (val.py)
+        return self._crop(x_out[0], c), self._report(c, reasons, damage[0], file_crc_ok)
+
+    def salvage_many(self, datas, max_workspace_bytes=1 << 31):
+        """[container bytes of format 4] -> [(image, SalvageReport)], element i equal to salvage(datas[i]).  As decompress_many:
+        every file is parsed and checked first (the first refusal raises with the index of the file in front, nothing has reached
+        the device); then per tile extent the intact tiles of all files in one decode launch per workspace chunk, one concealment
+        launch, q staying on the device, and the autoencoder passes up to IN_FLIGHT at a time."""
+        import torch
+        heads = []
+        for i, data in enumerate(datas):
+            try:
+                heads.append(self._salvage_head(data))
+            except ValueError as e:
+                raise ValueError('file {}: {}'.format(i, e))
+        out = [None] * len(datas)
+        for extent in sorted(set((c.th, c.tw) for c, _, _ in heads)):
+            members = [i for i, (c, _, _) in enumerate(heads) if (c.th, c.tw) == extent]
+            qs, damage = self.pred.decode_tiles_batch([(heads[i][0].streams, heads[i][0].first_syms, (heads[i][0].C, heads[i][0].h, heads[i][0].w))
+                                                       for i in members], extent[0], extent[1], want='q', conceal=True,
+                                                      max_workspace_bytes=max_workspace_bytes)
+            imgs = self._in_flight(qs, lambda ae, q: ae.decode(q[None], is_training=False).to(torch.uint8)[0])    # tf.cast truncates (val.py)
+            for i, x, dmg in zip(members, imgs, damage):
+                c, reasons, file_crc_ok = heads[i]
+                out[i] = (self._crop(x, c), self._report(c, reasons, dmg, file_crc_ok))
         return out
 
     def compress_file(self, image_path, out_path):
@@ -532,7 +715,7 @@ def _resolve_config(arg, tree, env):
 def _compress_line(path, data, pixels):
     c = parse_container(data)
     payload = len(c.payload)
-    tiles = ', {} tiles'.format(len(c.streams)) if isinstance(c, TiledContainer) else ''
+    tiles = ', {} tiles'.format(len(c.streams)) if isinstance(c, _TILED) else ''
     return '{}: {} bytes, payload {} bytes = {:.4f} bpp, file {:.4f} bpp{}'.format(
         path, len(data), payload, 8.0 * payload / pixels, 8.0 * len(data) / pixels, tiles)
 
@@ -541,8 +724,29 @@ def _decompress_line(path, img, size):
     return '{}: {} x {} from {} bytes = {:.4f} bpp'.format(path, img.shape[0], img.shape[1], size, 8.0 * size / (img.shape[0] * img.shape[1]))
 
 
+def _damage_line(path, report):
+    """one line for a salvaged file: the damaged tiles and where they lie in the image"""
+    if not report.damaged:
+        return '{}: salvaged, all {} tiles intact, the CRC over the file is missing or wrong'.format(path, report.ntiles)
+    return '{}: salvaged, {} of {} tiles damaged: {}'.format(path, len(report.damaged), report.ntiles, ', '.join(
+        'tile {} ({}) pixels y {}..{} x {}..{}'.format(d.index, d.reason, d.pixels[0], d.pixels[0] + d.pixels[2], d.pixels[1],
+                                                      d.pixels[1] + d.pixels[3]) for d in report.damaged))
+
+
+def check_option_args(flags):
+    """--checked / --salvage against the command and --tile: decided before any model is built"""
+    if getattr(flags, 'checked', False):
+        if flags.command not in ('compress', 'compress-dir'):
+            raise ValueError('--checked belongs to compress / compress-dir: a file says by itself what it is')
+        if flags.tile is None:
+            raise ValueError('--checked needs --tile: the checksums of format 4 are per tile')
+    if getattr(flags, 'salvage', False) and flags.command not in ('decompress', 'decompress-dir'):
+        raise ValueError('--salvage belongs to decompress / decompress-dir')
+
+
 def check_dir_args(flags, factor):
     """everything about a -dir command line that can be refused without a device -> (jobs, tile or None)"""
+    check_option_args(flags)
     if flags.batch < 1:
         raise ValueError('--batch {} is not at least 1'.format(flags.batch))
     tile = None
@@ -567,9 +771,11 @@ def _main_dir(flags, ae_config, pc_config):
         wts = _weights.synthetic_weights(ae_config, pc_config, seed=flags.synthetic_seed)
     else:
         wts = val.load_weights_for_job(None, flags.weights, ae_config, pc_config)
-    codec = Codec(ae_config, pc_config, wts, flags.device, tile=tile)
+    codec = Codec(ae_config, pc_config, wts, flags.device, tile=tile, checked=flags.checked)
     os.makedirs(flags.output, exist_ok=True)
     total_in = total_out = total_pixels = 0
+    if flags.command == 'decompress-dir' and flags.salvage:
+        return _salvage_dir(flags, codec, jobs)
     for start in range(0, len(jobs), flags.batch):
         part = jobs[start:start + flags.batch]
         if flags.command == 'compress-dir':
@@ -600,7 +806,110 @@ def _main_dir(flags, ae_config, pc_config):
     return 0
 
 
+def _salvage_dir(flags, codec, jobs):
+    """decompress-dir --salvage: strict for the files that pass (any format), salvage for the others; a file of which nothing can be
+    recovered is named on stderr and skipped.  Exit status 0 when every file gave an image, else 2."""
+    from PIL import Image
+    total_in = total_pixels = written = 0
+    for start in range(0, len(jobs), flags.batch):
+        part = jobs[start:start + flags.batch]
+        datas, good = [], []
+        for src, _ in part:
+            with open(src, 'rb') as f:
+                datas.append(f.read())
+        results = [None] * len(part)
+        for i, data in enumerate(datas):
+            try:
+                parse_container(data)
+                good.append(i)
+            except ValueError:
+                pass
+        try:
+            for i, img in zip(good, codec.decompress_many([datas[i] for i in good])):
+                results[i] = (img, None)
+        except ValueError:
+            good = []                                      # (another model, a decoder status: file by file below)
+        rest = [i for i in range(len(part)) if results[i] is None]
+        try:
+            for i, r in zip(rest, codec.salvage_many([datas[i] for i in rest])):
+                results[i] = r
+        except ValueError:
+            for i in rest:                                 # one of them cannot be recovered: find out which
+                try:
+                    results[i] = (codec.decompress(datas[i]), None)
+                except ValueError:
+                    try:
+                        results[i] = codec.salvage(datas[i])
+                    except ValueError as e:
+                        print('error: {}: {}'.format(part[i][0], e), file=sys.stderr)
+        for (src, dst), data, res in zip(part, datas, results):
+            if res is None:
+                continue
+            img, report = res
+            Image.fromarray(img).save(dst)
+            print(_decompress_line(dst, img, len(data)))
+            if report is not None and (report.damaged or not report.file_crc_ok):
+                print(_damage_line(src, report))
+            written, total_in, total_pixels = written + 1, total_in + len(data), total_pixels + img.shape[0] * img.shape[1]
+    print('total: {} of {} files, {} pixels from {} bytes'.format(written, len(jobs), total_pixels, total_in))
+    return 0 if written == len(jobs) else 2
+
+
+def list_verify_files(paths):
+    """verify's arguments -> the files it checks: a file as it is, a directory's *.icf sorted by name"""
+    files = []
+    for path in paths:
+        if os.path.isdir(path):
+            files += [os.path.join(path, n) for n in sorted(os.listdir(path))
+                      if n.lower().endswith('.icf') and os.path.isfile(os.path.join(path, n))]
+        else:
+            files.append(path)
+    return files
+
+
+def verify_file(data):
+    """container bytes -> (ok, text).  The strict reader decides; for a format-4 file that it refuses, the salvage reader names
+    the damaged tiles.  Host only: no model, no device."""
+    try:
+        c = parse_container(data)
+        return True, 'ok (format {}, {} bytes)'.format(c.version, len(data))
+    except ValueError as strict:
+        try:
+            c, damage, file_crc_ok = parse_salvage(data)
+        except ValueError as e:
+            if len(data) >= 6 and data[:4] == MAGIC and struct.unpack('<H', data[4:6])[0] == FORMAT_VERSION_CHECKED:
+                return False, str(e)
+            return False, str(strict)
+        if not damage:
+            return False, 'all {} tiles intact, but {}'.format(len(c.streams), strict)
+        return False, '{} of {} tiles damaged: {}'.format(len(damage), len(c.streams), ', '.join(
+            'tile {} ({})'.format(t, why) for t, why in damage))
+
+
+def _main_verify(argv):
+    p = argparse.ArgumentParser(prog='codec verify', description='check codec files on the host: no model, no device')
+    p.add_argument('paths', nargs='+', metavar='PATH', help='a codec file, or a directory whose *.icf files are checked')
+    flags = p.parse_args(argv)
+    bad = 0
+    files = list_verify_files(flags.paths)
+    for path in files:
+        try:
+            with open(path, 'rb') as f:
+                ok, text = verify_file(f.read())
+        except (IOError, OSError) as e:
+            ok, text = False, 'cannot read: {}'.format(e)
+        bad += not ok
+        print('{}: {}'.format(path, text))
+    if not files:
+        print('verify: no file to check', file=sys.stderr)
+        return 1
+    return 1 if bad else 0
+
+
 def main(argv=None):
+    argv = sys.argv[1:] if argv is None else list(argv)
+    if argv and argv[0] == 'verify':
+        return _main_verify(argv[1:])
     p = argparse.ArgumentParser(description='compress an image to a codec file, or a codec file back to an image; '
                                             'the -dir commands do so for every file of a directory, --batch files per call')
     p.add_argument('command', choices=['compress', 'decompress', 'compress-dir', 'decompress-dir'])
@@ -616,6 +925,10 @@ def main(argv=None):
                    help='compress: square tiles of this many image pixels (a positive multiple of the subsampling factor), one stream '
                         'per tile, decoded concurrently (format 2); default: one stream (format 1)')
     p.add_argument('--batch', type=int, default=8, metavar='N', help='compress-dir / decompress-dir: files per call (default 8)')
+    p.add_argument('--checked', action='store_true', help='compress / compress-dir with --tile: a CRC per tile stream and one over the '
+                                                          'header (format 4), so that a damaged file can be salvaged')
+    p.add_argument('--salvage', action='store_true', help='decompress / decompress-dir: read what a damaged format-4 file still holds; '
+                                                          'damaged tiles are filled from their neighbours and named')
     flags = p.parse_args(argv)
     from . import config_parser, val, weights as _weights
     try:
@@ -623,6 +936,7 @@ def main(argv=None):
         pc_config, _ = config_parser.parse(_resolve_config(flags.pc_config, 'pc_configs', 'CONFIG_BASE_PC'))
         if flags.command.endswith('-dir'):
             return _main_dir(flags, ae_config, pc_config)
+        check_option_args(flags)
         if flags.weights == 'synthetic':
             wts = _weights.synthetic_weights(ae_config, pc_config, seed=flags.synthetic_seed)
         else:
@@ -633,8 +947,21 @@ def main(argv=None):
                 if flags.tile <= 0 or flags.tile % codec.factor != 0:
                     raise ValueError('--tile {} is not a positive multiple of the subsampling factor {}'.format(flags.tile, codec.factor))
                 codec.tile = (flags.tile // codec.factor, flags.tile // codec.factor)
+                codec.checked = flags.checked
             data, pixels = codec.compress_file(flags.input, flags.output)
             print(_compress_line(flags.output, data, pixels))
+        elif flags.salvage:
+            from PIL import Image
+            with open(flags.input, 'rb') as f:
+                data = f.read()
+            try:
+                img, report = codec.decompress(data), None
+            except ValueError:
+                img, report = codec.salvage(data)
+            Image.fromarray(img).save(flags.output)
+            print(_decompress_line(flags.output, img, len(data)))
+            if report is not None and (report.damaged or not report.file_crc_ok):
+                print(_damage_line(flags.input, report))
         else:
             img = codec.decompress_file(flags.input, flags.output)
             print(_decompress_line(flags.output, img, os.path.getsize(flags.input)))

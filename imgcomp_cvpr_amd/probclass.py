@@ -471,20 +471,25 @@ class PredictionNetwork(object):
                 res[n][t] = r
         return res
 
-    def decode_tiles_batch(self, volumes, th, tw, want='q', max_workspace_bytes=1 << 31, flags=0):
+    def decode_tiles_batch(self, volumes, th, tw, want='q', max_workspace_bytes=1 << 31, flags=0, conceal=False):
         """The mirror of encode_tiles_batch: the tiles of ALL volumes decoded by one launch per chunk (ic_pc_decode_tiles_batch_f32,
         one work-group per tile).  volumes: [(streams, first_syms, (C,h,w))], each as decode_tiles takes them, one C throughout.
         want: 'q' -> per volume the (C,h,w) float32 DEVICE tensor centers[symbols] (what ae.decode consumes: the symbols never
         visit the host), 'symbols' -> the (C,h,w) int64 device tensor, 'both' -> (q, symbols) pairs.
         The workspace is one slot per tile, so the tile list is cut into chunks whose workspace stays within max_workspace_bytes
-        (chunk_tiles; a cut may fall inside a volume); the chunks run one after the other on the current stream."""
+        (chunk_tiles; a cut may fall inside a volume); the chunks run one after the other on the current stream.
+        A subset: streams[t] may be None -- that tile is skipped, nothing of it is uploaded and no work-group runs for it.
+        conceal=False: its cells are 0 (symbol 0, q 0.0).  conceal=True: skipped tiles (reason 'missing') and tiles whose decoder
+        status is not 0 (reason 'decoder', instead of the ValueError) are the damaged set; one launch of ic_pc_conceal_tiles
+        behind the decoder fills them from their intact neighbours (include/imgcomp_hip.h has the rule; the fallback symbol is
+        the centre of smallest magnitude), and the call returns (result as above, [per volume [(tile, reason)] in tile order])."""
         from .codec import tile_grid, chunk_tiles
         if want not in ('q', 'symbols', 'both'):
             raise ValueError("want is 'q', 'symbols' or 'both', got {!r}".format(want))
         if not volumes:
-            return []
+            return ([], []) if conceal else []
         dev = self.centers.device
-        shapes, tiles, where, blobs, pos = [], [], [], [], 0
+        shapes, grids, tiles, where, blobs, pos, missing = [], [], [], [], [], 0, []
         for n, (streams, first_syms, shape) in enumerate(volumes):
             C, h, w = (int(v) for v in shape)
             if C != int(volumes[0][2][0]):
@@ -494,7 +499,11 @@ class PredictionNetwork(object):
                 raise ValueError('volume {}: {} streams and {} first symbols for a grid of {} tiles'.format(
                     n, len(streams), len(first_syms), len(grid)))
             shapes.append((C, h, w))
+            grids.append(grid)
             for t, (y0, x0, a, b) in enumerate(grid):
+                if streams[t] is None:
+                    missing.append((n, t))
+                    continue
                 tiles.append((y0, x0, a, b, pos, len(streams[t]), first_syms[t], n))
                 where.append((n, t, y0, x0))
                 blobs.append(bytes(streams[t]))
@@ -508,28 +517,60 @@ class PredictionNetwork(object):
         chunks = chunk_tiles([(a, b) for _, _, a, b, _, _, _, _ in tiles], need, int(max_workspace_bytes))
         table = _lib.tile_table(tiles)
         data = torch.frombuffer(bytearray(b''.join(blobs)) or bytearray(1), dtype=torch.uint8).to(dev)
-        q = torch.empty(total, dtype=torch.float32, device=dev) if want in ('q', 'both') else None
-        sym = torch.empty(total, dtype=torch.int64, device=dev) if want in ('symbols', 'both') else None
+        alloc = torch.zeros if missing else torch.empty
+        q = alloc(total, dtype=torch.float32, device=dev) if want in ('q', 'both') else None
+        sym = alloc(total, dtype=torch.int64, device=dev) if want in ('symbols', 'both') or conceal else None    # the rule reads symbols
         status = torch.zeros(len(tiles), dtype=torch.int32, device=dev)
-        ws_bytes = max(need(max(tiles[i][2] for i in range(a, b)), max(tiles[i][3] for i in range(a, b)), b - a) for a, b in chunks)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
         centers = self.centers.contiguous().float()
+        if chunks:
+            ws_bytes = max(need(max(tiles[i][2] for i in range(a, b)), max(tiles[i][3] for i in range(a, b)), b - a) for a, b in chunks)
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
         step = ctypes.sizeof(_lib.PcTile)
         for a, b in chunks:
             check(lib.ic_pc_decode_tiles_batch_f32(ptr(data), pos, ctypes.c_void_p(ctypes.addressof(table) + a * step), b - a,
                                                    vtable, len(shapes), self.pc._tab, ptr(centers), k, self.pc.L,
                                                    self.freqs_resolution, ptr(sym), ptr(q), ptr(status[a:b]), C, ptr(ws), ws_bytes,
                                                    int(flags), _lib.current_stream(dev)), 'ic_pc_decode_tiles_batch_f32')
+        damage = [[] for _ in shapes]
+        for n, t in missing:
+            damage[n].append((t, 'missing'))
         for i, st in enumerate(status.tolist()):            # (the host waits here: the tables and the streams are done with)
             if st != 0:
                 n, t, y0, x0 = where[i]
-                raise ValueError('Cannot decode symbol because total is too large (volume {}, tile {} at ({}, {}))'.format(n, t, y0, x0))
+                if not conceal:
+                    raise ValueError('Cannot decode symbol because total is too large (volume {}, tile {} at ({}, {}))'.format(n, t, y0, x0))
+                damage[n].append((t, 'decoder'))
+        damage = [sorted(d) for d in damage]
+        if conceal and any(damage):
+            self._conceal(sym, q, shapes, grids, vtable, damage, th, tw, centers)
         cut = lambda buf: [buf[o:o + c * h * w].view(c, h, w) for (c, h, w), o in zip(shapes, offs)]
-        if want == 'q':
-            return cut(q)
-        if want == 'symbols':
-            return cut(sym)
-        return list(zip(cut(q), cut(sym)))
+        res = cut(q) if want == 'q' else cut(sym) if want == 'symbols' else list(zip(cut(q), cut(sym)))
+        return (res, damage) if conceal else res
+
+    def conceal_fallback(self):
+        """the symbol a tile gets that has no intact neighbour: the centre of smallest magnitude (ties: the smallest index), what
+        the quantiser emits where the importance map has masked a channel"""
+        return int(np.argmin(np.abs(self.centers.detach().float().cpu().numpy())))
+
+    def _conceal(self, sym, q, shapes, grids, vtable, damage, th, tw, centers):
+        """one ic_pc_conceal_tiles launch on the current stream for the damaged tiles of all volumes; sym / q as decode_tiles_batch
+        lays them out (q may be None)"""
+        dev = self.centers.device
+        marks, tiles = [], []
+        for n, (grid, dmg) in enumerate(zip(grids, damage)):
+            m = bytearray(len(grid))
+            for t, _ in dmg:
+                m[t] = 1
+                tiles.append(grid[t] + (0, 0, 0, n))
+            marks.append(bytes(m))
+        marks = b''.join(marks)
+        table, host_marks = _lib.tile_table(tiles), ctypes.create_string_buffer(marks, len(marks))
+        need = int(lib.ic_pc_conceal_tiles_workspace_bytes(len(tiles), len(shapes), len(marks)))
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        check(lib.ic_pc_conceal_tiles(ptr(sym), ptr(q), table, len(tiles), vtable, len(shapes), host_marks, ptr(centers), self.pc.L,
+                                      self.conceal_fallback(), shapes[0][0], int(th), int(tw), ptr(ws), need,
+                                      _lib.current_stream(dev)), 'ic_pc_conceal_tiles')
+        torch.cuda.current_stream(dev).synchronize()        # the three host tables and the workspace are done with
 
     def get_pr(self, input_ctx):
         """:param input_ctx: symbols of ONE context, CHW = input_ctx_shape -> (L,) float32."""

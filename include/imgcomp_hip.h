@@ -315,6 +315,26 @@ int ic_pc_decode_tiles_batch_f32(const uint8_t* bitstreams, long long total_byte
                                  const ic_pc_volume_t* volumes_host, int nvolumes, const float* const* wtab_host,
                                  const float* centers, int k, int L, float resolution, int64_t* symbols, float* q, int* status,
                                  int C, void* workspace, size_t workspace_bytes, int flags, ic_stream_t stream);
+/* Concealment: what stands in the volumes where a tile could not be decoded (a damaged file; codec.py, salvage).  Stated on symbols,
+ * so exact: for a damaged tile T and a channel c the candidates are the symbols of channel c directly above T's top row, below its
+ * bottom row, left of its left column and right of its right column (no corners) that lie inside the volume and in a tile that
+ * is not damaged; every position of T in channel c gets the most frequent candidate (ties: the smallest symbol; a symbol outside
+ * [0, L) is no candidate), or `fallback` where there is none.  Damaged tiles never read each other: one launch of ntiles x C
+ * work-groups, no order among them; it belongs on the stream behind the decode launch that filled the intact tiles.
+ *   symbols: in / out, device int64, laid out by volumes_host as for ic_pc_decode_tiles_batch_f32;  q: out, may be NULL:
+ *     centers[symbol] at the same positions (q_off).  Only cells of the listed tiles are written, only cells of tiles that the
+ *     map calls intact are read.
+ *   tiles_host: HOST array of the ntiles DAMAGED tiles (y0, x0, th, tw, volume; the stream fields and first_sym are not read).
+ *   th, tw: the nominal tile extent of every volume's grid;  damaged_host: HOST bytes, one per grid cell, volume after volume in
+ *     raster order (ceil(h / th) * ceil(w / tw) per volume), non-zero = damaged.  All three tables are read before the call returns.
+ *   Checked on the host before any device call (IC_ERR_ARG): non-null pointers, ntiles, nvolumes, C, L >= 1, C <= 65535, th, tw >= 1,
+ *     0 <= fallback < L, every volume as above, every tile inside its volume AND exactly one cell of its grid AND damaged in the map.
+ *     L > 16: IC_ERR_UNSUPPORTED.  workspace: ic_pc_conceal_tiles_workspace_bytes(ntiles, nvolumes, number of grid cells). */
+size_t ic_pc_conceal_tiles_workspace_bytes(int ntiles, int nvolumes, long long ngrid);
+int ic_pc_conceal_tiles(int64_t* symbols, float* q, const ic_pc_tile_t* tiles_host, int ntiles,
+                        const ic_pc_volume_t* volumes_host, int nvolumes, const uint8_t* damaged_host,
+                        const float* centers, int L, int fallback, int C, int th, int tw,
+                        void* workspace, size_t workspace_bytes, ic_stream_t stream);
 /* The encoder side of the real-bpp path on the device: the mirror image of ic_pc_decode_f32.  Codes N symbol volumes in one
  * launch (one work-group per volume) with the 32-bit range coder of arithmetic_coding.py; the stream of each volume is byte
  * for byte arithmetic_coding.encode_sequence(symbols[1:], freqs[1:]) over the tables ic_pc_logits_to_freqs_f32 derives from
