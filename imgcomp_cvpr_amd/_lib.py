@@ -40,6 +40,7 @@ def CONV3_IN_FLIGHT(n):
     return (min(int(n), 15) & 0xf) << 19
 PC_DECODE_PER_LAYER = 0x01
 PC_DECODE_RECOMPUTE = 0x02
+PC_DECODE_WAVEFRONT = 0x04           # ic_pc_decode_tiles_batch_f32: streams in wavefront order (format 5)
 
 
 def conv3_leave_idle_layers(n):

@@ -1,9 +1,9 @@
 """Image codec: an image to a self-describing file and back.
 
     python -m imgcomp_cvpr_amd.codec compress   IN.png  OUT.icf [--ae_config cvpr/low] [--pc_config cvpr/res_shallow] [--weights synthetic|FILE.npz|CKPT]
-                                                                [--tile PIXELS [--checked]]
+                                                                [--tile PIXELS [--checked | --wavefront]]
     python -m imgcomp_cvpr_amd.codec decompress IN.icf  OUT.png [same options] [--salvage]
-    python -m imgcomp_cvpr_amd.codec compress-dir   IN_DIR OUT_DIR [--tile PIXELS [--checked]] [--batch N]   every *.png / *.jpg -> OUT_DIR/<stem>.icf
+    python -m imgcomp_cvpr_amd.codec compress-dir   IN_DIR OUT_DIR [--tile PIXELS [--checked | --wavefront]] [--batch N]   every *.png / *.jpg -> OUT_DIR/<stem>.icf
     python -m imgcomp_cvpr_amd.codec decompress-dir IN_DIR OUT_DIR [--batch N] [--salvage]                   every *.icf -> OUT_DIR/<stem>.png
     python -m imgcomp_cvpr_amd.codec verify PATH [PATH ...]         files or directories of *.icf: the checksums, without model or device
 
@@ -54,6 +54,13 @@ filled on the device from their intact neighbours (ic_pc_conceal_tiles) and name
     ..      4     header CRC-32: of every byte before it (magic up to and including the payload length)
     ..      n     payload: the tiles' streams back to back, in table order
     ..      4     CRC-32 of every byte before it (u32)
+--tile --wavefront (Codec(tile=(th, tw), order='wavefront')): format 5, "wavefront tiles" -- the layout of format 4 byte for byte
+(header, 10-byte tile rows with a CRC per stream, header CRC, file CRC; --checked is implied), version 5, but a tile's stream codes
+its symbols in wavefront order: sorted by (T, c, y, x) with T = x + 2 y + 4 c in the tile's own coordinates (wavefront_order; every
+tile by its own extent), the first of them -- (0, 0, 0) -- uncoded as first_sym.  The four masked layers of the context model make a
+symbol depend only on symbols of smaller T (wavefront_is_valid derives that from the masks), so the decoder evaluates the network
+for all symbols of one T at once and only the range decoder's step per symbol stays serial.  The tables are those of the tile coded
+as its own volume, as in format 2; only their order in the stream differs.  salvage and verify read it like format 4.
 Every failure of parse / decompress is a ValueError that names the cause; nothing of a refused file reaches the device.
 The -dir commands and Codec.compress_many / decompress_many work on a list of images at once: the same bytes and the same pixels as
 the single-image calls, file by file, but the tiles of all files are coded by one launch each way (ic_pc_decode_tiles_batch_f32: one
@@ -85,7 +92,11 @@ TiledContainer = namedtuple('TiledContainer', ['version', 'ae_name', 'pc_name', 
 
 FORMAT_VERSION_CHECKED = 4                                           # 3 is not used: it stays "unsupported"
 CheckedContainer = namedtuple('CheckedContainer', TiledContainer._fields + ('stream_crcs',))
-_TILED = (TiledContainer, CheckedContainer)
+FORMAT_VERSION_WAVEFRONT = 5                                         # the layout of 4, the streams in wavefront order
+WavefrontContainer = namedtuple('WavefrontContainer', CheckedContainer._fields)
+_TILED = (TiledContainer, CheckedContainer, WavefrontContainer)
+_WITH_CRCS = (FORMAT_VERSION_CHECKED, FORMAT_VERSION_WAVEFRONT)
+WAVEFRONT_COEFFS = (2, 4)                                            # T = x + 2 y + 4 c: fixed by format 5
 
 # what salvage tells about a file: damaged is [DamagedTile] in tile order; latent = (y0, x0, th, tw) in the symbol volume, pixels =
 # (y0, x0, height, width) in the returned image, clipped to it (height or width 0: the tile lies in the padding)
@@ -100,6 +111,69 @@ def tile_grid(h, w, th, tw):
     if h < 1 or w < 1 or th < 1 or tw < 1:
         raise ValueError('tile grid: plane {} x {} and tile {} x {} must all be at least 1'.format(h, w, th, tw))
     return [(y0, x0, min(th, h - y0), min(tw, w - x0)) for y0 in range(0, h, th) for x0 in range(0, w, tw)]
+
+
+def wavefront_dependencies(masks, num_layers):
+    """the positions a symbol's table depends on, as offsets (dc, dy, dx) from it: masks = (first mask, other mask), each
+    (KD, KH, KW[, 1, 1]) with the current position at the centre of the last slice; the first layer uses the first mask, the
+    num_layers - 1 layers behind it the other one.  The set is the Minkowski sum of the layers' live offsets."""
+    first, other = (np.asarray(m, dtype=np.float64) for m in masks)
+    first, other = first.reshape(first.shape[:3]), other.reshape(other.shape[:3])
+    if int(num_layers) < 1:
+        raise ValueError('a context model has at least one layer, got {}'.format(num_layers))
+
+    def live(mask):
+        KD, KH, KW = mask.shape
+        return [(kd - (KD - 1), kh - KH // 2, kw - KW // 2) for kd in range(KD) for kh in range(KH) for kw in range(KW) if mask[kd, kh, kw] != 0]
+
+    deps = set(live(first))
+    for _ in range(int(num_layers) - 1):
+        step = live(other)
+        deps = set((a[0] + b[0], a[1] + b[1], a[2] + b[2]) for a in deps for b in step)
+    return deps
+
+
+def wavefront_is_valid(masks, num_layers, a, b):
+    """does T = x + a y + b c order the symbols so that every symbol depends only on symbols of strictly smaller T?  Then all
+    symbols of one T are independent of each other and can be decoded together."""
+    return all(dx + a * dy + b * dc < 0 for dc, dy, dx in wavefront_dependencies(masks, num_layers))
+
+
+def wavefront_coeffs(pc):
+    """(a, b) of format 5 -- always WAVEFRONT_COEFFS = (2, 4) -- for a context model (probclass network object) whose own masks
+    and layer count make it a valid order and whose width the wavefront decoder covers (k = 24); a ValueError otherwise."""
+    a, b = WAVEFRONT_COEFFS
+    if not wavefront_is_valid((pc.create_first_mask(), pc.create_other_mask()), pc.get_num_layers(), a, b):
+        raise ValueError('wavefront order: T = x + {} y + {} c does not order the dependencies of this context model '
+                         '({} layers)'.format(a, b, pc.get_num_layers()))
+    k = getattr(pc, '_k', None)
+    if k is None:
+        k = int(pc.config.arch_param__k)
+    if int(k) != 24:
+        raise ValueError('wavefront order: the wavefront decoder covers context models of width k = 24, this one has k = {}'.format(k))
+    return a, b
+
+
+_ORDER_CACHE = {}
+
+
+def wavefront_order(C, th, tw):
+    """the coding order of format 5 for a (C, th, tw) tile: the flat raster indices c * th * tw + y * tw + x sorted by (T, c, y, x),
+    T = x + 2 y + 4 c -> int64 array of C * th * tw elements.  Element 0 is index 0, the uncoded first symbol."""
+    C, th, tw = int(C), int(th), int(tw)
+    if C < 1 or th < 1 or tw < 1:
+        raise ValueError('wavefront order: tile {} x {} x {} must be at least 1 in every extent'.format(C, th, tw))
+    key = (C, th, tw)
+    if key not in _ORDER_CACHE:
+        a, b = WAVEFRONT_COEFFS
+        c, y, x = np.meshgrid(np.arange(C), np.arange(th), np.arange(tw), indexing='ij')
+        # raster order already is (c, y, x): a stable sort by T alone keeps it inside a front
+        order = np.argsort((x + a * y + b * c).reshape(-1), kind='stable').astype(np.int64)
+        order.setflags(write=False)
+        if len(_ORDER_CACHE) > 64:
+            _ORDER_CACHE.clear()
+        _ORDER_CACHE[key] = order
+    return _ORDER_CACHE[key]
 
 
 def chunk_tiles(tile_shapes, need, budget):
@@ -175,6 +249,17 @@ def build_checked_container(ae_name, pc_name, H, W, C, h, w, L, resolution, fing
     return body + struct.pack('<I', zlib.crc32(body) & 0xffffffff)
 
 
+def build_wavefront_container(ae_name, pc_name, H, W, C, h, w, L, resolution, fingerprint, th, tw, first_syms, streams):
+    """format 5: the bytes of format 4 with version 5; streams[t] codes tile t's symbols in wavefront_order(C, th', tw')."""
+    streams = [bytes(b) for b in streams]
+    assert len(first_syms) == len(streams)
+    head = _tiled_head(FORMAT_VERSION_WAVEFRONT, ae_name, pc_name, H, W, C, h, w, L, resolution, fingerprint, th, tw,
+                       [struct.pack('<HII', f, len(b), zlib.crc32(b) & 0xffffffff) for f, b in zip(first_syms, streams)],
+                       sum(len(b) for b in streams))
+    body = head + struct.pack('<I', zlib.crc32(head) & 0xffffffff) + b''.join(streams)
+    return body + struct.pack('<I', zlib.crc32(body) & 0xffffffff)
+
+
 def build_container(ae_name, pc_name, H, W, C, h, w, L, first_sym, resolution, fingerprint, payload):
     a, p = ae_name.encode('utf-8'), pc_name.encode('utf-8')
     head = b''.join([
@@ -206,18 +291,19 @@ class _Reader(object):
 
 
 def parse_container(data):
-    """bytes -> Container (version 1), TiledContainer (version 2) or CheckedContainer (version 4).  Order: size, magic, version, CRC
-    over the whole file -- only then are the header's lengths read, each against the bytes that remain; the payload length must
-    equal exactly what is left before the CRC.  Version 4 in addition: its header CRC and every tile's stream CRC."""
+    """bytes -> Container (version 1), TiledContainer (version 2), CheckedContainer (version 4) or WavefrontContainer (version 5).
+    Order: size, magic, version, CRC over the whole file -- only then are the header's lengths read, each against the bytes that
+    remain; the payload length must equal exactly what is left before the CRC.  Versions 4 and 5 in addition: the header CRC and
+    every tile's stream CRC."""
     data = bytes(data)
     if len(data) < _MIN_SIZE:
         raise ValueError('truncated file: {} bytes, the smallest container has {}'.format(len(data), _MIN_SIZE))
     if data[:4] != MAGIC:
         raise ValueError('wrong magic {!r}: not a codec file (expected {!r})'.format(data[:4], MAGIC))
     version, = struct.unpack('<H', data[4:6])
-    if version not in (FORMAT_VERSION, FORMAT_VERSION_TILED, FORMAT_VERSION_CHECKED):
-        raise ValueError('unsupported format version {} (this codec reads versions {}, {} and {})'.format(
-            version, FORMAT_VERSION, FORMAT_VERSION_TILED, FORMAT_VERSION_CHECKED))
+    if version not in (FORMAT_VERSION, FORMAT_VERSION_TILED, FORMAT_VERSION_CHECKED, FORMAT_VERSION_WAVEFRONT):
+        raise ValueError('unsupported format version {} (this codec reads versions {}, {} and {}) and the wavefront version {}'.format(
+            version, FORMAT_VERSION, FORMAT_VERSION_TILED, FORMAT_VERSION_CHECKED, FORMAT_VERSION_WAVEFRONT))
     stored, = struct.unpack('<I', data[-4:])
     actual = zlib.crc32(data[:-4]) & 0xffffffff
     if stored != actual:
@@ -251,7 +337,7 @@ def _parse_front(r):
 
 
 def _parse_tile_table(r, version, h, w):
-    """L .. payload length of a format-2 / format-4 header, every length against the bytes that remain -> (L, resolution,
+    """L .. payload length of a format-2 / format-4 / format-5 header, every length against the bytes that remain -> (L, resolution,
     fingerprint, th, tw, first_syms, lengths, crcs or None, n)"""
     L, = r.unpack('<H', 'L')
     resolution, = r.unpack('<d', 'frequency resolution')
@@ -266,7 +352,7 @@ def _parse_tile_table(r, version, h, w):
     if ntiles != expected:
         raise ValueError('tile count {} does not equal the {} tiles of a {} x {} volume cut into {} x {}'.format(
             ntiles, expected, h, w, th, tw))
-    checked = version == FORMAT_VERSION_CHECKED
+    checked = version in _WITH_CRCS
     row = 10 if checked else 6
     table = r.take(row * ntiles, 'tile table')            # against the bytes that remain, before anything of its size is built
     first_syms, lengths, crcs = [], [], [] if checked else None
@@ -287,7 +373,7 @@ def _parse_tile_table(r, version, h, w):
 
 
 def _parse_tiled(r, version, ae_name, pc_name, H, W, C, h, w):
-    """the rest of a format-2 / format-4 file after the symbol volume shape (the CRC over the file has been checked)."""
+    """the rest of a format-2 / format-4 / format-5 file after the symbol volume shape (the CRC over the file has been checked)."""
     L, resolution, fingerprint, th, tw, first_syms, lengths, crcs, n = _parse_tile_table(r, version, h, w)
     if crcs is not None:
         end = r.pos
@@ -309,11 +395,12 @@ def _parse_tiled(r, version, ae_name, pc_name, H, W, C, h, w):
         actual = zlib.crc32(b) & 0xffffffff
         if actual != crc:
             raise ValueError('stream CRC mismatch in tile {}: the table says {:08x}, the stream gives {:08x}'.format(t, crc, actual))
-    return CheckedContainer(version, ae_name, pc_name, H, W, C, h, w, L, resolution, fingerprint, th, tw, first_syms, streams, payload, crcs)
+    cls = WavefrontContainer if version == FORMAT_VERSION_WAVEFRONT else CheckedContainer
+    return cls(version, ae_name, pc_name, H, W, C, h, w, L, resolution, fingerprint, th, tw, first_syms, streams, payload, crcs)
 
 
 def parse_salvage(data):
-    """what a possibly damaged format-4 file still holds -> (CheckedContainer, damage, file_crc_ok).  damage: [(tile, reason)] in
+    """what a possibly damaged format-4 or format-5 file still holds -> (CheckedContainer or WavefrontContainer, damage, file_crc_ok).  damage: [(tile, reason)] in
     tile order, reason 'crc' (the bytes are there, their CRC differs) or 'truncated' (the tile's byte range is not complete);
     streams[t] of such a tile is None.  Order: size, magic, version, then the header up to its own CRC, every length against the
     bytes that are there; a header that fails its CRC is a ValueError, nothing of it is believed.  Behind a good header the
@@ -328,8 +415,9 @@ def parse_salvage(data):
     if version in (FORMAT_VERSION, FORMAT_VERSION_TILED):
         raise ValueError('format version {} has nothing to salvage with: one CRC over the whole file, none per tile (only version {}, '
                          'written with --tile --checked, can be salvaged)'.format(version, FORMAT_VERSION_CHECKED))
-    if version != FORMAT_VERSION_CHECKED:
-        raise ValueError('unsupported format version {} (only version {} can be salvaged)'.format(version, FORMAT_VERSION_CHECKED))
+    if version not in _WITH_CRCS:
+        raise ValueError('unsupported format version {} (only version {} can be salvaged) or the wavefront version {}'.format(
+            version, FORMAT_VERSION_CHECKED, FORMAT_VERSION_WAVEFRONT))
     r = _Reader(data)
     try:
         ae_name, pc_name, H, W, C, h, w = _parse_front(r)
@@ -341,8 +429,8 @@ def parse_salvage(data):
         raise ValueError('header damaged: nothing can be recovered ({})'.format(e))
     actual = zlib.crc32(data[:end]) & 0xffffffff
     if stored != actual:
-        raise ValueError('header damaged: nothing can be recovered (header CRC mismatch: file says {:08x}, the header gives {:08x})'.format(
-            stored, actual))
+        raise ValueError('header damaged: nothing can be recovered (header CRC mismatch: file says {:08x}, the header of this '
+                         'version-{} file gives {:08x})'.format(stored, version, actual))
     start = r.pos
     payload = data[start:start + n]                        # what arrived of it
     streams, damage, pos = [], [], 0
@@ -358,8 +446,8 @@ def parse_salvage(data):
         pos += n_t
     tail = data[start + n:start + n + 4]
     file_crc_ok = len(payload) == n and len(tail) == 4 and struct.unpack('<I', tail)[0] == zlib.crc32(data[:start + n]) & 0xffffffff
-    return (CheckedContainer(version, ae_name, pc_name, H, W, C, h, w, L, resolution, fingerprint, th, tw, first_syms, streams, payload,
-                             crcs), damage, file_crc_ok)
+    cls = WavefrontContainer if version == FORMAT_VERSION_WAVEFRONT else CheckedContainer
+    return cls(version, ae_name, pc_name, H, W, C, h, w, L, resolution, fingerprint, th, tw, first_syms, streams, payload, crcs), damage, file_crc_ok
 
 
 def model_fingerprint(centers, pc_params):
@@ -386,23 +474,37 @@ class Codec(object):
     device_encode: which range encoder writes the payload -- the bytes are the same either way (tests/test_gpu_codec.py); the
     default is the one that measured faster end to end on a Kodak volume.
     tile: None writes format 1; (th, tw) in symbol-volume units writes format 2, one stream per tile; with checked=True format 4,
-    the same streams with a CRC each (salvage reads what a damaged one still holds).  Reading needs no option: the file's version
-    decides."""
+    the same streams with a CRC each (salvage reads what a damaged one still holds).  order: 'raster' as above; 'wavefront' (needs
+    a tile extent) writes format 5, the layout of format 4 with every tile's symbols coded front by front, which the decoder
+    takes a front at a time -- refused here, with a ValueError, for a context model whose masks do not make T = x + 2 y + 4 c a
+    valid order or whose width the wavefront decoder does not cover.  Reading needs no option: the file's version decides."""
 
-    def __init__(self, ae_config, pc_config, weights, device='cuda', plan_flags=0, device_encode=True, tile=None, checked=False):
+    def __init__(self, ae_config, pc_config, weights, device='cuda', plan_flags=0, device_encode=True, tile=None, checked=False,
+                 order='raster'):
         if tile is not None:
             tile = (int(tile[0]), int(tile[1]))
             if not (1 <= tile[0] <= 0xffff and 1 <= tile[1] <= 0xffff):
                 raise ValueError('tile extent {} x {} is outside 1 .. 65535'.format(*tile))
         if checked and tile is None:
             raise ValueError('checked=True needs a tile extent: the checksums of format 4 are per tile')
-        self.tile, self.checked = tile, bool(checked)
+        if order not in ('raster', 'wavefront'):
+            raise ValueError("order is 'raster' or 'wavefront', got {!r}".format(order))
+        if order == 'wavefront' and tile is None:
+            raise ValueError("order='wavefront' needs a tile extent: format 5 is a tiled format")
+        self.tile, self.checked, self.order = tile, bool(checked), order
         import torch
         from . import autoencoder, probclass
         self.device = torch.device(device)
         self.ae = autoencoder.get_network_cls(ae_config)(ae_config).load_weights(weights, self.device)
         self.pc = probclass.get_network_cls(pc_config)(pc_config, num_centers=ae_config.num_centers).load_weights(weights, self.device)
         self.ae.plan_flags = int(plan_flags)
+        try:
+            wavefront_coeffs(self.pc)
+            self.wavefront_refusal = None
+        except ValueError as e:
+            self.wavefront_refusal = str(e)
+        if order == 'wavefront' and self.wavefront_refusal:
+            raise ValueError(self.wavefront_refusal)
         self.pred = probclass.PredictionNetwork(self.pc, pc_config, self.ae.get_centers_variable())
         self.ae_name, self.pc_name = config_name(ae_config), config_name(pc_config)
         self.factor = int(self.ae.get_subsampling_factor())
@@ -447,7 +549,7 @@ class Codec(object):
         C, h, w = (int(v) for v in sym.shape)
         if self.tile is not None:
             th, tw = self.tile
-            coded = self.pred.encode_tiles(sym, th, tw)
+            coded = self.pred.encode_tiles(sym, th, tw, order=self._order())
             return self._build_tiled(self.ae_name, self.pc_name, H, W, C, h, w, self.L, self.pred.freqs_resolution,
                                          self.fingerprint, th, tw, [f for _, f in coded], [b for b, _ in coded])
         if self.device_encode:
@@ -457,10 +559,23 @@ class Codec(object):
         return build_container(self.ae_name, self.pc_name, H, W, C, h, w, self.L, first_sym, self.pred.freqs_resolution,
                                self.fingerprint, payload)
 
+    def _order(self):
+        """the order compress writes (the attributes may have been set after construction, as main does)"""
+        if self.order not in ('raster', 'wavefront'):
+            raise ValueError("order is 'raster' or 'wavefront', got {!r}".format(self.order))
+        if self.order == 'wavefront':
+            if self.tile is None:
+                raise ValueError("order='wavefront' needs a tile extent: format 5 is a tiled format")
+            if self.wavefront_refusal:
+                raise ValueError(self.wavefront_refusal)
+        return self.order
+
     @property
     def _build_tiled(self):
         if self.checked and self.tile is None:
             raise ValueError('checked=True needs a tile extent: the checksums of format 4 are per tile')
+        if self._order() == 'wavefront':
+            return build_wavefront_container                 # (checked or not: format 5 always carries the checksums)
         return build_checked_container if self.checked else build_tiled_container
 
     def check_container(self, c):
@@ -481,6 +596,8 @@ class Codec(object):
         if (c.h, c.w) != (eh, ew):
             raise ValueError('header mismatch: symbol volume {} x {} does not belong to a {} x {} image (expected {} x {})'.format(
                 c.h, c.w, c.H, c.W, eh, ew))
+        if isinstance(c, WavefrontContainer) and self.wavefront_refusal:
+            raise ValueError('format 5 cannot be read with this model: {}'.format(self.wavefront_refusal))
         for first_sym in (c.first_syms if isinstance(c, _TILED) else [c.first_sym]):
             if first_sym >= c.L:
                 raise ValueError('header mismatch: first symbol {} is not below L = {}'.format(first_sym, c.L))
@@ -493,7 +610,10 @@ class Codec(object):
         c = parse_container(data)
         self.check_container(c)
         try:
-            if isinstance(c, _TILED):
+            if isinstance(c, WavefrontContainer):        # a batch of one: the order is a flag of the batch entry
+                sym = self.pred.decode_tiles_batch([(c.streams, c.first_syms, (c.C, c.h, c.w))], c.th, c.tw, want='symbols',
+                                                   order='wavefront')[0].cpu().numpy()
+            elif isinstance(c, _TILED):
                 sym = self.pred.decode_tiles(c.streams, c.first_syms, (c.C, c.h, c.w), c.th, c.tw)
             else:
                 sym = self.pred.decode_stream(c.payload, (c.C, c.h, c.w), c.first_sym)
@@ -568,7 +688,7 @@ class Codec(object):
         out = [None] * len(syms)
         if self.tile is not None:
             th, tw = self.tile
-            for i, coded in enumerate(self.pred.encode_tiles_batch(syms, th, tw)):
+            for i, coded in enumerate(self.pred.encode_tiles_batch(syms, th, tw, order=self._order())):
                 C, h, w = (int(v) for v in syms[i].shape)
                 out[i] = self._build_tiled(self.ae_name, self.pc_name, sizes[i][0], sizes[i][1], C, h, w, self.L,
                                                self.pred.freqs_resolution, self.fingerprint, th, tw,
@@ -595,7 +715,8 @@ class Codec(object):
         Every file is parsed and checked first; the first refusal raises its ValueError with the index of the file in front and
         nothing has reached the device.  The format-2 / format-4 files of the most frequent tile extent are decoded together
         (decode_tiles_batch: the tiles of all of them in one launch per workspace chunk, the centres q staying on the device) and
-        go through the decoder up to IN_FLIGHT at a time; format-1 files and other tile extents take the single-file path."""
+        go through the decoder up to IN_FLIGHT at a time; so are, in launches of their own (the order is a flag of the call), the
+        format-5 files of their most frequent extent; format-1 files and other tile extents take the single-file path."""
         import torch
         heads = []
         for i, data in enumerate(datas):
@@ -605,15 +726,18 @@ class Codec(object):
             except ValueError as e:
                 raise ValueError('file {}: {}'.format(i, e))
             heads.append(c)
-        extents = [(c.th, c.tw) for c in heads if isinstance(c, _TILED)]
-        major = max(sorted(set(extents)), key=extents.count) if extents else None
-        together = [i for i, c in enumerate(heads) if isinstance(c, _TILED) and (c.th, c.tw) == major]
         out = [None] * len(datas)
-        if together:
+        for order in ('raster', 'wavefront'):
+            mine = [i for i, c in enumerate(heads) if isinstance(c, _TILED) and isinstance(c, WavefrontContainer) == (order == 'wavefront')]
+            extents = [(heads[i].th, heads[i].tw) for i in mine]
+            major = max(sorted(set(extents)), key=extents.count) if extents else None
+            together = [i for i in mine if (heads[i].th, heads[i].tw) == major]
+            if not together:
+                continue
             try:
                 qs = self.pred.decode_tiles_batch([(heads[i].streams, heads[i].first_syms, (heads[i].C, heads[i].h, heads[i].w))
                                                    for i in together], major[0], major[1], want='q',
-                                                  max_workspace_bytes=max_workspace_bytes)
+                                                  max_workspace_bytes=max_workspace_bytes, order=order)
             except ValueError as e:
                 m = re.search(r'volume (\d+)', str(e))
                 where = 'file {}: '.format(together[int(m.group(1))]) if m else ''
@@ -650,20 +774,21 @@ class Codec(object):
         return SalvageReport(len(grid), bool(file_crc_ok), damaged)
 
     def salvage(self, data):
-        """container bytes of format 4, possibly damaged -> (HWC uint8 image, SalvageReport).  Tiles whose bytes are there and match
+        """container bytes of format 4 or 5, possibly damaged -> (HWC uint8 image, SalvageReport).  Tiles whose bytes are there and match
         their CRC are decoded; the others -- and any whose decoder status is not 0 -- are filled on the device from their intact
         neighbours (ic_pc_conceal_tiles) and listed in report.damaged.  An intact file gives decompress(data) and an empty list.
         A ValueError where nothing can be recovered: another format, a damaged header, another model."""
         import torch
         c, reasons, file_crc_ok = self._salvage_head(data)
-        qs, damage = self.pred.decode_tiles_batch([(c.streams, c.first_syms, (c.C, c.h, c.w))], c.th, c.tw, want='q', conceal=True)
+        qs, damage = self.pred.decode_tiles_batch([(c.streams, c.first_syms, (c.C, c.h, c.w))], c.th, c.tw, want='q', conceal=True,
+                                                  order='wavefront' if isinstance(c, WavefrontContainer) else 'raster')
         x_out = self.ae.decode(qs[0][None], is_training=False).to(torch.uint8)   # tf.cast truncates (val.py)
         return self._crop(x_out[0], c), self._report(c, reasons, damage[0], file_crc_ok)
 
     def salvage_many(self, datas, max_workspace_bytes=1 << 31):
-        """[container bytes of format 4] -> [(image, SalvageReport)], element i equal to salvage(datas[i]).  As decompress_many:
+        """[container bytes of format 4 or 5] -> [(image, SalvageReport)], element i equal to salvage(datas[i]).  As decompress_many:
         every file is parsed and checked first (the first refusal raises with the index of the file in front, nothing has reached
-        the device); then per tile extent the intact tiles of all files in one decode launch per workspace chunk, one concealment
+        the device); then per tile extent and order the intact tiles of all files in one decode launch per workspace chunk, one concealment
         launch, q staying on the device, and the autoencoder passes up to IN_FLIGHT at a time."""
         import torch
         heads = []
@@ -673,11 +798,12 @@ class Codec(object):
             except ValueError as e:
                 raise ValueError('file {}: {}'.format(i, e))
         out = [None] * len(datas)
-        for extent in sorted(set((c.th, c.tw) for c, _, _ in heads)):
-            members = [i for i, (c, _, _) in enumerate(heads) if (c.th, c.tw) == extent]
+        kind = lambda c: (c.th, c.tw, 'wavefront' if isinstance(c, WavefrontContainer) else 'raster')
+        for extent in sorted(set(kind(c) for c, _, _ in heads)):
+            members = [i for i, (c, _, _) in enumerate(heads) if kind(c) == extent]
             qs, damage = self.pred.decode_tiles_batch([(heads[i][0].streams, heads[i][0].first_syms, (heads[i][0].C, heads[i][0].h, heads[i][0].w))
                                                        for i in members], extent[0], extent[1], want='q', conceal=True,
-                                                      max_workspace_bytes=max_workspace_bytes)
+                                                      max_workspace_bytes=max_workspace_bytes, order=extent[2])
             imgs = self._in_flight(qs, lambda ae, q: ae.decode(q[None], is_training=False).to(torch.uint8)[0])    # tf.cast truncates (val.py)
             for i, x, dmg in zip(members, imgs, damage):
                 c, reasons, file_crc_ok = heads[i]
@@ -734,12 +860,17 @@ def _damage_line(path, report):
 
 
 def check_option_args(flags):
-    """--checked / --salvage against the command and --tile: decided before any model is built"""
+    """--checked / --wavefront / --salvage against the command and --tile: decided before any model is built"""
     if getattr(flags, 'checked', False):
         if flags.command not in ('compress', 'compress-dir'):
             raise ValueError('--checked belongs to compress / compress-dir: a file says by itself what it is')
         if flags.tile is None:
             raise ValueError('--checked needs --tile: the checksums of format 4 are per tile')
+    if getattr(flags, 'wavefront', False):
+        if flags.command not in ('compress', 'compress-dir'):
+            raise ValueError('--wavefront belongs to compress / compress-dir: a file says by itself what it is')
+        if flags.tile is None:
+            raise ValueError('--wavefront needs --tile: format 5 codes every tile front by front')
     if getattr(flags, 'salvage', False) and flags.command not in ('decompress', 'decompress-dir'):
         raise ValueError('--salvage belongs to decompress / decompress-dir')
 
@@ -771,7 +902,8 @@ def _main_dir(flags, ae_config, pc_config):
         wts = _weights.synthetic_weights(ae_config, pc_config, seed=flags.synthetic_seed)
     else:
         wts = val.load_weights_for_job(None, flags.weights, ae_config, pc_config)
-    codec = Codec(ae_config, pc_config, wts, flags.device, tile=tile, checked=flags.checked)
+    codec = Codec(ae_config, pc_config, wts, flags.device, tile=tile, checked=flags.checked,
+                  order='wavefront' if flags.wavefront and tile is not None else 'raster')
     os.makedirs(flags.output, exist_ok=True)
     total_in = total_out = total_pixels = 0
     if flags.command == 'decompress-dir' and flags.salvage:
@@ -877,7 +1009,7 @@ def verify_file(data):
         try:
             c, damage, file_crc_ok = parse_salvage(data)
         except ValueError as e:
-            if len(data) >= 6 and data[:4] == MAGIC and struct.unpack('<H', data[4:6])[0] == FORMAT_VERSION_CHECKED:
+            if len(data) >= 6 and data[:4] == MAGIC and struct.unpack('<H', data[4:6])[0] in _WITH_CRCS:
                 return False, str(e)
             return False, str(strict)
         if not damage:
@@ -927,7 +1059,9 @@ def main(argv=None):
     p.add_argument('--batch', type=int, default=8, metavar='N', help='compress-dir / decompress-dir: files per call (default 8)')
     p.add_argument('--checked', action='store_true', help='compress / compress-dir with --tile: a CRC per tile stream and one over the '
                                                           'header (format 4), so that a damaged file can be salvaged')
-    p.add_argument('--salvage', action='store_true', help='decompress / decompress-dir: read what a damaged format-4 file still holds; '
+    p.add_argument('--wavefront', action='store_true', help='compress / compress-dir with --tile: the layout of --checked, every tile coded '
+                                                            'front by front (format 5), which decodes a front at a time')
+    p.add_argument('--salvage', action='store_true', help='decompress / decompress-dir: read what a damaged format-4 / format-5 file still holds; '
                                                           'damaged tiles are filled from their neighbours and named')
     flags = p.parse_args(argv)
     from . import config_parser, val, weights as _weights
@@ -948,6 +1082,7 @@ def main(argv=None):
                     raise ValueError('--tile {} is not a positive multiple of the subsampling factor {}'.format(flags.tile, codec.factor))
                 codec.tile = (flags.tile // codec.factor, flags.tile // codec.factor)
                 codec.checked = flags.checked
+                codec.order = 'wavefront' if flags.wavefront else 'raster'
             data, pixels = codec.compress_file(flags.input, flags.output)
             print(_compress_line(flags.output, data, pixels))
         elif flags.salvage:

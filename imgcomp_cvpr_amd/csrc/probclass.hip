@@ -1590,6 +1590,222 @@ __global__ __launch_bounds__(256) void pc_dec_tiles_batch_kernel(const PcTilesBa
     }
 }
 
+// ---- wavefront-ordered tiles (container format 5, IC_PC_DECODE_WAVEFRONT) ----------------------------------------------------
+// The four masked layers make symbol (c, y, x) depend only on symbols of strictly smaller T = x + 2 y + 4 c (codec.py derives
+// this from the masks), so a stream that codes a tile front by front -- all symbols of one T, in (c, y, x) order -- lets the
+// decoder evaluate the network for a whole front at once; only the range decoder's step per symbol stays serial.
+// Same work mapping and workspace slot as pc_dec_cached_body (one work-group per tile: padded volume V and the caches A0, A1,
+// A2, channels-last), but the sweep runs over hyperplanes of the padded volume, T = J + 2 I + 4 D.  The last live tap of a
+// window has the largest T of its taps: offset 7 for the (1,1,1) corner of the "other" mask, 6 for the first mask (three taps
+// share it, all of them V).  With every V of T' < T known, step T runs four phases behind barriers:
+//     1. A0 voxels of front T - 7      (taps: V up to front T - 1)
+//     2. A1 voxels of front T - 14     (taps: A0 up to front T - 7)
+//     3. A2 voxels of front T - 21     (taps: A1 up to front T - 14; skip operand A0[d+2][i+2][j+2] on front T - 7)
+//     4. logits of the symbols on front T of V (taps: A2 up to front T - 21), 64 candidates at a time into LDS,
+// then wave 0 decodes that chunk's symbols one after the other with pc_dec_symbol_wave and stores their centres into V.
+// Every cache voxel a later phase reads -- halo voxels included -- is written exactly once, at the step its front comes up,
+// before its first read; voxels whose front lies beyond the last symbol's are never read and never written.
+// Each phase is parallel over (voxel, group of output channels).  One output is the four fmaf chains of pc_mfma_kernel's K
+// sequence (pc_chain_idx order, cut at 84 = 42 channel pairs), summed (p0 + p1) + (p2 + p3), then bias / ReLU / skip exactly as
+// pc_dec_cached_body does: the logits are bit-identical to the parallel pass, which the tables are a function of.
+
+// the voxels (d, i, j) of a box ND x NI x NJ with j + 2 i + 4 d == S as a dense range of candidates e in [0, nd * iw): d ascending,
+// then i ascending (j follows), so the candidates that are voxels come in (d, i, j) order
+struct PcFront { int S, NI, NJ, d_lo, nd, iw; };
+__device__ __forceinline__ int pc_cdiv_pos(int n, int k) { return n <= 0 ? 0 : (n + k - 1) / k; }
+__device__ __forceinline__ PcFront pc_front(int S, int ND, int NI, int NJ) {
+    PcFront f;
+    f.S = S; f.NI = NI; f.NJ = NJ;
+    f.d_lo = pc_cdiv_pos(S - (NJ - 1) - 2 * (NI - 1), 4);
+    const int d_hi = min(ND - 1, S >> 2);
+    f.nd = S < 0 ? 0 : max(d_hi - f.d_lo + 1, 0);
+    f.iw = min(NI, (NJ + 1) >> 1);                         // no d has more voxels on one front
+    return f;
+}
+__device__ __forceinline__ bool pc_front_voxel(const PcFront& f, int e, int& d, int& i, int& j) {
+    const int dd = e / f.iw, ii = e - dd * f.iw;
+    d = f.d_lo + dd;
+    const int R = f.S - 4 * d;                             // >= 0: d <= S / 4
+    i = pc_cdiv_pos(R - (f.NJ - 1), 2) + ii;               // the smallest i with j <= NJ - 1, then upwards
+    j = R - 2 * i;
+    return i < f.NI && j >= 0;
+}
+
+// COB outputs (channels co0 .. co0 + COB - 1 of a layer with `cout` outputs, w already moved to co0) of the voxel whose window
+// starts at `in` in a channels-last cache of row stride NJ and plane stride NI * NJ voxels
+template <int COB>
+__device__ __forceinline__ void pc_wave_chain(const float* __restrict__ in, int NI, int NJ, const float* __restrict__ w, int cout,
+                                              float (&v)[COB]) {
+    constexpr int K = 24;
+    static_assert(COB == 1 || COB == 4, "one output, or four through 16-byte filter loads");
+    float acc[PC_NP][COB];
+#pragma unroll
+    for (int p = 0; p < PC_NP; ++p)
+#pragma unroll
+        for (int r = 0; r < COB; ++r) acc[p][r] = 0.f;
+    const int rs = NJ * K, ds = NI * rs;
+    // a part is 21 steps of four chain positions, 8 * (c8 * 14 + t) + 4 * half + c; the parts are unrolled (their accumulators are
+    // registers), the steps inside one are a loop of uniform address arithmetic: unrolled as a whole, the 420 loads of one output
+    // group are hoisted together and spill
+#pragma unroll
+    for (int part = 0; part < PC_NP; ++part) {
+#pragma unroll 3
+        for (int uu = 0; uu < 21; ++uu) {
+            const int u = 21 * part + uu, c8 = u / 28, t = (u - 28 * c8) >> 1, ci0 = 8 * c8 + 4 * (u & 1);
+            // live tap t of the "other" mask is TF tap t: (kd, kh, kw) = (0, t / 3, t % 3), (1, 0, t - 9), (1, 1, t - 12)
+            const int kd = t >= 9 ? 1 : 0, kh = t < 9 ? t / 3 : (t < 12 ? 0 : 1), kw = t < 9 ? t - 3 * kh : (t < 12 ? t - 9 : t - 12);
+            const pc_f32x4 x = *reinterpret_cast<const pc_f32x4*>(in + kd * ds + kh * rs + kw * K + ci0);
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                const float* wp = w + (t * K + ci0 + c) * cout;
+                if constexpr (COB == 4) {
+                    const pc_f32x4 wv = *reinterpret_cast<const pc_f32x4*>(wp);
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) acc[part][r] = fmaf(wv[r], x[c], acc[part][r]);
+                } else {
+                    acc[part][0] = fmaf(wp[0], x[c], acc[part][0]);
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < COB; ++r) v[r] = (acc[0][r] + acc[1][r]) + (acc[2][r] + acc[3][r]);
+}
+
+template <bool SYMS>
+__device__ __forceinline__ void pc_dec_wave_body(const PcCachedArgs& f, const unsigned char* bits, long long nbytes, int h, int w, int first_sym,
+                                                 float* vol, float* c0, float* c1, float* c2, int* status,
+                                                 long long* __restrict__ out, long long out_cs, int out_rs) {
+    constexpr int K = 24, G = K / 4, CH = 64;             // CH: candidates of a front whose logits are in LDS at once
+    __shared__ float s_logits[CH][16];
+    __shared__ float s_centers[16];
+    const PcDecArgs& a = f.d;
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int L = a.L, C = a.C;
+    if (tid < L) s_centers[tid] = a.centers[tid];
+    PcDecState s;                                         // wave 0 keeps the coder state, identical in all its lanes
+    s.low = 0; s.high = (1ull << PC_AC_BITS) - 1; s.code = 0;
+    s.byte_pos = -1; s.bit_left = 0; s.cur_byte = 0; s.nxt_byte = nbytes > 0 ? bits[0] : 0; s.error = 0; s.next = 1;
+    if (wave == 0)
+        for (int i = 0; i < PC_AC_BITS; ++i) s.code = (s.code << 1) | (unsigned)pc_dec_bit(bits, nbytes, s);
+    const int PH = h + 8, PW = w + 8;
+    const int N0i = h + 6, N0j = w + 6, N1i = h + 4, N1j = w + 4, N2i = h + 2, N2j = w + 2;
+    const int T_last = (w + 3) + 2 * (h + 3) + 4 * (C + 3);    // the last symbol's front
+    __syncthreads();
+    for (int T = 7; T <= T_last; ++T) {
+        {   // ---- 1: A0, first mask (13 live taps = TF taps 0..12), + bias, ReLU ----
+            const PcFront fr = pc_front(T - 7, C + 3, N0i, N0j);
+            for (int n = tid; n < fr.nd * fr.iw * G; n += 256) {
+                const int e = n / G, cg = n - e * G;
+                int d, i, j;
+                if (!pc_front_voxel(fr, e, d, i, j)) continue;
+                const float* vp = vol + ((size_t)d * PH + i) * PW + j;
+                float acc[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int lt = 0; lt < 13; ++lt) {
+                    const int kd = lt < 9 ? 0 : 1, kh = lt < 9 ? lt / 3 : (lt < 12 ? 0 : 1), kw = lt < 9 ? lt % 3 : (lt < 12 ? lt - 9 : 0);
+                    const float xv = vp[(kd * PH + kh) * PW + kw];
+                    const pc_f32x4 wv = *reinterpret_cast<const pc_f32x4*>(f.w0 + lt * K + 4 * cg);
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) acc[r] = fmaf(xv, wv[r], acc[r]);
+                }
+                const pc_f32x4 b = *reinterpret_cast<const pc_f32x4*>(f.b0 + 4 * cg);
+                pc_f32x4 o;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) o[r] = fmaxf(acc[r] + b[r], 0.f);
+                *reinterpret_cast<pc_f32x4*>(c0 + (((size_t)d * N0i + i) * N0j + j) * K + 4 * cg) = o;
+            }
+        }
+        __syncthreads();
+        {   // ---- 2: A1 = relu(conv1(A0) + bias) ----
+            const PcFront fr = pc_front(T - 14, C + 2, N1i, N1j);
+            for (int n = tid; n < fr.nd * fr.iw * G; n += 256) {
+                const int e = n / G, cg = n - e * G;
+                int d, i, j;
+                if (!pc_front_voxel(fr, e, d, i, j)) continue;
+                float v[4];
+                pc_wave_chain<4>(c0 + (((size_t)d * N0i + i) * N0j + j) * K, N0i, N0j, f.w1 + 4 * cg, K, v);
+                const pc_f32x4 b = *reinterpret_cast<const pc_f32x4*>(f.b1 + 4 * cg);
+                pc_f32x4 o;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) o[r] = fmaxf(v[r] + b[r], 0.f);
+                *reinterpret_cast<pc_f32x4*>(c1 + (((size_t)d * N1i + i) * N1j + j) * K + 4 * cg) = o;
+            }
+        }
+        __syncthreads();
+        {   // ---- 3: A2 = conv2(A1) + bias + A0[d+2][i+2][j+2] ----
+            const PcFront fr = pc_front(T - 21, C + 1, N2i, N2j);
+            for (int n = tid; n < fr.nd * fr.iw * G; n += 256) {
+                const int e = n / G, cg = n - e * G;
+                int d, i, j;
+                if (!pc_front_voxel(fr, e, d, i, j)) continue;
+                float v[4];
+                pc_wave_chain<4>(c1 + (((size_t)d * N1i + i) * N1j + j) * K, N1i, N1j, f.w2 + 4 * cg, K, v);
+                const pc_f32x4 b = *reinterpret_cast<const pc_f32x4*>(f.b2 + 4 * cg);
+                const pc_f32x4 sk = *reinterpret_cast<const pc_f32x4*>(c0 + (((size_t)(d + 2) * N0i + i + 2) * N0j + j + 2) * K + 4 * cg);
+                pc_f32x4 o;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) { float a2 = v[r] + b[r]; a2 += sk[r]; o[r] = a2; }
+                *reinterpret_cast<pc_f32x4*>(c2 + (((size_t)d * N2i + i) * N2j + j) * K + 4 * cg) = o;
+            }
+        }
+        __syncthreads();
+        // ---- 4: the symbols (c, y, x) with x + 2 y + 4 c == T - 28: logits, then the range decoder in (c, y, x) order ----
+        const PcFront fr = pc_front(T - 28, C, h, w);
+        const int ncand = fr.nd * fr.iw;
+        for (int cb = 0; cb < ncand; cb += CH) {
+            const int nc = min(CH, ncand - cb);
+            for (int n = tid; n < nc * L; n += 256) {
+                const int slot = n / L, co = n - slot * L;
+                int c, y, x;
+                if (!pc_front_voxel(fr, cb + slot, c, y, x)) continue;
+                float v[1];
+                pc_wave_chain<1>(c2 + (((size_t)c * N2i + y) * N2j + x) * K, N2i, N2j, f.w3 + co, L, v);
+                s_logits[slot][co] = fmaxf(v[0] + f.b3[co], 0.f);
+            }
+            __syncthreads();
+            if (wave == 0) {
+                for (int k = 0; k < nc; ++k) {
+                    int c, y, x;
+                    if (!pc_front_voxel(fr, cb + k, c, y, x)) continue;          // wave-uniform
+                    int sym = first_sym;                                          // the first symbol is not coded
+                    if ((c | y | x) != 0) {
+                        const float logit = (lane >= 48 && lane < 48 + L) ? s_logits[k][lane - 48] : 0.f;
+                        sym = L == 6 ? pc_dec_symbol_wave<6>(bits, nbytes, L, a.resolution, s, logit)
+                                     : pc_dec_symbol_wave<0>(bits, nbytes, L, a.resolution, s, logit);
+                    }
+                    if (lane == 0) {
+                        if (SYMS) out[(long long)c * out_cs + (long long)y * out_rs + x] = sym;
+                        vol[((size_t)(c + 4) * PH + y + 4) * PW + x + 4] = s_centers[sym];
+                    }
+                }
+            }
+            __syncthreads();                              // V of this front before the next step's conv0; s_logits free again
+        }
+    }
+    if (tid == 0) *status = s.error;
+}
+
+template <bool SYMS>
+__global__ __launch_bounds__(256) void pc_dec_tiles_batch_wave_kernel(const PcTilesBatchArgs t) {
+    const ic_pc_tile_t tl = t.tiles[blockIdx.x];
+    const ic_pc_volume_t v = t.volumes[tl.volume];
+    char* slot = t.slots + (size_t)blockIdx.x * t.slot_bytes;
+    const long long corner = (long long)tl.y0 * v.w + tl.x0, plane = (long long)v.h * v.w;
+    pc_dec_wave_body<SYMS>(t.f, t.bits + tl.stream_off, tl.stream_bytes, tl.th, tl.tw, tl.first_sym, (float*)slot,
+                           (float*)(slot + t.off_c0), (float*)(slot + t.off_c1), (float*)(slot + t.off_c2), t.status + blockIdx.x,
+                           SYMS ? t.symbols + v.symbols_off + corner : nullptr, plane, v.w);
+    if (t.q == nullptr) return;
+    __syncthreads();
+    const float* vol = (const float*)slot;
+    float* q = t.q + v.q_off + corner;
+    const int PH = tl.th + 8, PW = tl.tw + 8, n = t.f.d.C * tl.th * tl.tw;
+    for (int i = threadIdx.x; i < n; i += 256) {
+        const int x = i % tl.tw, y = (i / tl.tw) % tl.th, c = i / (tl.tw * tl.th);
+        q[(long long)c * plane + (long long)y * v.w + x] = vol[((size_t)(c + 4) * PH + y + 4) * PW + x + 4];
+    }
+}
+
 // slow path of ic_pc_decode_tiles_batch_f32: a tile decoded into a buffer of its own -> its place in its volume, as symbols
 // and / or centres
 __global__ __launch_bounds__(256) void pc_tile_place_batch_kernel(const long long* __restrict__ src, long long* __restrict__ dst,
@@ -1628,7 +1844,7 @@ extern "C" int ic_pc_decode_f32(const uint8_t* bitstream, long long nbytes, int 
                                 int C, int h, int w, void* workspace, size_t workspace_bytes, int flags, ic_stream_t stream) {
     IC_CHECK_ARG(bitstream && wtab_host && centers && symbols && status && workspace);
     IC_CHECK_ARG(nbytes >= 0 && C > 0 && h > 0 && w > 0 && k > 0 && L > 0 && first_sym >= 0 && first_sym < L);
-    if (L > 16) return IC_ERR_UNSUPPORTED;
+    if (L > 16 || (flags & IC_PC_DECODE_WAVEFRONT)) return IC_ERR_UNSUPPORTED;      // (the wavefront order: the batch entry only)
     if (workspace_bytes < ic_pc_decode_workspace_bytes(C, h, w, k)) return IC_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     char* p = (char*)workspace;
@@ -1779,7 +1995,7 @@ extern "C" int ic_pc_decode_tiles_f32(const uint8_t* bitstreams, long long total
         th_max = d.th > th_max ? d.th : th_max;
         tw_max = d.tw > tw_max ? d.tw : tw_max;
     }
-    if (L > 16) return IC_ERR_UNSUPPORTED;
+    if (L > 16 || (flags & IC_PC_DECODE_WAVEFRONT)) return IC_ERR_UNSUPPORTED;      // (the wavefront order: the batch entry only)
     if (workspace_bytes < ic_pc_decode_tiles_workspace_bytes(C, th_max, tw_max, ntiles, k)) return IC_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     char* p = (char*)workspace;
@@ -1853,12 +2069,15 @@ extern "C" int ic_pc_decode_tiles_batch_f32(const uint8_t* bitstreams, long long
         tw_max = d.tw > tw_max ? d.tw : tw_max;
     }
     if (L > 16) return IC_ERR_UNSUPPORTED;
+    // the wavefront order has one decoder, the k = 24 kernel: no slow path, no combination with the test flags
+    const bool wavefront = (flags & IC_PC_DECODE_WAVEFRONT) != 0;
+    if (wavefront && (k != 24 || flags != IC_PC_DECODE_WAVEFRONT)) return IC_ERR_UNSUPPORTED;
     if (workspace_bytes < ic_pc_decode_tiles_batch_workspace_bytes(C, th_max, tw_max, ntiles, nvolumes, k)) return IC_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     char* p = (char*)workspace;
     const size_t table_bytes = pc_dec_align((size_t)ntiles * sizeof(ic_pc_tile_t));
     const size_t vtable_bytes = pc_dec_align((size_t)nvolumes * sizeof(ic_pc_volume_t));
-    if (k == 24 && flags == 0) {
+    if (k == 24 && (flags == 0 || wavefront)) {
         ic_pc_tile_t* tiles_dev = (ic_pc_tile_t*)p; p += table_bytes;
         ic_pc_volume_t* volumes_dev = (ic_pc_volume_t*)p; p += vtable_bytes;
         // both tables are pageable host memory: the runtime has taken its copy of them when these return
@@ -1877,7 +2096,9 @@ extern "C" int ic_pc_decode_tiles_batch_f32(const uint8_t* bitstreams, long long
         const long long nvol = (long long)(C + 4) * (th_max + 8) * (tw_max + 8);
         hipLaunchKernelGGL(pc_dec_fill_slots_kernel, dim3((unsigned)((nvol + 255) / 256), (unsigned)ntiles), dim3(256), 0, st,
                            a.slots, a.slot_bytes, nvol, centers);
-        if (symbols) hipLaunchKernelGGL(pc_dec_tiles_batch_kernel<true>, dim3((unsigned)ntiles), dim3(256), 0, st, a);
+        if (wavefront && symbols) hipLaunchKernelGGL(pc_dec_tiles_batch_wave_kernel<true>, dim3((unsigned)ntiles), dim3(256), 0, st, a);
+        else if (wavefront) hipLaunchKernelGGL(pc_dec_tiles_batch_wave_kernel<false>, dim3((unsigned)ntiles), dim3(256), 0, st, a);
+        else if (symbols) hipLaunchKernelGGL(pc_dec_tiles_batch_kernel<true>, dim3((unsigned)ntiles), dim3(256), 0, st, a);
         else hipLaunchKernelGGL(pc_dec_tiles_batch_kernel<false>, dim3((unsigned)ntiles), dim3(256), 0, st, a);
         IC_LAUNCH_CHECK();
         return IC_OK;

@@ -346,13 +346,15 @@ class PredictionNetwork(object):
         """(pr, freqs), each (num_contexts, L), contexts in the order of iter_over_blocks."""
         return self._tables(symbols_padded)
 
-    def encode_stream(self, symbols, capacity=None):
+    def encode_stream(self, symbols, capacity=None, order='raster'):
         """The mirror of decode_stream: the whole coding side on the device (ic_pc_encode_f32).  symbols: un-padded (C,h,w) numpy /
         tensor -> (stream_bytes, first_sym); a batch (N,C,h,w) -> a list of N such pairs, coded concurrently by ONE launch.
         The tables are bit for bit those of get_all(pad_symbols_volume(symbols)) -- the symbol volume padded with symbol 0, the
         centres gathered, pc.logits on the padded volume, as _tables does -- but they never exist in memory: the kernel takes
         (cum_lo, cum_hi, total) of each symbol from a table row held in registers, and only the stream comes back to the host.
-        capacity: bytes reserved per stream (tests); default ic_pc_encode_capacity_bytes, which always suffices."""
+        capacity: bytes reserved per stream (tests); default ic_pc_encode_capacity_bytes, which always suffices.
+        order='wavefront': the same tables and symbols, coded in the order of codec.wavefront_order(C, h, w) -- logits and symbols
+        are gathered through the permutation on the device, the kernel codes what it is given; the first symbol is the same."""
         dev = self.centers.device
         sym = symbols if torch.is_tensor(symbols) else torch.as_tensor(np.ascontiguousarray(symbols))
         batched = sym.dim() == 4
@@ -365,11 +367,19 @@ class PredictionNetwork(object):
         q = self.centers[torch.nn.functional.pad(sym, (pad, pad, pad, pad, pad, 0))].contiguous()    # (N,C+4,h+8,w+8), symbol 0 around
         logits = self.pc.logits(q, is_training=False)                  # (N,C,h,w,L)
         count = C * h * w
+        coded = sym
+        if order == 'wavefront':
+            from .codec import wavefront_order
+            perm = torch.as_tensor(np.array(wavefront_order(C, h, w))).to(dev)       # (a copy: the cached order is read-only)
+            logits = logits.view(N, count, self.pc.L).index_select(1, perm).contiguous()
+            coded = sym.view(N, count).index_select(1, perm).contiguous()
+        elif order != 'raster':
+            raise ValueError("order is 'raster' or 'wavefront', got {!r}".format(order))
         cap = int(lib.ic_pc_encode_capacity_bytes(count)) if capacity is None else int(capacity)
         out = torch.empty((N, max(cap, 1)), dtype=torch.uint8, device=dev)
         info = torch.zeros((2, N), dtype=torch.int64, device=dev)       # row 0: nbytes; row 1: status (int32 in the low words)
         status = info[1].view(torch.int32)[:N]
-        check(lib.ic_pc_encode_f32(ptr(logits), ptr(sym), N, count, self.pc.L, self.freqs_resolution, ptr(out), cap,
+        check(lib.ic_pc_encode_f32(ptr(logits), ptr(coded), N, count, self.pc.L, self.freqs_resolution, ptr(out), cap,
                                    ptr(info[0]), ptr(status), _lib.current_stream(dev)), 'ic_pc_encode_f32')
         nbytes = info[0].tolist()
         status = status.tolist()
@@ -403,10 +413,11 @@ class PredictionNetwork(object):
             raise ValueError('Cannot decode symbol because total is too large')
         return out.cpu().numpy()
 
-    def encode_tiles(self, symbols, th, tw):
+    def encode_tiles(self, symbols, th, tw, order='raster'):
         """symbols: un-padded (C,h,w) -> [(stream_bytes, first_sym)] for the tiles of codec.tile_grid(h, w, th, tw), in grid order.
         Every tile is coded as a volume of its own: its stream is encode_stream(symbols[:, y0:y0+th', x0:x0+tw']) byte for byte.
-        Tiles of one shape (at most four: interior, right column, bottom row, corner) are one encode_stream batch, one launch."""
+        Tiles of one shape (at most four: interior, right column, bottom row, corner) are one encode_stream batch, one launch.
+        order='wavefront': every tile's stream in the wavefront order of its own extent (encode_stream)."""
         from .codec import tile_grid
         sym = symbols if torch.is_tensor(symbols) else torch.as_tensor(np.ascontiguousarray(symbols))
         assert sym.dim() == 3, 'Expected CHW symbols'
@@ -418,7 +429,7 @@ class PredictionNetwork(object):
         res = [None] * len(grid)
         for (a, b), members in by_shape.items():
             batch = torch.stack([sym[:, grid[t][0]:grid[t][0] + a, grid[t][1]:grid[t][1] + b] for t in members])
-            for t, r in zip(members, self.encode_stream(batch)):
+            for t, r in zip(members, self.encode_stream(batch, order=order)):
                 res[t] = r
         return res
 
@@ -448,7 +459,7 @@ class PredictionNetwork(object):
                 raise ValueError('Cannot decode symbol because total is too large (tile {} at ({}, {}))'.format(t, grid[t][0], grid[t][1]))
         return out.cpu().numpy()
 
-    def encode_tiles_batch(self, volumes, th, tw):
+    def encode_tiles_batch(self, volumes, th, tw, order='raster'):
         """encode_tiles for a list of un-padded (C,h,w) symbol volumes of any mix of (h, w): -> per volume the list encode_tiles
         gives for it, byte for byte.  The tiles of ALL volumes are grouped by tile shape -- for a folder of equal-sized images the
         same four shapes as for one -- and each group is one encode_stream batch, one ic_pc_encode_f32 launch."""
@@ -467,11 +478,11 @@ class PredictionNetwork(object):
         res = [[None] * len(grid) for grid in grids]
         for (_, a, b), members in by_shape.items():
             batch = torch.stack([syms[n][:, grids[n][t][0]:grids[n][t][0] + a, grids[n][t][1]:grids[n][t][1] + b] for n, t in members])
-            for (n, t), r in zip(members, self.encode_stream(batch)):
+            for (n, t), r in zip(members, self.encode_stream(batch, order=order)):
                 res[n][t] = r
         return res
 
-    def decode_tiles_batch(self, volumes, th, tw, want='q', max_workspace_bytes=1 << 31, flags=0, conceal=False):
+    def decode_tiles_batch(self, volumes, th, tw, want='q', max_workspace_bytes=1 << 31, flags=0, conceal=False, order='raster'):
         """The mirror of encode_tiles_batch: the tiles of ALL volumes decoded by one launch per chunk (ic_pc_decode_tiles_batch_f32,
         one work-group per tile).  volumes: [(streams, first_syms, (C,h,w))], each as decode_tiles takes them, one C throughout.
         want: 'q' -> per volume the (C,h,w) float32 DEVICE tensor centers[symbols] (what ae.decode consumes: the symbols never
@@ -482,10 +493,16 @@ class PredictionNetwork(object):
         conceal=False: its cells are 0 (symbol 0, q 0.0).  conceal=True: skipped tiles (reason 'missing') and tiles whose decoder
         status is not 0 (reason 'decoder', instead of the ValueError) are the damaged set; one launch of ic_pc_conceal_tiles
         behind the decoder fills them from their intact neighbours (include/imgcomp_hip.h has the rule; the fallback symbol is
-        the centre of smallest magnitude), and the call returns (result as above, [per volume [(tile, reason)] in tile order])."""
+        the centre of smallest magnitude), and the call returns (result as above, [per volume [(tile, reason)] in tile order]).
+        order='wavefront': the streams are in wavefront order (encode_tiles(order='wavefront')); sets PC_DECODE_WAVEFRONT, the
+        decoder that takes a front at a time.  The order is per call: raster and wavefront volumes do not share one."""
         from .codec import tile_grid, chunk_tiles
         if want not in ('q', 'symbols', 'both'):
             raise ValueError("want is 'q', 'symbols' or 'both', got {!r}".format(want))
+        if order not in ('raster', 'wavefront'):
+            raise ValueError("order is 'raster' or 'wavefront', got {!r}".format(order))
+        if order == 'wavefront':
+            flags = int(flags) | _lib.PC_DECODE_WAVEFRONT
         if not volumes:
             return ([], []) if conceal else []
         dev = self.centers.device

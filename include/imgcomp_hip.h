@@ -102,6 +102,9 @@ int ic_build_has_tuning_forms(void);
 /* ic_pc_decode_f32, k = 24: the persistent work-group that recomputes each symbol's whole 5x9x9 context (round-1 kernel)
  * instead of the one with activation caches (tests, A/B) */
 #define IC_PC_DECODE_RECOMPUTE    0x02
+/* ic_pc_decode_tiles_batch_f32: every tile's stream codes its symbols front by front -- sorted by (T, c, y, x) with
+ * T = x + 2 y + 4 c in tile coordinates, the first one uncoded (container format 5) -- and is decoded a front at a time */
+#define IC_PC_DECODE_WAVEFRONT    0x04
 
 int ic_abi_version(void);
 /* static string for a return code of this library (hipGetErrorString for codes > 0) */
@@ -307,6 +310,8 @@ int ic_pc_decode_tiles_f32(const uint8_t* bitstreams, long long total_bytes, con
  *   symbols: out, may be NULL;  q: out, may be NULL: q[c,y,x] = centers[symbols[c,y,x]], the tensor ic_ae_decode_f32 consumes,
  *     written by the tile's work-group when its tile is done.  Not both NULL (IC_ERR_ARG).  status: out, device int (ntiles).
  *   k = 24, flags = 0: ONE launch of ntiles work-groups over all volumes; other k or the slow-path flags: tile after tile.
+ *   flags = IC_PC_DECODE_WAVEFRONT (k = 24 only): the same launch shape, tables and workspace for streams in wavefront order; with
+ *     another k or together with another flag: IC_ERR_UNSUPPORTED.  The single-volume entries refuse the flag.
  *   workspace: ic_pc_decode_tiles_batch_workspace_bytes(C, largest th, largest tw, ntiles, nvolumes, k), one slot per tile as
  *     above: a caller with many files cuts the tile list into several calls (any cut will do, also inside a volume). */
 typedef struct { int h, w; long long symbols_off, q_off; } ic_pc_volume_t;
