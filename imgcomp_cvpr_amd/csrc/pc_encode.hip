@@ -1,4 +1,4 @@
-// Device range ENCODER of the real-bpp path: the mirror image of ic_pc_decode_f32 (probclass.hip).
+// Device range ENCODER of the real-bpp path: the mirror image of ic_pc_decode_f32 (pc_decode.hip).
 //   host statement: arithmetic_coding.encode_sequence(symbols[1:], freqs[1:]) over the tables of PredictionNetwork.get_all;
 //   the bytes written here are identical to that coder's (tests/test_gpu_codec.py), which tests/golden/arithcoding.npz pins to
 //   the reference coder.

@@ -1,5 +1,5 @@
 // The arithmetic coder's integer frequency table of one context: the ONE expression that the parallel table pass
-// (logits_to_freqs_kernel), the device decoder (probclass.hip) and the device encoder (pc_encode.hip) share.
+// (logits_to_freqs_kernel), the device decoder (pc_decode.hip) and the device encoder (pc_encode.hip) share.
 #pragma once
 #include "common.h"
 

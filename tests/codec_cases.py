@@ -1,7 +1,7 @@
 """Shared by tests/test_cpu_codec*.py and tests/test_gpu_codec*.py: a word-level model of the device range encoder
 (csrc/pc_encode.hip) in plain Python, the host coder wrapped so that its pending-underflow count can be observed, and the
 constructed sequences (long pending runs, worst-case cost) as logits whose softmax tables give them.  For the decoders: a
-word-level model of pc_dec_symbol_wave (csrc/probclass.hip), the host decoder as a function of (bytes, tables), context-model
+word-level model of pc_dec_symbol_wave (csrc/pc_decode.hip), the host decoder as a function of (bytes, tables), context-model
 weights whose table is one chosen row at every position, and the byte strings no encoder wrote."""
 import io
 

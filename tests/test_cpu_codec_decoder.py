@@ -1,5 +1,5 @@
 """The decode side of the codec, the parts that need no GPU: a word-level model of the device range-decoder step
-(pc_dec_symbol_wave with pc_udiv, csrc/probclass.hip) against arithmetic_coding's ArithmeticDecoder, symbol for symbol -- on
+(pc_dec_symbol_wave with pc_udiv, csrc/pc_decode.hip) against arithmetic_coding's ArithmeticDecoder, symbol for symbol -- on
 streams the host encoder wrote (golden sequence, random tables up to the coder's limit, pending runs, frequency-1 symbols) and on
 byte strings no encoder wrote.  Every comparison is an equality."""
 import os

@@ -259,3 +259,28 @@ def test_decode_tiles_workspace_bytes():
     # it covers what the single-volume decoder needs for the largest tile (the slow path runs inside it)
     for k in (24, 64):
         assert ws(32, 16, 16, 1, k) >= _lib.lib.ic_pc_decode_workspace_bytes(32, 16, 16, k) + 32 * 16 * 16 * 8
+
+
+# (C, th, tw, ntiles, nvolumes, k) -> ic_pc_workspace_bytes(1, C, th, tw, k), ic_pc_decode_workspace_bytes(C, th, tw, k),
+# ic_pc_decode_tiles_workspace_bytes(C, th, tw, ntiles, k), ic_pc_decode_tiles_batch_workspace_bytes(C, th, tw, ntiles, nvolumes, k),
+# recorded from the library before the decoder moved into a source file of its own
+PINNED_WORKSPACE_BYTES = {
+    (4, 3, 5, 2, 2, 24): (270144, 304992, 305760, 306016),
+    (4, 3, 5, 2, 2, 64): (949760, 711680, 712448, 712704),
+    (32, 16, 16, 24, 8, 24): (4108800, 4222048, 96996352, 96996608),
+    (32, 16, 16, 24, 8, 64): (11186176, 790016, 856576, 856832),
+    (1, 1, 1, 1, 1, 24): (178272, 210528, 211040, 211296),
+    (1, 1, 1, 1, 1, 64): (704768, 708864, 709376, 709632),
+}
+
+
+def test_workspace_bytes_pinned():
+    """the workspace sizes are ABI: callers allocate by them and the entries lay their workspace out by them, so they are what
+    they were -- byte for byte, for both k paths, a small ragged shape, the 24-tile Kodak shape and the smallest volume"""
+    from imgcomp_cvpr_amd import _lib
+    lib = _lib.lib
+    for (C, th, tw, ntiles, nvolumes, k), want in PINNED_WORKSPACE_BYTES.items():
+        got = (lib.ic_pc_workspace_bytes(1, C, th, tw, k), lib.ic_pc_decode_workspace_bytes(C, th, tw, k),
+               lib.ic_pc_decode_tiles_workspace_bytes(C, th, tw, ntiles, k),
+               lib.ic_pc_decode_tiles_batch_workspace_bytes(C, th, tw, ntiles, nvolumes, k))
+        assert got == want, ((C, th, tw, ntiles, nvolumes, k), got, want)

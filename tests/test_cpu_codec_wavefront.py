@@ -139,7 +139,7 @@ def _cdiv_pos(n, k):
 
 
 def _front(S, ND, NI, NJ):
-    """pc_front / pc_front_voxel of csrc/probclass.hip: the voxels of a box with j + 2 i + 4 d == S, in candidate order"""
+    """pc_front / pc_front_voxel of csrc/pc_decode.hip: the voxels of a box with j + 2 i + 4 d == S, in candidate order"""
     d_lo, d_hi = _cdiv_pos(S - (NJ - 1) - 2 * (NI - 1), 4), min(ND - 1, S >> 2)
     nd, iw, out = (0 if S < 0 else max(d_hi - d_lo + 1, 0)), min(NI, (NJ + 1) >> 1), []
     for e in range(nd * iw):
