@@ -29,6 +29,7 @@ struct BnArgs {
     double* partial;          // workspace
     float* out0; float* out1; // stats: mean, var ; bwd_apply: dx
     int N, C, HW, relu;
+    int vec;                  // reductions: 16-byte loads (HW % 4 == 0 and x, dy 16-byte aligned -- bn_reduce_args decides, once per call)
     long long count;          // bwd_apply: elements per channel the sums run over (0 = N * HW; larger under sync BatchNorm)
     double* sums_out;         // bwd_apply with partials: where the designated work-group of a channel leaves the totals (or nullptr)
     float* dbeta; float* dgamma;
@@ -59,7 +60,7 @@ __device__ __forceinline__ void bn_channel_sums(const BnArgs& a, int c, int n0, 
             s0 += g; s1 += (double)g * ((xv - mu) * is);
         }
     };
-    if ((a.HW & 3) == 0) {
+    if (a.vec) {
         // flattened float4 index i = n * HW4 + p4, stepped by 1024 with a carry instead of a division per load; four loads
         // in flight per thread
         const int HW4 = a.HW >> 2;
@@ -299,6 +300,8 @@ static inline bool bn_vec_ok(int HW, const void* p0, const void* p1, const void*
     auto al = [](const void* p) { return p == nullptr || ((uintptr_t)p & 15) == 0; };
     return (HW & 3) == 0 && al(p0) && al(p1) && al(p2) && al(p3) && al(p4);
 }
+// the reductions follow the rule of the element-wise kernels: 16-byte loads only from 16-byte aligned tensors, the scalar loop otherwise
+static inline void bn_reduce_args(BnArgs& a) { a.vec = bn_vec_ok(a.HW, a.x, a.dy, nullptr, nullptr, nullptr); }
 static inline dim3 bn_ew_grid(int HW, int N, int C, bool vec) {
     int gx = ic_cdiv(HW, 1024);                   // elements of a plane per work-group of 256 threads: one float4 or four floats per thread
     return dim3(gx < 1 ? 1 : gx, vec ? C * ic_cdiv(N, BN_PL) : N * C);
@@ -322,6 +325,7 @@ extern "C" int ic_bn_stats_f32(const float* x, float* mean, float* var, int N, i
     BnArgs a{};
     a.x = x; a.N = N; a.C = C; a.HW = HW; a.partial = (double*)workspace;
     hipStream_t st = (hipStream_t)stream;
+    bn_reduce_args(a);
     hipLaunchKernelGGL(bn_partial_kernel<0>, dim3(BN_SPLIT, C), dim3(1024), 0, st, a);
     hipLaunchKernelGGL(bn_finish_kernel<0>, dim3(ic_cdiv(C, 64)), dim3(64), 0, st, a.partial, C, (long long)N * HW, (double*)nullptr, mean, var, BnFoldArgs{});
     IC_LAUNCH_CHECK();
@@ -336,6 +340,7 @@ extern "C" int ic_bn_train_stats_f32(const float* x, const float* gamma, const f
     a.x = x; a.N = N; a.C = C; a.HW = HW; a.partial = (double*)workspace;
     hipStream_t st = (hipStream_t)stream;
     const BnFoldArgs f{gamma, beta, moving_mean, moving_var, decay, eps, mean, invstd, scale, shift};
+    bn_reduce_args(a);
     hipLaunchKernelGGL(bn_partial_kernel<0>, dim3(BN_SPLIT, C), dim3(1024), 0, st, a);
     hipLaunchKernelGGL(bn_finish_kernel<2>, dim3(ic_cdiv(C, 64)), dim3(64), 0, st, a.partial, C, (long long)N * HW, (double*)nullptr, (float*)nullptr, (float*)nullptr, f);
     IC_LAUNCH_CHECK();
@@ -352,6 +357,7 @@ extern "C" int ic_bn_train_forward_f32(const float* x, const float* gamma, const
     BnArgs a{};
     a.x = x; a.N = N; a.C = C; a.HW = HW; a.partial = (double*)workspace;
     hipStream_t st = (hipStream_t)stream;
+    bn_reduce_args(a);
     hipLaunchKernelGGL(bn_partial_kernel<0>, dim3(BN_SPLIT, C), dim3(1024), 0, st, a);
     const BnFoldArgs f{gamma, beta, moving_mean, moving_var, decay, eps, mean, invstd, scale, shift};
     BnApplyArgs ap{x, nullptr, nullptr, res1, res2, y, N, C, HW, relu, a.partial, (long long)N * HW, nullptr, 0};
@@ -386,6 +392,7 @@ extern "C" int ic_bn_moments_f32(const float* x, double* sums, int N, int C, int
     BnArgs a{};
     a.x = x; a.N = N; a.C = C; a.HW = HW; a.partial = (double*)workspace;
     hipStream_t st = (hipStream_t)stream;
+    bn_reduce_args(a);
     hipLaunchKernelGGL(bn_partial_kernel<0>, dim3(BN_SPLIT, C), dim3(1024), 0, st, a);
     hipLaunchKernelGGL(bn_finish_kernel<1>, dim3(ic_cdiv(C, 64)), dim3(64), 0, st, a.partial, C, (long long)N * HW, sums, (float*)nullptr, (float*)nullptr, BnFoldArgs{});
     IC_LAUNCH_CHECK();
@@ -419,6 +426,7 @@ extern "C" int ic_bn_backward_reduce_f32(const float* dy, const float* x, const 
     a.x = x; a.dy = dy; a.scale = scale; a.shift = shift; a.mean = mean; a.invstd = invstd;
     a.N = N; a.C = C; a.HW = HW; a.relu = relu; a.partial = (double*)workspace;
     hipStream_t st = (hipStream_t)stream;
+    bn_reduce_args(a);
     hipLaunchKernelGGL(bn_partial_kernel<1>, dim3(BN_SPLIT, C), dim3(1024), 0, st, a);
     hipLaunchKernelGGL(bn_finish_kernel<1>, dim3(ic_cdiv(C, 64)), dim3(64), 0, st, a.partial, C, (long long)N * HW, sums, dbeta, dgamma, BnFoldArgs{});
     IC_LAUNCH_CHECK();
@@ -457,6 +465,7 @@ extern "C" int ic_bn_backward_f32(const float* dy, const float* x, const float* 
     a.partial = (double*)workspace;
     a.sums = nullptr; a.sums_out = nullptr; a.dbeta = dbeta; a.dgamma = dgamma; a.out0 = dx;
     hipStream_t st = (hipStream_t)stream;
+    bn_reduce_args(a);
     hipLaunchKernelGGL(bn_partial_kernel<1>, dim3(BN_SPLIT, C), dim3(1024), 0, st, a);
     bn_launch_bwd_apply(a, st);
     IC_LAUNCH_CHECK();

@@ -436,7 +436,8 @@ int ic_bn_train_forward_cstats_f32(const float* x, const float* conv_stats, int 
  * ic_bn_backward_reduce_f32, ic_bn_backward_f32): each call is TWO launches that communicate through it -- the first writes per-block
  * partial sums [C][blocks][0..3], the second (the element-wise kernel included) re-reads them in every work-group.  A workspace
  * must therefore NOT be shared by calls that can overlap in time: one per stream (calls on one stream are ordered and may
- * share one, as imgcomp_cvpr_amd/training.py does with its single compute stream).  Sharing across streams is a silent race. */
+ * share one, as imgcomp_cvpr_amd/training.py does with its single compute stream).  Sharing across streams is a silent race.
+ * Every ic_bn_* entry accepts any 4-byte-aligned float tensors (16-byte accesses only where HW % 4 == 0 and the tensors allow them). */
 size_t ic_bn_workspace_bytes(int C);
 /* batch mean and BIASED variance per channel of x (N,C,HW) (autoencoder.py:114-125, is_training=True) */
 int ic_bn_stats_f32(const float* x, float* mean, float* var, int N, int C, int HW, void* workspace, ic_stream_t stream);

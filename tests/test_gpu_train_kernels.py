@@ -1,7 +1,8 @@
 """-m gpu: the training-side backward kernels through the C ABI, each against a float64 evaluation on the CPU -- every plan form
 of the 2-D filter gradient, the context model's 3-D filter gradient in its four layer roles (k = 24 and 64), the logits'
 cross-entropy gradient, the bias sums and the quantiser / importance-map backward at training size.  Every case runs twice and
-must give the same bits: each reduction here claims a fixed order."""
+must give the same bits: each reduction here claims a fixed order.  (BatchNorm: tests/test_gpu_bn_kernels.py.)  Last, the fused
+Adam update on counts that reach its scalar tail and its grid-stride loop."""
 import numpy as np
 import pytest
 import torch
@@ -283,3 +284,59 @@ def test_quantizer_backward_training_size(cuda, heatmap, C, L, with_dhm):
     tag = 'quantiser bwd {} C={} L={}{}'.format('heatmap' if heatmap else 'no heatmap', C, L, ' d_heatmap' if gh is not None else '')
     assert_close(db, ref_db, tag + ': d bottleneck', 1e-5)
     assert_close(dc, ct.grad, tag + ': d centers', 1e-5)
+
+
+# ---- ic_adam_tf_f32: the scalar tail and the grid-stride loop ----------------------------------------------------------------
+
+ADAM_COUNTS = [1, 2, 3, 5, 1023, 4 * 2048 * 256 + 4 * 77 + 3]
+
+
+@pytest.mark.parametrize('count', ADAM_COUNTS)
+def test_fused_adam_tail_and_grid_stride(cuda, count):
+    """ic_adam_tf_f32 called directly on counts that are no multiple of 4 (the scalar tail; no float4 at all below 4) and on more
+    float4 than the 2048-block grid covers in one round (the grid-stride loop, then 77 float4 of a partial round, then a tail
+    of 3).  Two steps, each against the float64 statement of the three update lines on that step's own fp32 inputs; the 16
+    floats behind each array keep their bits; a pointer 4 bytes off is refused and nothing is written."""
+    Lb = _L()
+    rs = np.random.RandomState(count % 9973)
+    G = 16
+    if count > 4:
+        assert count % 4 != 0
+    if count > 1023:
+        assert count // 4 > 2048 * 256 and (count // 4) % (2048 * 256) != 0
+    sentinel = np.float32(-12345.678)
+
+    def guarded(a):
+        return dev(np.concatenate([a.astype(np.float32), np.full(G, sentinel, np.float32)]), cuda)
+    p = guarded(rs.normal(0, 1, count))
+    m = guarded(rs.normal(0, 0.1, count))
+    v = guarded(rs.uniform(1e-4, 1e-1, count))
+    f = lambda t: float(np.float32(t))
+    b1, b2, eps = f(0.9), f(0.999), f(1e-8)
+    for step in (1, 2):
+        g = guarded(rs.normal(0, 10.0 ** -(step - 1), count))
+        lr_t = f(3e-3 * np.sqrt(1.0 - 0.999 ** step) / (1.0 - 0.9 ** step))
+        p0, m0, v0, g0 = (t[:count].double().cpu() for t in (p, m, v, g))
+        # 1 - b1 and 1 - b2 are exact in fp32 (b >= 0.5), so the kernel's c1 and c2 are these values
+        m_ref = b1 * m0 + (1.0 - b1) * g0
+        v_ref = b2 * v0 + (1.0 - b2) * g0 * g0
+        p_ref = p0 - lr_t * m_ref / (torch.sqrt(v_ref) + eps)
+        Lb.check(Lb.lib.ic_adam_tf_f32(Lb.ptr(p), Lb.ptr(g), Lb.ptr(m), Lb.ptr(v), count, lr_t, b1, b2, eps, Lb.current_stream()))
+        torch.cuda.synchronize()
+        assert_close(m[:count], m_ref, 'fused Adam direct: m', 1e-6)
+        assert_close(v[:count], v_ref, 'fused Adam direct: v', 1e-6)
+        assert_close(p[:count], p_ref, 'fused Adam direct: variable', 1e-6)
+        assert torch.equal(g[:count].double().cpu(), g0), 'the gradient was written'
+        for name, t in (('variable', p), ('gradient', g), ('m', m), ('v', v)):
+            assert bool((t[count:].cpu().view(torch.int32) == torch.tensor(sentinel).view(torch.int32)).all()), \
+                'fused Adam wrote behind the end of ' + name
+    # a pointer 4 bytes off, in each position: the argument error, before any launch
+    arrays = [p, g, m, v]
+    before = [t.clone() for t in arrays]
+    for k in range(4):
+        ptrs = [Lb.ptr(t) for t in arrays]
+        ptrs[k] = type(ptrs[k])(arrays[k].data_ptr() + 4)
+        assert Lb.lib.ic_adam_tf_f32(ptrs[0], ptrs[1], ptrs[2], ptrs[3], max(count - 1, 1), lr_t, b1, b2, eps, Lb.current_stream()) == -1      # IC_ERR_ARG
+    torch.cuda.synchronize()
+    for t, t0 in zip(arrays, before):
+        assert torch.equal(t.view(torch.int32), t0.view(torch.int32)), 'a refused call wrote something'
