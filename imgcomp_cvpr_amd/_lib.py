@@ -144,6 +144,11 @@ PROTOTYPES = {
     'ic_pc_decode_tiles_batch_workspace_bytes': (c_size_t, [c_int] * 6),
     'ic_pc_decode_tiles_batch_f32': (c_int, [c_void_p, c_longlong, c_void_p, c_int, c_void_p, c_int, POINTER(c_void_p), c_void_p, c_int,
                                              c_int, c_float, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_int, c_void_p]),
+    'ic_pc_decode_channels_f32': (c_int, [c_void_p, c_longlong, c_int, POINTER(c_void_p), c_void_p, c_int, c_int, c_float,
+                                          c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_int, c_void_p, c_int, c_int]),
+    'ic_pc_decode_tiles_batch_channels_f32': (c_int, [c_void_p, c_longlong, c_void_p, c_int, c_void_p, c_int, POINTER(c_void_p), c_void_p,
+                                                      c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_size_t,
+                                                      c_int, c_void_p, c_int, c_int]),
     'ic_pc_conceal_tiles_workspace_bytes': (c_size_t, [c_int, c_int, c_longlong]),
     'ic_pc_conceal_tiles': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p] + [c_int] * 5 +
                             [c_void_p, c_size_t, c_void_p]),

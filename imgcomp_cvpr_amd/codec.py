@@ -2,9 +2,9 @@
 
     python -m imgcomp_cvpr_amd.codec compress   IN.png  OUT.icf [--ae_config cvpr/low] [--pc_config cvpr/res_shallow] [--weights synthetic|FILE.npz|CKPT]
                                                                 [--tile PIXELS [--checked | --wavefront]]
-    python -m imgcomp_cvpr_amd.codec decompress IN.icf  OUT.png [same options] [--salvage]
+    python -m imgcomp_cvpr_amd.codec decompress IN.icf  OUT.png [same options] [--salvage | --channels K]
     python -m imgcomp_cvpr_amd.codec compress-dir   IN_DIR OUT_DIR [--tile PIXELS [--checked | --wavefront]] [--batch N]   every *.png / *.jpg -> OUT_DIR/<stem>.icf
-    python -m imgcomp_cvpr_amd.codec decompress-dir IN_DIR OUT_DIR [--batch N] [--salvage]                   every *.icf -> OUT_DIR/<stem>.png
+    python -m imgcomp_cvpr_amd.codec decompress-dir IN_DIR OUT_DIR [--batch N] [--salvage | --channels K]    every *.icf -> OUT_DIR/<stem>.png
     python -m imgcomp_cvpr_amd.codec verify PATH [PATH ...]         files or directories of *.icf: the checksums, without model or device
 
 compress:   pad to a multiple of the subsampling factor (val.add_padding) -> ae.encode -> PredictionNetwork.encode_stream (the
@@ -65,6 +65,12 @@ Every failure of parse / decompress is a ValueError that names the cause; nothin
 The -dir commands and Codec.compress_many / decompress_many work on a list of images at once: the same bytes and the same pixels as
 the single-image calls, file by file, but the tiles of all files are coded by one launch each way (ic_pc_decode_tiles_batch_f32: one
 work-group per tile, whichever file it belongs to) and up to four autoencoder passes are in flight.  The file formats are unchanged.
+--channels K (decompress*(channels=K)): a preview from the first K of the C latent channels of any file of any format.  Only those
+are decoded; the others get fill_symbol(centres), the centre nearest zero, which is what the quantiser emits where the importance
+map has masked a channel -- the decoder network knows such volumes (preview_symbols is the rule).  Raster streams (formats 1, 2, 4)
+code (c, y, x) order, so the decoder stops after a prefix of every stream: (K + 3) / (C + 3) of its steps.  A format-5 decoder
+must step through the symbols of later channels that share a front with wanted ones (wavefront_prefix_count) and saves less.
+All CRCs are checked as always; damage in the bytes a preview does not reach cannot show in the decoder's status.
 """
 import argparse
 import io
@@ -174,6 +180,52 @@ def wavefront_order(C, th, tw):
             _ORDER_CACHE.clear()
         _ORDER_CACHE[key] = order
     return _ORDER_CACHE[key]
+
+
+def fill_symbol(centers):
+    """the symbol that stands where nothing was decoded: the index of the centre of smallest magnitude, ties to the smallest index --
+    what the quantiser emits where the importance map has masked a channel.  Concealment's fallback and the fill of a preview."""
+    c = np.asarray(centers).reshape(-1)
+    if c.size < 1:
+        raise ValueError('fill symbol: no centres')
+    return int(np.argmin(np.abs(c)))
+
+
+def preview_symbols(symbols_chw, channels, fill):
+    """the rule of a preview decode, on a full (C, h, w) symbol volume: a copy with [:channels] kept and [channels:] = fill."""
+    out = np.array(symbols_chw, copy=True)
+    out[int(channels):] = fill
+    return out
+
+
+def check_channels(channels, C):
+    """the channels argument of the decompress calls: None (all of them) or an integer in 1 .. C; else a ValueError naming C"""
+    if channels is None:
+        return None
+    if isinstance(channels, (bool, np.bool_)) or not isinstance(channels, (int, np.integer)) or not 1 <= int(channels) <= int(C):
+        raise ValueError('channels = {!r}: a preview decodes an integer number of channels in 1 .. C = {}'.format(channels, int(C)))
+    return int(channels)
+
+
+def _below(m, h, w):
+    """the number of (y, x), 0 <= y < h, 0 <= x < w, with x + 2 y <= m"""
+    if m < 0:
+        return 0
+    Y = min(h - 1, m // 2)                                   # rows with a position at all; row y has min(w, m - 2 y + 1)
+    full = min(max((m + 1 - w) // 2 + 1, 0), Y + 1)          # rows 0 .. full - 1 are whole
+    rest = Y + 1 - full
+    return full * w + rest * (m + 1) - (Y * (Y + 1) - full * (full - 1))
+
+
+def wavefront_prefix_count(C, h, w, channels):
+    """how many symbols of wavefront_order(C, h, w) a decoder steps through for the first `channels` channels: those with
+    T = x + 2 y + 4 c <= (w - 1) + 2 (h - 1) + 4 (channels - 1), the front of that part's last symbol.  They are a prefix of the
+    order (it is sorted by T first) and hold every symbol of the channels below `channels`; the uncoded first symbol counts."""
+    C, h, w, channels = int(C), int(h), int(w), int(channels)
+    if C < 1 or h < 1 or w < 1 or not 1 <= channels <= C:
+        raise ValueError('wavefront prefix: tile {} x {} x {}, {} channels'.format(C, h, w, channels))
+    T = (w - 1) + 2 * (h - 1) + 4 * (channels - 1)
+    return sum(_below(T - 4 * c, h, w) for c in range(C))
 
 
 def chunk_tiles(tile_shapes, need, budget):
@@ -605,25 +657,28 @@ class Codec(object):
             raise ValueError('header mismatch: frequency resolution {} in the file, {} in the model'.format(
                 c.resolution, self.pred.freqs_resolution))
 
-    def decode_symbols(self, data):
-        """container bytes of either format -> (symbols (C,h,w) int64 numpy, Container or TiledContainer)."""
+    def decode_symbols(self, data, channels=None):
+        """container bytes of either format -> (symbols (C,h,w) int64 numpy, Container or TiledContainer).
+        channels=K: a preview -- only channels 0 .. K - 1 are decoded, the result is preview_symbols(full decode, K, fill symbol)."""
+        channels = check_channels(channels, self.C)
         c = parse_container(data)
         self.check_container(c)
         try:
             if isinstance(c, WavefrontContainer):        # a batch of one: the order is a flag of the batch entry
                 sym = self.pred.decode_tiles_batch([(c.streams, c.first_syms, (c.C, c.h, c.w))], c.th, c.tw, want='symbols',
-                                                   order='wavefront')[0].cpu().numpy()
+                                                   order='wavefront', channels=channels)[0].cpu().numpy()
             elif isinstance(c, _TILED):
-                sym = self.pred.decode_tiles(c.streams, c.first_syms, (c.C, c.h, c.w), c.th, c.tw)
+                sym = self.pred.decode_tiles(c.streams, c.first_syms, (c.C, c.h, c.w), c.th, c.tw, channels=channels)
             else:
-                sym = self.pred.decode_stream(c.payload, (c.C, c.h, c.w), c.first_sym)
+                sym = self.pred.decode_stream(c.payload, (c.C, c.h, c.w), c.first_sym, channels=channels)
         except ValueError as e:
             raise ValueError('decoder status is not 0: {}'.format(e))
         return sym, c
 
-    def decompress(self, data):
+    def decompress(self, data, channels=None):
+        """container bytes -> HWC uint8 image; channels=K: the preview from the first K latent channels (decode_symbols)"""
         import torch
-        sym, c = self.decode_symbols(data)
+        sym, c = self.decode_symbols(data, channels=channels)
         s = torch.as_tensor(sym).to(self.device)
         q = self.ae.get_centers_variable()[s][None].contiguous()
         x_out = self.ae.decode(q, is_training=False).to(torch.uint8)            # tf.cast truncates (val.py)
@@ -710,14 +765,16 @@ class Codec(object):
         t, l = ((-c.H) % f) // 2, ((-c.W) % f) // 2                               # val.add_padding's offsets
         return np.ascontiguousarray(img[t:t + c.H, l:l + c.W, :])
 
-    def decompress_many(self, datas, max_workspace_bytes=1 << 31):
-        """[container bytes] of either format, any mix of shapes -> [HWC uint8], element i equal to decompress(datas[i]).
+    def decompress_many(self, datas, max_workspace_bytes=1 << 31, channels=None):
+        """[container bytes] of either format, any mix of shapes -> [HWC uint8], element i equal to decompress(datas[i]); with
+        channels=K to decompress(datas[i], channels=K), one K for the call.
         Every file is parsed and checked first; the first refusal raises its ValueError with the index of the file in front and
         nothing has reached the device.  The format-2 / format-4 files of the most frequent tile extent are decoded together
         (decode_tiles_batch: the tiles of all of them in one launch per workspace chunk, the centres q staying on the device) and
         go through the decoder up to IN_FLIGHT at a time; so are, in launches of their own (the order is a flag of the call), the
         format-5 files of their most frequent extent; format-1 files and other tile extents take the single-file path."""
         import torch
+        channels = check_channels(channels, self.C)
         heads = []
         for i, data in enumerate(datas):
             try:
@@ -737,7 +794,7 @@ class Codec(object):
             try:
                 qs = self.pred.decode_tiles_batch([(heads[i].streams, heads[i].first_syms, (heads[i].C, heads[i].h, heads[i].w))
                                                    for i in together], major[0], major[1], want='q',
-                                                  max_workspace_bytes=max_workspace_bytes, order=order)
+                                                  max_workspace_bytes=max_workspace_bytes, order=order, channels=channels)
             except ValueError as e:
                 m = re.search(r'volume (\d+)', str(e))
                 where = 'file {}: '.format(together[int(m.group(1))]) if m else ''
@@ -748,7 +805,7 @@ class Codec(object):
         for i, data in enumerate(datas):
             if out[i] is None:
                 try:
-                    out[i] = self.decompress(data)
+                    out[i] = self.decompress(data, channels=channels)
                 except ValueError as e:
                     raise ValueError('file {}: {}'.format(i, e))
         return out
@@ -818,11 +875,12 @@ class Codec(object):
             f.write(data)
         return data, img.shape[0] * img.shape[1]
 
-    def decompress_file(self, in_path, image_path):
+    def decompress_file(self, in_path, image_path, channels=None):
         from PIL import Image
+        channels = check_channels(channels, self.C)
         with open(in_path, 'rb') as f:
             data = f.read()
-        img = self.decompress(data)
+        img = self.decompress(data, channels=channels)
         Image.fromarray(img).save(image_path)
         return img
 
@@ -846,8 +904,9 @@ def _compress_line(path, data, pixels):
         path, len(data), payload, 8.0 * payload / pixels, 8.0 * len(data) / pixels, tiles)
 
 
-def _decompress_line(path, img, size):
-    return '{}: {} x {} from {} bytes = {:.4f} bpp'.format(path, img.shape[0], img.shape[1], size, 8.0 * size / (img.shape[0] * img.shape[1]))
+def _decompress_line(path, img, size, channels=None, C=None):
+    line = '{}: {} x {} from {} bytes = {:.4f} bpp'.format(path, img.shape[0], img.shape[1], size, 8.0 * size / (img.shape[0] * img.shape[1]))
+    return line if channels is None else '{}, preview from {} of {} channels'.format(line, channels, C)
 
 
 def _damage_line(path, report):
@@ -860,7 +919,14 @@ def _damage_line(path, report):
 
 
 def check_option_args(flags):
-    """--checked / --wavefront / --salvage against the command and --tile: decided before any model is built"""
+    """--checked / --wavefront / --salvage / --channels against the command and --tile: decided before any model is built"""
+    if getattr(flags, 'channels', None) is not None:
+        if flags.command not in ('decompress', 'decompress-dir'):
+            raise ValueError('--channels belongs to decompress / decompress-dir: a preview is a way of reading a file')
+        if getattr(flags, 'salvage', False):
+            raise ValueError('--channels does not go with --salvage: a preview of a damaged file is not offered')
+        if flags.channels < 1:
+            raise ValueError('--channels {} is not at least 1'.format(flags.channels))
     if getattr(flags, 'checked', False):
         if flags.command not in ('compress', 'compress-dir'):
             raise ValueError('--checked belongs to compress / compress-dir: a file says by itself what it is')
@@ -904,6 +970,7 @@ def _main_dir(flags, ae_config, pc_config):
         wts = val.load_weights_for_job(None, flags.weights, ae_config, pc_config)
     codec = Codec(ae_config, pc_config, wts, flags.device, tile=tile, checked=flags.checked,
                   order='wavefront' if flags.wavefront and tile is not None else 'raster')
+    channels = check_channels(getattr(flags, 'channels', None), codec.C)
     os.makedirs(flags.output, exist_ok=True)
     total_in = total_out = total_pixels = 0
     if flags.command == 'decompress-dir' and flags.salvage:
@@ -923,13 +990,13 @@ def _main_dir(flags, ae_config, pc_config):
                 with open(src, 'rb') as f:
                     datas.append(f.read())
             try:
-                imgs = codec.decompress_many(datas)
+                imgs = codec.decompress_many(datas, channels=channels)
             except ValueError as e:
                 m = re.match(r'file (\d+): ', str(e))
                 raise ValueError('{}: {}'.format(part[int(m.group(1))][0], str(e)[m.end():]) if m else str(e))
             for (src, dst), data, img in zip(part, datas, imgs):
                 Image.fromarray(img).save(dst)
-                print(_decompress_line(dst, img, len(data)))
+                print(_decompress_line(dst, img, len(data), channels, codec.C))
                 total_in, total_out, total_pixels = total_in + len(data), total_out + os.path.getsize(dst), total_pixels + img.shape[0] * img.shape[1]
     if flags.command == 'compress-dir':
         print('total: {} files, {} pixels, {} bytes = {:.4f} bpp'.format(len(jobs), total_pixels, total_out, 8.0 * total_out / total_pixels))
@@ -1063,6 +1130,9 @@ def main(argv=None):
                                                             'front by front (format 5), which decodes a front at a time')
     p.add_argument('--salvage', action='store_true', help='decompress / decompress-dir: read what a damaged format-4 / format-5 file still holds; '
                                                           'damaged tiles are filled from their neighbours and named')
+    p.add_argument('--channels', type=int, default=None, metavar='K',
+                   help='decompress / decompress-dir: a preview from the first K latent channels only (any format; the decoder stops '
+                        'after them, the other channels get the centre nearest zero); not with --salvage')
     flags = p.parse_args(argv)
     from . import config_parser, val, weights as _weights
     try:
@@ -1098,8 +1168,9 @@ def main(argv=None):
             if report is not None and (report.damaged or not report.file_crc_ok):
                 print(_damage_line(flags.input, report))
         else:
-            img = codec.decompress_file(flags.input, flags.output)
-            print(_decompress_line(flags.output, img, os.path.getsize(flags.input)))
+            channels = check_channels(flags.channels, codec.C)
+            img = codec.decompress_file(flags.input, flags.output, channels=channels)
+            print(_decompress_line(flags.output, img, os.path.getsize(flags.input), channels, codec.C))
     except ValueError as e:
         print('error: {}'.format(e), file=sys.stderr)
         return 2

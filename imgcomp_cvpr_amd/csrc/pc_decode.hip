@@ -2,7 +2,8 @@
 // probclass.hip reproduced bit for bit -- the launch-per-layer loop (any k), the persistent kernels for k = 24 (whole context
 // recomputed; activation caches), tiles of one or several volumes in one launch, tiles coded in wavefront order.
 //   reference: code/bit_counter.py:137-164 (decode loop), fjcommon arithmetic_coding.py (ArithmeticDecoder)
-// Host entry points: ic_pc_decode_f32, ic_pc_decode_tiles_f32, ic_pc_decode_tiles_batch_f32 and their *_workspace_bytes.
+// Host entry points: ic_pc_decode_f32, ic_pc_decode_tiles_f32, ic_pc_decode_tiles_batch_f32 and their *_workspace_bytes;
+// ic_pc_decode_channels_f32 and ic_pc_decode_tiles_batch_channels_f32 decode only the first channels of every stream (preview).
 #include "common.h"
 #include "pc_table.h"
 #include "pc_internal.h"
@@ -451,10 +452,14 @@ __device__ __forceinline__ int pc_chain_idx(int t, int ci) { return 8 * ((ci >> 
 // moved to the tile's corner, for a tile.
 // SYMS = false (ic_pc_decode_tiles_batch_f32 with symbols == NULL): nothing is stored through out; the padded volume still
 // receives every symbol's centre, which is what that caller copies out.
-template <bool SYMS = true>
+// LIM = true (the *_channels entries, preview): only channels 0 .. cdec - 1 are decoded, 1 <= cdec < C.  The stream codes its symbols
+// in (c, y, x) order and the masks are causal in c, so these are a prefix of the stream and the sweep simply ends after plane
+// D = cdec + 3; nothing of the per-symbol path changes, and the strides of the caches and of V do not depend on C.  cdec is a plain,
+// uniform value like the others (not a patched copy of f, see above); LIM = false does not read it and is the full decoder as before.
+template <bool SYMS = true, bool LIM = false>
 __device__ __forceinline__ void pc_dec_cached_body(const PcCachedArgs& f, const unsigned char* bits, long long nbytes, int h, int w, int first_sym,
                                                    float* vol, float* c0, float* c1, float* c2, int* status,
-                                                   long long* __restrict__ out, long long out_cs, int out_rs) {
+                                                   long long* __restrict__ out, long long out_cs, int out_rs, int cdec = 0) {
     constexpr int K = 24, KT = PC_NT * K;                 // 336 inputs per output
     __shared__ __attribute__((aligned(16))) float s_in[3][KT];          // inputs of conv1 / conv2 / conv3 in chain order
     __shared__ __attribute__((aligned(16))) float s_v[16];              // the 13 live taps of conv0
@@ -491,7 +496,7 @@ __device__ __forceinline__ void pc_dec_cached_body(const PcCachedArgs& f, const 
     const int pdst = 8 * ((pq >> 1) * PC_NT + pt) + 4 * (pq & 1);      // chain position of channels 4 pq .. 4 pq + 3 of tap pt
     const int vkd = tid < 9 ? 0 : 1, vkh = tid < 9 ? tid / 3 : 0, vkw = tid < 9 ? tid % 3 : tid - 9;
     const int PH = h + 8, PW = w + 8;
-    const int D1 = a.C + 3, I1 = h + 6, J1 = w + 5;       // last D, I, J of the sweep
+    const int D1 = (LIM ? cdec : a.C) + 3, I1 = h + 6, J1 = w + 5;       // last D, I, J of the sweep
     auto layer_valid = [&](int l, int D, int I, int J) -> bool {     // does step (D, I, J) produce a voxel of layer l + 1?
         return D >= 2 + l && I >= 2 + l && J >= 1 + l && I <= h + 5 - l && J <= w + 4 - l;
     };
@@ -621,6 +626,16 @@ __global__ __launch_bounds__(256) void pc_dec_cached_kernel(const PcCachedArgs f
                        f.d.symbols, (long long)f.d.h * f.d.w, f.d.w);
 }
 
+// the first cdec < C channels of one volume (ic_pc_decode_channels_f32): the sweep stops after them, then the same work-group
+// writes `fill` into the channels it did not decode -- every position of `symbols` is written
+__global__ __launch_bounds__(256) void pc_dec_cached_channels_kernel(const PcCachedArgs f, const int cdec, const int fill) {
+    pc_dec_cached_body<true, true>(f, f.d.bits, f.d.nbytes, f.d.h, f.d.w, f.d.first_sym, f.d.vol, f.c0, f.c1, f.c2, f.status,
+                                   f.d.symbols, (long long)f.d.h * f.d.w, f.d.w, cdec);
+    const long long plane = (long long)f.d.h * f.d.w, n = (long long)(f.d.C - cdec) * plane;
+    long long* rest = f.d.symbols + (long long)cdec * plane;
+    for (long long i = threadIdx.x; i < n; i += 256) rest[i] = fill;
+}
+
 // ---- wavefront-ordered tiles (container format 5, IC_PC_DECODE_WAVEFRONT) ----------------------------------------------------
 // The four masked layers make symbol (c, y, x) depend only on symbols of strictly smaller T = x + 2 y + 4 c (codec.py derives
 // this from the masks), so a stream that codes a tile front by front -- all symbols of one T, in (c, y, x) order -- lets the
@@ -703,10 +718,15 @@ __device__ __forceinline__ void pc_wave_chain(const float* __restrict__ in, int 
     for (int r = 0; r < COB; ++r) v[r] = (acc[0][r] + acc[1][r]) + (acc[2][r] + acc[3][r]);
 }
 
-template <bool SYMS>
+// LIM = true (preview of the first cdec < C channels): the loop ends at the front of the last symbol of channel cdec - 1,
+// T_stop = (w + 3) + 2 (h + 3) + 4 (cdec + 3).  A front <= T_stop also holds symbols of channels >= cdec, and the stream has them
+// in between the others: the range decoder steps through them like through any symbol, their centres go into V (later fronts of
+// the wanted channels have them in their context) and every cache phase keeps its full depth range; they are only not stored
+// through out.  The symbols stepped through are the first codec.wavefront_prefix_count(C, h, w, cdec) of the stream's order.
+template <bool SYMS, bool LIM = false>
 __device__ __forceinline__ void pc_dec_wave_body(const PcCachedArgs& f, const unsigned char* bits, long long nbytes, int h, int w, int first_sym,
                                                  float* vol, float* c0, float* c1, float* c2, int* status,
-                                                 long long* __restrict__ out, long long out_cs, int out_rs) {
+                                                 long long* __restrict__ out, long long out_cs, int out_rs, int cdec = 0) {
     constexpr int K = 24, G = K / 4, CH = 64;             // CH: candidates of a front whose logits are in LDS at once
     __shared__ float s_logits[CH][16];
     __shared__ float s_centers[16];
@@ -720,7 +740,7 @@ __device__ __forceinline__ void pc_dec_wave_body(const PcCachedArgs& f, const un
         for (int i = 0; i < PC_AC_BITS; ++i) s.code = (s.code << 1) | (unsigned)pc_dec_bit(bits, nbytes, s);
     const int PH = h + 8, PW = w + 8;
     const int N0i = h + 6, N0j = w + 6, N1i = h + 4, N1j = w + 4, N2i = h + 2, N2j = w + 2;
-    const int T_last = (w + 3) + 2 * (h + 3) + 4 * (C + 3);    // the last symbol's front
+    const int T_last = (w + 3) + 2 * (h + 3) + 4 * ((LIM ? cdec : C) + 3);    // the last symbol's front (LIM: of channel cdec - 1)
     __syncthreads();
     for (int T = 7; T <= T_last; ++T) {
         {   // ---- 1: A0, first mask (13 live taps = TF taps 0..12), + bias, ReLU ----
@@ -805,7 +825,7 @@ __device__ __forceinline__ void pc_dec_wave_body(const PcCachedArgs& f, const un
                                      : pc_dec_symbol_wave<0>(bits, nbytes, L, a.resolution, s, logit);
                     }
                     if (lane == 0) {
-                        if (SYMS) out[(long long)c * out_cs + (long long)y * out_rs + x] = sym;
+                        if (SYMS && (!LIM || c < cdec)) out[(long long)c * out_cs + (long long)y * out_rs + x] = sym;
                         vol[((size_t)(c + 4) * PH + y + 4) * PW + x + 4] = s_centers[sym];
                     }
                 }
@@ -829,6 +849,9 @@ __device__ __forceinline__ void pc_dec_wave_body(const PcCachedArgs& f, const un
 // q = centers[symbols] is what the decoder's padded volume holds at the end of the sweep (every decoded symbol's centre was
 // stored there for the context gathers), so after the body the work-group copies its tile's interior out: all 256 threads,
 // consecutive x on consecutive lanes, once per tile -- nothing is added to the per-symbol path of the bodies.
+// LIM (ic_pc_decode_tiles_batch_channels_f32, cdec < C): the bodies stop after channel cdec - 1 and the same copy loop writes the
+// rest -- q = centers[fill] and, with SYMS, symbols = fill for c >= cdec.  V is not read there: in the wavefront order it holds
+// the centres of the symbols of later channels that the coder had to step through.
 struct PcTilesBatchArgs {
     PcCachedArgs f;                   // weights, centres, C, L, resolution only: the rest comes from tiles[blockIdx.x]
     const unsigned char* bits;        // all streams
@@ -837,9 +860,10 @@ struct PcTilesBatchArgs {
     ic_pc_volume_t one;
     char* slots; size_t slot_bytes, off_c0, off_c1, off_c2;
     long long* symbols; float* q; int* status;
+    int cdec, fill;                   // LIM kernels only
 };
 
-template <bool WAVE, bool SYMS>
+template <bool WAVE, bool SYMS, bool LIM = false>
 __global__ __launch_bounds__(256) void pc_dec_tiles_batch_kernel(const PcTilesBatchArgs t) {
     const ic_pc_tile_t tl = t.tiles[blockIdx.x];
     // v = volumes ? volumes[tl.volume] : one, as a uniform branch around a scalar load.  (Written as a select, it becomes a select
@@ -849,22 +873,40 @@ __global__ __launch_bounds__(256) void pc_dec_tiles_batch_kernel(const PcTilesBa
     if (t.volumes) { v = t.volumes[tl.volume]; asm volatile("" ::: "memory"); }
     char* slot = t.slots + (size_t)blockIdx.x * t.slot_bytes;
     const long long corner = (long long)tl.y0 * v.w + tl.x0, plane = (long long)v.h * v.w;
+    const int cdec = LIM ? t.cdec : 0;
     if constexpr (WAVE)
-        pc_dec_wave_body<SYMS>(t.f, t.bits + tl.stream_off, tl.stream_bytes, tl.th, tl.tw, tl.first_sym, (float*)slot,
-                               (float*)(slot + t.off_c0), (float*)(slot + t.off_c1), (float*)(slot + t.off_c2), t.status + blockIdx.x,
-                               SYMS ? t.symbols + v.symbols_off + corner : nullptr, plane, v.w);
+        pc_dec_wave_body<SYMS, LIM>(t.f, t.bits + tl.stream_off, tl.stream_bytes, tl.th, tl.tw, tl.first_sym, (float*)slot,
+                                    (float*)(slot + t.off_c0), (float*)(slot + t.off_c1), (float*)(slot + t.off_c2), t.status + blockIdx.x,
+                                    SYMS ? t.symbols + v.symbols_off + corner : nullptr, plane, v.w, cdec);
     else
-        pc_dec_cached_body<SYMS>(t.f, t.bits + tl.stream_off, tl.stream_bytes, tl.th, tl.tw, tl.first_sym, (float*)slot,
-                                 (float*)(slot + t.off_c0), (float*)(slot + t.off_c1), (float*)(slot + t.off_c2), t.status + blockIdx.x,
-                                 SYMS ? t.symbols + v.symbols_off + corner : nullptr, plane, v.w);
-    if (t.q == nullptr) return;
+        pc_dec_cached_body<SYMS, LIM>(t.f, t.bits + tl.stream_off, tl.stream_bytes, tl.th, tl.tw, tl.first_sym, (float*)slot,
+                                      (float*)(slot + t.off_c0), (float*)(slot + t.off_c1), (float*)(slot + t.off_c2), t.status + blockIdx.x,
+                                      SYMS ? t.symbols + v.symbols_off + corner : nullptr, plane, v.w, cdec);
+    if (!(LIM && SYMS) && t.q == nullptr) return;
     __syncthreads();                  // the volume's last stores (lane 0 of wave 0) are visible to the whole work-group
     const float* vol = (const float*)slot;
-    float* q = t.q + v.q_off + corner;
+    float* q;
+    if constexpr (LIM) q = t.q ? t.q + v.q_off + corner : nullptr;
+    else q = t.q + v.q_off + corner;
     const int PH = tl.th + 8, PW = tl.tw + 8, n = t.f.d.C * tl.th * tl.tw;
-    for (int i = threadIdx.x; i < n; i += 256) {
-        const int x = i % tl.tw, y = (i / tl.tw) % tl.th, c = i / (tl.tw * tl.th);
-        q[(long long)c * plane + (long long)y * v.w + x] = vol[((size_t)(c + 4) * PH + y + 4) * PW + x + 4];
+    if constexpr (!LIM) {
+        for (int i = threadIdx.x; i < n; i += 256) {
+            const int x = i % tl.tw, y = (i / tl.tw) % tl.th, c = i / (tl.tw * tl.th);
+            q[(long long)c * plane + (long long)y * v.w + x] = vol[((size_t)(c + 4) * PH + y + 4) * PW + x + 4];
+        }
+    } else {
+        const float qfill = t.f.d.centers[t.fill];
+        long long* syms = SYMS ? t.symbols + v.symbols_off + corner : nullptr;
+        for (int i = threadIdx.x; i < n; i += 256) {
+            const int x = i % tl.tw, y = (i / tl.tw) % tl.th, c = i / (tl.tw * tl.th);
+            const long long o = (long long)c * plane + (long long)y * v.w + x;
+            if (c < cdec) {
+                if (q) q[o] = vol[((size_t)(c + 4) * PH + y + 4) * PW + x + 4];
+            } else {
+                if (q) q[o] = qfill;
+                if (SYMS) syms[o] = t.fill;
+            }
+        }
     }
 }
 
@@ -908,13 +950,11 @@ extern "C" size_t ic_pc_decode_workspace_bytes(int C, int h, int w, int k) {
            pc_dec_cache_bytes(C, h, w, k);
 }
 
-extern "C" int ic_pc_decode_f32(const uint8_t* bitstream, long long nbytes, int first_sym, const float* const* wtab_host,
-                                const float* centers, int k, int L, float resolution, int64_t* symbols, int* status,
-                                int C, int h, int w, void* workspace, size_t workspace_bytes, int flags, ic_stream_t stream) {
-    IC_CHECK_ARG(bitstream && wtab_host && centers && symbols && status && workspace);
-    IC_CHECK_ARG(nbytes >= 0 && C > 0 && h > 0 && w > 0 && k > 0 && L > 0 && first_sym >= 0 && first_sym < L);
-    if (L > 16 || (flags & IC_PC_DECODE_WAVEFRONT)) return IC_ERR_UNSUPPORTED;      // (the wavefront order: the batch entry only)
-    if (workspace_bytes < ic_pc_decode_workspace_bytes(C, h, w, k)) return IC_ERR_WORKSPACE;
+// One volume, behind the entries' checks.  channels == C: the full decode, whatever fill_sym.  channels < C (k = 24, flags 0,
+// which ic_pc_decode_channels_f32 has checked): the first channels only, the others filled with fill_sym.
+static int pc_decode_impl(const uint8_t* bitstream, long long nbytes, int first_sym, const float* const* wtab_host,
+                          const float* centers, int k, int L, float resolution, int64_t* symbols, int* status,
+                          int C, int h, int w, void* workspace, int flags, int channels, int fill_sym, ic_stream_t stream) {
     hipStream_t st = (hipStream_t)stream;
     char* p = (char*)workspace;
     PcDecArgs a{};
@@ -939,7 +979,8 @@ extern "C" int ic_pc_decode_f32(const uint8_t* bitstream, long long nbytes, int 
         f.c1 = (float*)p; p += pc_dec_align(pc_dec_cache_floats(C, h, w, k, 1) * sizeof(float));
         f.c2 = (float*)p;
         f.status = status;
-        hipLaunchKernelGGL(pc_dec_cached_kernel, dim3(1), dim3(256), 0, st, f);
+        if (channels < C) hipLaunchKernelGGL(pc_dec_cached_channels_kernel, dim3(1), dim3(256), 0, st, f, channels, fill_sym);
+        else hipLaunchKernelGGL(pc_dec_cached_kernel, dim3(1), dim3(256), 0, st, f);
         IC_LAUNCH_CHECK();
         return IC_OK;
     }
@@ -1035,6 +1076,31 @@ extern "C" int ic_pc_decode_f32(const uint8_t* bitstream, long long nbytes, int 
     return IC_OK;
 }
 
+extern "C" int ic_pc_decode_f32(const uint8_t* bitstream, long long nbytes, int first_sym, const float* const* wtab_host,
+                                const float* centers, int k, int L, float resolution, int64_t* symbols, int* status,
+                                int C, int h, int w, void* workspace, size_t workspace_bytes, int flags, ic_stream_t stream) {
+    IC_CHECK_ARG(bitstream && wtab_host && centers && symbols && status && workspace);
+    IC_CHECK_ARG(nbytes >= 0 && C > 0 && h > 0 && w > 0 && k > 0 && L > 0 && first_sym >= 0 && first_sym < L);
+    if (L > 16 || (flags & IC_PC_DECODE_WAVEFRONT)) return IC_ERR_UNSUPPORTED;      // (the wavefront order: the batch entry only)
+    if (workspace_bytes < ic_pc_decode_workspace_bytes(C, h, w, k)) return IC_ERR_WORKSPACE;
+    return pc_decode_impl(bitstream, nbytes, first_sym, wtab_host, centers, k, L, resolution, symbols, status, C, h, w, workspace,
+                          flags, C, 0, stream);
+}
+
+// preview: channels 0 .. channels - 1 decoded, the others fill_sym.  Only the k = 24 kernel has the limit: no slow path.
+extern "C" int ic_pc_decode_channels_f32(const uint8_t* bitstream, long long nbytes, int first_sym, const float* const* wtab_host,
+                                         const float* centers, int k, int L, float resolution, int64_t* symbols, int* status,
+                                         int C, int h, int w, void* workspace, size_t workspace_bytes, int flags, ic_stream_t stream,
+                                         int channels, int fill_sym) {
+    IC_CHECK_ARG(bitstream && wtab_host && centers && symbols && status && workspace);
+    IC_CHECK_ARG(nbytes >= 0 && C > 0 && h > 0 && w > 0 && k > 0 && L > 0 && first_sym >= 0 && first_sym < L);
+    IC_CHECK_ARG(channels >= 1 && channels <= C && fill_sym >= 0 && fill_sym < L);
+    if (L > 16 || k != 24 || flags != 0) return IC_ERR_UNSUPPORTED;
+    if (workspace_bytes < ic_pc_decode_workspace_bytes(C, h, w, k)) return IC_ERR_WORKSPACE;
+    return pc_decode_impl(bitstream, nbytes, first_sym, wtab_host, centers, k, L, resolution, symbols, status, C, h, w, workspace,
+                          flags, channels, fill_sym, stream);
+}
+
 // workspace of ic_pc_decode_tiles_f32: the table, then either one slot per tile (k = 24, flags 0) or what the single-volume
 // paths need for the largest tile plus that tile's symbols
 static size_t pc_dec_tile_slot_bytes(int C, int th, int tw, int k) {
@@ -1057,11 +1123,12 @@ static bool pc_tile_ok(const ic_pc_tile_t& d, int h, int w, long long total_byte
 
 // The tiles of one call, behind the entries' checks of arguments, flags and workspace size.  nvolumes > 0: the volume table
 // gets its device copy behind the tile table.  nvolumes == 0: one volume, volumes_host[0], which travels in the kernel
-// arguments; the `volume` field of the tiles is not read.
+// arguments; the `volume` field of the tiles is not read.  channels == C: the full decode; channels < C (k = 24 kernels only, checked
+// by the caller): the first channels of every tile, the others fill_sym.
 static int pc_decode_tiles_impl(const uint8_t* bitstreams, const ic_pc_tile_t* tiles_host, int ntiles, int th_max, int tw_max,
                                 const ic_pc_volume_t* volumes_host, int nvolumes, const float* const* wtab_host, const float* centers,
                                 int k, int L, float resolution, int64_t* symbols, float* q, int* status, int C, void* workspace,
-                                int flags, ic_stream_t stream) {
+                                int flags, int channels, int fill_sym, ic_stream_t stream) {
     const bool wavefront = (flags & IC_PC_DECODE_WAVEFRONT) != 0;
     hipStream_t st = (hipStream_t)stream;
     char* p = (char*)workspace;
@@ -1091,8 +1158,12 @@ static int pc_decode_tiles_impl(const uint8_t* bitstreams, const ic_pc_tile_t* t
         const long long nvol = (long long)(C + 4) * (th_max + 8) * (tw_max + 8);
         hipLaunchKernelGGL(pc_dec_fill_slots_kernel, dim3((unsigned)((nvol + 255) / 256), (unsigned)ntiles), dim3(256), 0, st,
                            a.slots, a.slot_bytes, nvol, centers);
-        const auto kernel = wavefront ? (symbols ? pc_dec_tiles_batch_kernel<true, true> : pc_dec_tiles_batch_kernel<true, false>)
-                                      : (symbols ? pc_dec_tiles_batch_kernel<false, true> : pc_dec_tiles_batch_kernel<false, false>);
+        a.cdec = channels; a.fill = fill_sym;
+        const auto full = wavefront ? (symbols ? pc_dec_tiles_batch_kernel<true, true> : pc_dec_tiles_batch_kernel<true, false>)
+                                    : (symbols ? pc_dec_tiles_batch_kernel<false, true> : pc_dec_tiles_batch_kernel<false, false>);
+        const auto lim = wavefront ? (symbols ? pc_dec_tiles_batch_kernel<true, true, true> : pc_dec_tiles_batch_kernel<true, false, true>)
+                                   : (symbols ? pc_dec_tiles_batch_kernel<false, true, true> : pc_dec_tiles_batch_kernel<false, false, true>);
+        const auto kernel = channels < C ? lim : full;
         hipLaunchKernelGGL(kernel, dim3((unsigned)ntiles), dim3(256), 0, st, a);
         IC_LAUNCH_CHECK();
         return IC_OK;
@@ -1134,7 +1205,7 @@ extern "C" int ic_pc_decode_tiles_f32(const uint8_t* bitstreams, long long total
     if (workspace_bytes < ic_pc_decode_tiles_workspace_bytes(C, th_max, tw_max, ntiles, k)) return IC_ERR_WORKSPACE;
     const ic_pc_volume_t one = {h, w, 0, 0};
     return pc_decode_tiles_impl(bitstreams, tiles_host, ntiles, th_max, tw_max, &one, 0, wtab_host, centers, k, L, resolution,
-                                symbols, nullptr, status, C, workspace, flags, stream);
+                                symbols, nullptr, status, C, workspace, flags, C, 0, stream);
 }
 
 // workspace of ic_pc_decode_tiles_batch_f32: the tile table, the volume table, then as ic_pc_decode_tiles_f32
@@ -1169,5 +1240,32 @@ extern "C" int ic_pc_decode_tiles_batch_f32(const uint8_t* bitstreams, long long
     if ((flags & IC_PC_DECODE_WAVEFRONT) && (k != 24 || flags != IC_PC_DECODE_WAVEFRONT)) return IC_ERR_UNSUPPORTED;
     if (workspace_bytes < ic_pc_decode_tiles_batch_workspace_bytes(C, th_max, tw_max, ntiles, nvolumes, k)) return IC_ERR_WORKSPACE;
     return pc_decode_tiles_impl(bitstreams, tiles_host, ntiles, th_max, tw_max, volumes_host, nvolumes, wtab_host, centers, k, L,
-                                resolution, symbols, q, status, C, workspace, flags, stream);
+                                resolution, symbols, q, status, C, workspace, flags, C, 0, stream);
+}
+
+// preview of the tiles of several volumes: as above with the channel limit; flags is 0 or IC_PC_DECODE_WAVEFRONT, k is 24
+extern "C" int ic_pc_decode_tiles_batch_channels_f32(const uint8_t* bitstreams, long long total_bytes, const ic_pc_tile_t* tiles_host, int ntiles,
+                                                     const ic_pc_volume_t* volumes_host, int nvolumes, const float* const* wtab_host,
+                                                     const float* centers, int k, int L, float resolution, int64_t* symbols, float* q,
+                                                     int* status, int C, void* workspace, size_t workspace_bytes, int flags,
+                                                     ic_stream_t stream, int channels, int fill_sym) {
+    IC_CHECK_ARG(bitstreams && tiles_host && volumes_host && wtab_host && centers && (symbols || q) && status && workspace);
+    IC_CHECK_ARG(total_bytes >= 0 && ntiles > 0 && nvolumes > 0 && C > 0 && k > 0 && L > 0);
+    IC_CHECK_ARG(channels >= 1 && channels <= C && fill_sym >= 0 && fill_sym < L);
+    for (int n = 0; n < nvolumes; ++n) {
+        const ic_pc_volume_t& v = volumes_host[n];
+        IC_CHECK_ARG(v.h >= 1 && v.w >= 1 && v.symbols_off >= 0 && v.q_off >= 0);
+    }
+    int th_max = 0, tw_max = 0;
+    for (int t = 0; t < ntiles; ++t) {
+        const ic_pc_tile_t& d = tiles_host[t];
+        IC_CHECK_ARG(d.volume >= 0 && d.volume < nvolumes);
+        IC_CHECK_ARG(pc_tile_ok(d, volumes_host[d.volume].h, volumes_host[d.volume].w, total_bytes, L));
+        th_max = d.th > th_max ? d.th : th_max;
+        tw_max = d.tw > tw_max ? d.tw : tw_max;
+    }
+    if (L > 16 || k != 24 || (flags != 0 && flags != IC_PC_DECODE_WAVEFRONT)) return IC_ERR_UNSUPPORTED;
+    if (workspace_bytes < ic_pc_decode_tiles_batch_workspace_bytes(C, th_max, tw_max, ntiles, nvolumes, k)) return IC_ERR_WORKSPACE;
+    return pc_decode_tiles_impl(bitstreams, tiles_host, ntiles, th_max, tw_max, volumes_host, nvolumes, wtab_host, centers, k, L,
+                                resolution, symbols, q, status, C, workspace, flags, channels, fill_sym, stream);
 }

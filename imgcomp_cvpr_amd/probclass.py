@@ -393,12 +393,26 @@ class PredictionNetwork(object):
             res.append((bytes(out[n, :nbytes[n]].cpu().numpy()), int(sym[n, 0, 0, 0])))
         return res if batched else res[0]
 
-    def decode_stream(self, stream_bytes, symbols_shape, first_sym, flags=0):
+    def _preview(self, channels, C):
+        """channels=None -> None (the full decode, the old entries); else (channels, fill symbol) for the *_channels entries, which
+        exist for the k = 24 kernels only"""
+        if channels is None:
+            return None
+        from .codec import check_channels
+        channels = check_channels(channels, C)
+        if self.pc._k != 24:
+            raise ValueError('a preview (channels={}) needs a context model of width k = 24, this one has k = {}'.format(channels, self.pc._k))
+        return channels, self.conceal_fallback()
+
+    def decode_stream(self, stream_bytes, symbols_shape, first_sym, flags=0, channels=None):
         """Row N3: the whole sequential decode on the device (ic_pc_decode_f32) -- per symbol the same context-model
         kernels as get_freqs, the table, the arithmetic-decoder step and the gather of the next context are enqueued
         back to back without a host round trip.  stream_bytes: what the encoder wrote; symbols_shape: un-padded
-        (C,h,w); first_sym: the uncoded first symbol.  -> (C,h,w) int64 numpy."""
+        (C,h,w); first_sym: the uncoded first symbol.  -> (C,h,w) int64 numpy.
+        channels=K: a preview (ic_pc_decode_channels_f32) -- the decoder stops after channels 0 .. K - 1, the others hold the fill
+        symbol (conceal_fallback): codec.preview_symbols of the full decode.  None: all channels, the call as it always was."""
         C, h, w = (int(v) for v in symbols_shape)
+        preview = self._preview(channels, C)
         dev = self.centers.device
         data = torch.frombuffer(bytearray(stream_bytes) or bytearray(1), dtype=torch.uint8).to(dev)
         out = torch.empty((C, h, w), dtype=torch.int64, device=dev)
@@ -406,9 +420,12 @@ class PredictionNetwork(object):
         need = lib.ic_pc_decode_workspace_bytes(C, h, w, self.pc._k)
         ws = torch.empty(need, dtype=torch.uint8, device=dev)
         centers = self.centers.contiguous().float()
-        check(lib.ic_pc_decode_f32(ptr(data), len(stream_bytes), int(first_sym), self.pc._tab, ptr(centers), self.pc._k,
-                                   self.pc.L, self.freqs_resolution, ptr(out), ptr(status), C, h, w, ptr(ws), need,
-                                   int(flags), _lib.current_stream(dev)), 'ic_pc_decode_f32')
+        args = (ptr(data), len(stream_bytes), int(first_sym), self.pc._tab, ptr(centers), self.pc._k, self.pc.L, self.freqs_resolution,
+                ptr(out), ptr(status), C, h, w, ptr(ws), need, int(flags), _lib.current_stream(dev))
+        if preview is None:
+            check(lib.ic_pc_decode_f32(*args), 'ic_pc_decode_f32')
+        else:
+            check(lib.ic_pc_decode_channels_f32(*(args + preview)), 'ic_pc_decode_channels_f32')
         if int(status.item()) != 0:
             raise ValueError('Cannot decode symbol because total is too large')
         return out.cpu().numpy()
@@ -433,12 +450,19 @@ class PredictionNetwork(object):
                 res[t] = r
         return res
 
-    def decode_tiles(self, streams, first_syms, symbols_shape, th, tw, flags=0):
+    def decode_tiles(self, streams, first_syms, symbols_shape, th, tw, flags=0, channels=None):
         """The mirror of encode_tiles: all tiles of a volume decoded by ONE launch, one work-group per tile
         (ic_pc_decode_tiles_f32; other k than 24 or non-zero flags: tile after tile, the slow path).  streams / first_syms in the
-        order of codec.tile_grid(h, w, th, tw); symbols_shape: un-padded (C,h,w).  -> (C,h,w) int64 numpy."""
+        order of codec.tile_grid(h, w, th, tw); symbols_shape: un-padded (C,h,w).  -> (C,h,w) int64 numpy.
+        channels=K: a preview, through the batch entry as a batch of one (decode_tiles_batch)."""
         from .codec import tile_grid
         C, h, w = (int(v) for v in symbols_shape)
+        if channels is not None:
+            try:
+                return self.decode_tiles_batch([(streams, first_syms, (C, h, w))], th, tw, want='symbols', flags=flags,
+                                               channels=channels)[0].cpu().numpy()
+            except ValueError as e:
+                raise ValueError(str(e).replace('(volume 0, tile ', '(tile '))
         grid = tile_grid(h, w, th, tw)
         if len(streams) != len(grid) or len(first_syms) != len(grid):
             raise ValueError('{} streams and {} first symbols for a grid of {} tiles'.format(len(streams), len(first_syms), len(grid)))
@@ -482,7 +506,8 @@ class PredictionNetwork(object):
                 res[n][t] = r
         return res
 
-    def decode_tiles_batch(self, volumes, th, tw, want='q', max_workspace_bytes=1 << 31, flags=0, conceal=False, order='raster'):
+    def decode_tiles_batch(self, volumes, th, tw, want='q', max_workspace_bytes=1 << 31, flags=0, conceal=False, order='raster',
+                           channels=None):
         """The mirror of encode_tiles_batch: the tiles of ALL volumes decoded by one launch per chunk (ic_pc_decode_tiles_batch_f32,
         one work-group per tile).  volumes: [(streams, first_syms, (C,h,w))], each as decode_tiles takes them, one C throughout.
         want: 'q' -> per volume the (C,h,w) float32 DEVICE tensor centers[symbols] (what ae.decode consumes: the symbols never
@@ -495,8 +520,12 @@ class PredictionNetwork(object):
         behind the decoder fills them from their intact neighbours (include/imgcomp_hip.h has the rule; the fallback symbol is
         the centre of smallest magnitude), and the call returns (result as above, [per volume [(tile, reason)] in tile order]).
         order='wavefront': the streams are in wavefront order (encode_tiles(order='wavefront')); sets PC_DECODE_WAVEFRONT, the
-        decoder that takes a front at a time.  The order is per call: raster and wavefront volumes do not share one."""
+        decoder that takes a front at a time.  The order is per call: raster and wavefront volumes do not share one.
+        channels=K: a preview (ic_pc_decode_tiles_batch_channels_f32) -- every tile's decoder stops after channels 0 .. K - 1 (in
+        wavefront order: after their last front), the others hold the fill symbol / its centre.  Not with conceal=True."""
         from .codec import tile_grid, chunk_tiles
+        if channels is not None and conceal:
+            raise ValueError('channels={} with conceal=True: a preview of a damaged file is not offered'.format(channels))
         if want not in ('q', 'symbols', 'both'):
             raise ValueError("want is 'q', 'symbols' or 'both', got {!r}".format(want))
         if order not in ('raster', 'wavefront'):
@@ -526,6 +555,7 @@ class PredictionNetwork(object):
                 blobs.append(bytes(streams[t]))
                 pos += len(streams[t])
         C, k = shapes[0][0], self.pc._k
+        preview = self._preview(channels, C)
         vtable, offs, total = _lib.packed_volume_table(shapes)
 
         def need(th_max, tw_max, ntiles):
@@ -544,10 +574,13 @@ class PredictionNetwork(object):
             ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
         step = ctypes.sizeof(_lib.PcTile)
         for a, b in chunks:
-            check(lib.ic_pc_decode_tiles_batch_f32(ptr(data), pos, ctypes.c_void_p(ctypes.addressof(table) + a * step), b - a,
-                                                   vtable, len(shapes), self.pc._tab, ptr(centers), k, self.pc.L,
-                                                   self.freqs_resolution, ptr(sym), ptr(q), ptr(status[a:b]), C, ptr(ws), ws_bytes,
-                                                   int(flags), _lib.current_stream(dev)), 'ic_pc_decode_tiles_batch_f32')
+            args = (ptr(data), pos, ctypes.c_void_p(ctypes.addressof(table) + a * step), b - a, vtable, len(shapes), self.pc._tab,
+                    ptr(centers), k, self.pc.L, self.freqs_resolution, ptr(sym), ptr(q), ptr(status[a:b]), C, ptr(ws), ws_bytes,
+                    int(flags), _lib.current_stream(dev))
+            if preview is None:
+                check(lib.ic_pc_decode_tiles_batch_f32(*args), 'ic_pc_decode_tiles_batch_f32')
+            else:
+                check(lib.ic_pc_decode_tiles_batch_channels_f32(*(args + preview)), 'ic_pc_decode_tiles_batch_channels_f32')
         damage = [[] for _ in shapes]
         for n, t in missing:
             damage[n].append((t, 'missing'))
@@ -567,7 +600,8 @@ class PredictionNetwork(object):
     def conceal_fallback(self):
         """the symbol a tile gets that has no intact neighbour: the centre of smallest magnitude (ties: the smallest index), what
         the quantiser emits where the importance map has masked a channel"""
-        return int(np.argmin(np.abs(self.centers.detach().float().cpu().numpy())))
+        from .codec import fill_symbol
+        return fill_symbol(self.centers.detach().float().cpu().numpy())
 
     def _conceal(self, sym, q, shapes, grids, vtable, damage, th, tw, centers):
         """one ic_pc_conceal_tiles launch on the current stream for the damaged tiles of all volumes; sym / q as decode_tiles_batch

@@ -320,6 +320,32 @@ int ic_pc_decode_tiles_batch_f32(const uint8_t* bitstreams, long long total_byte
                                  const ic_pc_volume_t* volumes_host, int nvolumes, const float* const* wtab_host,
                                  const float* centers, int k, int L, float resolution, int64_t* symbols, float* q, int* status,
                                  int C, void* workspace, size_t workspace_bytes, int flags, ic_stream_t stream);
+/* Preview: only the first `channels` of the C latent channels are decoded, the others are filled with one symbol.  The importance
+ * map zeroes, per latent position, every channel above a learned depth, so the autoencoder's decoder was trained on volumes whose
+ * trailing channels hold the centre nearest zero: channels 0 .. channels - 1 as decoded and fill_sym (the index of the centre of
+ * smallest magnitude, ties to the smallest index -- the caller passes it) everywhere else is a legitimate lower-quality input.
+ * The raster streams code their symbols in (c, y, x) order and the masks are causal in c, so the wanted symbols are a prefix of
+ * every stream and the decoder stops after them: (channels + 3) of (C + 3) planes of the sweep.  In the wavefront order a front
+ * also holds symbols of later channels; the decoder steps through them (they are in the stream, and in the context of later
+ * fronts) but does not store them: 4 (C - channels) of the (w + 3) + 2 (h + 3) + 4 (C + 3) - 6 steps are saved, less than raster.
+ * Both take the parameters and the workspace of their parents, then channels and fill_sym.
+ *   1 <= channels <= C and 0 <= fill_sym < L, else IC_ERR_ARG; only the k = 24 kernels have the limit: another k, or
+ *   IC_PC_DECODE_PER_LAYER / IC_PC_DECODE_RECOMPUTE, is IC_ERR_UNSUPPORTED (flags: 0; the batch entry also takes
+ *   IC_PC_DECODE_WAVEFRONT).  All of it is decided on the host before any device call; a refused call writes nothing.
+ *   Every position of symbols / q of every listed tile is written: [c < channels] as the parent writes it, [c >= channels] fill_sym
+ *   and centers[fill_sym].  channels == C is the parent's call, bit for bit.
+ *   status: the coder's error flag at the point where decoding stopped.  DAMAGE BEYOND THE PREFIX IS NOT SEEN by a prefix decode: a
+ *   stream whose full decode ends with status 1 may give status 0 here.  The container's CRCs (codec.py) are checked on the host
+ *   before anything reaches the device, whatever the number of channels. */
+int ic_pc_decode_channels_f32(const uint8_t* bitstream, long long nbytes, int first_sym, const float* const* wtab_host,
+                              const float* centers, int k, int L, float resolution, int64_t* symbols, int* status,
+                              int C, int h, int w, void* workspace, size_t workspace_bytes, int flags, ic_stream_t stream,
+                              int channels, int fill_sym);
+int ic_pc_decode_tiles_batch_channels_f32(const uint8_t* bitstreams, long long total_bytes, const ic_pc_tile_t* tiles_host, int ntiles,
+                                          const ic_pc_volume_t* volumes_host, int nvolumes, const float* const* wtab_host,
+                                          const float* centers, int k, int L, float resolution, int64_t* symbols, float* q,
+                                          int* status, int C, void* workspace, size_t workspace_bytes, int flags,
+                                          ic_stream_t stream, int channels, int fill_sym);
 /* Concealment: what stands in the volumes where a tile could not be decoded (a damaged file; codec.py, salvage).  Stated on symbols,
  * so exact: for a damaged tile T and a channel c the candidates are the symbols of channel c directly above T's top row, below its
  * bottom row, left of its left column and right of its right column (no corners) that lie inside the volume and in a tile that
