@@ -124,6 +124,7 @@ PROTOTYPES = {
                                 [c_int] * 4 + [c_void_p]),
     'ic_pc_workspace_bytes': (c_size_t, [c_int] * 5),
     'ic_pc_packed_floats': (c_size_t, [c_int, c_int]),
+    'ic_pc_mid_tile': (c_int, [c_int, c_int, c_int]),
     'ic_pc_pack_filters_f32': (c_int, [POINTER(c_void_p), c_int, c_int, c_void_p, c_void_p]),
     'ic_pc_logits_f32': (c_int, [c_void_p, POINTER(c_void_p), c_int, c_int, c_float, c_void_p] +
                          [c_int] * 4 + [c_void_p, c_size_t, c_void_p]),

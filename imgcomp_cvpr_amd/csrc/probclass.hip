@@ -673,21 +673,30 @@ static int launch_pc(const PcLayerArgs& a, hipStream_t st) {
     return IC_OK;
 }
 
+// tile shape of a middle (k -> k) layer per plane extent: a work-group computes TR x TC voxels and the launch runs
+// ceil(OH / TR) x ceil(OW / TC) of them per plane -- a 68 x 100 plane is 84 % useful in 8 x 16 tiles and 95 % in 5 x 25 (Kodak
+// volume, layer 1).  The first shape with the fewest work-groups wins.
+static const int PC_MID_SHAPES[3][2] = {{8, 16}, {5, 25}, {6, 21}};
+
+extern "C" int ic_pc_mid_tile(int k, int OH, int OW) {
+    if (OH <= 0 || OW <= 0 || !pc_mfma_supported(k, 1)) return -1;
+    if (k == 64) return 3;
+    int best = 0; long long best_cost = -1;
+    for (int i = 0; i < 3; ++i) {
+        const long long cost = (long long)ic_cdiv(OH, PC_MID_SHAPES[i][0]) * ic_cdiv(OW, PC_MID_SHAPES[i][1]);
+        if (best_cost < 0 || cost < best_cost) { best = i; best_cost = cost; }
+    }
+    return best;
+}
+
 static int launch_pc_mfma(const PcLayerArgs& a, const float* wpk, int k, bool final, hipStream_t st) {
     if (k == 24) {
         if (final) {
             dim3 g(a.OD * ic_cdiv(a.OH, 8) * ic_cdiv(a.OW, 16), 1, a.N);
             hipLaunchKernelGGL((pc_mfma_kernel<24, 24, 1, 4, 8, 16, true>), g, dim3(256), 0, st, a, wpk);
         } else {
-            // tile shape per layer: a work-group computes TR x TC voxels and the launch runs ceil(OH / TR) x ceil(OW / TC) of them
-            // per plane -- a 68 x 100 plane is 84 % useful in 8 x 16 tiles and 95 % in 5 x 25 (Kodak volume, layer 1)
-            const int shapes[3][2] = {{8, 16}, {5, 25}, {6, 21}};
-            int best = 0; long long best_cost = -1;
-            for (int i = 0; i < 3; ++i) {
-                const long long cost = (long long)ic_cdiv(a.OH, shapes[i][0]) * ic_cdiv(a.OW, shapes[i][1]);
-                if (best_cost < 0 || cost < best_cost) { best = i; best_cost = cost; }
-            }
-            dim3 g((unsigned)(a.OD * best_cost), 1, a.N);
+            const int best = ic_pc_mid_tile(k, a.OH, a.OW);
+            dim3 g((unsigned)((long long)a.OD * ic_cdiv(a.OH, PC_MID_SHAPES[best][0]) * ic_cdiv(a.OW, PC_MID_SHAPES[best][1])), 1, a.N);
             if (best == 0) hipLaunchKernelGGL((pc_mfma_kernel<24, 24, 1, 4, 8, 16, false>), g, dim3(256), 0, st, a, wpk);
             else if (best == 1) hipLaunchKernelGGL((pc_mfma_kernel<24, 24, 1, 4, 5, 25, false>), g, dim3(256), 0, st, a, wpk);
             else hipLaunchKernelGGL((pc_mfma_kernel<24, 24, 1, 4, 6, 21, false>), g, dim3(256), 0, st, a, wpk);

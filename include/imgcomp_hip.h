@@ -245,6 +245,10 @@ int ic_heatmap_quantize_f32(const float* bottleneck, const float* centers, int L
 size_t ic_pc_workspace_bytes(int N, int C, int h, int w, int k);
 size_t ic_pc_packed_floats(int k, int L);       /* 0: this (k, L) runs the any-shape VALU kernels, nothing to pack */
 int ic_pc_pack_filters_f32(const float* const* wtab_host, int k, int L, float* packed, ic_stream_t stream);
+/* the tile a work-group of a middle (k -> k) layer computes on an output plane of OH x OW voxels (host arithmetic, no device
+ * call; layer res1/conv1 of a (C,h,w) volume has the plane (h+4, w+4), res1/conv2 (h+2, w+2)): k = 24: 0 = 8 x 16, 1 = 5 x 25,
+ * 2 = 6 x 21, whichever covers the plane with the fewest tiles; k = 64: 3 = 4 x 16; -1: this k runs the VALU kernels */
+int ic_pc_mid_tile(int k, int OH, int OW);
 int ic_pc_logits_f32(const float* q, const float* const* wtab_host, int k, int L, float pad_value,
                      float* logits, int N, int C, int h, int w,
                      void* workspace, size_t workspace_bytes, ic_stream_t stream);
