@@ -67,6 +67,19 @@ class PcVolume(ctypes.Structure):
     _fields_ = [('h', c_int), ('w', c_int), ('symbols_off', c_longlong), ('q_off', c_longlong)]
 
 
+class PcSeg(ctypes.Structure):
+    """ic_pc_seg_t: one segment of ic_pc_decode_tiles_batch_layers_f32, nbytes bytes at bitstreams + off"""
+    _fields_ = [('off', c_longlong), ('nbytes', c_longlong)]
+
+
+def seg_table(segs):
+    """[(off, nbytes)], tile-major (ntiles x nlayers) -> host array of ic_pc_seg_t"""
+    arr = (PcSeg * max(len(segs), 1))()
+    for i, (off, n) in enumerate(segs):
+        arr[i] = PcSeg(int(off), int(n))
+    return arr
+
+
 def tile_table(tiles):
     """[(y0, x0, th, tw, stream_off, stream_bytes, first_sym[, volume])] -> host array of ic_pc_tile_t (volume 0 where not given)."""
     arr = (PcTile * len(tiles))()
@@ -150,6 +163,12 @@ PROTOTYPES = {
     'ic_pc_decode_tiles_batch_channels_f32': (c_int, [c_void_p, c_longlong, c_void_p, c_int, c_void_p, c_int, POINTER(c_void_p), c_void_p,
                                                       c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_size_t,
                                                       c_int, c_void_p, c_int, c_int]),
+    'ic_pc_decode_tiles_batch_layers_workspace_bytes': (c_size_t, [c_int] * 7),
+    'ic_pc_decode_tiles_batch_layers_f32': (c_int, [c_void_p, c_longlong, c_void_p, c_int, c_void_p, c_int, POINTER(c_void_p), c_void_p,
+                                                    c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_size_t,
+                                                    c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p]),
+    'ic_pc_encode_segments_f32': (c_int, [c_void_p, c_void_p, c_int, c_longlong, c_int, c_float, c_void_p, c_int, c_void_p, c_longlong,
+                                          c_void_p, c_void_p, c_void_p]),
     'ic_pc_conceal_tiles_workspace_bytes': (c_size_t, [c_int, c_int, c_longlong]),
     'ic_pc_conceal_tiles': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p] + [c_int] * 5 +
                             [c_void_p, c_size_t, c_void_p]),

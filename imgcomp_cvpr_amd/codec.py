@@ -1,10 +1,10 @@
 """Image codec: an image to a self-describing file and back.
 
     python -m imgcomp_cvpr_amd.codec compress   IN.png  OUT.icf [--ae_config cvpr/low] [--pc_config cvpr/res_shallow] [--weights synthetic|FILE.npz|CKPT]
-                                                                [--tile PIXELS [--checked | --wavefront]]
-    python -m imgcomp_cvpr_amd.codec decompress IN.icf  OUT.png [same options] [--salvage | --channels K]
-    python -m imgcomp_cvpr_amd.codec compress-dir   IN_DIR OUT_DIR [--tile PIXELS [--checked | --wavefront]] [--batch N]   every *.png / *.jpg -> OUT_DIR/<stem>.icf
-    python -m imgcomp_cvpr_amd.codec decompress-dir IN_DIR OUT_DIR [--batch N] [--salvage | --channels K]    every *.icf -> OUT_DIR/<stem>.png
+                                                                [--tile PIXELS [--checked | --wavefront | --layers a,b,.. | --progressive]]
+    python -m imgcomp_cvpr_amd.codec decompress IN.icf  OUT.png [same options] [--salvage | --channels K | --partial]
+    python -m imgcomp_cvpr_amd.codec compress-dir   IN_DIR OUT_DIR [--tile PIXELS [--checked | --wavefront | --layers a,b,.. | --progressive]] [--batch N]   every *.png / *.jpg -> OUT_DIR/<stem>.icf
+    python -m imgcomp_cvpr_amd.codec decompress-dir IN_DIR OUT_DIR [--batch N] [--salvage | --channels K | --partial]    every *.icf -> OUT_DIR/<stem>.png
     python -m imgcomp_cvpr_amd.codec verify PATH [PATH ...]         files or directories of *.icf: the checksums, without model or device
 
 compress:   pad to a multiple of the subsampling factor (val.add_padding) -> ae.encode -> PredictionNetwork.encode_stream (the
@@ -71,6 +71,28 @@ map has masked a channel -- the decoder network knows such volumes (preview_symb
 code (c, y, x) order, so the decoder stops after a prefix of every stream: (K + 3) / (C + 3) of its steps.  A format-5 decoder
 must step through the symbols of later channels that share a front with wanted ones (wavefront_prefix_count) and saves less.
 All CRCs are checked as always; damage in the bytes a preview does not reach cannot show in the decoder's status.
+--tile --layers a,b,.. / --tile --progressive (Codec(tile=(th, tw), layers=[..] | 'default')): format 6, "layered tiles" -- a progressive
+file.  Autoencoder, tiling and tables are those of formats 2 and 4 (every tile a volume of its own, raster order, first symbol
+uncoded); only the cutting and the placing of the coded bytes differ.  Layer ends e_0 < e_1 < .. < e_{G-1} = C, 1 <= G <= 16: layer g
+holds channels [e_{g-1}, e_g), e_{-1} = 0 (--progressive: default_layer_ends(C) = C/8, C/4, C/2, C).  Segment (t, g) is the range coder
+started afresh over tile t's symbols of layer g in raster order, over those symbols' rows of the tile's own tables, terminated like
+every stream: arithmetic_coding.encode_sequence(flat[a:b], freqs[a:b]) with a = max(1, e_{g-1} th' tw'), b = e_g th' tw'.  The context
+crosses the layer boundaries (the lower channels are known to the decoder), only the coder state restarts; G = 1 is the format-4
+stream of every tile.  The payload holds the segments LAYER first, so the bytes [0, layer_prefix_bytes(g)) are the header and the
+layers 0 .. g - 1 of every tile: a reader holding them decodes channels 0 .. e_{g-1} - 1 of the whole image (decompress --partial,
+Codec.decompress_partial; the other channels as in a --channels preview).
+    0       4     magic  b'ICVF'
+    4       2     format version (u16) = 6
+    ..            ae name, pc name, H, W, C, h, w, L, resolution, fingerprint, th, tw, ntiles: as version 4
+    ..      2     G, the number of layers (u16)
+    ..      2*G   layer ends e_0 .. e_{G-1} (u16 each)
+    ..      2*nt  first_sym per tile, raster order (u16)
+    ..      8*G*nt segment table, LAYER-major (for g: for t:): length in bytes (u32), CRC-32 of the segment's bytes (u32)
+    ..      8     payload length n (u64) = the sum of the lengths
+    ..      4     header CRC-32: of every byte before it
+    ..      n     payload: the segments in table order (all tiles' layer 0, then all tiles' layer 1, ..)
+    ..      4     CRC-32 of every byte before it (u32)
+decompress reads it as strictly as format 4; salvage of format 6 is not offered; verify checks it on the host.
 """
 import argparse
 import io
@@ -100,7 +122,13 @@ FORMAT_VERSION_CHECKED = 4                                           # 3 is not 
 CheckedContainer = namedtuple('CheckedContainer', TiledContainer._fields + ('stream_crcs',))
 FORMAT_VERSION_WAVEFRONT = 5                                         # the layout of 4, the streams in wavefront order
 WavefrontContainer = namedtuple('WavefrontContainer', CheckedContainer._fields)
-_TILED = (TiledContainer, CheckedContainer, WavefrontContainer)
+FORMAT_VERSION_LAYERED = 6                                           # raster tiles cut into layers, stored layer first
+MAX_LAYERS = 16
+# streams[t] is tile t's list of G segments (what decode_tiles_batch(layer_ends=...) takes), segments[g][t] the same bytes layer-major
+# (the file's order), segment_crcs[g][t] their CRCs; a segment that parse_partial found incomplete is None in both views
+LayeredContainer = namedtuple('LayeredContainer', TiledContainer._fields + ('layer_ends', 'segments', 'segment_crcs'))
+PartialReport = namedtuple('PartialReport', ['layers_total', 'layers_decoded', 'channels', 'file_crc_ok'])
+_TILED = (TiledContainer, CheckedContainer, WavefrontContainer, LayeredContainer)
 _WITH_CRCS = (FORMAT_VERSION_CHECKED, FORMAT_VERSION_WAVEFRONT)
 WAVEFRONT_COEFFS = (2, 4)                                            # T = x + 2 y + 4 c: fixed by format 5
 
@@ -312,6 +340,47 @@ def build_wavefront_container(ae_name, pc_name, H, W, C, h, w, L, resolution, fi
     return body + struct.pack('<I', zlib.crc32(body) & 0xffffffff)
 
 
+def default_layer_ends(C):
+    """the layer ends of --progressive / layers='default': [max(1, C // 8), C // 4, C // 2, C] with repeats and zeros dropped --
+    4, 8, 16, 32 for C = 32; increasing, at most four, the last one C"""
+    C = int(C)
+    if C < 1:
+        raise ValueError('layer ends: C = {} is not at least 1'.format(C))
+    return sorted(set(e for e in (max(1, C // 8), C // 4, C // 2, C) if e > 0))
+
+
+def check_layer_ends(layer_ends, C):
+    """layer ends e_0 < e_1 < .. < e_{G-1} = C with 1 <= G <= 16 and e_0 >= 1 -> list of int; else a ValueError naming the cause"""
+    try:
+        ends = [int(e) for e in layer_ends]
+        whole = all(not isinstance(e, (bool, np.bool_)) and int(e) == e for e in layer_ends)
+    except (TypeError, ValueError):
+        raise ValueError('layer ends {!r} are not a sequence of integers'.format(layer_ends))
+    if not whole:
+        raise ValueError('layer ends {!r} are not a sequence of integers'.format(layer_ends))
+    if not 1 <= len(ends) <= MAX_LAYERS:
+        raise ValueError('layer count G = {} is outside 1 .. {}'.format(len(ends), MAX_LAYERS))
+    if ends[0] < 1 or any(b <= a for a, b in zip(ends, ends[1:])):
+        raise ValueError('layer ends {} are not increasing from at least 1'.format(ends))
+    if ends[-1] != int(C):
+        raise ValueError('last layer end {} is not C = {}: the layers must hold every channel'.format(ends[-1], int(C)))
+    return ends
+
+
+def build_layered_container(ae_name, pc_name, H, W, C, h, w, L, resolution, fingerprint, th, tw, first_syms, layer_ends, segments):
+    """format 6: segments[g][t] = the bytes of layer g of tile t (tiles in the order of tile_grid(h, w, th, tw))."""
+    ends = check_layer_ends(layer_ends, C)
+    segments = [[bytes(b) for b in layer] for layer in segments]
+    assert len(segments) == len(ends) and all(len(layer) == len(first_syms) for layer in segments)
+    front = _tiled_head(FORMAT_VERSION_LAYERED, ae_name, pc_name, H, W, C, h, w, L, resolution, fingerprint, th, tw, [b''] * len(first_syms), 0)[:-8]
+    flat = [b for layer in segments for b in layer]
+    head = b''.join([front, struct.pack('<H', len(ends)), struct.pack('<{}H'.format(len(ends)), *ends),
+                     struct.pack('<{}H'.format(len(first_syms)), *first_syms)] +
+                    [struct.pack('<II', len(b), zlib.crc32(b) & 0xffffffff) for b in flat] + [struct.pack('<Q', sum(len(b) for b in flat))])
+    body = head + struct.pack('<I', zlib.crc32(head) & 0xffffffff) + b''.join(flat)
+    return body + struct.pack('<I', zlib.crc32(body) & 0xffffffff)
+
+
 def build_container(ae_name, pc_name, H, W, C, h, w, L, first_sym, resolution, fingerprint, payload):
     a, p = ae_name.encode('utf-8'), pc_name.encode('utf-8')
     head = b''.join([
@@ -353,15 +422,16 @@ def parse_container(data):
     if data[:4] != MAGIC:
         raise ValueError('wrong magic {!r}: not a codec file (expected {!r})'.format(data[:4], MAGIC))
     version, = struct.unpack('<H', data[4:6])
-    if version not in (FORMAT_VERSION, FORMAT_VERSION_TILED, FORMAT_VERSION_CHECKED, FORMAT_VERSION_WAVEFRONT):
-        raise ValueError('unsupported format version {} (this codec reads versions {}, {} and {}) and the wavefront version {}'.format(
-            version, FORMAT_VERSION, FORMAT_VERSION_TILED, FORMAT_VERSION_CHECKED, FORMAT_VERSION_WAVEFRONT))
+    if version not in (FORMAT_VERSION, FORMAT_VERSION_TILED, FORMAT_VERSION_CHECKED, FORMAT_VERSION_WAVEFRONT, FORMAT_VERSION_LAYERED):
+        raise ValueError(_unsupported(version))
     stored, = struct.unpack('<I', data[-4:])
     actual = zlib.crc32(data[:-4]) & 0xffffffff
     if stored != actual:
         raise ValueError('CRC mismatch: file says {:08x}, content gives {:08x} (corrupt or truncated file)'.format(stored, actual))
     r = _Reader(data[:-4])
     ae_name, pc_name, H, W, C, h, w = _parse_front(r)
+    if version == FORMAT_VERSION_LAYERED:
+        return _parse_layered(r, ae_name, pc_name, H, W, C, h, w, strict=True)[0]
     if version != FORMAT_VERSION:
         return _parse_tiled(r, version, ae_name, pc_name, H, W, C, h, w)
     L, first_sym = r.unpack('<HH', 'L and first symbol')
@@ -372,6 +442,12 @@ def parse_container(data):
     if n != left:
         raise ValueError('payload length {} does not equal the {} bytes that remain in the file'.format(n, left))
     return Container(version, ae_name, pc_name, H, W, C, h, w, L, first_sym, resolution, fingerprint, r.take(n, 'payload'))
+
+
+def _unsupported(version):
+    return ('unsupported format version {} (this codec reads versions {}, {} and {}) and the wavefront version {} and the layered '
+            'version {}'.format(version, FORMAT_VERSION, FORMAT_VERSION_TILED, FORMAT_VERSION_CHECKED, FORMAT_VERSION_WAVEFRONT,
+                                FORMAT_VERSION_LAYERED))
 
 
 def _parse_front(r):
@@ -388,9 +464,8 @@ def _parse_front(r):
     return ae_name, pc_name, H, W, C, h, w
 
 
-def _parse_tile_table(r, version, h, w):
-    """L .. payload length of a format-2 / format-4 / format-5 header, every length against the bytes that remain -> (L, resolution,
-    fingerprint, th, tw, first_syms, lengths, crcs or None, n)"""
+def _parse_tile_extent(r, h, w):
+    """L .. tile count, which every tiled format has -> (L, resolution, fingerprint, th, tw, ntiles)"""
     L, = r.unpack('<H', 'L')
     resolution, = r.unpack('<d', 'frequency resolution')
     fingerprint, = r.unpack('<I', 'model fingerprint')
@@ -404,6 +479,13 @@ def _parse_tile_table(r, version, h, w):
     if ntiles != expected:
         raise ValueError('tile count {} does not equal the {} tiles of a {} x {} volume cut into {} x {}'.format(
             ntiles, expected, h, w, th, tw))
+    return L, resolution, fingerprint, th, tw, ntiles
+
+
+def _parse_tile_table(r, version, h, w):
+    """L .. payload length of a format-2 / format-4 / format-5 header, every length against the bytes that remain -> (L, resolution,
+    fingerprint, th, tw, first_syms, lengths, crcs or None, n)"""
+    L, resolution, fingerprint, th, tw, ntiles = _parse_tile_extent(r, h, w)
     checked = version in _WITH_CRCS
     row = 10 if checked else 6
     table = r.take(row * ntiles, 'tile table')            # against the bytes that remain, before anything of its size is built
@@ -451,6 +533,131 @@ def _parse_tiled(r, version, ae_name, pc_name, H, W, C, h, w):
     return cls(version, ae_name, pc_name, H, W, C, h, w, L, resolution, fingerprint, th, tw, first_syms, streams, payload, crcs)
 
 
+def _parse_layered(r, ae_name, pc_name, H, W, C, h, w, strict):
+    """the rest of a format-6 file after the symbol volume shape -> (LayeredContainer, layers_complete, payload complete).
+    The header: every length against the bytes that remain, then its own CRC.  strict (parse_container; the CRC over the file has
+    been checked): the payload length must equal what is left and every segment must match its CRC.  Not strict (parse_partial): the
+    payload is what arrived of it; a segment that is not whole or fails its CRC is None."""
+    L, resolution, fingerprint, th, tw, ntiles = _parse_tile_extent(r, h, w)
+    G, = r.unpack('<H', 'layer count')
+    if not 1 <= G <= MAX_LAYERS:
+        raise ValueError('layer count G = {} is outside 1 .. {}'.format(G, MAX_LAYERS))
+    ends = check_layer_ends(r.unpack('<{}H'.format(G), 'layer ends'), C)
+    first_syms = list(r.unpack('<{}H'.format(ntiles), 'first symbols'))
+    for t, f in enumerate(first_syms):
+        if f >= L:
+            raise ValueError('first symbol {} of tile {} is not below L = {}'.format(f, t, L))
+    table = r.take(8 * G * ntiles, 'segment table')        # against the bytes that remain, before anything of its size is built
+    rows = struct.unpack('<{}I'.format(2 * G * ntiles), table)
+    lengths = [[rows[2 * (g * ntiles + t)] for t in range(ntiles)] for g in range(G)]
+    crcs = [[rows[2 * (g * ntiles + t) + 1] for t in range(ntiles)] for g in range(G)]
+    n, = r.unpack('<Q', 'payload length')
+    total = sum(sum(layer) for layer in lengths)
+    if total != n:
+        raise ValueError('segment lengths of the {} layers of {} tiles sum to {}, the payload length is {}'.format(G, ntiles, total, n))
+    end = r.pos
+    stored, = r.unpack('<I', 'header CRC')
+    actual = zlib.crc32(r.data[:end]) & 0xffffffff
+    if stored != actual:
+        raise ValueError('header CRC mismatch: file says {:08x}, the header gives {:08x}'.format(stored, actual))
+    left = len(r.data) - r.pos
+    if strict and n != left:
+        raise ValueError('payload length {} does not equal the {} bytes that remain in the file'.format(n, left))
+    payload = r.data[r.pos:r.pos + n]
+    segments, pos, complete = [], 0, 0
+    for g in range(G):
+        layer = []
+        for t in range(ntiles):
+            b = payload[pos:pos + lengths[g][t]]
+            pos += lengths[g][t]
+            if pos <= len(payload) and zlib.crc32(b) & 0xffffffff == crcs[g][t]:
+                layer.append(b)
+            elif strict:
+                raise ValueError('segment CRC mismatch in layer {}, tile {}: the table says {:08x}, the segment gives {:08x}'.format(
+                    g, t, crcs[g][t], zlib.crc32(b) & 0xffffffff))
+            else:
+                layer.append(None)
+        if complete == g and all(b is not None for b in layer):
+            complete = g + 1
+        segments.append(layer)
+    streams = [[segments[g][t] for g in range(G)] for t in range(ntiles)]
+    c = LayeredContainer(FORMAT_VERSION_LAYERED, ae_name, pc_name, H, W, C, h, w, L, resolution, fingerprint, th, tw, first_syms, streams,
+                         payload, ends, segments, crcs)
+    return c, complete, len(payload) == n
+
+
+def _check_layer_index(g, G):
+    if isinstance(g, (bool, np.bool_)) or not isinstance(g, (int, np.integer)) or not 0 <= int(g) <= G:
+        raise ValueError('layer prefix: g = {!r} is outside 0 .. G = {}'.format(g, G))
+    return int(g)
+
+
+def layer_prefix_bytes(data_or_container, g):
+    """the length of the prefix of a format-6 file that holds the header and the layers 0 .. g - 1 of every tile, g in 0 .. G
+    (g = 0: the header alone; g = G: the file without its last 4 bytes, the CRC over the file).  Takes the file's bytes -- a prefix
+    that holds the whole header will do -- or a LayeredContainer of parse_container."""
+    c = data_or_container
+    if not isinstance(c, LayeredContainer):
+        return _prefix_from_bytes(bytes(c), g)
+    g = _check_layer_index(g, len(c.layer_ends))
+    if any(b is None for layer in c.segments[:g] for b in layer):
+        raise ValueError('layer prefix: this container has incomplete layers, take the lengths from the bytes of the file')
+    a, p, nt, G = len(c.ae_name.encode('utf-8')), len(c.pc_name.encode('utf-8')), len(c.first_syms), len(c.layer_ends)
+    header = 4 + 2 + 2 + a + 2 + p + 8 + 10 + 2 + 8 + 4 + 4 + 4 + 2 + 2 * G + 2 * nt + 8 * G * nt + 8 + 4
+    return header + sum(len(b) for layer in c.segments[:g] for b in layer)
+
+
+def _prefix_from_bytes(data, g):
+    r, version = _partial_open(data)
+    try:
+        ae_name, pc_name, H, W, C, h, w = _parse_front(r)
+        L, resolution, fingerprint, th, tw, ntiles = _parse_tile_extent(r, h, w)
+        G, = r.unpack('<H', 'layer count')
+        if not 1 <= G <= MAX_LAYERS:
+            raise ValueError('layer count G = {} is outside 1 .. {}'.format(G, MAX_LAYERS))
+        r.take(2 * G + 2 * ntiles, 'layer ends and first symbols')
+        rows = struct.unpack('<{}I'.format(2 * G * ntiles), r.take(8 * G * ntiles, 'segment table'))
+        r.take(8, 'payload length')
+        end = r.pos
+        stored, = r.unpack('<I', 'header CRC')
+    except ValueError as e:
+        raise ValueError('header damaged: {}'.format(e))
+    if stored != zlib.crc32(data[:end]) & 0xffffffff:
+        raise ValueError('header damaged: header CRC mismatch')
+    return r.pos + sum(rows[2 * i] for i in range(_check_layer_index(g, G) * ntiles))
+
+
+def _partial_open(data):
+    if len(data) < _MIN_SIZE:
+        raise ValueError('header damaged: truncated file: {} bytes, the smallest container has {}'.format(len(data), _MIN_SIZE))
+    if data[:4] != MAGIC:
+        raise ValueError('header damaged: wrong magic {!r}: not a codec file (expected {!r})'.format(data[:4], MAGIC))
+    version, = struct.unpack('<H', data[4:6])
+    if version != FORMAT_VERSION_LAYERED:
+        raise ValueError('header damaged: format version {} is not the layered version {}: only a layered file (--tile --layers / '
+                         '--progressive) decodes from a prefix'.format(version, FORMAT_VERSION_LAYERED))
+    return _Reader(data), version
+
+
+def parse_partial(data):
+    """a prefix of a format-6 file (or the whole file, or a damaged one) -> (LayeredContainer, layers_complete, file_crc_ok).
+    The header must be whole and pass its own CRC, else ValueError('header damaged: ...').  Behind it nothing raises: a layer is
+    complete when all its segments are there and match their CRCs, layers_complete counts the leading complete layers, every
+    segment that is not whole or fails its CRC is None in the container; file_crc_ok says whether the CRC over the file is there
+    and right.  Bytes behind the declared end are ignored."""
+    data = bytes(data)
+    r, _ = _partial_open(data)
+    try:
+        ae_name, pc_name, H, W, C, h, w = _parse_front(r)
+        c, complete, whole = _parse_layered(r, ae_name, pc_name, H, W, C, h, w, strict=False)
+    except ValueError as e:
+        raise ValueError('header damaged: nothing can be decoded ({})'.format(e))
+    end = _prefix_from_bytes(data, len(c.layer_ends))       # where the CRC over the file stands
+    tail = data[end:end + 4]
+    file_crc_ok = whole and len(tail) == 4 and struct.unpack('<I', tail)[0] == zlib.crc32(data[:end]) & 0xffffffff
+    return c, complete, bool(file_crc_ok)
+
+
 def parse_salvage(data):
     """what a possibly damaged format-4 or format-5 file still holds -> (CheckedContainer or WavefrontContainer, damage, file_crc_ok).  damage: [(tile, reason)] in
     tile order, reason 'crc' (the bytes are there, their CRC differs) or 'truncated' (the tile's byte range is not complete);
@@ -467,6 +674,9 @@ def parse_salvage(data):
     if version in (FORMAT_VERSION, FORMAT_VERSION_TILED):
         raise ValueError('format version {} has nothing to salvage with: one CRC over the whole file, none per tile (only version {}, '
                          'written with --tile --checked, can be salvaged)'.format(version, FORMAT_VERSION_CHECKED))
+    if version == FORMAT_VERSION_LAYERED:
+        raise ValueError('format version {} (layered tiles) is not salvaged: salvage of layered files is out of scope; '
+                         'decompress --partial (Codec.decompress_partial) reads the complete layers of a cut file'.format(version))
     if version not in _WITH_CRCS:
         raise ValueError('unsupported format version {} (only version {} can be salvaged) or the wavefront version {}'.format(
             version, FORMAT_VERSION_CHECKED, FORMAT_VERSION_WAVEFRONT))
@@ -529,10 +739,14 @@ class Codec(object):
     the same streams with a CRC each (salvage reads what a damaged one still holds).  order: 'raster' as above; 'wavefront' (needs
     a tile extent) writes format 5, the layout of format 4 with every tile's symbols coded front by front, which the decoder
     takes a front at a time -- refused here, with a ValueError, for a context model whose masks do not make T = x + 2 y + 4 c a
-    valid order or whose width the wavefront decoder does not cover.  Reading needs no option: the file's version decides."""
+    valid order or whose width the wavefront decoder does not cover.  layers: None as above; 'default' (default_layer_ends(C)) or a
+    sequence of layer ends e_0 < .. < e_{G-1} = C writes format 6, every tile's raster stream cut into G segments and stored layer
+    first, so that a prefix of the file decodes (decompress_partial); needs a tile extent, not with order='wavefront', carries the
+    checksums whatever `checked` says; refused, like the wavefront order, for a context model of another width than k = 24.
+    Reading needs no option: the file's version decides."""
 
     def __init__(self, ae_config, pc_config, weights, device='cuda', plan_flags=0, device_encode=True, tile=None, checked=False,
-                 order='raster'):
+                 order='raster', layers=None):
         if tile is not None:
             tile = (int(tile[0]), int(tile[1]))
             if not (1 <= tile[0] <= 0xffff and 1 <= tile[1] <= 0xffff):
@@ -543,7 +757,15 @@ class Codec(object):
             raise ValueError("order is 'raster' or 'wavefront', got {!r}".format(order))
         if order == 'wavefront' and tile is None:
             raise ValueError("order='wavefront' needs a tile extent: format 5 is a tiled format")
-        self.tile, self.checked, self.order = tile, bool(checked), order
+        if layers is not None:
+            if tile is None:
+                raise ValueError('layers needs a tile extent: format 6 is a tiled format')
+            if order == 'wavefront':
+                raise ValueError("layers does not go with order='wavefront': a layer is no prefix of a wavefront-ordered stream")
+            layers = layers if isinstance(layers, str) else check_layer_ends(layers, ae_config.num_chan_bn)
+            if isinstance(layers, str) and layers != 'default':
+                raise ValueError("layers is None, 'default' or a sequence of layer ends, got {!r}".format(layers))
+        self.tile, self.checked, self.order, self.layers = tile, bool(checked), order, layers
         import torch
         from . import autoencoder, probclass
         self.device = torch.device(device)
@@ -557,6 +779,11 @@ class Codec(object):
             self.wavefront_refusal = str(e)
         if order == 'wavefront' and self.wavefront_refusal:
             raise ValueError(self.wavefront_refusal)
+        k = int(getattr(self.pc, '_k', None) or pc_config.arch_param__k)
+        self.layered_refusal = None if k == 24 else ('layered tiles: the decoder that restarts at layer cuts covers context models of '
+                                                     'width k = 24, this one has k = {}'.format(k))
+        if layers is not None and self.layered_refusal:
+            raise ValueError(self.layered_refusal)
         self.pred = probclass.PredictionNetwork(self.pc, pc_config, self.ae.get_centers_variable())
         self.ae_name, self.pc_name = config_name(ae_config), config_name(pc_config)
         self.factor = int(self.ae.get_subsampling_factor())
@@ -599,6 +826,12 @@ class Codec(object):
         enc, (H, W) = self.encode_symbols(img_hwc_uint8)
         sym = enc.symbols[0]
         C, h, w = (int(v) for v in sym.shape)
+        ends = self._layer_ends()
+        if ends is not None:
+            th, tw = self.tile
+            coded = self.pred.encode_tiles(sym, th, tw, layer_ends=ends)
+            return build_layered_container(self.ae_name, self.pc_name, H, W, C, h, w, self.L, self.pred.freqs_resolution, self.fingerprint,
+                                           th, tw, [f for _, f in coded], ends, [[segs[g] for segs, _ in coded] for g in range(len(ends))])
         if self.tile is not None:
             th, tw = self.tile
             coded = self.pred.encode_tiles(sym, th, tw, order=self._order())
@@ -610,6 +843,22 @@ class Codec(object):
             payload, first_sym = self._host_encode_stream(sym.cpu().numpy())
         return build_container(self.ae_name, self.pc_name, H, W, C, h, w, self.L, first_sym, self.pred.freqs_resolution,
                                self.fingerprint, payload)
+
+    def _layer_ends(self):
+        """the layer ends compress writes, or None (the attributes may have been set after construction, as main does)"""
+        if self.layers is None:
+            return None
+        if self.tile is None:
+            raise ValueError('layers needs a tile extent: format 6 is a tiled format')
+        if self.order == 'wavefront':
+            raise ValueError("layers does not go with order='wavefront': a layer is no prefix of a wavefront-ordered stream")
+        if self.layered_refusal:
+            raise ValueError(self.layered_refusal)
+        if isinstance(self.layers, str):
+            if self.layers != 'default':
+                raise ValueError("layers is None, 'default' or a sequence of layer ends, got {!r}".format(self.layers))
+            return default_layer_ends(self.C)
+        return check_layer_ends(self.layers, self.C)
 
     def _order(self):
         """the order compress writes (the attributes may have been set after construction, as main does)"""
@@ -650,6 +899,8 @@ class Codec(object):
                 c.h, c.w, c.H, c.W, eh, ew))
         if isinstance(c, WavefrontContainer) and self.wavefront_refusal:
             raise ValueError('format 5 cannot be read with this model: {}'.format(self.wavefront_refusal))
+        if isinstance(c, LayeredContainer) and self.layered_refusal:
+            raise ValueError('format 6 cannot be read with this model: {}'.format(self.layered_refusal))
         for first_sym in (c.first_syms if isinstance(c, _TILED) else [c.first_sym]):
             if first_sym >= c.L:
                 raise ValueError('header mismatch: first symbol {} is not below L = {}'.format(first_sym, c.L))
@@ -664,7 +915,10 @@ class Codec(object):
         c = parse_container(data)
         self.check_container(c)
         try:
-            if isinstance(c, WavefrontContainer):        # a batch of one: the order is a flag of the batch entry
+            if isinstance(c, LayeredContainer):          # a batch of one: the layers are arguments of the batch entry
+                sym = self.pred.decode_tiles_batch([(c.streams, c.first_syms, (c.C, c.h, c.w))], c.th, c.tw, want='symbols',
+                                                   channels=channels, layer_ends=c.layer_ends)[0].cpu().numpy()
+            elif isinstance(c, WavefrontContainer):      # a batch of one: the order is a flag of the batch entry
                 sym = self.pred.decode_tiles_batch([(c.streams, c.first_syms, (c.C, c.h, c.w))], c.th, c.tw, want='symbols',
                                                    order='wavefront', channels=channels)[0].cpu().numpy()
             elif isinstance(c, _TILED):
@@ -675,10 +929,30 @@ class Codec(object):
             raise ValueError('decoder status is not 0: {}'.format(e))
         return sym, c
 
+    def decompress_partial(self, data):
+        """a prefix of a format-6 file -> (HWC uint8 image, PartialReport(layers_total, layers_decoded, channels, file_crc_ok)): the
+        leading complete layers (parse_partial) decoded as the preview of their channels, decompress(whole file, channels=e_{g-1});
+        the whole file gives decompress(data).  A ValueError for another format, a damaged header, another model, no complete layer."""
+        c, complete, file_crc_ok = parse_partial(data)
+        self.check_container(c)
+        if complete < 1:
+            raise ValueError('no complete layer: the file holds {} bytes, layer 0 ends at byte {}'.format(len(data), layer_prefix_bytes(data, 1)))
+        channels = c.layer_ends[complete - 1]
+        try:
+            sym = self.pred.decode_tiles_batch([(c.streams, c.first_syms, (c.C, c.h, c.w))], c.th, c.tw, want='symbols',
+                                               channels=channels, layer_ends=c.layer_ends)[0].cpu().numpy()
+        except ValueError as e:
+            raise ValueError('decoder status is not 0: {}'.format(e))
+        return self._image(sym, c), PartialReport(len(c.layer_ends), complete, channels, file_crc_ok)
+
     def decompress(self, data, channels=None):
         """container bytes -> HWC uint8 image; channels=K: the preview from the first K latent channels (decode_symbols)"""
-        import torch
         sym, c = self.decode_symbols(data, channels=channels)
+        return self._image(sym, c)
+
+    def _image(self, sym, c):
+        """symbols (C,h,w) numpy of container c -> the HWC uint8 image"""
+        import torch
         s = torch.as_tensor(sym).to(self.device)
         q = self.ae.get_centers_variable()[s][None].contiguous()
         x_out = self.ae.decode(q, is_training=False).to(torch.uint8)            # tf.cast truncates (val.py)
@@ -741,6 +1015,15 @@ class Codec(object):
             xs.append(torch.as_tensor(np.ascontiguousarray(np.transpose(padded, (2, 0, 1)))[None]).to(self.device).float())
         syms = self._in_flight(xs, lambda ae, x: ae.encode(x, is_training=False).symbols[0])
         out = [None] * len(syms)
+        ends = self._layer_ends()
+        if ends is not None:
+            th, tw = self.tile
+            for i, coded in enumerate(self.pred.encode_tiles_batch(syms, th, tw, layer_ends=ends)):
+                C, h, w = (int(v) for v in syms[i].shape)
+                out[i] = build_layered_container(self.ae_name, self.pc_name, sizes[i][0], sizes[i][1], C, h, w, self.L,
+                                                 self.pred.freqs_resolution, self.fingerprint, th, tw, [f for _, f in coded], ends,
+                                                 [[segs[g] for segs, _ in coded] for g in range(len(ends))])
+            return out
         if self.tile is not None:
             th, tw = self.tile
             for i, coded in enumerate(self.pred.encode_tiles_batch(syms, th, tw, order=self._order())):
@@ -772,7 +1055,8 @@ class Codec(object):
         nothing has reached the device.  The format-2 / format-4 files of the most frequent tile extent are decoded together
         (decode_tiles_batch: the tiles of all of them in one launch per workspace chunk, the centres q staying on the device) and
         go through the decoder up to IN_FLIGHT at a time; so are, in launches of their own (the order is a flag of the call), the
-        format-5 files of their most frequent extent; format-1 files and other tile extents take the single-file path."""
+        format-5 files of their most frequent extent, and the format-6 files of their most frequent (tile extent, layer ends);
+        format-1 files and the other tiled files take the single-file path."""
         import torch
         channels = check_channels(channels, self.C)
         heads = []
@@ -784,17 +1068,19 @@ class Codec(object):
                 raise ValueError('file {}: {}'.format(i, e))
             heads.append(c)
         out = [None] * len(datas)
-        for order in ('raster', 'wavefront'):
-            mine = [i for i, c in enumerate(heads) if isinstance(c, _TILED) and isinstance(c, WavefrontContainer) == (order == 'wavefront')]
-            extents = [(heads[i].th, heads[i].tw) for i in mine]
+        kind = lambda c: 'layered' if isinstance(c, LayeredContainer) else 'wavefront' if isinstance(c, WavefrontContainer) else 'raster'
+        for order in ('raster', 'wavefront', 'layered'):
+            mine = [i for i, c in enumerate(heads) if isinstance(c, _TILED) and kind(c) == order]
+            extents = [(heads[i].th, heads[i].tw) + (tuple(heads[i].layer_ends) if order == 'layered' else ()) for i in mine]
             major = max(sorted(set(extents)), key=extents.count) if extents else None
-            together = [i for i in mine if (heads[i].th, heads[i].tw) == major]
+            together = [i for i, e in zip(mine, extents) if e == major]
             if not together:
                 continue
             try:
                 qs = self.pred.decode_tiles_batch([(heads[i].streams, heads[i].first_syms, (heads[i].C, heads[i].h, heads[i].w))
                                                    for i in together], major[0], major[1], want='q',
-                                                  max_workspace_bytes=max_workspace_bytes, order=order, channels=channels)
+                                                  max_workspace_bytes=max_workspace_bytes, channels=channels,
+                                                  **({'layer_ends': list(major[2:])} if order == 'layered' else {'order': order}))
             except ValueError as e:
                 m = re.search(r'volume (\d+)', str(e))
                 where = 'file {}: '.format(together[int(m.group(1))]) if m else ''
@@ -919,7 +1205,8 @@ def _damage_line(path, report):
 
 
 def check_option_args(flags):
-    """--checked / --wavefront / --salvage / --channels against the command and --tile: decided before any model is built"""
+    """--checked / --wavefront / --salvage / --channels / --layers / --progressive / --partial against the command, --tile and each
+    other: decided before any model is built"""
     if getattr(flags, 'channels', None) is not None:
         if flags.command not in ('decompress', 'decompress-dir'):
             raise ValueError('--channels belongs to decompress / decompress-dir: a preview is a way of reading a file')
@@ -939,6 +1226,45 @@ def check_option_args(flags):
             raise ValueError('--wavefront needs --tile: format 5 codes every tile front by front')
     if getattr(flags, 'salvage', False) and flags.command not in ('decompress', 'decompress-dir'):
         raise ValueError('--salvage belongs to decompress / decompress-dir')
+    layers, progressive = getattr(flags, 'layers', None), getattr(flags, 'progressive', False)
+    if layers is not None or progressive:
+        name = '--layers' if layers is not None else '--progressive'
+        if flags.command not in ('compress', 'compress-dir'):
+            raise ValueError('{} belongs to compress / compress-dir: a file says by itself what it is'.format(name))
+        if flags.tile is None:
+            raise ValueError('{} needs --tile: format 6 cuts every tile into layers'.format(name))
+        if getattr(flags, 'wavefront', False):
+            raise ValueError('{} does not go with --wavefront: a layer is no prefix of a wavefront-ordered stream'.format(name))
+        if layers is not None and progressive:
+            raise ValueError('--layers does not go with --progressive: the one names the layer ends, the other takes the default ones')
+        if layers is not None:
+            parse_layers_arg(layers)
+    if getattr(flags, 'partial', False):
+        if flags.command not in ('decompress', 'decompress-dir'):
+            raise ValueError('--partial belongs to decompress / decompress-dir: it reads a prefix of a layered file')
+        if getattr(flags, 'salvage', False):
+            raise ValueError('--partial does not go with --salvage: salvage of layered files is not offered')
+        if getattr(flags, 'channels', None) is not None:
+            raise ValueError('--partial does not go with --channels: the complete layers decide the channels')
+
+
+def parse_layers_arg(text):
+    """'4,8,16,32' -> [4, 8, 16, 32]; a ValueError for anything but comma-separated positive integers (C is checked by the codec)"""
+    try:
+        ends = [int(v) for v in str(text).split(',')]
+    except ValueError:
+        raise ValueError('--layers {!r} is not a comma-separated list of integers'.format(text))
+    if not 1 <= len(ends) <= MAX_LAYERS or ends[0] < 1 or any(b <= a for a, b in zip(ends, ends[1:])):
+        raise ValueError('--layers {!r}: 1 to {} increasing layer ends from at least 1, the last one C'.format(text, MAX_LAYERS))
+    return ends
+
+
+def _layers_option(flags, C):
+    """the `layers` argument of Codec for a command line, --layers checked against the C of the autoencoder's config: decided
+    before any model is built"""
+    if getattr(flags, 'layers', None) is not None:
+        return check_layer_ends(parse_layers_arg(flags.layers), C)
+    return 'default' if getattr(flags, 'progressive', False) else None
 
 
 def check_dir_args(flags, factor):
@@ -964,17 +1290,21 @@ def _main_dir(flags, ae_config, pc_config):
     from PIL import Image
     from . import autoencoder, val, weights as _weights
     jobs, tile = check_dir_args(flags, int(autoencoder.get_network_cls(ae_config).get_subsampling_factor()))
+    layers = _layers_option(flags, ae_config.num_chan_bn) if tile is not None else None
     if flags.weights == 'synthetic':
         wts = _weights.synthetic_weights(ae_config, pc_config, seed=flags.synthetic_seed)
     else:
         wts = val.load_weights_for_job(None, flags.weights, ae_config, pc_config)
     codec = Codec(ae_config, pc_config, wts, flags.device, tile=tile, checked=flags.checked,
-                  order='wavefront' if flags.wavefront and tile is not None else 'raster')
+                  order='wavefront' if flags.wavefront and tile is not None else 'raster',
+                  layers=layers)
     channels = check_channels(getattr(flags, 'channels', None), codec.C)
     os.makedirs(flags.output, exist_ok=True)
     total_in = total_out = total_pixels = 0
     if flags.command == 'decompress-dir' and flags.salvage:
         return _salvage_dir(flags, codec, jobs)
+    if flags.command == 'decompress-dir' and flags.partial:
+        return _partial_dir(codec, jobs)
     for start in range(0, len(jobs), flags.batch):
         part = jobs[start:start + flags.batch]
         if flags.command == 'compress-dir':
@@ -1003,6 +1333,32 @@ def _main_dir(flags, ae_config, pc_config):
     else:
         print('total: {} files, {} pixels from {} bytes = {:.4f} bpp'.format(len(jobs), total_pixels, total_in, 8.0 * total_in / total_pixels))
     return 0
+
+
+def _partial_line(path, report):
+    return '{}: layers decoded {} of {}: {} channels{}'.format(path, report.layers_decoded, report.layers_total, report.channels,
+                                                             '' if report.file_crc_ok else ', the CRC over the file is missing or wrong')
+
+
+def _partial_dir(codec, jobs):
+    """decompress-dir --partial: every file through decompress_partial; a file of which nothing can be decoded is named on stderr
+    and skipped.  Exit status 0 when every file gave an image, else 2."""
+    from PIL import Image
+    written = 0
+    for src, dst in jobs:
+        with open(src, 'rb') as f:
+            data = f.read()
+        try:
+            img, report = codec.decompress_partial(data)
+        except ValueError as e:
+            print('error: {}: {}'.format(src, e), file=sys.stderr)
+            continue
+        Image.fromarray(img).save(dst)
+        print(_decompress_line(dst, img, len(data)))
+        print(_partial_line(src, report))
+        written += 1
+    print('total: {} of {} files'.format(written, len(jobs)))
+    return 0 if written == len(jobs) else 2
 
 
 def _salvage_dir(flags, codec, jobs):
@@ -1071,8 +1427,18 @@ def verify_file(data):
     the damaged tiles.  Host only: no model, no device."""
     try:
         c = parse_container(data)
+        if isinstance(c, LayeredContainer):
+            G = len(c.layer_ends)
+            return True, 'ok (format {}, {} bytes, G = {} layers, ends {}, prefix lengths {})'.format(
+                c.version, len(data), G, ','.join(str(e) for e in c.layer_ends), ','.join(str(layer_prefix_bytes(c, g)) for g in range(G + 1)))
         return True, 'ok (format {}, {} bytes)'.format(c.version, len(data))
     except ValueError as strict:
+        if len(data) >= 6 and data[:4] == MAGIC and struct.unpack('<H', data[4:6])[0] == FORMAT_VERSION_LAYERED:
+            try:
+                c, complete, _ = parse_partial(data)
+            except ValueError as e:
+                return False, str(e)
+            return False, '{} of {} layers complete, but {}'.format(complete, len(c.layer_ends), strict)
         try:
             c, damage, file_crc_ok = parse_salvage(data)
         except ValueError as e:
@@ -1128,6 +1494,12 @@ def main(argv=None):
                                                           'header (format 4), so that a damaged file can be salvaged')
     p.add_argument('--wavefront', action='store_true', help='compress / compress-dir with --tile: the layout of --checked, every tile coded '
                                                             'front by front (format 5), which decodes a front at a time')
+    p.add_argument('--layers', default=None, metavar='a,b,..',
+                   help='compress / compress-dir with --tile: layered tiles (format 6) with these layer ends, increasing, the last one C: '
+                        'a prefix of the file decodes as a preview; not with --wavefront')
+    p.add_argument('--progressive', action='store_true', help='compress / compress-dir with --tile: --layers with the default ends C/8, C/4, C/2, C')
+    p.add_argument('--partial', action='store_true', help='decompress / decompress-dir: decode the complete layers of a (cut) format-6 file and '
+                                                          'print how many of them; not with --salvage or --channels')
     p.add_argument('--salvage', action='store_true', help='decompress / decompress-dir: read what a damaged format-4 / format-5 file still holds; '
                                                           'damaged tiles are filled from their neighbours and named')
     p.add_argument('--channels', type=int, default=None, metavar='K',
@@ -1141,6 +1513,7 @@ def main(argv=None):
         if flags.command.endswith('-dir'):
             return _main_dir(flags, ae_config, pc_config)
         check_option_args(flags)
+        layers = _layers_option(flags, ae_config.num_chan_bn)
         if flags.weights == 'synthetic':
             wts = _weights.synthetic_weights(ae_config, pc_config, seed=flags.synthetic_seed)
         else:
@@ -1153,8 +1526,17 @@ def main(argv=None):
                 codec.tile = (flags.tile // codec.factor, flags.tile // codec.factor)
                 codec.checked = flags.checked
                 codec.order = 'wavefront' if flags.wavefront else 'raster'
+                codec.layers = layers
             data, pixels = codec.compress_file(flags.input, flags.output)
             print(_compress_line(flags.output, data, pixels))
+        elif flags.partial:
+            from PIL import Image
+            with open(flags.input, 'rb') as f:
+                data = f.read()
+            img, report = codec.decompress_partial(data)
+            Image.fromarray(img).save(flags.output)
+            print(_decompress_line(flags.output, img, len(data)))
+            print(_partial_line(flags.input, report))
         elif flags.salvage:
             from PIL import Image
             with open(flags.input, 'rb') as f:

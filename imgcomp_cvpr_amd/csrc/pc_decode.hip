@@ -3,7 +3,8 @@
 // recomputed; activation caches), tiles of one or several volumes in one launch, tiles coded in wavefront order.
 //   reference: code/bit_counter.py:137-164 (decode loop), fjcommon arithmetic_coding.py (ArithmeticDecoder)
 // Host entry points: ic_pc_decode_f32, ic_pc_decode_tiles_f32, ic_pc_decode_tiles_batch_f32 and their *_workspace_bytes;
-// ic_pc_decode_channels_f32 and ic_pc_decode_tiles_batch_channels_f32 decode only the first channels of every stream (preview).
+// ic_pc_decode_channels_f32 and ic_pc_decode_tiles_batch_channels_f32 decode only the first channels of every stream (preview);
+// ic_pc_decode_tiles_batch_layers_f32 reads every tile's stream as segments cut at channel planes (container format 6).
 #include "common.h"
 #include "pc_table.h"
 #include "pc_internal.h"
@@ -456,10 +457,20 @@ __device__ __forceinline__ int pc_chain_idx(int t, int ci) { return 8 * ((ci >> 
 // in (c, y, x) order and the masks are causal in c, so these are a prefix of the stream and the sweep simply ends after plane
 // D = cdec + 3; nothing of the per-symbol path changes, and the strides of the caches and of V do not depend on C.  cdec is a plain,
 // uniform value like the others (not a patched copy of f, see above); LIM = false does not read it and is the full decoder as before.
-template <bool SYMS = true, bool LIM = false>
+// SEG = true (ic_pc_decode_tiles_batch_layers_f32, container format 6): the stream is cut at channel planes into nlayers segments,
+// each a coder run of its own.  bits / nbytes are segment 0; segment g >= 1 is segs[g] (offsets from seg_base) and begins with the
+// first symbol of channel ends[g - 1].  The step that decodes that symbol -- D - 4 == ends[g - 1], I == 4, J == 3 -- is the cut: wave
+// 0 folds s.error into a sticky word, re-initialises the coder state on segment g and reads the 32 code bits, exactly as at the
+// start of a stream; the sweep, the caches and the context know nothing of it.  Past its end a segment reads as zeros (its own
+// nbytes bounds pc_dec_bit).  segs and ends are the tile's rows of device tables in the workspace, the index is uniform: scalar
+// loads, a handful per tile, and no per-lane copy of either table.  With LIM the sweep ends before the cuts of the layers that
+// begin at or above cdec: their segments are never read.  SEG = false reads none of this and is the decoder as before.
+template <bool SYMS = true, bool LIM = false, bool SEG = false>
 __device__ __forceinline__ void pc_dec_cached_body(const PcCachedArgs& f, const unsigned char* bits, long long nbytes, int h, int w, int first_sym,
                                                    float* vol, float* c0, float* c1, float* c2, int* status,
-                                                   long long* __restrict__ out, long long out_cs, int out_rs, int cdec = 0) {
+                                                   long long* __restrict__ out, long long out_cs, int out_rs, int cdec = 0,
+                                                   const unsigned char* seg_base = nullptr, const ic_pc_seg_t* __restrict__ segs = nullptr,
+                                                   const int* __restrict__ ends = nullptr, int nlayers = 0) {
     constexpr int K = 24, KT = PC_NT * K;                 // 336 inputs per output
     __shared__ __attribute__((aligned(16))) float s_in[3][KT];          // inputs of conv1 / conv2 / conv3 in chain order
     __shared__ __attribute__((aligned(16))) float s_v[16];              // the 13 live taps of conv0
@@ -514,6 +525,13 @@ __device__ __forceinline__ void pc_dec_cached_body(const PcCachedArgs& f, const 
     if (wave == 0)
         for (int i = 0; i < PC_AC_BITS; ++i) s.code = (s.code << 1) | (unsigned)pc_dec_bit(bits, nbytes, s);
     if (tid == 0) s_v[12] = pad;                          // V[1][1][0]
+    // SEG: the layer whose segment comes next, the channel it begins with (-1: none left), and the sticky error of the segments done
+    // (the two tables were written by the copies that precede the launch and nothing in the kernel stores to them: they are read
+    // through the constant address space, which is what lets a uniform index become a scalar load behind the kernel's own stores)
+    typedef const __attribute__((address_space(4))) ic_pc_seg_t* seg_cptr;
+    typedef const __attribute__((address_space(4))) int* int_cptr;
+    int seg_next = 1, seg_cut = -1, sticky = 0;
+    if constexpr (SEG) seg_cut = nlayers > 1 ? ((int_cptr)ends)[0] : -1;
     // LDS hand-over between the waves: wait for this wave's LDS operations only.  (__syncthreads() also waits for the global
     // stores of the cache voxels to be acknowledged; their readers are a row of steps away and every wave drains its
     // memory counter at the top of each step, where it consumes its prefetch.)
@@ -595,6 +613,18 @@ __device__ __forceinline__ void pc_dec_cached_body(const PcCachedArgs& f, const 
             float vnext = pad;
             if (v3) {
                 const bool first = D == 4 && I == 4 && J == 3;                  // the first symbol is not coded
+                if constexpr (SEG) {
+                    if (I == 4 && J == 3 && D - 4 == seg_cut) {                 // the cut: this symbol is the first of segment seg_next
+                        seg_next = __builtin_amdgcn_readfirstlane(seg_next);
+                        const long long seg_off = ((seg_cptr)segs)[seg_next].off, seg_bytes = ((seg_cptr)segs)[seg_next].nbytes;
+                        sticky |= s.error;
+                        bits = seg_base + seg_off; nbytes = seg_bytes;
+                        pc_dec_state_init(s, bits, nbytes);
+                        for (int i = 0; i < PC_AC_BITS; ++i) s.code = (s.code << 1) | (unsigned)pc_dec_bit(bits, nbytes, s);
+                        ++seg_next;
+                        seg_cut = seg_next < nlayers ? ((int_cptr)ends)[seg_next - 1] : -1;
+                    }
+                }
                 const int sym = first ? first_sym : (L == 6 ? pc_dec_symbol_wave<6>(bits, nbytes, L, a.resolution, s, logit) : pc_dec_symbol_wave<0>(bits, nbytes, L, a.resolution, s, logit));
                 vnext = s_centers[sym];
                 if (lane == 0) {
@@ -614,7 +644,7 @@ __device__ __forceinline__ void pc_dec_cached_body(const PcCachedArgs& f, const 
         D = Dn; I = In; J = Jn;
         prefetch(D, I, J);
     }
-    if (tid == 0) *status = s.error;
+    if (tid == 0) *status = SEG ? (sticky | s.error) : s.error;
 #ifdef PC_DEC_PROF
     if (tid == 0) printf("pc_dec_cached phases (clocks, thread 0): wait+stage %llu | conv0 %llu | conv1 %llu | conv2 %llu | conv3 %llu | decode %llu | tail+prefetch issue %llu\n",
                          ph[0], ph[1], ph[2], ph[3], ph[4], ph[5], ph[6]);
@@ -861,10 +891,16 @@ struct PcTilesBatchArgs {
     char* slots; size_t slot_bytes, off_c0, off_c1, off_c2;
     long long* symbols; float* q; int* status;
     int cdec, fill;                   // LIM kernels only
+    const ic_pc_seg_t* segs;          // SEG kernels only: device copy of the segment table (ntiles x nlayers, tile-major),
+    const int* ends;                  //   of the layer ends (nlayers),
+    int nlayers;                      //   and their number
 };
 
-template <bool WAVE, bool SYMS, bool LIM = false>
+// SEG (ic_pc_decode_tiles_batch_layers_f32, raster only): the tile's stream is its nlayers segments, segs[blockIdx.x * nlayers + g];
+// the descriptor's stream_off / stream_bytes are not read.
+template <bool WAVE, bool SYMS, bool LIM = false, bool SEG = false>
 __global__ __launch_bounds__(256) void pc_dec_tiles_batch_kernel(const PcTilesBatchArgs t) {
+    static_assert(!(WAVE && SEG), "a layer is no prefix of a wavefront-ordered stream");
     const ic_pc_tile_t tl = t.tiles[blockIdx.x];
     // v = volumes ? volumes[tl.volume] : one, as a uniform branch around a scalar load.  (Written as a select, it becomes a select
     // between the two ADDRESSES, kernel arguments or global memory, and a load through a flat pointer into vector registers:
@@ -878,7 +914,15 @@ __global__ __launch_bounds__(256) void pc_dec_tiles_batch_kernel(const PcTilesBa
         pc_dec_wave_body<SYMS, LIM>(t.f, t.bits + tl.stream_off, tl.stream_bytes, tl.th, tl.tw, tl.first_sym, (float*)slot,
                                     (float*)(slot + t.off_c0), (float*)(slot + t.off_c1), (float*)(slot + t.off_c2), t.status + blockIdx.x,
                                     SYMS ? t.symbols + v.symbols_off + corner : nullptr, plane, v.w, cdec);
-    else
+    else if constexpr (SEG) {
+        const ic_pc_seg_t* segs = t.segs + (size_t)blockIdx.x * t.nlayers;
+        typedef const __attribute__((address_space(4))) ic_pc_seg_t* seg_cptr;      // (a table no kernel writes: see the body)
+        const long long off0 = ((seg_cptr)segs)[0].off, nbytes0 = ((seg_cptr)segs)[0].nbytes;
+        pc_dec_cached_body<SYMS, LIM, true>(t.f, t.bits + off0, nbytes0, tl.th, tl.tw, tl.first_sym, (float*)slot,
+                                            (float*)(slot + t.off_c0), (float*)(slot + t.off_c1), (float*)(slot + t.off_c2), t.status + blockIdx.x,
+                                            SYMS ? t.symbols + v.symbols_off + corner : nullptr, plane, v.w, cdec,
+                                            t.bits, segs, t.ends, t.nlayers);
+    } else
         pc_dec_cached_body<SYMS, LIM>(t.f, t.bits + tl.stream_off, tl.stream_bytes, tl.th, tl.tw, tl.first_sym, (float*)slot,
                                       (float*)(slot + t.off_c0), (float*)(slot + t.off_c1), (float*)(slot + t.off_c2), t.status + blockIdx.x,
                                       SYMS ? t.symbols + v.symbols_off + corner : nullptr, plane, v.w, cdec);
@@ -1128,7 +1172,8 @@ static bool pc_tile_ok(const ic_pc_tile_t& d, int h, int w, long long total_byte
 static int pc_decode_tiles_impl(const uint8_t* bitstreams, const ic_pc_tile_t* tiles_host, int ntiles, int th_max, int tw_max,
                                 const ic_pc_volume_t* volumes_host, int nvolumes, const float* const* wtab_host, const float* centers,
                                 int k, int L, float resolution, int64_t* symbols, float* q, int* status, int C, void* workspace,
-                                int flags, int channels, int fill_sym, ic_stream_t stream) {
+                                int flags, int channels, int fill_sym, ic_stream_t stream,
+                                const int* layer_ends_host = nullptr, int nlayers = 0, const ic_pc_seg_t* segs_host = nullptr) {
     const bool wavefront = (flags & IC_PC_DECODE_WAVEFRONT) != 0;
     hipStream_t st = (hipStream_t)stream;
     char* p = (char*)workspace;
@@ -1145,6 +1190,13 @@ static int pc_decode_tiles_impl(const uint8_t* bitstreams, const ic_pc_tile_t* t
             a.volumes = volumes_dev;
         } else {
             a.one = volumes_host[0];
+        }
+        if (nlayers) {                // the layers entry (k = 24, flags 0): segment table and layer ends behind the two tables
+            ic_pc_seg_t* segs_dev = (ic_pc_seg_t*)p; p += pc_dec_align((size_t)ntiles * nlayers * sizeof(ic_pc_seg_t));
+            int* ends_dev = (int*)p; p += pc_dec_align((size_t)nlayers * sizeof(int));
+            if (hipMemcpyAsync(segs_dev, segs_host, (size_t)ntiles * nlayers * sizeof(ic_pc_seg_t), hipMemcpyHostToDevice, st) != hipSuccess) return IC_ERR_ARG;
+            if (hipMemcpyAsync(ends_dev, layer_ends_host, (size_t)nlayers * sizeof(int), hipMemcpyHostToDevice, st) != hipSuccess) return IC_ERR_ARG;
+            a.segs = segs_dev; a.ends = ends_dev; a.nlayers = nlayers;
         }
         a.f.d.centers = centers; a.f.d.C = C; a.f.d.L = L; a.f.d.resolution = resolution;
         a.f.w0 = wtab_host[0]; a.f.b0 = wtab_host[1]; a.f.w1 = wtab_host[2]; a.f.b1 = wtab_host[3];
@@ -1163,7 +1215,9 @@ static int pc_decode_tiles_impl(const uint8_t* bitstreams, const ic_pc_tile_t* t
                                     : (symbols ? pc_dec_tiles_batch_kernel<false, true> : pc_dec_tiles_batch_kernel<false, false>);
         const auto lim = wavefront ? (symbols ? pc_dec_tiles_batch_kernel<true, true, true> : pc_dec_tiles_batch_kernel<true, false, true>)
                                    : (symbols ? pc_dec_tiles_batch_kernel<false, true, true> : pc_dec_tiles_batch_kernel<false, false, true>);
-        const auto kernel = channels < C ? lim : full;
+        const auto seg_full = symbols ? pc_dec_tiles_batch_kernel<false, true, false, true> : pc_dec_tiles_batch_kernel<false, false, false, true>;
+        const auto seg_lim = symbols ? pc_dec_tiles_batch_kernel<false, true, true, true> : pc_dec_tiles_batch_kernel<false, false, true, true>;
+        const auto kernel = nlayers ? (channels < C ? seg_lim : seg_full) : (channels < C ? lim : full);
         hipLaunchKernelGGL(kernel, dim3((unsigned)ntiles), dim3(256), 0, st, a);
         IC_LAUNCH_CHECK();
         return IC_OK;
@@ -1268,4 +1322,53 @@ extern "C" int ic_pc_decode_tiles_batch_channels_f32(const uint8_t* bitstreams, 
     if (workspace_bytes < ic_pc_decode_tiles_batch_workspace_bytes(C, th_max, tw_max, ntiles, nvolumes, k)) return IC_ERR_WORKSPACE;
     return pc_decode_tiles_impl(bitstreams, tiles_host, ntiles, th_max, tw_max, volumes_host, nvolumes, wtab_host, centers, k, L,
                                 resolution, symbols, q, status, C, workspace, flags, channels, fill_sym, stream);
+}
+
+// ---- layered tiles (container format 6): every tile's raster stream as nlayers segments --------------------------------------
+static size_t pc_dec_layers_tables_bytes(int ntiles, int nlayers) {
+    return pc_dec_align((size_t)ntiles * nlayers * sizeof(ic_pc_seg_t)) + pc_dec_align((size_t)nlayers * sizeof(int));
+}
+
+extern "C" size_t ic_pc_decode_tiles_batch_layers_workspace_bytes(int C, int th_max, int tw_max, int ntiles, int nvolumes, int k, int nlayers) {
+    if (nlayers < 1 || nlayers > 16) return 0;
+    const size_t base = ic_pc_decode_tiles_batch_workspace_bytes(C, th_max, tw_max, ntiles, nvolumes, k);
+    return base ? base + pc_dec_layers_tables_bytes(ntiles, nlayers) : 0;
+}
+
+extern "C" int ic_pc_decode_tiles_batch_layers_f32(const uint8_t* bitstreams, long long total_bytes, const ic_pc_tile_t* tiles_host, int ntiles,
+                                                   const ic_pc_volume_t* volumes_host, int nvolumes, const float* const* wtab_host,
+                                                   const float* centers, int k, int L, float resolution, int64_t* symbols, float* q,
+                                                   int* status, int C, void* workspace, size_t workspace_bytes, int flags,
+                                                   ic_stream_t stream, int channels, int fill_sym,
+                                                   const int* layer_ends_host, int nlayers, const ic_pc_seg_t* segs_host) {
+    // everything about the four tables is decided here, on the host, before the first HIP call
+    IC_CHECK_ARG(bitstreams && tiles_host && volumes_host && wtab_host && centers && (symbols || q) && status && workspace);
+    IC_CHECK_ARG(layer_ends_host && segs_host);
+    IC_CHECK_ARG(total_bytes >= 0 && ntiles > 0 && nvolumes > 0 && C > 0 && k > 0 && L > 0);
+    IC_CHECK_ARG(channels >= 1 && channels <= C && fill_sym >= 0 && fill_sym < L);
+    IC_CHECK_ARG(nlayers >= 1 && nlayers <= 16);
+    IC_CHECK_ARG(layer_ends_host[0] >= 1 && layer_ends_host[nlayers - 1] == C);
+    for (int g = 1; g < nlayers; ++g) IC_CHECK_ARG(layer_ends_host[g] > layer_ends_host[g - 1]);
+    for (int n = 0; n < nvolumes; ++n) {
+        const ic_pc_volume_t& v = volumes_host[n];
+        IC_CHECK_ARG(v.h >= 1 && v.w >= 1 && v.symbols_off >= 0 && v.q_off >= 0);
+    }
+    int th_max = 0, tw_max = 0;
+    for (int t = 0; t < ntiles; ++t) {
+        ic_pc_tile_t d = tiles_host[t];
+        IC_CHECK_ARG(d.volume >= 0 && d.volume < nvolumes);
+        d.stream_off = 0; d.stream_bytes = 0;             // not read: the segments stand for them
+        IC_CHECK_ARG(pc_tile_ok(d, volumes_host[d.volume].h, volumes_host[d.volume].w, total_bytes, L));
+        for (int g = 0; g < nlayers && (g == 0 || layer_ends_host[g - 1] < channels); ++g) {     // the layers that begin below `channels`
+            const ic_pc_seg_t& sg = segs_host[(size_t)t * nlayers + g];
+            IC_CHECK_ARG(sg.off >= 0 && sg.nbytes >= 0 && sg.off <= total_bytes && sg.nbytes <= total_bytes - sg.off);
+        }
+        th_max = d.th > th_max ? d.th : th_max;
+        tw_max = d.tw > tw_max ? d.tw : tw_max;
+    }
+    if (L > 16 || k != 24 || flags != 0) return IC_ERR_UNSUPPORTED;
+    if (workspace_bytes < ic_pc_decode_tiles_batch_layers_workspace_bytes(C, th_max, tw_max, ntiles, nvolumes, k, nlayers)) return IC_ERR_WORKSPACE;
+    return pc_decode_tiles_impl(bitstreams, tiles_host, ntiles, th_max, tw_max, volumes_host, nvolumes, wtab_host, centers, k, L,
+                                resolution, symbols, q, status, C, workspace, flags, channels, fill_sym, stream,
+                                layer_ends_host, nlayers, segs_host);
 }

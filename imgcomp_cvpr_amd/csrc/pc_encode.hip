@@ -8,7 +8,7 @@
 // in the registers of one lane for as long as it takes to pick (cum_lo, cum_hi, total) of the symbol that occurred; nothing
 // but the byte stream (~18 KB for that volume) is written.
 //
-// Work mapping: one work-group of two waves per volume (grid = N).
+// Work mapping: one work-group of two waves per volume (grid = N); ic_pc_encode_segments_f32: per segment of a volume (grid = N * nsegs).
 //   wave 1, producer: chunk c + 1 = 64 consecutive symbols, one per lane: pc_table_row (softmax, L expf, truncation -- the
 //       expression the decoder uses), prefix sums up to the symbol, 1.0 / total in double.  Result: three LDS words + one double
 //       per symbol, double-buffered.
@@ -90,19 +90,22 @@ __device__ __forceinline__ unsigned long long pce_div(unsigned long long n, unsi
 
 __device__ __forceinline__ unsigned pce_lane_u32(unsigned v, int src) { return (unsigned)__builtin_amdgcn_readlane((int)v, src); }
 
+// One coder run by one work-group of two waves: symbols [first, end) of the volume whose logits / symbols start at `logits` /
+// `symbols` (first >= 1: symbol 0 of a volume is never coded), the coder started afresh and terminated at the end, its bytes at
+// out[0 .. cap), their number and the status in *nbytes_out / *status_out.  first == end is the one byte 0x80.
 template <int LC>
-__global__ __launch_bounds__(128) void pc_encode_kernel(const PcEncArgs a) {
+__device__ __forceinline__ void pce_code_range(const float* __restrict__ logits, const long long* __restrict__ symbols, long long first,
+                                               long long end, float resolution, unsigned char* out, long long cap,
+                                               long long* nbytes_out, int* status_out) {
     __shared__ unsigned s_lo[2][PCE_CHUNK], s_hi[2][PCE_CHUNK], s_tot[2][PCE_CHUNK];
     __shared__ double s_inv[2][PCE_CHUNK];
     __shared__ int s_stop[2];            // by chunk parity: a wave still reading chunk c's flag is not overtaken by chunk c + 1's
-    const int vol = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const float* logits = a.logits + (size_t)vol * a.count * LC;
-    const long long* symbols = a.symbols + (size_t)vol * a.count;
-    const long long ncoded = a.count - 1;                                // symbol 0 is not coded
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long long ncoded = end - first;
     const long long nchunks = (ncoded + PCE_CHUNK - 1) / PCE_CHUNK;
 
     PceSink o;
-    o.p = a.out + (size_t)vol * a.capacity; o.pos = 0; o.cap = a.capacity; o.res = 0; o.nres = 0; o.ovf = 0;
+    o.p = out; o.pos = 0; o.cap = cap; o.res = 0; o.nres = 0; o.ovf = 0;
     unsigned low = 0, high = 0xffffffffu;
     long long pending = 0;
     int err = 0;
@@ -112,14 +115,14 @@ __global__ __launch_bounds__(128) void pc_encode_kernel(const PcEncArgs a) {
     for (long long c = 0; c <= nchunks; ++c) {
         if (wave == 1 && c < nchunks) {
             // ---- producer: the table of symbol i, reduced to what the coder needs of it ----
-            const long long i = 1 + c * PCE_CHUNK + lane;
+            const long long i = first + c * PCE_CHUNK + lane;
             const int b = (int)(c & 1);
-            if (i < a.count) {
+            if (i < end) {
                 float l[LC];
 #pragma unroll
                 for (int j = 0; j < LC; ++j) l[j] = logits[i * LC + j];
                 long long fr[LC];
-                pc_table_row(l, LC, a.resolution, fr, nullptr);
+                pc_table_row(l, LC, resolution, fr, nullptr);
                 const long long sym = symbols[i];
                 unsigned long long lo = 0, f = 0, total = 0;
                 bool big = false;
@@ -194,10 +197,41 @@ __global__ __launch_bounds__(128) void pc_encode_kernel(const PcEncArgs a) {
             if (o.nres) pce_put(o, 0ull, 8 - o.nres, lane);               // BitOutputStream.close(): zero padding
         }
         if (lane == 0) {
-            a.nbytes[vol] = o.pos;
-            a.status[vol] = err ? err : o.ovf ? 2 : 0;
+            *nbytes_out = o.pos;
+            *status_out = err ? err : o.ovf ? 2 : 0;
         }
     }
+}
+
+template <int LC>
+__global__ __launch_bounds__(128) void pc_encode_kernel(const PcEncArgs a) {
+    const int vol = blockIdx.x;
+    pce_code_range<LC>(a.logits + (size_t)vol * a.count * LC, a.symbols + (size_t)vol * a.count, 1, a.count, a.resolution,
+                       a.out + (size_t)vol * a.capacity, a.capacity, a.nbytes + vol, a.status + vol);     // symbol 0 is not coded
+}
+
+// ---- segments (container format 6): sub-ranges of a volume as independent coder runs, one work-group each ----------------------
+// Work-group vol * nsegs + s codes symbols [max(1, ends[s - 1]), ends[s]) of volume vol into out[vol][s][0 .. capacity).  The tables
+// are those of the whole volume (the logits are given), only the coder state starts afresh.  The ends travel in the kernel
+// arguments; they are picked by a chain of selects over constant indices (an index computed at run time into a by-value array
+// makes the compiler keep a private copy of it).
+#define PCE_MAX_SEGS 16
+struct PcEncSegArgs {
+    PcEncArgs e;                  // out: (N, nsegs, capacity), nbytes / status: (N, nsegs)
+    int nsegs;
+    long long ends[PCE_MAX_SEGS]; // cumulative symbol counts, strictly increasing, ends[0] >= 1, ends[nsegs - 1] == count
+};
+
+template <int LC>
+__global__ __launch_bounds__(128) void pc_encode_segments_kernel(const PcEncSegArgs a) {
+    const int vol = (int)(blockIdx.x / (unsigned)a.nsegs), seg = (int)(blockIdx.x - (unsigned)vol * (unsigned)a.nsegs);
+    long long first = 1, end = a.ends[0];
+#pragma unroll
+    for (int j = 1; j < PCE_MAX_SEGS; ++j)
+        if (j == seg) { first = a.ends[j - 1]; end = a.ends[j]; }
+    const size_t slot = (size_t)vol * a.nsegs + seg;
+    pce_code_range<LC>(a.e.logits + (size_t)vol * a.e.count * LC, a.e.symbols + (size_t)vol * a.e.count, first, end, a.e.resolution,
+                       a.e.out + slot * a.e.capacity, a.e.capacity, a.e.nbytes + slot, a.e.status + slot);
 }
 
 extern "C" size_t ic_pc_encode_capacity_bytes(long long count) {
@@ -214,6 +248,32 @@ extern "C" int ic_pc_encode_f32(const float* logits, const int64_t* symbols, int
     a.count = count; a.capacity = capacity; a.resolution = resolution;
     hipStream_t st = (hipStream_t)stream;
 #define PCE_CASE(l) case l: hipLaunchKernelGGL(pc_encode_kernel<l>, dim3((unsigned)N), dim3(128), 0, st, a); break;
+    switch (L) {
+        PCE_CASE(1) PCE_CASE(2) PCE_CASE(3) PCE_CASE(4) PCE_CASE(5) PCE_CASE(6) PCE_CASE(7) PCE_CASE(8)
+        PCE_CASE(9) PCE_CASE(10) PCE_CASE(11) PCE_CASE(12) PCE_CASE(13) PCE_CASE(14) PCE_CASE(15) PCE_CASE(16)
+    }
+#undef PCE_CASE
+    IC_LAUNCH_CHECK();
+    return IC_OK;
+}
+
+extern "C" int ic_pc_encode_segments_f32(const float* logits, const int64_t* symbols, int N, long long count, int L, float resolution,
+                                         const long long* seg_ends_host, int nsegs, uint8_t* bitstream, long long capacity,
+                                         long long* nbytes, int* status, ic_stream_t stream) {
+    // everything is decided here, on the host, before the launch: a refused call writes nothing
+    IC_CHECK_ARG(logits && symbols && bitstream && nbytes && status && seg_ends_host);
+    IC_CHECK_ARG(N > 0 && count > 0 && L > 0 && capacity >= 0 && resolution > 0.f && nsegs >= 1);
+    if (L > 16 || nsegs > PCE_MAX_SEGS) return IC_ERR_UNSUPPORTED;
+    IC_CHECK_ARG(seg_ends_host[0] >= 1 && seg_ends_host[nsegs - 1] == count);
+    for (int s = 1; s < nsegs; ++s) IC_CHECK_ARG(seg_ends_host[s] > seg_ends_host[s - 1]);
+    IC_CHECK_ARG((long long)N * nsegs <= 0x7fffffffLL);
+    PcEncSegArgs a{};
+    a.e.logits = logits; a.e.symbols = (const long long*)symbols; a.e.out = bitstream; a.e.nbytes = nbytes; a.e.status = status;
+    a.e.count = count; a.e.capacity = capacity; a.e.resolution = resolution;
+    a.nsegs = nsegs;
+    for (int s = 0; s < PCE_MAX_SEGS; ++s) a.ends[s] = seg_ends_host[s < nsegs ? s : nsegs - 1];
+    hipStream_t st = (hipStream_t)stream;
+#define PCE_CASE(l) case l: hipLaunchKernelGGL(pc_encode_segments_kernel<l>, dim3((unsigned)(N * nsegs)), dim3(128), 0, st, a); break;
     switch (L) {
         PCE_CASE(1) PCE_CASE(2) PCE_CASE(3) PCE_CASE(4) PCE_CASE(5) PCE_CASE(6) PCE_CASE(7) PCE_CASE(8)
         PCE_CASE(9) PCE_CASE(10) PCE_CASE(11) PCE_CASE(12) PCE_CASE(13) PCE_CASE(14) PCE_CASE(15) PCE_CASE(16)

@@ -346,7 +346,7 @@ class PredictionNetwork(object):
         """(pr, freqs), each (num_contexts, L), contexts in the order of iter_over_blocks."""
         return self._tables(symbols_padded)
 
-    def encode_stream(self, symbols, capacity=None, order='raster'):
+    def encode_stream(self, symbols, capacity=None, order='raster', seg_ends=None):
         """The mirror of decode_stream: the whole coding side on the device (ic_pc_encode_f32).  symbols: un-padded (C,h,w) numpy /
         tensor -> (stream_bytes, first_sym); a batch (N,C,h,w) -> a list of N such pairs, coded concurrently by ONE launch.
         The tables are bit for bit those of get_all(pad_symbols_volume(symbols)) -- the symbol volume padded with symbol 0, the
@@ -354,7 +354,10 @@ class PredictionNetwork(object):
         (cum_lo, cum_hi, total) of each symbol from a table row held in registers, and only the stream comes back to the host.
         capacity: bytes reserved per stream (tests); default ic_pc_encode_capacity_bytes, which always suffices.
         order='wavefront': the same tables and symbols, coded in the order of codec.wavefront_order(C, h, w) -- logits and symbols
-        are gathered through the permutation on the device, the kernel codes what it is given; the first symbol is the same."""
+        are gathered through the permutation on the device, the kernel codes what it is given; the first symbol is the same.
+        seg_ends=[n_0 < n_1 < ... = C h w] (raster only; ic_pc_encode_segments_f32): the volume's symbols cut at these cumulative counts
+        into independent coder runs, one work-group each -- run s is arithmetic_coding.encode_sequence(flat[a:b], freqs[a:b]) with
+        a = max(1, n_{s-1}), b = n_s, over the same tables.  -> ([segment bytes ...], first_sym) per volume; capacity is per segment."""
         dev = self.centers.device
         sym = symbols if torch.is_tensor(symbols) else torch.as_tensor(np.ascontiguousarray(symbols))
         batched = sym.dim() == 4
@@ -375,6 +378,11 @@ class PredictionNetwork(object):
             coded = sym.view(N, count).index_select(1, perm).contiguous()
         elif order != 'raster':
             raise ValueError("order is 'raster' or 'wavefront', got {!r}".format(order))
+        if seg_ends is not None:
+            if order != 'raster':
+                raise ValueError("seg_ends cuts a raster stream: order is {!r}".format(order))
+            res = self._encode_segments(logits, sym, N, count, [int(e) for e in seg_ends], capacity)
+            return res if batched else res[0]
         cap = int(lib.ic_pc_encode_capacity_bytes(count)) if capacity is None else int(capacity)
         out = torch.empty((N, max(cap, 1)), dtype=torch.uint8, device=dev)
         info = torch.zeros((2, N), dtype=torch.int64, device=dev)       # row 0: nbytes; row 1: status (int32 in the low words)
@@ -392,6 +400,36 @@ class PredictionNetwork(object):
                     {2: 'stream capacity too small', 3: 'symbol outside [0, L)'}.get(status[n], 'error'), status[n]))
             res.append((bytes(out[n, :nbytes[n]].cpu().numpy()), int(sym[n, 0, 0, 0])))
         return res if batched else res[0]
+
+    @staticmethod
+    def _encode_status(st):
+        if st == 1:
+            raise ValueError('Cannot code symbol because total is too large')
+        if st != 0:
+            raise ValueError('device range encoder: {} (status {})'.format(
+                {2: 'stream capacity too small', 3: 'symbol outside [0, L)'}.get(st, 'error'), st))
+
+    def _encode_segments(self, logits, sym, N, count, ends, capacity):
+        """encode_stream(seg_ends=ends) behind the logits: one launch of N * len(ends) work-groups"""
+        dev = self.centers.device
+        G = len(ends)
+        if not 1 <= G <= 16 or ends[0] < 1 or ends[-1] != count or any(b <= a for a, b in zip(ends, ends[1:])):
+            raise ValueError('segment ends {} are not 1 to 16 increasing symbol counts from at least 1 to {}'.format(ends, count))
+        longest = max(b - max(1, a) for a, b in zip([0] + ends, ends))
+        cap = int(lib.ic_pc_encode_capacity_bytes(longest + 1)) if capacity is None else int(capacity)
+        out = torch.empty((N, G, max(cap, 1)), dtype=torch.uint8, device=dev)
+        info = torch.zeros((2, N * G), dtype=torch.int64, device=dev)   # row 0: nbytes; row 1: status (int32 in the low words)
+        status = info[1].view(torch.int32)[:N * G]
+        host_ends = (ctypes.c_longlong * G)(*ends)
+        check(lib.ic_pc_encode_segments_f32(ptr(logits), ptr(sym), N, count, self.pc.L, self.freqs_resolution, host_ends, G, ptr(out), cap,
+                                            ptr(info[0]), ptr(status), _lib.current_stream(dev)), 'ic_pc_encode_segments_f32')
+        nbytes, status, host = info[0].tolist(), status.tolist(), out.cpu().numpy()
+        res = []
+        for n in range(N):
+            for g in range(G):
+                self._encode_status(status[n * G + g])
+            res.append(([bytes(host[n, g, :nbytes[n * G + g]]) for g in range(G)], int(sym[n, 0, 0, 0])))
+        return res
 
     def _preview(self, channels, C):
         """channels=None -> None (the full decode, the old entries); else (channels, fill symbol) for the *_channels entries, which
@@ -430,11 +468,13 @@ class PredictionNetwork(object):
             raise ValueError('Cannot decode symbol because total is too large')
         return out.cpu().numpy()
 
-    def encode_tiles(self, symbols, th, tw, order='raster'):
+    def encode_tiles(self, symbols, th, tw, order='raster', layer_ends=None):
         """symbols: un-padded (C,h,w) -> [(stream_bytes, first_sym)] for the tiles of codec.tile_grid(h, w, th, tw), in grid order.
         Every tile is coded as a volume of its own: its stream is encode_stream(symbols[:, y0:y0+th', x0:x0+tw']) byte for byte.
         Tiles of one shape (at most four: interior, right column, bottom row, corner) are one encode_stream batch, one launch.
-        order='wavefront': every tile's stream in the wavefront order of its own extent (encode_stream)."""
+        order='wavefront': every tile's stream in the wavefront order of its own extent (encode_stream).
+        layer_ends=[e_0 < ... = C] (raster only, container format 6): every tile's stream cut at these channel planes into segments
+        (encode_stream(seg_ends=[e th' tw' ...])) -> [([segment bytes per layer], first_sym)]."""
         from .codec import tile_grid
         sym = symbols if torch.is_tensor(symbols) else torch.as_tensor(np.ascontiguousarray(symbols))
         assert sym.dim() == 3, 'Expected CHW symbols'
@@ -446,7 +486,8 @@ class PredictionNetwork(object):
         res = [None] * len(grid)
         for (a, b), members in by_shape.items():
             batch = torch.stack([sym[:, grid[t][0]:grid[t][0] + a, grid[t][1]:grid[t][1] + b] for t in members])
-            for t, r in zip(members, self.encode_stream(batch, order=order)):
+            seg_ends = None if layer_ends is None else [int(e) * a * b for e in layer_ends]
+            for t, r in zip(members, self.encode_stream(batch, order=order, seg_ends=seg_ends)):
                 res[t] = r
         return res
 
@@ -483,10 +524,11 @@ class PredictionNetwork(object):
                 raise ValueError('Cannot decode symbol because total is too large (tile {} at ({}, {}))'.format(t, grid[t][0], grid[t][1]))
         return out.cpu().numpy()
 
-    def encode_tiles_batch(self, volumes, th, tw, order='raster'):
+    def encode_tiles_batch(self, volumes, th, tw, order='raster', layer_ends=None):
         """encode_tiles for a list of un-padded (C,h,w) symbol volumes of any mix of (h, w): -> per volume the list encode_tiles
         gives for it, byte for byte.  The tiles of ALL volumes are grouped by tile shape -- for a folder of equal-sized images the
-        same four shapes as for one -- and each group is one encode_stream batch, one ic_pc_encode_f32 launch."""
+        same four shapes as for one -- and each group is one encode_stream batch, one ic_pc_encode_f32 launch.
+        layer_ends: as encode_tiles, the ends converted to symbol counts per tile shape (raster only)."""
         from .codec import tile_grid
         dev = self.centers.device
         syms, grids = [], []
@@ -502,12 +544,13 @@ class PredictionNetwork(object):
         res = [[None] * len(grid) for grid in grids]
         for (_, a, b), members in by_shape.items():
             batch = torch.stack([syms[n][:, grids[n][t][0]:grids[n][t][0] + a, grids[n][t][1]:grids[n][t][1] + b] for n, t in members])
-            for (n, t), r in zip(members, self.encode_stream(batch, order=order)):
+            seg_ends = None if layer_ends is None else [int(e) * a * b for e in layer_ends]
+            for (n, t), r in zip(members, self.encode_stream(batch, order=order, seg_ends=seg_ends)):
                 res[n][t] = r
         return res
 
     def decode_tiles_batch(self, volumes, th, tw, want='q', max_workspace_bytes=1 << 31, flags=0, conceal=False, order='raster',
-                           channels=None):
+                           channels=None, layer_ends=None):
         """The mirror of encode_tiles_batch: the tiles of ALL volumes decoded by one launch per chunk (ic_pc_decode_tiles_batch_f32,
         one work-group per tile).  volumes: [(streams, first_syms, (C,h,w))], each as decode_tiles takes them, one C throughout.
         want: 'q' -> per volume the (C,h,w) float32 DEVICE tensor centers[symbols] (what ae.decode consumes: the symbols never
@@ -522,8 +565,18 @@ class PredictionNetwork(object):
         order='wavefront': the streams are in wavefront order (encode_tiles(order='wavefront')); sets PC_DECODE_WAVEFRONT, the
         decoder that takes a front at a time.  The order is per call: raster and wavefront volumes do not share one.
         channels=K: a preview (ic_pc_decode_tiles_batch_channels_f32) -- every tile's decoder stops after channels 0 .. K - 1 (in
-        wavefront order: after their last front), the others hold the fill symbol / its centre.  Not with conceal=True."""
-        from .codec import tile_grid, chunk_tiles
+        wavefront order: after their last front), the others hold the fill symbol / its centre.  Not with conceal=True.
+        layer_ends=[e_0 < ... = C] (container format 6, ic_pc_decode_tiles_batch_layers_f32; raster, k = 24, flags 0, not with
+        conceal=True): streams[t] is the list of the tile's G segments, as encode_tiles(layer_ends=...) gives them; entries of layers
+        that begin at or above `channels` are not read and may be None."""
+        from .codec import tile_grid, chunk_tiles, check_channels, check_layer_ends
+        if layer_ends is not None:
+            if conceal:
+                raise ValueError('layer_ends with conceal=True: salvage of layered tiles is not offered')
+            if order != 'raster' or int(flags) != 0:
+                raise ValueError('layer_ends cuts raster streams for the k = 24 decoder: order {!r}, flags {}'.format(order, flags))
+            if self.pc._k != 24:
+                raise ValueError('layered tiles need a context model of width k = 24, this one has k = {}'.format(self.pc._k))
         if channels is not None and conceal:
             raise ValueError('channels={} with conceal=True: a preview of a damaged file is not offered'.format(channels))
         if want not in ('q', 'symbols', 'both'):
@@ -535,7 +588,12 @@ class PredictionNetwork(object):
         if not volumes:
             return ([], []) if conceal else []
         dev = self.centers.device
-        shapes, grids, tiles, where, blobs, pos, missing = [], [], [], [], [], 0, []
+        C0 = int(volumes[0][2][0])
+        if layer_ends is not None:
+            ends = check_layer_ends(layer_ends, C0)
+            upto = C0 if channels is None else check_channels(channels, C0)
+            needed = [g for g in range(len(ends)) if g == 0 or ends[g - 1] < upto]     # the layers that begin below `channels`
+        shapes, grids, tiles, where, blobs, pos, missing, segs = [], [], [], [], [], 0, [], []
         for n, (streams, first_syms, shape) in enumerate(volumes):
             C, h, w = (int(v) for v in shape)
             if C != int(volumes[0][2][0]):
@@ -550,15 +608,31 @@ class PredictionNetwork(object):
                 if streams[t] is None:
                     missing.append((n, t))
                     continue
+                if layer_ends is not None:
+                    if len(streams[t]) != len(ends) or any(streams[t][g] is None for g in needed):
+                        raise ValueError('volume {}, tile {}: {} layers need the segments {} of {}'.format(n, t, len(ends), needed, len(ends)))
+                    tiles.append((y0, x0, a, b, 0, 0, first_syms[t], n))
+                    where.append((n, t, y0, x0))
+                    for g in range(len(ends)):
+                        if g in needed:
+                            segs.append((pos, len(streams[t][g])))
+                            blobs.append(bytes(streams[t][g]))
+                            pos += len(streams[t][g])
+                        else:
+                            segs.append((0, 0))
+                    continue
                 tiles.append((y0, x0, a, b, pos, len(streams[t]), first_syms[t], n))
                 where.append((n, t, y0, x0))
                 blobs.append(bytes(streams[t]))
                 pos += len(streams[t])
         C, k = shapes[0][0], self.pc._k
         preview = self._preview(channels, C)
+        G = 0 if layer_ends is None else len(ends)
         vtable, offs, total = _lib.packed_volume_table(shapes)
 
         def need(th_max, tw_max, ntiles):
+            if G:
+                return int(lib.ic_pc_decode_tiles_batch_layers_workspace_bytes(C, th_max, tw_max, ntiles, len(shapes), k, G))
             return int(lib.ic_pc_decode_tiles_batch_workspace_bytes(C, th_max, tw_max, ntiles, len(shapes), k))
 
         chunks = chunk_tiles([(a, b) for _, _, a, b, _, _, _, _ in tiles], need, int(max_workspace_bytes))
@@ -573,11 +647,17 @@ class PredictionNetwork(object):
             ws_bytes = max(need(max(tiles[i][2] for i in range(a, b)), max(tiles[i][3] for i in range(a, b)), b - a) for a, b in chunks)
             ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
         step = ctypes.sizeof(_lib.PcTile)
+        if G:
+            seg_table, host_ends = _lib.seg_table(segs), (ctypes.c_int * G)(*ends)
+            layers = (C, self.conceal_fallback()) if preview is None else preview
         for a, b in chunks:
             args = (ptr(data), pos, ctypes.c_void_p(ctypes.addressof(table) + a * step), b - a, vtable, len(shapes), self.pc._tab,
                     ptr(centers), k, self.pc.L, self.freqs_resolution, ptr(sym), ptr(q), ptr(status[a:b]), C, ptr(ws), ws_bytes,
                     int(flags), _lib.current_stream(dev))
-            if preview is None:
+            if G:
+                seg_ptr = ctypes.c_void_p(ctypes.addressof(seg_table) + a * G * ctypes.sizeof(_lib.PcSeg))
+                check(lib.ic_pc_decode_tiles_batch_layers_f32(*(args + layers + (host_ends, G, seg_ptr))), 'ic_pc_decode_tiles_batch_layers_f32')
+            elif preview is None:
                 check(lib.ic_pc_decode_tiles_batch_f32(*args), 'ic_pc_decode_tiles_batch_f32')
             else:
                 check(lib.ic_pc_decode_tiles_batch_channels_f32(*(args + preview)), 'ic_pc_decode_tiles_batch_channels_f32')

@@ -350,6 +350,30 @@ int ic_pc_decode_tiles_batch_channels_f32(const uint8_t* bitstreams, long long t
                                           const float* centers, int k, int L, float resolution, int64_t* symbols, float* q,
                                           int* status, int C, void* workspace, size_t workspace_bytes, int flags,
                                           ic_stream_t stream, int channels, int fill_sym);
+/* Layered tiles (container format 6): a tile's raster stream cut at channel planes into nlayers SEGMENTS, each a coder run of its
+ * own, so that a file can store the bytes quality-layer first and a prefix of it decodes as a preview.  Layer g holds channels
+ * [e_{g-1}, e_g) with e_{-1} = 0 and e_{nlayers-1} = C; segment (t, g) is the range coder started afresh over tile t's symbols of
+ * layer g in raster order (layer 0 without the uncoded first symbol), over those symbols' rows of the tile's own tables, terminated
+ * like every stream.  The context crosses the cuts, only the coder state restarts: at the first symbol of a layer g >= 1 the
+ * decoder keeps its error flag, re-initialises the range decoder on segment g and primes it with 32 bits.
+ * The parameters of ic_pc_decode_tiles_batch_channels_f32 (channels and fill_sym included), then the layers:
+ *   layer_ends_host: HOST array e_0 < e_1 < ... < e_{nlayers-1} = C, e_0 >= 1, 1 <= nlayers <= 16 (else IC_ERR_ARG)
+ *   segs_host: HOST array, ntiles x nlayers, tile-major: segment (t, g) is the nbytes bytes at bitstreams + off.  The tile
+ *     descriptors' stream_off / stream_bytes are NOT read.  Only segments of layers that begin below `channels` are read; each of
+ *     them must lie inside [0, total_bytes) (IC_ERR_ARG).  The others may be {0, 0}: neither checked nor touched.  Past its end a
+ *     segment reads as zeros, never as the next segment's bytes.  Both arrays are read before the call returns.
+ *   channels == C is the full decode (fill_sym unused beyond its range check).  status: per tile, the error flag kept over the cuts.
+ *   flags other than 0 (IC_PC_DECODE_WAVEFRONT too: a layer is no prefix of a wavefront-ordered stream) and k != 24 are
+ *   IC_ERR_UNSUPPORTED; too small a workspace IC_ERR_WORKSPACE.  All decided on the host; a refused call writes nothing.
+ *   workspace: ic_pc_decode_tiles_batch_layers_workspace_bytes(C, largest th, largest tw, ntiles, nvolumes, k, nlayers). */
+typedef struct { long long off, nbytes; } ic_pc_seg_t;
+size_t ic_pc_decode_tiles_batch_layers_workspace_bytes(int C, int th_max, int tw_max, int ntiles, int nvolumes, int k, int nlayers);
+int ic_pc_decode_tiles_batch_layers_f32(const uint8_t* bitstreams, long long total_bytes, const ic_pc_tile_t* tiles_host, int ntiles,
+                                        const ic_pc_volume_t* volumes_host, int nvolumes, const float* const* wtab_host,
+                                        const float* centers, int k, int L, float resolution, int64_t* symbols, float* q,
+                                        int* status, int C, void* workspace, size_t workspace_bytes, int flags,
+                                        ic_stream_t stream, int channels, int fill_sym,
+                                        const int* layer_ends_host, int nlayers, const ic_pc_seg_t* segs_host);
 /* Concealment: what stands in the volumes where a tile could not be decoded (a damaged file; codec.py, salvage).  Stated on symbols,
  * so exact: for a damaged tile T and a channel c the candidates are the symbols of channel c directly above T's top row, below its
  * bottom row, left of its left column and right of its right column (no corners) that lie inside the volume and in a tile that
@@ -386,6 +410,15 @@ int ic_pc_conceal_tiles(int64_t* symbols, float* q, const ic_pc_tile_t* tiles_ho
 size_t ic_pc_encode_capacity_bytes(long long count);
 int ic_pc_encode_f32(const float* logits, const int64_t* symbols, int N, long long count, int L, float resolution,
                      uint8_t* bitstream, long long capacity, long long* nbytes, int* status, ic_stream_t stream);
+/* Sub-ranges of every volume as independent coder runs, one work-group each (N * nsegs of them): segment s codes symbols
+ * [max(1, ends[s-1]), ends[s]) of its volume over those symbols' table rows, the coder started afresh and terminated as above.
+ *   seg_ends_host: HOST array of nsegs cumulative symbol counts, strictly increasing, ends[0] >= 1, ends[nsegs-1] == count (else
+ *     IC_ERR_ARG); they travel in the kernel arguments.  nsegs > 16 or L > 16: IC_ERR_UNSUPPORTED.  A refused call writes nothing.
+ *   bitstream: out, device (N, nsegs, capacity);  nbytes, status: out, device (N, nsegs), values as ic_pc_encode_f32 per segment.
+ *   An empty segment (ends[0] == 1) is the one byte 0x80; nsegs == 1 is ic_pc_encode_f32 byte for byte. */
+int ic_pc_encode_segments_f32(const float* logits, const int64_t* symbols, int N, long long count, int L, float resolution,
+                              const long long* seg_ends_host, int nsegs, uint8_t* bitstream, long long capacity,
+                              long long* nbytes, int* status, ic_stream_t stream);
 /* bits -> sum(bits) (bits.py:4-14 numerator); deterministic two-stage reduction.
  * partial: >= 1024 floats of scratch.  out_sum: 1 float. */
 int ic_sum_f32(const float* v, long long count, float* partial, float* out_sum, ic_stream_t stream);
