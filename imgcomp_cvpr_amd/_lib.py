@@ -167,11 +167,18 @@ PROTOTYPES = {
     'ic_pc_decode_tiles_batch_layers_f32': (c_int, [c_void_p, c_longlong, c_void_p, c_int, c_void_p, c_int, POINTER(c_void_p), c_void_p,
                                                     c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_size_t,
                                                     c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p]),
+    'ic_pc_decode_tiles_batch_layers_pertile_workspace_bytes': (c_size_t, [c_int] * 7),
+    'ic_pc_decode_tiles_batch_layers_pertile_f32': (c_int, [c_void_p, c_longlong, c_void_p, c_int, c_void_p, c_int, POINTER(c_void_p), c_void_p,
+                                                            c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_size_t,
+                                                            c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p]),
     'ic_pc_encode_segments_f32': (c_int, [c_void_p, c_void_p, c_int, c_longlong, c_int, c_float, c_void_p, c_int, c_void_p, c_longlong,
                                           c_void_p, c_void_p, c_void_p]),
     'ic_pc_conceal_tiles_workspace_bytes': (c_size_t, [c_int, c_int, c_longlong]),
     'ic_pc_conceal_tiles': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p] + [c_int] * 5 +
                             [c_void_p, c_size_t, c_void_p]),
+    'ic_pc_conceal_tiles_channels_workspace_bytes': (c_size_t, [c_int, c_int, c_longlong]),
+    'ic_pc_conceal_tiles_channels': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p] + [c_int] * 5 +
+                                     [c_void_p, c_size_t, c_void_p]),
     'ic_sum_f32': (c_int, [c_void_p, c_longlong, c_void_p, c_void_p, c_void_p]),
     'ic_mean_f32': (c_int, [c_void_p, c_longlong, c_float, c_void_p, c_void_p, c_void_p]),
     'ic_mean_rows_f32': (c_int, [c_void_p, c_int, c_longlong, c_float, c_void_p, c_void_p, c_void_p]),

@@ -2,9 +2,9 @@
 
     python -m imgcomp_cvpr_amd.codec compress   IN.png  OUT.icf [--ae_config cvpr/low] [--pc_config cvpr/res_shallow] [--weights synthetic|FILE.npz|CKPT]
                                                                 [--tile PIXELS [--checked | --wavefront | --layers a,b,.. | --progressive]]
-    python -m imgcomp_cvpr_amd.codec decompress IN.icf  OUT.png [same options] [--salvage | --channels K | --partial]
+    python -m imgcomp_cvpr_amd.codec decompress IN.icf  OUT.png [same options] [--salvage | --channels K | --partial | --recover]
     python -m imgcomp_cvpr_amd.codec compress-dir   IN_DIR OUT_DIR [--tile PIXELS [--checked | --wavefront | --layers a,b,.. | --progressive]] [--batch N]   every *.png / *.jpg -> OUT_DIR/<stem>.icf
-    python -m imgcomp_cvpr_amd.codec decompress-dir IN_DIR OUT_DIR [--batch N] [--salvage | --channels K | --partial]    every *.icf -> OUT_DIR/<stem>.png
+    python -m imgcomp_cvpr_amd.codec decompress-dir IN_DIR OUT_DIR [--batch N] [--salvage | --channels K | --partial | --recover]    every *.icf -> OUT_DIR/<stem>.png
     python -m imgcomp_cvpr_amd.codec verify PATH [PATH ...]         files or directories of *.icf: the checksums, without model or device
 
 compress:   pad to a multiple of the subsampling factor (val.add_padding) -> ae.encode -> PredictionNetwork.encode_stream (the
@@ -93,6 +93,14 @@ Codec.decompress_partial; the other channels as in a --channels preview).
     ..      n     payload: the segments in table order (all tiles' layer 0, then all tiles' layer 1, ..)
     ..      4     CRC-32 of every byte before it (u32)
 decompress reads it as strictly as format 4; salvage of format 6 is not offered; verify checks it on the host.
+--recover (Codec.recover / recover_many, parse_recover): what a damaged or cut format-6 file still holds, tile by tile.  Every segment
+has its own length and CRC, so behind a header that passes its CRC every tile is read up to its own leading layers that are wholly
+there and match their CRCs (an intact segment behind a damaged one cannot be decoded: the coder's context is missing): one flipped
+bit costs one tile its upper layers, a download cut inside layer g keeps layer g of the tiles in front of the cut.  The decoder takes
+a channel limit per tile (ic_pc_decode_tiles_batch_layers_pertile_f32); then every missing (tile, channel) is filled on the device
+from the neighbouring tiles that hold that channel (ic_pc_conceal_tiles_channels: the most frequent symbol on the four edges, ties
+to the smallest), or with the fill symbol where no neighbour holds it -- if all tiles stop at one layer, that is --partial's image.
+The report names every tile with fewer than all layers.  --partial and --salvage read as before.
 """
 import argparse
 import io
@@ -136,6 +144,11 @@ WAVEFRONT_COEFFS = (2, 4)                                            # T = x + 2
 # (y0, x0, height, width) in the returned image, clipped to it (height or width 0: the tile lies in the padding)
 DamagedTile = namedtuple('DamagedTile', ['index', 'reason', 'latent', 'pixels'])
 SalvageReport = namedtuple('SalvageReport', ['ntiles', 'file_crc_ok', 'damaged'])
+# what recover tells about a layered file: tiles is [RecoveredTile] in tile order, only the tiles with fewer than all layers; layers /
+# channels = what was decoded of the tile, reason = 'crc' | 'truncated' (the first segment that could not be read) | 'decoder';
+# latent and pixels as in DamagedTile
+RecoveredTile = namedtuple('RecoveredTile', ['index', 'layers', 'channels', 'reason', 'latent', 'pixels'])
+RecoverReport = namedtuple('RecoverReport', ['ntiles', 'layers_total', 'file_crc_ok', 'tiles'])
 
 
 def tile_grid(h, w, th, tw):
@@ -658,6 +671,39 @@ def parse_partial(data):
     return c, complete, bool(file_crc_ok)
 
 
+def parse_recover(data):
+    """a format-6 file, whole, cut or damaged -> (LayeredContainer, layers, reasons, file_crc_ok).  layers[t] is the number of LEADING
+    segments of tile t that are wholly there and match their CRCs, 0 .. G: an intact segment behind a bad one cannot be decoded and is
+    dropped.  reasons: {tile: 'crc' | 'truncated'} for the tiles with layers[t] < G, that of the tile's first bad segment ('truncated':
+    its byte range is not complete; 'crc': the bytes are there, their CRC differs).  The header must be whole and pass its own CRC, as
+    for parse_partial, else ValueError('header damaged: ...'); behind it nothing raises.  Another format is a ValueError."""
+    data = bytes(data)
+    if len(data) >= 6 and data[:4] == MAGIC:
+        version, = struct.unpack('<H', data[4:6])
+        if version in (FORMAT_VERSION, FORMAT_VERSION_TILED) + _WITH_CRCS:
+            raise ValueError('format version {} is not the layered version {}: --recover reads layered files (--tile --layers / --progressive); '
+                             'a damaged format-{} / format-{} file is read with --salvage, an intact file of any format with '
+                             'decompress'.format(version, FORMAT_VERSION_LAYERED, FORMAT_VERSION_CHECKED, FORMAT_VERSION_WAVEFRONT))
+    c, _, file_crc_ok = parse_partial(data)
+    G, ntiles = len(c.layer_ends), len(c.first_syms)
+    start = _prefix_from_bytes(data, 0)                    # the payload's first byte; in front of it: header CRC, payload length, table
+    rows = struct.unpack_from('<{}I'.format(2 * G * ntiles), data, start - 4 - 8 - 8 * G * ntiles)
+    ends, pos = [[0] * ntiles for _ in range(G)], 0       # where segment (g, t) ends in the payload
+    for g in range(G):
+        for t in range(ntiles):
+            pos += rows[2 * (g * ntiles + t)]
+            ends[g][t] = pos
+    layers, reasons = [], {}
+    for t in range(ntiles):
+        g_t = 0
+        while g_t < G and c.segments[g_t][t] is not None:
+            g_t += 1
+        layers.append(g_t)
+        if g_t < G:
+            reasons[t] = 'truncated' if ends[g_t][t] > len(c.payload) else 'crc'
+    return c, layers, reasons, file_crc_ok
+
+
 def parse_salvage(data):
     """what a possibly damaged format-4 or format-5 file still holds -> (CheckedContainer or WavefrontContainer, damage, file_crc_ok).  damage: [(tile, reason)] in
     tile order, reason 'crc' (the bytes are there, their CRC differs) or 'truncated' (the tile's byte range is not complete);
@@ -1153,6 +1199,74 @@ class Codec(object):
                 out[i] = (self._crop(x, c), self._report(c, reasons, dmg, file_crc_ok))
         return out
 
+    # -- what a damaged or cut format-6 file still holds, tile by tile --
+
+    def _recover_head(self, data):
+        """parse_recover + the model checks -> (LayeredContainer, layers per tile, {tile: reason}, file_crc_ok); nothing on the device"""
+        c, layers, reasons, file_crc_ok = parse_recover(data)
+        self.check_container(c)
+        return c, layers, reasons, file_crc_ok
+
+    def _recover_decode(self, heads, want, max_workspace_bytes=1 << 31):
+        """heads of one (tile extent, layer ends) -> decode_tiles_batch(tile_layers=...): (per file q or symbols on the device, per file
+        the tiles with fewer than C channels)"""
+        c0 = heads[0][0]
+        return self.pred.decode_tiles_batch([(c.streams, c.first_syms, (c.C, c.h, c.w)) for c, _, _, _ in heads], c0.th, c0.tw, want=want,
+                                            max_workspace_bytes=max_workspace_bytes, layer_ends=c0.layer_ends,
+                                            tile_layers=[layers for _, layers, _, _ in heads])
+
+    def _recover_report(self, head, held):
+        """held: [(tile, layers_read, channels, reason)] of decode_tiles_batch(tile_layers=...); the reader's reason where it has one"""
+        c, _, reasons, file_crc_ok = head
+        f = self.factor
+        top, left = ((-c.H) % f) // 2, ((-c.W) % f) // 2                         # val.add_padding's offsets
+        grid, tiles = tile_grid(c.h, c.w, c.th, c.tw), []
+        for t, layers, channels, why in held:
+            y0, x0, a, b = grid[t]
+            py0, py1 = min(max(y0 * f - top, 0), c.H), min(max((y0 + a) * f - top, 0), c.H)
+            px0, px1 = min(max(x0 * f - left, 0), c.W), min(max((x0 + b) * f - left, 0), c.W)
+            tiles.append(RecoveredTile(t, layers, channels, why or reasons[t], (y0, x0, a, b), (py0, px0, py1 - py0, px1 - px0)))
+        return RecoverReport(len(grid), len(c.layer_ends), bool(file_crc_ok), tiles)
+
+    def recover_symbols(self, data):
+        """format-6 bytes, whole, cut or damaged -> (symbols (C,h,w) int64 numpy, LayeredContainer, RecoverReport): every tile's leading
+        intact layers decoded, every missing (tile, channel) filled from the neighbours that hold it (the rule: tests/recover_rule.py)"""
+        head = self._recover_head(data)
+        syms, held = self._recover_decode([head], 'symbols')
+        return syms[0].cpu().numpy(), head[0], self._recover_report(head, held[0])
+
+    def recover(self, data):
+        """format-6 bytes, whole, cut or damaged -> (HWC uint8 image, RecoverReport).  An intact file gives decompress(data) and an
+        empty list; a file cut at a layer end gives decompress_partial(data)'s image.  A ValueError where nothing can be read:
+        another format, a damaged header, another model."""
+        import torch
+        head = self._recover_head(data)
+        qs, held = self._recover_decode([head], 'q')
+        x_out = self.ae.decode(qs[0][None], is_training=False).to(torch.uint8)   # tf.cast truncates (val.py)
+        return self._crop(x_out[0], head[0]), self._recover_report(head, held[0])
+
+    def recover_many(self, datas, max_workspace_bytes=1 << 31):
+        """[format-6 bytes] -> [(image, RecoverReport)], element i equal to recover(datas[i]).  As salvage_many: every file is parsed
+        and checked first (the first refusal raises with the index of the file in front, nothing has reached the device); then per
+        (tile extent, layer ends) the tiles of all files in one decode launch per workspace chunk, one concealment launch, q staying
+        on the device, and the autoencoder passes up to IN_FLIGHT at a time."""
+        import torch
+        heads = []
+        for i, data in enumerate(datas):
+            try:
+                heads.append(self._recover_head(data))
+            except ValueError as e:
+                raise ValueError('file {}: {}'.format(i, e))
+        out = [None] * len(datas)
+        kind = lambda c: (c.th, c.tw) + tuple(c.layer_ends)
+        for group in sorted(set(kind(h[0]) for h in heads)):
+            members = [i for i, h in enumerate(heads) if kind(h[0]) == group]
+            qs, held = self._recover_decode([heads[i] for i in members], 'q', max_workspace_bytes)
+            imgs = self._in_flight(qs, lambda ae, q: ae.decode(q[None], is_training=False).to(torch.uint8)[0])    # tf.cast truncates (val.py)
+            for i, x, tiles in zip(members, imgs, held):
+                out[i] = (self._crop(x, heads[i][0]), self._recover_report(heads[i], tiles))
+        return out
+
     def compress_file(self, image_path, out_path):
         from PIL import Image
         img = np.asarray(Image.open(image_path).convert('RGB'), dtype=np.uint8)     # as val.load_image_chw reads it
@@ -1204,8 +1318,19 @@ def _damage_line(path, report):
                                                       d.pixels[1] + d.pixels[3]) for d in report.damaged))
 
 
+def _recover_line(path, report):
+    """one line for a recovered file: the tiles with fewer than all layers, what they hold and where they lie in the image"""
+    crc = '' if report.file_crc_ok else ', the CRC over the file is missing or wrong'
+    if not report.tiles:
+        return '{}: recovered, all {} tiles hold all {} layers{}'.format(path, report.ntiles, report.layers_total, crc)
+    return '{}: recovered, {} of {} tiles incomplete: {}{}'.format(path, len(report.tiles), report.ntiles, ', '.join(
+        'tile {} ({}) layers {} of {} = {} channels, pixels y {}..{} x {}..{}'.format(
+            d.index, d.reason, d.layers, report.layers_total, d.channels, d.pixels[0], d.pixels[0] + d.pixels[2], d.pixels[1],
+            d.pixels[1] + d.pixels[3]) for d in report.tiles), crc)
+
+
 def check_option_args(flags):
-    """--checked / --wavefront / --salvage / --channels / --layers / --progressive / --partial against the command, --tile and each
+    """--checked / --wavefront / --salvage / --channels / --layers / --progressive / --partial / --recover against the command, --tile and each
     other: decided before any model is built"""
     if getattr(flags, 'channels', None) is not None:
         if flags.command not in ('decompress', 'decompress-dir'):
@@ -1246,6 +1371,16 @@ def check_option_args(flags):
             raise ValueError('--partial does not go with --salvage: salvage of layered files is not offered')
         if getattr(flags, 'channels', None) is not None:
             raise ValueError('--partial does not go with --channels: the complete layers decide the channels')
+    if getattr(flags, 'recover', False):
+        if flags.command not in ('decompress', 'decompress-dir'):
+            raise ValueError('--recover belongs to decompress / decompress-dir: it reads what a damaged or cut layered file still holds')
+        if getattr(flags, 'salvage', False):
+            raise ValueError('--recover does not go with --salvage: the one reads layered files (format 6), the other formats 4 and 5')
+        if getattr(flags, 'partial', False):
+            raise ValueError('--recover does not go with --partial: the one reads every tile as far as it goes, the other the layers '
+                             'that are complete in all tiles')
+        if getattr(flags, 'channels', None) is not None:
+            raise ValueError('--recover does not go with --channels: what every tile still holds decides its channels')
 
 
 def parse_layers_arg(text):
@@ -1305,6 +1440,8 @@ def _main_dir(flags, ae_config, pc_config):
         return _salvage_dir(flags, codec, jobs)
     if flags.command == 'decompress-dir' and flags.partial:
         return _partial_dir(codec, jobs)
+    if flags.command == 'decompress-dir' and getattr(flags, 'recover', False):
+        return _recover_dir(flags, codec, jobs)
     for start in range(0, len(jobs), flags.batch):
         part = jobs[start:start + flags.batch]
         if flags.command == 'compress-dir':
@@ -1357,6 +1494,38 @@ def _partial_dir(codec, jobs):
         print(_decompress_line(dst, img, len(data)))
         print(_partial_line(src, report))
         written += 1
+    print('total: {} of {} files'.format(written, len(jobs)))
+    return 0 if written == len(jobs) else 2
+
+
+def _recover_dir(flags, codec, jobs):
+    """decompress-dir --recover: --batch files per recover_many call; a file of which nothing can be read is named on stderr and
+    skipped.  Exit status 0 when every file gave an image, else 2."""
+    from PIL import Image
+    written = 0
+    for start in range(0, len(jobs), flags.batch):
+        part = jobs[start:start + flags.batch]
+        datas = []
+        for src, _ in part:
+            with open(src, 'rb') as f:
+                datas.append(f.read())
+        try:
+            results = codec.recover_many(datas)
+        except ValueError:
+            results = []                                   # one of them cannot be read: find out which
+            for (src, _), data in zip(part, datas):
+                try:
+                    results.append(codec.recover(data))
+                except ValueError as e:
+                    print('error: {}: {}'.format(src, e), file=sys.stderr)
+                    results.append(None)
+        for (src, dst), data, res in zip(part, datas, results):
+            if res is None:
+                continue
+            Image.fromarray(res[0]).save(dst)
+            print(_decompress_line(dst, res[0], len(data)))
+            print(_recover_line(src, res[1]))
+            written += 1
     print('total: {} of {} files'.format(written, len(jobs)))
     return 0 if written == len(jobs) else 2
 
@@ -1500,6 +1669,9 @@ def main(argv=None):
     p.add_argument('--progressive', action='store_true', help='compress / compress-dir with --tile: --layers with the default ends C/8, C/4, C/2, C')
     p.add_argument('--partial', action='store_true', help='decompress / decompress-dir: decode the complete layers of a (cut) format-6 file and '
                                                           'print how many of them; not with --salvage or --channels')
+    p.add_argument('--recover', action='store_true', help='decompress / decompress-dir: read what a damaged or cut format-6 file still holds, every '
+                                                          'tile up to its own intact leading layers, the rest filled from the neighbours '
+                                                          'that hold it; names the incomplete tiles; not with --salvage, --partial or --channels')
     p.add_argument('--salvage', action='store_true', help='decompress / decompress-dir: read what a damaged format-4 / format-5 file still holds; '
                                                           'damaged tiles are filled from their neighbours and named')
     p.add_argument('--channels', type=int, default=None, metavar='K',
@@ -1537,6 +1709,14 @@ def main(argv=None):
             Image.fromarray(img).save(flags.output)
             print(_decompress_line(flags.output, img, len(data)))
             print(_partial_line(flags.input, report))
+        elif getattr(flags, 'recover', False):
+            from PIL import Image
+            with open(flags.input, 'rb') as f:
+                data = f.read()
+            img, report = codec.recover(data)
+            Image.fromarray(img).save(flags.output)
+            print(_decompress_line(flags.output, img, len(data)))
+            print(_recover_line(flags.input, report))
         elif flags.salvage:
             from PIL import Image
             with open(flags.input, 'rb') as f:

@@ -4,7 +4,8 @@
 //   reference: code/bit_counter.py:137-164 (decode loop), fjcommon arithmetic_coding.py (ArithmeticDecoder)
 // Host entry points: ic_pc_decode_f32, ic_pc_decode_tiles_f32, ic_pc_decode_tiles_batch_f32 and their *_workspace_bytes;
 // ic_pc_decode_channels_f32 and ic_pc_decode_tiles_batch_channels_f32 decode only the first channels of every stream (preview);
-// ic_pc_decode_tiles_batch_layers_f32 reads every tile's stream as segments cut at channel planes (container format 6).
+// ic_pc_decode_tiles_batch_layers_f32 reads every tile's stream as segments cut at channel planes (container format 6);
+// ic_pc_decode_tiles_batch_layers_pertile_f32 does so with a channel limit per tile (recovery of damaged or cut layered files).
 #include "common.h"
 #include "pc_table.h"
 #include "pc_internal.h"
@@ -453,7 +454,7 @@ __device__ __forceinline__ int pc_chain_idx(int t, int ci) { return 8 * ((ci >> 
 // moved to the tile's corner, for a tile.
 // SYMS = false (ic_pc_decode_tiles_batch_f32 with symbols == NULL): nothing is stored through out; the padded volume still
 // receives every symbol's centre, which is what that caller copies out.
-// LIM = true (the *_channels entries, preview): only channels 0 .. cdec - 1 are decoded, 1 <= cdec < C.  The stream codes its symbols
+// LIM = true (the *_channels entries, preview): only channels 0 .. cdec - 1 are decoded, 1 <= cdec < C (cdec == C, a tile of the per-tile entry that is whole, is the full sweep).  The stream codes its symbols
 // in (c, y, x) order and the masks are causal in c, so these are a prefix of the stream and the sweep simply ends after plane
 // D = cdec + 3; nothing of the per-symbol path changes, and the strides of the caches and of V do not depend on C.  cdec is a plain,
 // uniform value like the others (not a patched copy of f, see above); LIM = false does not read it and is the full decoder as before.
@@ -894,13 +895,19 @@ struct PcTilesBatchArgs {
     const ic_pc_seg_t* segs;          // SEG kernels only: device copy of the segment table (ntiles x nlayers, tile-major),
     const int* ends;                  //   of the layer ends (nlayers),
     int nlayers;                      //   and their number
+    const int* tile_channels;         // PER kernels only: device copy of the channel limit per tile (ntiles)
 };
 
 // SEG (ic_pc_decode_tiles_batch_layers_f32, raster only): the tile's stream is its nlayers segments, segs[blockIdx.x * nlayers + g];
 // the descriptor's stream_off / stream_bytes are not read.
-template <bool WAVE, bool SYMS, bool LIM = false, bool SEG = false>
+// PER (ic_pc_decode_tiles_batch_layers_pertile_f32): the channel limit is the tile's own, tile_channels[blockIdx.x] in 1 .. C, in
+// place of the launch's cdec.  A uniform index into a table that no kernel writes, read like the segment table through the constant
+// address space: one scalar load per tile, a uniform value as cdec is, and nothing of it in the body's per-symbol path.  A tile whose
+// limit is C is decoded whole; the copy loop then has no channel to fill.
+template <bool WAVE, bool SYMS, bool LIM = false, bool SEG = false, bool PER = false>
 __global__ __launch_bounds__(256) void pc_dec_tiles_batch_kernel(const PcTilesBatchArgs t) {
     static_assert(!(WAVE && SEG), "a layer is no prefix of a wavefront-ordered stream");
+    static_assert(!PER || (LIM && SEG && !WAVE), "the limit per tile belongs to the layered raster decoder");
     const ic_pc_tile_t tl = t.tiles[blockIdx.x];
     // v = volumes ? volumes[tl.volume] : one, as a uniform branch around a scalar load.  (Written as a select, it becomes a select
     // between the two ADDRESSES, kernel arguments or global memory, and a load through a flat pointer into vector registers:
@@ -909,7 +916,8 @@ __global__ __launch_bounds__(256) void pc_dec_tiles_batch_kernel(const PcTilesBa
     if (t.volumes) { v = t.volumes[tl.volume]; asm volatile("" ::: "memory"); }
     char* slot = t.slots + (size_t)blockIdx.x * t.slot_bytes;
     const long long corner = (long long)tl.y0 * v.w + tl.x0, plane = (long long)v.h * v.w;
-    const int cdec = LIM ? t.cdec : 0;
+    int cdec = LIM ? t.cdec : 0;
+    if constexpr (PER) cdec = ((const __attribute__((address_space(4))) int*)t.tile_channels)[blockIdx.x];
     if constexpr (WAVE)
         pc_dec_wave_body<SYMS, LIM>(t.f, t.bits + tl.stream_off, tl.stream_bytes, tl.th, tl.tw, tl.first_sym, (float*)slot,
                                     (float*)(slot + t.off_c0), (float*)(slot + t.off_c1), (float*)(slot + t.off_c2), t.status + blockIdx.x,
@@ -1173,7 +1181,8 @@ static int pc_decode_tiles_impl(const uint8_t* bitstreams, const ic_pc_tile_t* t
                                 const ic_pc_volume_t* volumes_host, int nvolumes, const float* const* wtab_host, const float* centers,
                                 int k, int L, float resolution, int64_t* symbols, float* q, int* status, int C, void* workspace,
                                 int flags, int channels, int fill_sym, ic_stream_t stream,
-                                const int* layer_ends_host = nullptr, int nlayers = 0, const ic_pc_seg_t* segs_host = nullptr) {
+                                const int* layer_ends_host = nullptr, int nlayers = 0, const ic_pc_seg_t* segs_host = nullptr,
+                                const int* tile_channels_host = nullptr) {
     const bool wavefront = (flags & IC_PC_DECODE_WAVEFRONT) != 0;
     hipStream_t st = (hipStream_t)stream;
     char* p = (char*)workspace;
@@ -1198,6 +1207,11 @@ static int pc_decode_tiles_impl(const uint8_t* bitstreams, const ic_pc_tile_t* t
             if (hipMemcpyAsync(ends_dev, layer_ends_host, (size_t)nlayers * sizeof(int), hipMemcpyHostToDevice, st) != hipSuccess) return IC_ERR_ARG;
             a.segs = segs_dev; a.ends = ends_dev; a.nlayers = nlayers;
         }
+        if (tile_channels_host) {     // the per-tile entry: the limits behind the segment table and the layer ends
+            int* limits_dev = (int*)p; p += pc_dec_align((size_t)ntiles * sizeof(int));
+            if (hipMemcpyAsync(limits_dev, tile_channels_host, (size_t)ntiles * sizeof(int), hipMemcpyHostToDevice, st) != hipSuccess) return IC_ERR_ARG;
+            a.tile_channels = limits_dev;
+        }
         a.f.d.centers = centers; a.f.d.C = C; a.f.d.L = L; a.f.d.resolution = resolution;
         a.f.w0 = wtab_host[0]; a.f.b0 = wtab_host[1]; a.f.w1 = wtab_host[2]; a.f.b1 = wtab_host[3];
         a.f.w2 = wtab_host[4]; a.f.b2 = wtab_host[5]; a.f.w3 = wtab_host[6]; a.f.b3 = wtab_host[7];
@@ -1217,7 +1231,8 @@ static int pc_decode_tiles_impl(const uint8_t* bitstreams, const ic_pc_tile_t* t
                                    : (symbols ? pc_dec_tiles_batch_kernel<false, true, true> : pc_dec_tiles_batch_kernel<false, false, true>);
         const auto seg_full = symbols ? pc_dec_tiles_batch_kernel<false, true, false, true> : pc_dec_tiles_batch_kernel<false, false, false, true>;
         const auto seg_lim = symbols ? pc_dec_tiles_batch_kernel<false, true, true, true> : pc_dec_tiles_batch_kernel<false, false, true, true>;
-        const auto kernel = nlayers ? (channels < C ? seg_lim : seg_full) : (channels < C ? lim : full);
+        const auto seg_per = symbols ? pc_dec_tiles_batch_kernel<false, true, true, true, true> : pc_dec_tiles_batch_kernel<false, false, true, true, true>;
+        const auto kernel = tile_channels_host ? seg_per : nlayers ? (channels < C ? seg_lim : seg_full) : (channels < C ? lim : full);
         hipLaunchKernelGGL(kernel, dim3((unsigned)ntiles), dim3(256), 0, st, a);
         IC_LAUNCH_CHECK();
         return IC_OK;
@@ -1371,4 +1386,50 @@ extern "C" int ic_pc_decode_tiles_batch_layers_f32(const uint8_t* bitstreams, lo
     return pc_decode_tiles_impl(bitstreams, tiles_host, ntiles, th_max, tw_max, volumes_host, nvolumes, wtab_host, centers, k, L,
                                 resolution, symbols, q, status, C, workspace, flags, channels, fill_sym, stream,
                                 layer_ends_host, nlayers, segs_host);
+}
+
+// ---- layered tiles with a channel limit per tile: what a damaged or cut format-6 file still holds of every tile ---------------
+extern "C" size_t ic_pc_decode_tiles_batch_layers_pertile_workspace_bytes(int C, int th_max, int tw_max, int ntiles, int nvolumes, int k, int nlayers) {
+    const size_t base = ic_pc_decode_tiles_batch_layers_workspace_bytes(C, th_max, tw_max, ntiles, nvolumes, k, nlayers);
+    return base ? base + pc_dec_align((size_t)ntiles * sizeof(int)) : 0;
+}
+
+extern "C" int ic_pc_decode_tiles_batch_layers_pertile_f32(const uint8_t* bitstreams, long long total_bytes, const ic_pc_tile_t* tiles_host, int ntiles,
+                                                           const ic_pc_volume_t* volumes_host, int nvolumes, const float* const* wtab_host,
+                                                           const float* centers, int k, int L, float resolution, int64_t* symbols, float* q,
+                                                           int* status, int C, void* workspace, size_t workspace_bytes, int flags,
+                                                           ic_stream_t stream, const int* tile_channels_host, int fill_sym,
+                                                           const int* layer_ends_host, int nlayers, const ic_pc_seg_t* segs_host) {
+    // everything about the five tables is decided here, on the host, before the first HIP call
+    IC_CHECK_ARG(bitstreams && tiles_host && volumes_host && wtab_host && centers && (symbols || q) && status && workspace);
+    IC_CHECK_ARG(tile_channels_host && layer_ends_host && segs_host);
+    IC_CHECK_ARG(total_bytes >= 0 && ntiles > 0 && nvolumes > 0 && C > 0 && k > 0 && L > 0);
+    IC_CHECK_ARG(fill_sym >= 0 && fill_sym < L);
+    IC_CHECK_ARG(nlayers >= 1 && nlayers <= 16);
+    IC_CHECK_ARG(layer_ends_host[0] >= 1 && layer_ends_host[nlayers - 1] == C);
+    for (int g = 1; g < nlayers; ++g) IC_CHECK_ARG(layer_ends_host[g] > layer_ends_host[g - 1]);
+    for (int n = 0; n < nvolumes; ++n) {
+        const ic_pc_volume_t& v = volumes_host[n];
+        IC_CHECK_ARG(v.h >= 1 && v.w >= 1 && v.symbols_off >= 0 && v.q_off >= 0);
+    }
+    int th_max = 0, tw_max = 0;
+    for (int t = 0; t < ntiles; ++t) {
+        ic_pc_tile_t d = tiles_host[t];
+        const int channels = tile_channels_host[t];
+        IC_CHECK_ARG(channels >= 1 && channels <= C);
+        IC_CHECK_ARG(d.volume >= 0 && d.volume < nvolumes);
+        d.stream_off = 0; d.stream_bytes = 0;             // not read: the segments stand for them
+        IC_CHECK_ARG(pc_tile_ok(d, volumes_host[d.volume].h, volumes_host[d.volume].w, total_bytes, L));
+        for (int g = 0; g < nlayers && (g == 0 || layer_ends_host[g - 1] < channels); ++g) {     // the layers that begin below THIS tile's limit
+            const ic_pc_seg_t& sg = segs_host[(size_t)t * nlayers + g];
+            IC_CHECK_ARG(sg.off >= 0 && sg.nbytes >= 0 && sg.off <= total_bytes && sg.nbytes <= total_bytes - sg.off);
+        }
+        th_max = d.th > th_max ? d.th : th_max;
+        tw_max = d.tw > tw_max ? d.tw : tw_max;
+    }
+    if (L > 16 || k != 24 || flags != 0) return IC_ERR_UNSUPPORTED;
+    if (workspace_bytes < ic_pc_decode_tiles_batch_layers_pertile_workspace_bytes(C, th_max, tw_max, ntiles, nvolumes, k, nlayers)) return IC_ERR_WORKSPACE;
+    return pc_decode_tiles_impl(bitstreams, tiles_host, ntiles, th_max, tw_max, volumes_host, nvolumes, wtab_host, centers, k, L,
+                                resolution, symbols, q, status, C, workspace, flags, C, fill_sym, stream,
+                                layer_ends_host, nlayers, segs_host, tile_channels_host);
 }

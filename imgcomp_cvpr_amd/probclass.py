@@ -550,7 +550,7 @@ class PredictionNetwork(object):
         return res
 
     def decode_tiles_batch(self, volumes, th, tw, want='q', max_workspace_bytes=1 << 31, flags=0, conceal=False, order='raster',
-                           channels=None, layer_ends=None):
+                           channels=None, layer_ends=None, tile_layers=None):
         """The mirror of encode_tiles_batch: the tiles of ALL volumes decoded by one launch per chunk (ic_pc_decode_tiles_batch_f32,
         one work-group per tile).  volumes: [(streams, first_syms, (C,h,w))], each as decode_tiles takes them, one C throughout.
         want: 'q' -> per volume the (C,h,w) float32 DEVICE tensor centers[symbols] (what ae.decode consumes: the symbols never
@@ -568,7 +568,15 @@ class PredictionNetwork(object):
         wavefront order: after their last front), the others hold the fill symbol / its centre.  Not with conceal=True.
         layer_ends=[e_0 < ... = C] (container format 6, ic_pc_decode_tiles_batch_layers_f32; raster, k = 24, flags 0, not with
         conceal=True): streams[t] is the list of the tile's G segments, as encode_tiles(layer_ends=...) gives them; entries of layers
-        that begin at or above `channels` are not read and may be None."""
+        that begin at or above `channels` are not read and may be None.
+        tile_layers=[per volume [g_t per tile]] (needs layer_ends; not with conceal=True or channels; recovery of a damaged or cut
+        format-6 file): tile t is read up to its leading g_t layers, 0 <= g_t <= G, through ic_pc_decode_tiles_batch_layers_pertile_f32.
+        g_t = 0 skips the tile like a None stream; its segments of layers >= g_t may be None.  A tile whose decoder status is not 0
+        counts as holding nothing (reason 'decoder', instead of the ValueError).  Then, if any tile holds fewer than C channels, one
+        ic_pc_conceal_tiles_channels launch fills every missing (tile, channel) from the neighbours that hold that channel (the
+        fallback is the fill symbol, so a channel no neighbour holds is that of a preview).  The call returns (result as above, [per
+        volume [(tile, layers_read, channels, reason)] in tile order for the tiles that hold fewer than C channels]); reason is
+        'decoder' or None (the caller's own limit)."""
         from .codec import tile_grid, chunk_tiles, check_channels, check_layer_ends
         if layer_ends is not None:
             if conceal:
@@ -577,6 +585,12 @@ class PredictionNetwork(object):
                 raise ValueError('layer_ends cuts raster streams for the k = 24 decoder: order {!r}, flags {}'.format(order, flags))
             if self.pc._k != 24:
                 raise ValueError('layered tiles need a context model of width k = 24, this one has k = {}'.format(self.pc._k))
+        if tile_layers is not None:
+            if layer_ends is None:
+                raise ValueError('tile_layers counts layers per tile: it needs layer_ends')
+            if conceal or channels is not None:
+                raise ValueError('tile_layers does not go with conceal=True or channels: it conceals per channel by itself, and '
+                                 'every tile has its own limit')
         if channels is not None and conceal:
             raise ValueError('channels={} with conceal=True: a preview of a damaged file is not offered'.format(channels))
         if want not in ('q', 'symbols', 'both'):
@@ -586,14 +600,16 @@ class PredictionNetwork(object):
         if order == 'wavefront':
             flags = int(flags) | _lib.PC_DECODE_WAVEFRONT
         if not volumes:
-            return ([], []) if conceal else []
+            return ([], []) if conceal or tile_layers is not None else []
         dev = self.centers.device
         C0 = int(volumes[0][2][0])
         if layer_ends is not None:
             ends = check_layer_ends(layer_ends, C0)
             upto = C0 if channels is None else check_channels(channels, C0)
             needed = [g for g in range(len(ends)) if g == 0 or ends[g - 1] < upto]     # the layers that begin below `channels`
-        shapes, grids, tiles, where, blobs, pos, missing, segs = [], [], [], [], [], 0, [], []
+        shapes, grids, tiles, where, blobs, pos, missing, segs, limits = [], [], [], [], [], 0, [], [], []
+        if tile_layers is not None and len(tile_layers) != len(volumes):
+            raise ValueError('tile_layers has {} entries for {} volumes'.format(len(tile_layers), len(volumes)))
         for n, (streams, first_syms, shape) in enumerate(volumes):
             C, h, w = (int(v) for v in shape)
             if C != int(volumes[0][2][0]):
@@ -604,7 +620,29 @@ class PredictionNetwork(object):
                     n, len(streams), len(first_syms), len(grid)))
             shapes.append((C, h, w))
             grids.append(grid)
+            if tile_layers is not None and len(tile_layers[n]) != len(grid):
+                raise ValueError('volume {}: tile_layers has {} entries for a grid of {} tiles'.format(n, len(tile_layers[n]), len(grid)))
             for t, (y0, x0, a, b) in enumerate(grid):
+                if tile_layers is not None:
+                    g_t = int(tile_layers[n][t])
+                    if not 0 <= g_t <= len(ends):
+                        raise ValueError('volume {}, tile {}: {} layers to read of {}'.format(n, t, g_t, len(ends)))
+                    if g_t == 0:
+                        missing.append((n, t))
+                        continue
+                    if streams[t] is None or len(streams[t]) != len(ends) or any(streams[t][g] is None for g in range(g_t)):
+                        raise ValueError('volume {}, tile {}: {} layers to read need the segments 0 .. {} of {}'.format(n, t, g_t, g_t - 1, len(ends)))
+                    tiles.append((y0, x0, a, b, 0, 0, first_syms[t], n))
+                    where.append((n, t, y0, x0))
+                    limits.append(ends[g_t - 1])
+                    for g in range(len(ends)):
+                        if g < g_t:
+                            segs.append((pos, len(streams[t][g])))
+                            blobs.append(bytes(streams[t][g]))
+                            pos += len(streams[t][g])
+                        else:
+                            segs.append((0, 0))
+                    continue
                 if streams[t] is None:
                     missing.append((n, t))
                     continue
@@ -631,6 +669,8 @@ class PredictionNetwork(object):
         vtable, offs, total = _lib.packed_volume_table(shapes)
 
         def need(th_max, tw_max, ntiles):
+            if tile_layers is not None:
+                return int(lib.ic_pc_decode_tiles_batch_layers_pertile_workspace_bytes(C, th_max, tw_max, ntiles, len(shapes), k, G))
             if G:
                 return int(lib.ic_pc_decode_tiles_batch_layers_workspace_bytes(C, th_max, tw_max, ntiles, len(shapes), k, G))
             return int(lib.ic_pc_decode_tiles_batch_workspace_bytes(C, th_max, tw_max, ntiles, len(shapes), k))
@@ -640,7 +680,7 @@ class PredictionNetwork(object):
         data = torch.frombuffer(bytearray(b''.join(blobs)) or bytearray(1), dtype=torch.uint8).to(dev)
         alloc = torch.zeros if missing else torch.empty
         q = alloc(total, dtype=torch.float32, device=dev) if want in ('q', 'both') else None
-        sym = alloc(total, dtype=torch.int64, device=dev) if want in ('symbols', 'both') or conceal else None    # the rule reads symbols
+        sym = alloc(total, dtype=torch.int64, device=dev) if want in ('symbols', 'both') or conceal or tile_layers is not None else None    # the rules read symbols
         status = torch.zeros(len(tiles), dtype=torch.int32, device=dev)
         centers = self.centers.contiguous().float()
         if chunks:
@@ -650,17 +690,36 @@ class PredictionNetwork(object):
         if G:
             seg_table, host_ends = _lib.seg_table(segs), (ctypes.c_int * G)(*ends)
             layers = (C, self.conceal_fallback()) if preview is None else preview
+            host_limits = (ctypes.c_int * max(len(limits), 1))(*limits)
         for a, b in chunks:
             args = (ptr(data), pos, ctypes.c_void_p(ctypes.addressof(table) + a * step), b - a, vtable, len(shapes), self.pc._tab,
                     ptr(centers), k, self.pc.L, self.freqs_resolution, ptr(sym), ptr(q), ptr(status[a:b]), C, ptr(ws), ws_bytes,
                     int(flags), _lib.current_stream(dev))
             if G:
                 seg_ptr = ctypes.c_void_p(ctypes.addressof(seg_table) + a * G * ctypes.sizeof(_lib.PcSeg))
+            if tile_layers is not None:
+                lim_ptr = ctypes.c_void_p(ctypes.addressof(host_limits) + a * ctypes.sizeof(ctypes.c_int))
+                check(lib.ic_pc_decode_tiles_batch_layers_pertile_f32(*(args + (lim_ptr, self.conceal_fallback(), host_ends, G, seg_ptr))),
+                      'ic_pc_decode_tiles_batch_layers_pertile_f32')
+            elif G:
                 check(lib.ic_pc_decode_tiles_batch_layers_f32(*(args + layers + (host_ends, G, seg_ptr))), 'ic_pc_decode_tiles_batch_layers_f32')
             elif preview is None:
                 check(lib.ic_pc_decode_tiles_batch_f32(*args), 'ic_pc_decode_tiles_batch_f32')
             else:
                 check(lib.ic_pc_decode_tiles_batch_channels_f32(*(args + preview)), 'ic_pc_decode_tiles_batch_channels_f32')
+        if tile_layers is not None:
+            failed = set(where[i][:2] for i, st in enumerate(status.tolist()) if st != 0)      # (the host waits here, as below)
+            held, have = [], []
+            for n, grid in enumerate(grids):
+                row = [0 if (n, t) in failed or int(tile_layers[n][t]) == 0 else ends[int(tile_layers[n][t]) - 1] for t in range(len(grid))]
+                have.append(row)
+                held.append([(t, 0 if (n, t) in failed else int(tile_layers[n][t]), row[t], 'decoder' if (n, t) in failed else None)
+                             for t in range(len(grid)) if row[t] < C])
+            if any(held):
+                self._conceal_channels(sym, q, shapes, grids, vtable, have, th, tw, centers)
+            cut = lambda buf: [buf[o:o + c * h * w].view(c, h, w) for (c, h, w), o in zip(shapes, offs)]
+            res = cut(q) if want == 'q' else cut(sym) if want == 'symbols' else list(zip(cut(q), cut(sym)))
+            return res, held
         damage = [[] for _ in shapes]
         for n, t in missing:
             damage[n].append((t, 'missing'))
@@ -701,6 +760,21 @@ class PredictionNetwork(object):
         check(lib.ic_pc_conceal_tiles(ptr(sym), ptr(q), table, len(tiles), vtable, len(shapes), host_marks, ptr(centers), self.pc.L,
                                       self.conceal_fallback(), shapes[0][0], int(th), int(tw), ptr(ws), need,
                                       _lib.current_stream(dev)), 'ic_pc_conceal_tiles')
+        torch.cuda.current_stream(dev).synchronize()        # the three host tables and the workspace are done with
+
+    def _conceal_channels(self, sym, q, shapes, grids, vtable, have, th, tw, centers):
+        """one ic_pc_conceal_tiles_channels launch on the current stream: have[n][t] = the leading channels tile t of volume n holds;
+        every (tile, channel) at or above it is filled.  sym / q as decode_tiles_batch lays them out (q may be None)"""
+        dev = self.centers.device
+        C = shapes[0][0]
+        tiles = [grid[t] + (0, 0, 0, n) for n, (grid, row) in enumerate(zip(grids, have)) for t in range(len(grid)) if row[t] < C]
+        flat = [int(v) for row in have for v in row]
+        table, host_have = _lib.tile_table(tiles), (ctypes.c_uint16 * len(flat))(*flat)
+        need = int(lib.ic_pc_conceal_tiles_channels_workspace_bytes(len(tiles), len(shapes), len(flat)))
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        check(lib.ic_pc_conceal_tiles_channels(ptr(sym), ptr(q), table, len(tiles), vtable, len(shapes), host_have, ptr(centers), self.pc.L,
+                                               self.conceal_fallback(), C, int(th), int(tw), ptr(ws), need,
+                                               _lib.current_stream(dev)), 'ic_pc_conceal_tiles_channels')
         torch.cuda.current_stream(dev).synchronize()        # the three host tables and the workspace are done with
 
     def get_pr(self, input_ctx):

@@ -374,6 +374,24 @@ int ic_pc_decode_tiles_batch_layers_f32(const uint8_t* bitstreams, long long tot
                                         int* status, int C, void* workspace, size_t workspace_bytes, int flags,
                                         ic_stream_t stream, int channels, int fill_sym,
                                         const int* layer_ends_host, int nlayers, const ic_pc_seg_t* segs_host);
+/* Layered tiles with a channel limit PER TILE: what a damaged or cut format-6 file still holds (codec.py, recover).  The parameters
+ * of ic_pc_decode_tiles_batch_layers_f32 with tile_channels_host in place of the scalar `channels`:
+ *   tile_channels_host: HOST array, one entry per listed tile, read before the call returns: tile t is decoded up to channel
+ *     tile_channels_host[t] in 1 .. C (else IC_ERR_ARG) -- any value, not only a layer end, as for `channels`; its channels at or
+ *     above the limit get fill_sym / centers[fill_sym].  Every position of every listed tile is written.
+ *   segs_host: checked PER TILE, only the rows of layers that begin below that tile's limit; the rows above it may hold anything and
+ *     are never read.
+ *   status[t]: the error flag kept over the cuts of the segments tile t actually read.
+ *   With every limit equal to K the result is that of ic_pc_decode_tiles_batch_layers_f32(channels = K), bit for bit.
+ *   k != 24, flags != 0, L > 16: IC_ERR_UNSUPPORTED; too small a workspace IC_ERR_WORKSPACE.  All decided on the host; a refused call
+ *   writes nothing.  workspace: ic_pc_decode_tiles_batch_layers_pertile_workspace_bytes(the arguments of the layers entry's). */
+size_t ic_pc_decode_tiles_batch_layers_pertile_workspace_bytes(int C, int th_max, int tw_max, int ntiles, int nvolumes, int k, int nlayers);
+int ic_pc_decode_tiles_batch_layers_pertile_f32(const uint8_t* bitstreams, long long total_bytes, const ic_pc_tile_t* tiles_host, int ntiles,
+                                                const ic_pc_volume_t* volumes_host, int nvolumes, const float* const* wtab_host,
+                                                const float* centers, int k, int L, float resolution, int64_t* symbols, float* q,
+                                                int* status, int C, void* workspace, size_t workspace_bytes, int flags,
+                                                ic_stream_t stream, const int* tile_channels_host, int fill_sym,
+                                                const int* layer_ends_host, int nlayers, const ic_pc_seg_t* segs_host);
 /* Concealment: what stands in the volumes where a tile could not be decoded (a damaged file; codec.py, salvage).  Stated on symbols,
  * so exact: for a damaged tile T and a channel c the candidates are the symbols of channel c directly above T's top row, below its
  * bottom row, left of its left column and right of its right column (no corners) that lie inside the volume and in a tile that
@@ -394,6 +412,22 @@ int ic_pc_conceal_tiles(int64_t* symbols, float* q, const ic_pc_tile_t* tiles_ho
                         const ic_pc_volume_t* volumes_host, int nvolumes, const uint8_t* damaged_host,
                         const float* centers, int L, int fallback, int C, int th, int tw,
                         void* workspace, size_t workspace_bytes, ic_stream_t stream);
+/* Concealment per (tile, channel): as ic_pc_conceal_tiles where a tile holds only its leading channels (a layered file that was cut
+ * or damaged).  In place of the damage map, have_host: HOST uint16, one per grid cell, volume after volume in raster order: the
+ * number of leading channels the cell's tile holds, 0 .. C.  For a listed tile T and a channel c >= have[T] the candidates are the
+ * symbols of channel c in the four edge rows and columns around T (no corners) that lie inside the volume and in a tile whose `have`
+ * EXCEEDS c; all of T in channel c becomes the most frequent candidate (ties: the smallest symbol; a symbol outside [0, L) is no
+ * candidate), or `fallback` where there is none.  Channels c < have[T] are not touched.  One launch of ntiles x C work-groups; one
+ * whose channel its tile holds returns at once; channel c is read only in tiles that nobody writes in channel c, so there is no
+ * order among them.  With have in {0, C} the result is that of ic_pc_conceal_tiles with the corresponding damage map.
+ *   tiles_host: the tiles with have < C.  Checked on the host before any device call (IC_ERR_ARG): as ic_pc_conceal_tiles, every
+ *     entry of the map <= C, every listed tile exactly one cell of its grid with have < C.  L > 16: IC_ERR_UNSUPPORTED.
+ *   workspace: ic_pc_conceal_tiles_channels_workspace_bytes(ntiles, nvolumes, number of grid cells). */
+size_t ic_pc_conceal_tiles_channels_workspace_bytes(int ntiles, int nvolumes, long long ngrid);
+int ic_pc_conceal_tiles_channels(int64_t* symbols, float* q, const ic_pc_tile_t* tiles_host, int ntiles,
+                                 const ic_pc_volume_t* volumes_host, int nvolumes, const uint16_t* have_host,
+                                 const float* centers, int L, int fallback, int C, int th, int tw,
+                                 void* workspace, size_t workspace_bytes, ic_stream_t stream);
 /* The encoder side of the real-bpp path on the device: the mirror image of ic_pc_decode_f32.  Codes N symbol volumes in one
  * launch (one work-group per volume) with the 32-bit range coder of arithmetic_coding.py; the stream of each volume is byte
  * for byte arithmetic_coding.encode_sequence(symbols[1:], freqs[1:]) over the tables ic_pc_logits_to_freqs_f32 derives from
