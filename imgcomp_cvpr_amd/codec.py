@@ -6,6 +6,7 @@
     python -m imgcomp_cvpr_amd.codec compress-dir   IN_DIR OUT_DIR [--tile PIXELS [--checked | --wavefront | --layers a,b,.. | --progressive]] [--batch N]   every *.png / *.jpg -> OUT_DIR/<stem>.icf
     python -m imgcomp_cvpr_amd.codec decompress-dir IN_DIR OUT_DIR [--batch N] [--salvage | --channels K | --partial | --recover]    every *.icf -> OUT_DIR/<stem>.png
     python -m imgcomp_cvpr_amd.codec verify PATH [PATH ...]         files or directories of *.icf: the checksums, without model or device
+    python -m imgcomp_cvpr_amd.codec stream IN.icf OUT_DIR [model options] [--chunk BYTES]    a format-6 file fed chunk by chunk, a picture per gained layer
 
 compress:   pad to a multiple of the subsampling factor (val.add_padding) -> ae.encode -> PredictionNetwork.encode_stream (the
             range coder on the device, ic_pc_encode_f32) -> container.
@@ -101,6 +102,13 @@ a channel limit per tile (ic_pc_decode_tiles_batch_layers_pertile_f32); then eve
 from the neighbouring tiles that hold that channel (ic_pc_conceal_tiles_channels: the most frequent symbol on the four edges, ties
 to the smallest), or with the fill symbol where no neighbour holds it -- if all tiles stop at one layer, that is --partial's image.
 The report names every tile with fewer than all layers.  --partial and --salvage read as before.
+stream (Codec.open_stream -> StreamDecoder): a format-6 file that is still arriving.  feed(chunk) takes the bytes as they come, image()
+gives recover's picture and report of the bytes so far -- but the decoder goes on where the last image() stopped: the session
+(PredictionNetwork.open_layers) keeps every tile's decoder workspace on the device and ic_pc_decode_tiles_batch_layers_resume_f32
+continues each tile at the first layer it has gained (resume_plan), so a viewer that redraws after every layer decodes every channel
+plane once, not once per redraw.  The command feeds IN.icf in chunks of --chunk bytes (default 16384), as a download would, and
+writes OUT_DIR/<stem>.<bytes fed, 9 digits>.png with a recover line each time a tile has gained a layer; the last picture of an intact
+file is decompress's.
 """
 import argparse
 import io
@@ -704,6 +712,54 @@ def parse_recover(data):
     return c, layers, reasons, file_crc_ok
 
 
+def resume_plan(done_layers, now_layers, layer_ends):
+    """what a decoder that holds the leading `done_layers` layers of a tile has to do when `now_layers` of them are there ->
+    (from_layer, channels) as ic_pc_decode_tiles_batch_layers_resume_f32 takes them per tile: continue with layer from_layer up to
+    channel `channels`.  done <= now: (done, e_{now-1}) -- with done == now nothing is decoded, the call only rewrites the fill above
+    the limit, and done == now == G says the tile is whole.  done == 0 (nothing yet, or a decoder failure dropped what there was):
+    the fresh start (0, e_{now-1}).  now < done (the caller takes layers back): a fresh start as well, what is held above is of no
+    use.  now == 0: (0, 0), the tile stays out of the launch."""
+    G = len(layer_ends)
+    done, now = int(done_layers), int(now_layers)
+    if not 0 <= done <= G or not 0 <= now <= G:
+        raise ValueError('resume plan: {} layers done, {} there now, of G = {}'.format(done, now, G))
+    if now == 0:
+        return 0, 0
+    return (done if done <= now else 0), int(layer_ends[now - 1])
+
+
+def stream_header_bytes(data):
+    """the length of the header of the format-6 file that begins with `data` (magic up to and including the header CRC), or None
+    while `data` is too short to tell.  A ValueError as soon as the bytes cannot be the beginning of a format-6 file: wrong magic,
+    another format (parse_recover's words), a layer count or a tile count that does not fit the rest.  Nothing is checked that the
+    whole header's own CRC covers: parse_recover does that once the header is there."""
+    data = bytes(data)
+    if data[:4] != MAGIC[:len(data[:4])]:
+        raise ValueError('header damaged: wrong magic {!r}: not a codec file (expected {!r})'.format(data[:4], MAGIC))
+    if len(data) < 6:
+        return None
+    version, = struct.unpack('<H', data[4:6])
+    if version != FORMAT_VERSION_LAYERED:
+        parse_recover(data + bytes(_MIN_SIZE))            # another format: its refusal, whatever the length so far
+        raise ValueError('header damaged: format version {} is not the layered version {}'.format(version, FORMAT_VERSION_LAYERED))
+    if len(data) < 8:
+        return None
+    a, = struct.unpack('<H', data[6:8])
+    if len(data) < 10 + a:
+        return None
+    p, = struct.unpack('<H', data[8 + a:10 + a])
+    base = 10 + a + p                                      # H, W, C, h, w, L, resolution, fingerprint, th, tw, ntiles, G: 42 bytes
+    if len(data) < base + 42:
+        return None
+    h, w = struct.unpack('<II', data[base + 10:base + 18])
+    th, tw, nt, G = struct.unpack('<HHIH', data[base + 32:base + 42])
+    if not 1 <= G <= MAX_LAYERS:
+        raise ValueError('header damaged: layer count G = {} is outside 1 .. {}'.format(G, MAX_LAYERS))
+    if th < 1 or tw < 1 or h < 1 or w < 1 or nt != ((h + th - 1) // th) * ((w + tw - 1) // tw):
+        raise ValueError('header damaged: {} tiles do not cover a {} x {} volume with tiles of {} x {}'.format(nt, h, w, th, tw))
+    return base + 42 + 2 * G + 2 * nt + 8 * G * nt + 8 + 4
+
+
 def parse_salvage(data):
     """what a possibly damaged format-4 or format-5 file still holds -> (CheckedContainer or WavefrontContainer, damage, file_crc_ok).  damage: [(tile, reason)] in
     tile order, reason 'crc' (the bytes are there, their CRC differs) or 'truncated' (the tile's byte range is not complete);
@@ -1267,6 +1323,10 @@ class Codec(object):
                 out[i] = (self._crop(x, heads[i][0]), self._recover_report(heads[i], tiles))
         return out
 
+    def open_stream(self, max_workspace_bytes=1 << 31):
+        """a StreamDecoder: a format-6 file fed as it arrives, recover's picture of the bytes so far, every layer decoded once"""
+        return StreamDecoder(self, max_workspace_bytes)
+
     def compress_file(self, image_path, out_path):
         from PIL import Image
         img = np.asarray(Image.open(image_path).convert('RGB'), dtype=np.uint8)     # as val.load_image_chw reads it
@@ -1283,6 +1343,67 @@ class Codec(object):
         img = self.decompress(data, channels=channels)
         Image.fromarray(img).save(image_path)
         return img
+
+
+class StreamDecoder(object):
+    """a format-6 file that is still arriving (Codec.open_stream).
+    feed(chunk): appends the bytes; False while the header is not whole, True once it is and passes its CRC and the model checks.  The
+        ValueErrors of recover -- another format, a damaged header, another model -- are raised by the feed that shows them.
+    progress(): the number of leading intact layers per tile in the bytes so far (parse_recover), () before the header; no device.
+    image(): (HWC uint8 image, RecoverReport), equal to Codec.recover(the bytes so far).  The first call opens the session
+        (PredictionNetwork.open_layers); every call decodes, per tile, only the layers gained since the last one, conceals per (tile,
+        channel) and runs one autoencoder pass.  ValueError('no complete layer ...') while no tile has a layer.  Without a new layer in
+        any tile the last picture is returned again and nothing is launched (the report is that of the bytes so far)."""
+
+    def __init__(self, codec, max_workspace_bytes=1 << 31):
+        self.codec, self.max_workspace_bytes = codec, int(max_workspace_bytes)
+        self._buf = bytearray()
+        self._header = None            # its length, once known
+        self._ready = False
+        self._head = None              # (bytes fed, _recover_head of them)
+        self._session = None
+        self._last = None              # (layers, image, held) of the last picture
+
+    @property
+    def bytes_fed(self):
+        return len(self._buf)
+
+    def feed(self, chunk):
+        self._buf += bytes(chunk)
+        if self._ready:
+            return True
+        if self._header is None:
+            self._header = stream_header_bytes(self._buf[:1 << 18])          # (the fields that give the length end below 2^18)
+        if self._header is None or len(self._buf) < self._header:
+            return False
+        self._parsed()                 # the header's CRC, the model checks: raises what recover raises
+        self._ready = True
+        return True
+
+    def _parsed(self):
+        if self._head is None or self._head[0] != len(self._buf):
+            self._head = (len(self._buf), self.codec._recover_head(bytes(self._buf)))
+        return self._head[1]
+
+    def progress(self):
+        return tuple(self._parsed()[1]) if self._ready else ()
+
+    def image(self):
+        import torch
+        if not self._ready:
+            raise ValueError('no complete layer: the header is not whole yet, {} bytes so far'.format(len(self._buf)))
+        head = self._parsed()
+        c, layers = head[0], list(head[1])
+        if not any(layers):
+            raise ValueError('no complete layer: no tile holds its layer 0 in the {} bytes so far'.format(len(self._buf)))
+        codec = self.codec
+        if self._last is None or self._last[0] != layers:
+            if self._session is None:
+                self._session = codec.pred.open_layers([(c.C, c.h, c.w)], c.th, c.tw, c.layer_ends, self.max_workspace_bytes)
+            qs, held = self._session.advance([(c.streams, c.first_syms)], [layers], want='q')
+            x_out = codec.ae.decode(qs[0][None], is_training=False).to(torch.uint8)      # tf.cast truncates (val.py)
+            self._last = (layers, codec._crop(x_out[0], c), held[0])
+        return self._last[1], codec._recover_report(head, self._last[2])
 
 
 def _resolve_config(arg, tree, env):
@@ -1330,8 +1451,22 @@ def _recover_line(path, report):
 
 
 def check_option_args(flags):
-    """--checked / --wavefront / --salvage / --channels / --layers / --progressive / --partial / --recover against the command, --tile and each
-    other: decided before any model is built"""
+    """--checked / --wavefront / --salvage / --channels / --layers / --progressive / --partial / --recover / --chunk against the command, --tile
+    and each other: decided before any model is built"""
+    if getattr(flags, 'chunk', None) is not None:
+        if flags.command != 'stream':
+            raise ValueError('--chunk belongs to stream: the size of the pieces the file is fed in')
+        if flags.chunk < 1:
+            raise ValueError('--chunk {} is not at least 1'.format(flags.chunk))
+    if flags.command == 'stream':
+        for name in ('salvage', 'partial', 'recover'):
+            if getattr(flags, name, False):
+                raise ValueError('--{} does not go with stream: it reads what has arrived of a layered file as --recover does, '
+                                 'tile by tile'.format(name))
+        if getattr(flags, 'channels', None) is not None:
+            raise ValueError('--channels does not go with stream: what every tile holds so far decides its channels')
+        if getattr(flags, 'tile', None) is not None:
+            raise ValueError('--tile belongs to compress / compress-dir: a file says by itself how it is tiled')
     if getattr(flags, 'channels', None) is not None:
         if flags.command not in ('decompress', 'decompress-dir'):
             raise ValueError('--channels belongs to decompress / decompress-dir: a preview is a way of reading a file')
@@ -1640,13 +1775,42 @@ def _main_verify(argv):
     return 1 if bad else 0
 
 
+STREAM_CHUNK = 16384
+
+
+def _main_stream(flags, codec):
+    """stream: the file fed chunk by chunk, a picture and a recover line each time a tile has gained a layer"""
+    from PIL import Image
+    if os.path.exists(flags.output) and not os.path.isdir(flags.output):
+        raise ValueError('stream: output {!r} exists and is not a directory'.format(flags.output))
+    with open(flags.input, 'rb') as f:
+        data = f.read()
+    chunk = STREAM_CHUNK if flags.chunk is None else flags.chunk
+    stem = os.path.splitext(os.path.basename(flags.input))[0]
+    dec, shown = codec.open_stream(), None
+    for pos in range(0, len(data), chunk):
+        if not dec.feed(data[pos:pos + chunk]):
+            continue
+        layers = dec.progress()
+        if layers == shown or not any(layers):
+            continue
+        img, report = dec.image()
+        shown = layers
+        os.makedirs(flags.output, exist_ok=True)
+        path = os.path.join(flags.output, '{}.{:09d}.png'.format(stem, dec.bytes_fed))
+        Image.fromarray(img).save(path)
+        print(_recover_line(path, report))
+    if shown is None:
+        raise ValueError('no complete layer: {} holds {} bytes and no tile\'s layer 0'.format(flags.input, len(data)))
+
+
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else list(argv)
     if argv and argv[0] == 'verify':
         return _main_verify(argv[1:])
     p = argparse.ArgumentParser(description='compress an image to a codec file, or a codec file back to an image; '
                                             'the -dir commands do so for every file of a directory, --batch files per call')
-    p.add_argument('command', choices=['compress', 'decompress', 'compress-dir', 'decompress-dir'])
+    p.add_argument('command', choices=['compress', 'decompress', 'compress-dir', 'decompress-dir', 'stream'])
     p.add_argument('input')
     p.add_argument('output')
     p.add_argument('--ae_config', default='cvpr/low', help='a config file, or a name below $CONFIG_BASE_AE / the package\'s ae_configs')
@@ -1677,6 +1841,8 @@ def main(argv=None):
     p.add_argument('--channels', type=int, default=None, metavar='K',
                    help='decompress / decompress-dir: a preview from the first K latent channels only (any format; the decoder stops '
                         'after them, the other channels get the centre nearest zero); not with --salvage')
+    p.add_argument('--chunk', type=int, default=None, metavar='BYTES',
+                   help='stream: feed the file in pieces of this many bytes (default {})'.format(STREAM_CHUNK))
     flags = p.parse_args(argv)
     from . import config_parser, val, weights as _weights
     try:
@@ -1701,6 +1867,8 @@ def main(argv=None):
                 codec.layers = layers
             data, pixels = codec.compress_file(flags.input, flags.output)
             print(_compress_line(flags.output, data, pixels))
+        elif flags.command == 'stream':
+            _main_stream(flags, codec)
         elif flags.partial:
             from PIL import Image
             with open(flags.input, 'rb') as f:

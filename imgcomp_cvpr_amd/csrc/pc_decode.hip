@@ -5,7 +5,8 @@
 // Host entry points: ic_pc_decode_f32, ic_pc_decode_tiles_f32, ic_pc_decode_tiles_batch_f32 and their *_workspace_bytes;
 // ic_pc_decode_channels_f32 and ic_pc_decode_tiles_batch_channels_f32 decode only the first channels of every stream (preview);
 // ic_pc_decode_tiles_batch_layers_f32 reads every tile's stream as segments cut at channel planes (container format 6);
-// ic_pc_decode_tiles_batch_layers_pertile_f32 does so with a channel limit per tile (recovery of damaged or cut layered files).
+// ic_pc_decode_tiles_batch_layers_pertile_f32 does so with a channel limit per tile (recovery of damaged or cut layered files);
+// ic_pc_decode_tiles_batch_layers_resume_f32 continues every tile at the layer where an earlier call on the same workspace stopped.
 #include "common.h"
 #include "pc_table.h"
 #include "pc_internal.h"
@@ -466,12 +467,17 @@ __device__ __forceinline__ int pc_chain_idx(int t, int ci) { return 8 * ((ci >> 
 // nbytes bounds pc_dec_bit).  segs and ends are the tile's rows of device tables in the workspace, the index is uniform: scalar
 // loads, a handful per tile, and no per-lane copy of either table.  With LIM the sweep ends before the cuts of the layers that
 // begin at or above cdec: their segments are never read.  SEG = false reads none of this and is the decoder as before.
-template <bool SYMS = true, bool LIM = false, bool SEG = false>
+// FROM = true (ic_pc_decode_tiles_batch_layers_resume_f32; only with LIM && SEG): gfrom is the layer the tile continues with, uniform
+// like cdec.  gfrom == 0 is the sweep from the start.  gfrom > 0: an earlier launch has swept this tile up to plane D = cfrom + 3 with
+// cfrom = ends[gfrom - 1] and has left V and the caches in the slot; this sweep begins at the step behind that one's last and runs up
+// to plane cdec + 3 > cfrom + 3.  FROM = false reads none of this and is the decoder as before.
+template <bool SYMS = true, bool LIM = false, bool SEG = false, bool FROM = false>
 __device__ __forceinline__ void pc_dec_cached_body(const PcCachedArgs& f, const unsigned char* bits, long long nbytes, int h, int w, int first_sym,
                                                    float* vol, float* c0, float* c1, float* c2, int* status,
                                                    long long* __restrict__ out, long long out_cs, int out_rs, int cdec = 0,
                                                    const unsigned char* seg_base = nullptr, const ic_pc_seg_t* __restrict__ segs = nullptr,
-                                                   const int* __restrict__ ends = nullptr, int nlayers = 0) {
+                                                   const int* __restrict__ ends = nullptr, int nlayers = 0, int gfrom = 0) {
+    static_assert(!FROM || (LIM && SEG), "a sweep continues at a layer cut of a limited sweep");
     constexpr int K = 24, KT = PC_NT * K;                 // 336 inputs per output
     __shared__ __attribute__((aligned(16))) float s_in[3][KT];          // inputs of conv1 / conv2 / conv3 in chain order
     __shared__ __attribute__((aligned(16))) float s_v[16];              // the 13 live taps of conv0
@@ -521,23 +527,43 @@ __device__ __forceinline__ void pc_dec_cached_body(const PcCachedArgs& f, const 
         }
         if (tid < 12) pv = vol[((size_t)(D - 1 + vkd) * PH + (I - 1 + vkh)) * PW + J + vkw];
     };
+    typedef const __attribute__((address_space(4))) ic_pc_seg_t* seg_cptr;
+    typedef const __attribute__((address_space(4))) int* int_cptr;
+    // FROM, gfrom > 0: the sweep continues at (cfrom + 4, 1, 0), the step behind the last one, (cfrom + 3, h + 6, w + 5), of the sweep
+    // that stopped at channel cfrom.  Nothing of that sweep's LDS or registers is needed: at J = 0 no layer is valid (layer_valid asks
+    // J >= 1 + l), so the step produces no cache voxel and no logits, and what it reads of s_in -- the tap-12 slots it never wrote
+    // included -- flows into nothing that is kept, exactly as at (1, 1, 0) of a fresh sweep and at the first step of every row; the
+    // tap-12 carry into J = 1 is this step's own A0 voxel.  V[D][1][0] is pad as at a fresh start.  The coder needs no state either:
+    // the first symbol of channel cfrom, at (cfrom + 4, 4, 3), is the cut that initialises it on segment gfrom, and no step before
+    // that one decodes.  So segment 0 is neither initialised from nor read: s holds a coder at rest until the cut.
+    bool resumed = false;
+    int cfrom = 0;
+    if constexpr (FROM) {
+        resumed = gfrom > 0;
+        if (resumed) cfrom = ((int_cptr)ends)[gfrom - 1];
+    }
     PcDecState s;                                         // wave 0 keeps the coder state, identical in all its lanes
-    pc_dec_state_init(s, bits, nbytes);
-    if (wave == 0)
-        for (int i = 0; i < PC_AC_BITS; ++i) s.code = (s.code << 1) | (unsigned)pc_dec_bit(bits, nbytes, s);
-    if (tid == 0) s_v[12] = pad;                          // V[1][1][0]
+    if (!resumed) {
+        pc_dec_state_init(s, bits, nbytes);
+        if (wave == 0)
+            for (int i = 0; i < PC_AC_BITS; ++i) s.code = (s.code << 1) | (unsigned)pc_dec_bit(bits, nbytes, s);
+    } else {
+        s.low = 0; s.high = (1ull << PC_AC_BITS) - 1; s.code = 0;
+        s.byte_pos = -1; s.bit_left = 0; s.cur_byte = 0; s.nxt_byte = 0; s.error = 0; s.next = 1;
+    }
+    if (tid == 0) s_v[12] = pad;                          // V[1][1][0]; resumed: V[cfrom + 4][1][0]
     // SEG: the layer whose segment comes next, the channel it begins with (-1: none left), and the sticky error of the segments done
     // (the two tables were written by the copies that precede the launch and nothing in the kernel stores to them: they are read
     // through the constant address space, which is what lets a uniform index become a scalar load behind the kernel's own stores)
-    typedef const __attribute__((address_space(4))) ic_pc_seg_t* seg_cptr;
-    typedef const __attribute__((address_space(4))) int* int_cptr;
     int seg_next = 1, seg_cut = -1, sticky = 0;
     if constexpr (SEG) seg_cut = nlayers > 1 ? ((int_cptr)ends)[0] : -1;
+    if constexpr (FROM) if (resumed) { seg_next = gfrom; seg_cut = cfrom; }      // the next cut is the first symbol this sweep decodes
     // LDS hand-over between the waves: wait for this wave's LDS operations only.  (__syncthreads() also waits for the global
     // stores of the cache voxels to be acknowledged; their readers are a row of steps away and every wave drains its
     // memory counter at the top of each step, where it consumes its prefetch.)
     auto lds_barrier = []() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); };
     int D = 1, I = 1, J = 0;
+    if constexpr (FROM) if (resumed) D = cfrom + 4;
     prefetch(D, I, J);
     // one chain pass: this wave's part of the K sequence for the output this lane holds the weights of
     auto chain = [&](const float* in) -> float {
@@ -896,6 +922,8 @@ struct PcTilesBatchArgs {
     const int* ends;                  //   of the layer ends (nlayers),
     int nlayers;                      //   and their number
     const int* tile_channels;         // PER kernels only: device copy of the channel limit per tile (ntiles)
+    const int* tile_from;             // FROM kernels only: device copy of the layer every tile continues with (ntiles),
+    int* done;                        //   and the channels the workspace holds of every tile (ntiles; written by the kernel alone)
 };
 
 // SEG (ic_pc_decode_tiles_batch_layers_f32, raster only): the tile's stream is its nlayers segments, segs[blockIdx.x * nlayers + g];
@@ -904,10 +932,18 @@ struct PcTilesBatchArgs {
 // place of the launch's cdec.  A uniform index into a table that no kernel writes, read like the segment table through the constant
 // address space: one scalar load per tile, a uniform value as cdec is, and nothing of it in the body's per-symbol path.  A tile whose
 // limit is C is decoded whole; the copy loop then has no channel to fill.
-template <bool WAVE, bool SYMS, bool LIM = false, bool SEG = false, bool PER = false>
+// FROM (ic_pc_decode_tiles_batch_layers_resume_f32): the tile continues with layer gfrom = tile_from[blockIdx.x], read like the limit.
+// gfrom == 0 is PER.  gfrom > 0: the slot holds the tile swept up to channel cfrom = ends[gfrom - 1] by an earlier launch on the same
+// stream, and done[blockIdx.x] says so -- a word per tile that only this kernel writes: cdec behind a sweep that ended with status
+// 0, -1 behind one that did not.  A work-group whose done word is not cfrom stores status 2 and returns: no symbol, no q, nothing
+// of its slot or of done is touched.  Otherwise the body sweeps the channels [cfrom, cdec) (none if cfrom == cdec: a uniform branch
+// around it) and the copy loop writes those and the fill above cdec; the channels below cfrom are the earlier call's and stay.
+// Still nothing passes between work-groups: a work-group reads its own slot and its own done word.
+template <bool WAVE, bool SYMS, bool LIM = false, bool SEG = false, bool PER = false, bool FROM = false>
 __global__ __launch_bounds__(256) void pc_dec_tiles_batch_kernel(const PcTilesBatchArgs t) {
     static_assert(!(WAVE && SEG), "a layer is no prefix of a wavefront-ordered stream");
     static_assert(!PER || (LIM && SEG && !WAVE), "the limit per tile belongs to the layered raster decoder");
+    static_assert(!FROM || PER, "a sweep continues where a sweep with a limit per tile stopped");
     const ic_pc_tile_t tl = t.tiles[blockIdx.x];
     // v = volumes ? volumes[tl.volume] : one, as a uniform branch around a scalar load.  (Written as a select, it becomes a select
     // between the two ADDRESSES, kernel arguments or global memory, and a load through a flat pointer into vector registers:
@@ -918,7 +954,30 @@ __global__ __launch_bounds__(256) void pc_dec_tiles_batch_kernel(const PcTilesBa
     const long long corner = (long long)tl.y0 * v.w + tl.x0, plane = (long long)v.h * v.w;
     int cdec = LIM ? t.cdec : 0;
     if constexpr (PER) cdec = ((const __attribute__((address_space(4))) int*)t.tile_channels)[blockIdx.x];
-    if constexpr (WAVE)
+    int cfrom = 0;                    // FROM: the channels below it are the earlier call's
+    if constexpr (FROM) {
+        typedef const __attribute__((address_space(4))) int* int_cptr;
+        typedef const __attribute__((address_space(4))) ic_pc_seg_t* seg_cptr;
+        const int gfrom = ((int_cptr)t.tile_from)[blockIdx.x];
+        const ic_pc_seg_t* segs = t.segs + (size_t)blockIdx.x * t.nlayers;
+        long long off0 = 0, nbytes0 = 0;                   // segment 0 of a tile that continues is not looked at
+        if (gfrom > 0) {
+            cfrom = ((int_cptr)t.ends)[gfrom - 1];
+            if (t.done[blockIdx.x] != cfrom) {              // the slot does not hold this tile up to cfrom (uniform)
+                if (threadIdx.x == 0) t.status[blockIdx.x] = 2;
+                return;
+            }
+        } else {
+            off0 = ((seg_cptr)segs)[0].off; nbytes0 = ((seg_cptr)segs)[0].nbytes;
+        }
+        if (cfrom < cdec)
+            pc_dec_cached_body<SYMS, true, true, true>(t.f, t.bits + off0, nbytes0, tl.th, tl.tw, tl.first_sym, (float*)slot,
+                                                       (float*)(slot + t.off_c0), (float*)(slot + t.off_c1), (float*)(slot + t.off_c2), t.status + blockIdx.x,
+                                                       SYMS ? t.symbols + v.symbols_off + corner : nullptr, plane, v.w, cdec,
+                                                       t.bits, segs, t.ends, t.nlayers, gfrom);
+        else if (threadIdx.x == 0) t.status[blockIdx.x] = 0;
+        if (threadIdx.x == 0) t.done[blockIdx.x] = t.status[blockIdx.x] == 0 ? cdec : -1;       // (thread 0 stored the status)
+    } else if constexpr (WAVE)
         pc_dec_wave_body<SYMS, LIM>(t.f, t.bits + tl.stream_off, tl.stream_bytes, tl.th, tl.tw, tl.first_sym, (float*)slot,
                                     (float*)(slot + t.off_c0), (float*)(slot + t.off_c1), (float*)(slot + t.off_c2), t.status + blockIdx.x,
                                     SYMS ? t.symbols + v.symbols_off + corner : nullptr, plane, v.w, cdec);
@@ -949,7 +1008,7 @@ __global__ __launch_bounds__(256) void pc_dec_tiles_batch_kernel(const PcTilesBa
     } else {
         const float qfill = t.f.d.centers[t.fill];
         long long* syms = SYMS ? t.symbols + v.symbols_off + corner : nullptr;
-        for (int i = threadIdx.x; i < n; i += 256) {
+        for (int i = threadIdx.x + (FROM ? cfrom * tl.th * tl.tw : 0); i < n; i += 256) {       // FROM: channels >= cfrom only
             const int x = i % tl.tw, y = (i / tl.tw) % tl.th, c = i / (tl.tw * tl.th);
             const long long o = (long long)c * plane + (long long)y * v.w + x;
             if (c < cdec) {
@@ -967,6 +1026,13 @@ __global__ __launch_bounds__(256) void pc_dec_fill_slots_kernel(char* __restrict
                                                                 const float* __restrict__ centers) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i < n) ((float*)(slots + (size_t)blockIdx.y * slot_bytes))[i] = centers[0];
+}
+
+// the same for the tiles that start afresh (from[tile] == 0); the slot of a tile that continues keeps what the earlier launch left
+__global__ __launch_bounds__(256) void pc_dec_fill_fresh_slots_kernel(char* __restrict__ slots, size_t slot_bytes, long long n,
+                                                                      const float* __restrict__ centers, const int* __restrict__ from) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (from[blockIdx.y] == 0 && i < n) ((float*)(slots + (size_t)blockIdx.y * slot_bytes))[i] = centers[0];
 }
 
 // slow path of the tile entries: a tile decoded into a buffer of its own -> its place in its volume, as symbols
@@ -1182,7 +1248,7 @@ static int pc_decode_tiles_impl(const uint8_t* bitstreams, const ic_pc_tile_t* t
                                 int k, int L, float resolution, int64_t* symbols, float* q, int* status, int C, void* workspace,
                                 int flags, int channels, int fill_sym, ic_stream_t stream,
                                 const int* layer_ends_host = nullptr, int nlayers = 0, const ic_pc_seg_t* segs_host = nullptr,
-                                const int* tile_channels_host = nullptr) {
+                                const int* tile_channels_host = nullptr, const int* tile_from_host = nullptr) {
     const bool wavefront = (flags & IC_PC_DECODE_WAVEFRONT) != 0;
     hipStream_t st = (hipStream_t)stream;
     char* p = (char*)workspace;
@@ -1212,6 +1278,12 @@ static int pc_decode_tiles_impl(const uint8_t* bitstreams, const ic_pc_tile_t* t
             if (hipMemcpyAsync(limits_dev, tile_channels_host, (size_t)ntiles * sizeof(int), hipMemcpyHostToDevice, st) != hipSuccess) return IC_ERR_ARG;
             a.tile_channels = limits_dev;
         }
+        if (tile_from_host) {         // the resume entry: the layers to continue with behind the limits, then `done`, which no copy touches
+            int* from_dev = (int*)p; p += pc_dec_align((size_t)ntiles * sizeof(int));
+            if (hipMemcpyAsync(from_dev, tile_from_host, (size_t)ntiles * sizeof(int), hipMemcpyHostToDevice, st) != hipSuccess) return IC_ERR_ARG;
+            a.tile_from = from_dev;
+            a.done = (int*)p; p += pc_dec_align((size_t)ntiles * sizeof(int));
+        }
         a.f.d.centers = centers; a.f.d.C = C; a.f.d.L = L; a.f.d.resolution = resolution;
         a.f.w0 = wtab_host[0]; a.f.b0 = wtab_host[1]; a.f.w1 = wtab_host[2]; a.f.b1 = wtab_host[3];
         a.f.w2 = wtab_host[4]; a.f.b2 = wtab_host[5]; a.f.w3 = wtab_host[6]; a.f.b3 = wtab_host[7];
@@ -1222,8 +1294,12 @@ static int pc_decode_tiles_impl(const uint8_t* bitstreams, const ic_pc_tile_t* t
         a.off_c2 = a.off_c1 + pc_dec_align(pc_dec_cache_floats(C, th_max, tw_max, k, 1) * sizeof(float));
         a.symbols = (long long*)symbols; a.q = q; a.status = status;
         const long long nvol = (long long)(C + 4) * (th_max + 8) * (tw_max + 8);
-        hipLaunchKernelGGL(pc_dec_fill_slots_kernel, dim3((unsigned)((nvol + 255) / 256), (unsigned)ntiles), dim3(256), 0, st,
-                           a.slots, a.slot_bytes, nvol, centers);
+        if (tile_from_host)
+            hipLaunchKernelGGL(pc_dec_fill_fresh_slots_kernel, dim3((unsigned)((nvol + 255) / 256), (unsigned)ntiles), dim3(256), 0, st,
+                               a.slots, a.slot_bytes, nvol, centers, a.tile_from);
+        else
+            hipLaunchKernelGGL(pc_dec_fill_slots_kernel, dim3((unsigned)((nvol + 255) / 256), (unsigned)ntiles), dim3(256), 0, st,
+                               a.slots, a.slot_bytes, nvol, centers);
         a.cdec = channels; a.fill = fill_sym;
         const auto full = wavefront ? (symbols ? pc_dec_tiles_batch_kernel<true, true> : pc_dec_tiles_batch_kernel<true, false>)
                                     : (symbols ? pc_dec_tiles_batch_kernel<false, true> : pc_dec_tiles_batch_kernel<false, false>);
@@ -1232,7 +1308,8 @@ static int pc_decode_tiles_impl(const uint8_t* bitstreams, const ic_pc_tile_t* t
         const auto seg_full = symbols ? pc_dec_tiles_batch_kernel<false, true, false, true> : pc_dec_tiles_batch_kernel<false, false, false, true>;
         const auto seg_lim = symbols ? pc_dec_tiles_batch_kernel<false, true, true, true> : pc_dec_tiles_batch_kernel<false, false, true, true>;
         const auto seg_per = symbols ? pc_dec_tiles_batch_kernel<false, true, true, true, true> : pc_dec_tiles_batch_kernel<false, false, true, true, true>;
-        const auto kernel = tile_channels_host ? seg_per : nlayers ? (channels < C ? seg_lim : seg_full) : (channels < C ? lim : full);
+        const auto seg_resume = symbols ? pc_dec_tiles_batch_kernel<false, true, true, true, true, true> : pc_dec_tiles_batch_kernel<false, false, true, true, true, true>;
+        const auto kernel = tile_from_host ? seg_resume : tile_channels_host ? seg_per : nlayers ? (channels < C ? seg_lim : seg_full) : (channels < C ? lim : full);
         hipLaunchKernelGGL(kernel, dim3((unsigned)ntiles), dim3(256), 0, st, a);
         IC_LAUNCH_CHECK();
         return IC_OK;
@@ -1432,4 +1509,53 @@ extern "C" int ic_pc_decode_tiles_batch_layers_pertile_f32(const uint8_t* bitstr
     return pc_decode_tiles_impl(bitstreams, tiles_host, ntiles, th_max, tw_max, volumes_host, nvolumes, wtab_host, centers, k, L,
                                 resolution, symbols, q, status, C, workspace, flags, C, fill_sym, stream,
                                 layer_ends_host, nlayers, segs_host, tile_channels_host);
+}
+
+// ---- layered tiles, continued: every tile from the layer where an earlier call on the same workspace stopped --------------------
+extern "C" size_t ic_pc_decode_tiles_batch_layers_resume_workspace_bytes(int C, int th_max, int tw_max, int ntiles, int nvolumes, int k, int nlayers) {
+    const size_t base = ic_pc_decode_tiles_batch_layers_pertile_workspace_bytes(C, th_max, tw_max, ntiles, nvolumes, k, nlayers);
+    return base ? base + 2 * pc_dec_align((size_t)ntiles * sizeof(int)) : 0;       // from, done
+}
+
+extern "C" int ic_pc_decode_tiles_batch_layers_resume_f32(const uint8_t* bitstreams, long long total_bytes, const ic_pc_tile_t* tiles_host, int ntiles,
+                                                          const ic_pc_volume_t* volumes_host, int nvolumes, const float* const* wtab_host,
+                                                          const float* centers, int k, int L, float resolution, int64_t* symbols, float* q,
+                                                          int* status, int C, void* workspace, size_t workspace_bytes, int flags,
+                                                          ic_stream_t stream, const int* tile_from_layer_host, const int* tile_channels_host,
+                                                          int fill_sym, const int* layer_ends_host, int nlayers, const ic_pc_seg_t* segs_host) {
+    // everything about the six tables is decided here, on the host, before the first HIP call
+    IC_CHECK_ARG(bitstreams && tiles_host && volumes_host && wtab_host && centers && (symbols || q) && status && workspace);
+    IC_CHECK_ARG(tile_from_layer_host && tile_channels_host && layer_ends_host && segs_host);
+    IC_CHECK_ARG(total_bytes >= 0 && ntiles > 0 && nvolumes > 0 && C > 0 && k > 0 && L > 0);
+    IC_CHECK_ARG(fill_sym >= 0 && fill_sym < L);
+    IC_CHECK_ARG(nlayers >= 1 && nlayers <= 16);
+    IC_CHECK_ARG(layer_ends_host[0] >= 1 && layer_ends_host[nlayers - 1] == C);
+    for (int g = 1; g < nlayers; ++g) IC_CHECK_ARG(layer_ends_host[g] > layer_ends_host[g - 1]);
+    for (int n = 0; n < nvolumes; ++n) {
+        const ic_pc_volume_t& v = volumes_host[n];
+        IC_CHECK_ARG(v.h >= 1 && v.w >= 1 && v.symbols_off >= 0 && v.q_off >= 0);
+    }
+    int th_max = 0, tw_max = 0;
+    for (int t = 0; t < ntiles; ++t) {
+        ic_pc_tile_t d = tiles_host[t];
+        const int from = tile_from_layer_host[t], channels = tile_channels_host[t];
+        IC_CHECK_ARG(from >= 0 && from <= nlayers);       // (from == nlayers: the tile is whole, its limit can only be C)
+        const int cfrom = from ? layer_ends_host[from - 1] : 0;
+        IC_CHECK_ARG(channels >= 1 && channels <= C && cfrom <= channels);
+        IC_CHECK_ARG(d.volume >= 0 && d.volume < nvolumes);
+        d.stream_off = 0; d.stream_bytes = 0;             // not read: the segments stand for them
+        IC_CHECK_ARG(pc_tile_ok(d, volumes_host[d.volume].h, volumes_host[d.volume].w, total_bytes, L));
+        // the layers THIS call reads: from `from` on (segment 0 only for a tile that starts afresh), those that begin below the limit
+        for (int g = from; g < nlayers && (g == 0 || layer_ends_host[g - 1] < channels); ++g) {
+            const ic_pc_seg_t& sg = segs_host[(size_t)t * nlayers + g];
+            IC_CHECK_ARG(sg.off >= 0 && sg.nbytes >= 0 && sg.off <= total_bytes && sg.nbytes <= total_bytes - sg.off);
+        }
+        th_max = d.th > th_max ? d.th : th_max;
+        tw_max = d.tw > tw_max ? d.tw : tw_max;
+    }
+    if (L > 16 || k != 24 || flags != 0) return IC_ERR_UNSUPPORTED;
+    if (workspace_bytes < ic_pc_decode_tiles_batch_layers_resume_workspace_bytes(C, th_max, tw_max, ntiles, nvolumes, k, nlayers)) return IC_ERR_WORKSPACE;
+    return pc_decode_tiles_impl(bitstreams, tiles_host, ntiles, th_max, tw_max, volumes_host, nvolumes, wtab_host, centers, k, L,
+                                resolution, symbols, q, status, C, workspace, flags, C, fill_sym, stream,
+                                layer_ends_host, nlayers, segs_host, tile_channels_host, tile_from_layer_host);
 }

@@ -736,6 +736,12 @@ class PredictionNetwork(object):
         res = cut(q) if want == 'q' else cut(sym) if want == 'symbols' else list(zip(cut(q), cut(sym)))
         return (res, damage) if conceal else res
 
+    def open_layers(self, volumes_geometry, th, tw, layer_ends, max_workspace_bytes=1 << 31):
+        """a LayerSession over the volumes [(C,h,w)] cut into th x tw tiles of layered streams (container format 6): the decoder's
+        workspace, symbols and q stay on the device between its advance() calls, so that every layer of every tile is decoded once
+        however often the caller looks at what has arrived (ic_pc_decode_tiles_batch_layers_resume_f32)"""
+        return LayerSession(self, volumes_geometry, th, tw, layer_ends, max_workspace_bytes)
+
     def conceal_fallback(self):
         """the symbol a tile gets that has no intact neighbour: the centre of smallest magnitude (ties: the smallest index), what
         the quantiser emits where the importance map has masked a channel"""
@@ -793,6 +799,134 @@ class PredictionNetwork(object):
 
 
 # -- host-side helpers of the reference's NumPy branch (reference code/probclass.py:268-292,341-351,367-387) --
+
+class LayerSession(object):
+    """decode_tiles_batch(tile_layers=...) that goes on where its last call stopped (PredictionNetwork.open_layers).
+    The session owns, on the device, ONE workspace for all tiles of its volumes (one slot per tile: a chunk's slots would not outlive
+    the chunk, so nothing is chunked -- a ValueError names both sizes if the workspace exceeds max_workspace_bytes), the symbols and q
+    of all volumes, and on the host the number of layers every tile's slot holds.
+    advance(volumes_segments, tile_layers, want): volumes_segments = [(streams, first_syms)] as decode_tiles_batch takes them (a third
+    entry, the shape, is compared with the session's), tile_layers = [per volume [g_t per tile]], the leading layers of every tile
+    that are there now.  One ic_pc_decode_tiles_batch_layers_resume_f32 launch decodes, per tile, the layers between what its slot
+    holds and g_t (codec.resume_plan), one ic_pc_conceal_tiles_channels launch behind it rewrites every (tile, channel) at or above
+    the tile's limit, and the call returns what decode_tiles_batch(tile_layers=...) returns for the same bytes: (per volume q /
+    symbols / (q, symbols), copies, [per volume [(tile, layers_read, channels, reason)]]).
+    Tiles with 0 layers are left out of the launch.  The entry ties a slot to the tile's index in the launch and to the launch's shape
+    (number of tiles, largest tile), so a tile continues only while both are what they were when its slot was written and starts
+    afresh otherwise: in a format-6 file, which stores layer 0 of all tiles first, the launches change shape only while layer 0
+    arrives, when there is nothing to continue.  A tile whose status is not 0 is reported with reason 'decoder' and starts afresh in
+    the next call, as does a tile that is given fewer layers than its slot holds."""
+
+    def __init__(self, pred, volumes_geometry, th, tw, layer_ends, max_workspace_bytes=1 << 31):
+        from .codec import tile_grid, check_layer_ends
+        self.pred = pred
+        self.shapes = [tuple(int(v) for v in shape) for shape in volumes_geometry]
+        if not self.shapes:
+            raise ValueError('a session needs at least one volume')
+        C = self.shapes[0][0]
+        for n, shape in enumerate(self.shapes):
+            if shape[0] != C:
+                raise ValueError('volume {} has {} channels, volume 0 has {}'.format(n, shape[0], C))
+        if pred.pc._k != 24:
+            raise ValueError('layered tiles need a context model of width k = 24, this one has k = {}'.format(pred.pc._k))
+        self.ends = check_layer_ends(layer_ends, C)
+        self.th, self.tw = int(th), int(tw)
+        self.grids = [tile_grid(h, w, self.th, self.tw) for _, h, w in self.shapes]
+        self.vtable, self.offs, self.total = _lib.packed_volume_table(self.shapes)
+        dev = pred.centers.device
+        need = self._need(max(a for grid in self.grids for _, _, a, _ in grid), max(b for grid in self.grids for _, _, _, b in grid),
+                          sum(len(grid) for grid in self.grids))
+        if need > int(max_workspace_bytes):
+            raise ValueError('the session keeps one workspace slot per tile and cannot be chunked: {} tiles need {} bytes, '
+                             'max_workspace_bytes is {}'.format(sum(len(grid) for grid in self.grids), need, int(max_workspace_bytes)))
+        self.ws = torch.zeros(need, dtype=torch.uint8, device=dev)             # zero: no slot holds anything yet
+        self.sym = torch.zeros(self.total, dtype=torch.int64, device=dev)
+        self.q = torch.zeros(self.total, dtype=torch.float32, device=dev)
+        self.done = [[0] * len(grid) for grid in self.grids]                   # layers the tile's slot holds
+        self.place = [[None] * len(grid) for grid in self.grids]               # (index in the launch, shape of the launch) of that slot
+        self.launches = 0
+
+    def _need(self, th_max, tw_max, ntiles):
+        return int(lib.ic_pc_decode_tiles_batch_layers_resume_workspace_bytes(self.shapes[0][0], th_max, tw_max, ntiles, len(self.shapes),
+                                                                              self.pred.pc._k, len(self.ends)))
+
+    def advance(self, volumes_segments, tile_layers, want='q'):
+        from .codec import resume_plan
+        pred, ends, G, C = self.pred, self.ends, len(self.ends), self.shapes[0][0]
+        if want not in ('q', 'symbols', 'both'):
+            raise ValueError("want is 'q', 'symbols' or 'both', got {!r}".format(want))
+        if len(volumes_segments) != len(self.shapes) or len(tile_layers) != len(self.shapes):
+            raise ValueError('{} volumes and {} rows of tile_layers for a session of {} volumes'.format(
+                len(volumes_segments), len(tile_layers), len(self.shapes)))
+        listed = []
+        for n, (volume, grid) in enumerate(zip(volumes_segments, self.grids)):
+            streams, first_syms = volume[0], volume[1]
+            if len(volume) > 2 and tuple(int(v) for v in volume[2]) != self.shapes[n]:
+                raise ValueError('volume {} is {}, the session was opened for {}'.format(n, tuple(volume[2]), self.shapes[n]))
+            if len(streams) != len(grid) or len(first_syms) != len(grid) or len(tile_layers[n]) != len(grid):
+                raise ValueError('volume {}: {} streams, {} first symbols and {} entries of tile_layers for a grid of {} tiles'.format(
+                    n, len(streams), len(first_syms), len(tile_layers[n]), len(grid)))
+            for t, (y0, x0, a, b) in enumerate(grid):
+                g_t = int(tile_layers[n][t])
+                if not 0 <= g_t <= G:
+                    raise ValueError('volume {}, tile {}: {} layers to read of {}'.format(n, t, g_t, G))
+                if g_t == 0:
+                    continue
+                if streams[t] is None or len(streams[t]) != G or any(streams[t][g] is None for g in range(g_t)):
+                    raise ValueError('volume {}, tile {}: {} layers to read need the segments 0 .. {} of {}'.format(n, t, g_t, g_t - 1, G))
+                listed.append((n, t, y0, x0, a, b, int(first_syms[t]), g_t, streams[t]))
+        dev = pred.centers.device
+        centers = pred.centers.contiguous().float()
+        for n, grid in enumerate(self.grids):                                  # a tile that holds nothing now has no slot to continue in
+            for t in range(len(grid)):
+                if int(tile_layers[n][t]) == 0:
+                    self.done[n][t], self.place[n][t] = 0, None
+        failed = set()
+        if listed:
+            shape = (len(listed), max(v[4] for v in listed), max(v[5] for v in listed))
+            tiles, segs, blobs, pos, froms, limits = [], [], [], 0, [], []
+            for i, (n, t, y0, x0, a, b, first, g_t, streams) in enumerate(listed):
+                have = self.done[n][t] if self.place[n][t] == (i, shape) else 0
+                g_from, channels = resume_plan(have, g_t, ends)
+                tiles.append((y0, x0, a, b, 0, 0, first, n))
+                froms.append(g_from)
+                limits.append(channels)
+                for g in range(G):
+                    if g_from <= g < g_t:
+                        segs.append((pos, len(streams[g])))
+                        blobs.append(bytes(streams[g]))
+                        pos += len(streams[g])
+                    else:
+                        segs.append((0, 0))
+            need = self._need(shape[1], shape[2], shape[0])
+            assert need <= self.ws.numel()
+            table, seg_table = _lib.tile_table(tiles), _lib.seg_table(segs)
+            host_ends, host_from, host_limits = (ctypes.c_int * G)(*ends), (ctypes.c_int * len(froms))(*froms), (ctypes.c_int * len(limits))(*limits)
+            data = torch.frombuffer(bytearray(b''.join(blobs)) or bytearray(1), dtype=torch.uint8).to(dev)
+            status = torch.zeros(len(tiles), dtype=torch.int32, device=dev)
+            check(lib.ic_pc_decode_tiles_batch_layers_resume_f32(
+                ptr(data), pos, table, len(tiles), self.vtable, len(self.shapes), pred.pc._tab, ptr(centers), pred.pc._k, pred.pc.L,
+                pred.freqs_resolution, ptr(self.sym), ptr(self.q), ptr(status), C, ptr(self.ws), need, 0, _lib.current_stream(dev),
+                host_from, host_limits, pred.conceal_fallback(), host_ends, G, seg_table), 'ic_pc_decode_tiles_batch_layers_resume_f32')
+            self.launches += 1
+            for (n, t, _, _, _, _, _, g_t, _), i, st in zip(listed, range(len(listed)), status.tolist()):      # (the host waits here)
+                if st != 0:
+                    failed.add((n, t))
+                    self.done[n][t], self.place[n][t] = 0, None
+                else:
+                    self.done[n][t], self.place[n][t] = g_t, (i, shape)
+        held, have = [], []
+        for n, grid in enumerate(self.grids):
+            row = [0 if (n, t) in failed or int(tile_layers[n][t]) == 0 else ends[int(tile_layers[n][t]) - 1] for t in range(len(grid))]
+            have.append(row)
+            held.append([(t, 0 if (n, t) in failed else int(tile_layers[n][t]), row[t], 'decoder' if (n, t) in failed else None)
+                         for t in range(len(grid)) if row[t] < C])
+        if any(held):
+            pred._conceal_channels(self.sym, self.q, self.shapes, self.grids, self.vtable, have, self.th, self.tw, centers)
+        cut = lambda buf: [buf[o:o + c * h * w].view(c, h, w).clone() for (c, h, w), o in zip(self.shapes, self.offs)]
+        res = cut(self.q) if want == 'q' else cut(self.sym) if want == 'symbols' else list(zip(cut(self.q), cut(self.sym)))
+        return res, held
+
 
 def pad_for_probclass3d(x, context_size, pad_value=0, learn_pad_var=False):
     """numpy CHW / NCHW or torch NCHW: constant-pad depth (front only), H and W by context_size // 2."""

@@ -392,6 +392,42 @@ int ic_pc_decode_tiles_batch_layers_pertile_f32(const uint8_t* bitstreams, long 
                                                 int* status, int C, void* workspace, size_t workspace_bytes, int flags,
                                                 ic_stream_t stream, const int* tile_channels_host, int fill_sym,
                                                 const int* layer_ends_host, int nlayers, const ic_pc_seg_t* segs_host);
+/* Layered tiles, CONTINUED: every tile from the layer where an earlier call on the same workspace stopped (codec.py, stream: a picture
+ * redrawn after each layer of a file that is still arriving decodes every plane once).  When a sweep with a limit ends, the tile's slot
+ * of the workspace holds all that the next planes need -- the padded volume and the three activation caches up to the limit -- and the
+ * coder starts afresh at every layer, so no coder state has to survive.  The parameters of ic_pc_decode_tiles_batch_layers_pertile_f32
+ * with one more table in front of the limits:
+ *   tile_from_layer_host: HOST array, one entry per listed tile, read before the call returns: the layer tile t continues with,
+ *     0 .. nlayers (else IC_ERR_ARG).  0: the tile starts afresh, exactly as in the per-tile entry.  g > 0: the tile holds the
+ *     channels below cfrom = layer_ends[g - 1] and this call decodes [cfrom, tile_channels[t]).  g == nlayers says that the tile is
+ *     whole (cfrom = C): nothing is decoded and nothing of it is written.
+ *   tile_channels_host[t]: in 1 .. C and at least cfrom (else IC_ERR_ARG); equal to cfrom: nothing is decoded, the fill is written.
+ *   segs_host: checked per tile for the layers g >= from[t] that begin below tile_channels[t]; a tile that continues does not need
+ *     segment 0 and no row below from[t] is checked or read.
+ *   symbols / q: of a tile that continues, the channels below cfrom are NOT written -- they are the caller's, from the earlier call;
+ *     [cfrom, limit) are decoded, [limit, C) get fill_sym / centers[fill_sym].  A tile that starts afresh is written wholly.
+ *   status[t]: 0, or 1 (the coder's error flag, kept over the cuts this call made), or
+ *     2: THE WORKSPACE DOES NOT HOLD THIS TILE DECODED UP TO from[t].  Nothing of the tile was read or written, symbols / q included.
+ *   The contract of a tile with from[t] > 0: the same workspace, the same seven shape arguments (C, largest th, largest tw -- taken
+ *     from the tile table as everywhere --, ntiles, nvolumes, k, nlayers), the same tile at the same index t, and an earlier call of
+ *     THIS entry on the same stream that ended tile t at exactly cfrom with status 0.  The layout of the workspace is a function of
+ *     the seven shape arguments alone, so the slots lie where they lay.  The entry guards the contract with one word per tile in the
+ *     workspace (`done`: the channels the slot holds, -1 behind a coder error), which no table upload touches and only the kernel
+ *     writes; a tile that starts afresh does not read it.  The word can only tell what the kernel wrote there: before its first use
+ *     with from[t] > 0 a workspace must have been zero-filled once or have seen tile index t decoded by this entry (0 and -1 match no
+ *     cfrom).  What the guard cannot see -- another tile decoded at the same index, other weights -- is the caller's to keep.
+ *   With every from[t] == 0 the result is that of the per-tile entry, bit for bit.  No new synchronisation: a work-group reads its own
+ *     slot, written by itself or by an earlier launch on the same stream.
+ *   k != 24, flags != 0, L > 16: IC_ERR_UNSUPPORTED; too small a workspace IC_ERR_WORKSPACE.  All decided on the host; a refused call
+ *   writes nothing.  workspace: ic_pc_decode_tiles_batch_layers_resume_workspace_bytes(the arguments of the layers entry's): the per-tile
+ *   entry's size and two aligned int[ntiles] tables. */
+size_t ic_pc_decode_tiles_batch_layers_resume_workspace_bytes(int C, int th_max, int tw_max, int ntiles, int nvolumes, int k, int nlayers);
+int ic_pc_decode_tiles_batch_layers_resume_f32(const uint8_t* bitstreams, long long total_bytes, const ic_pc_tile_t* tiles_host, int ntiles,
+                                               const ic_pc_volume_t* volumes_host, int nvolumes, const float* const* wtab_host,
+                                               const float* centers, int k, int L, float resolution, int64_t* symbols, float* q,
+                                               int* status, int C, void* workspace, size_t workspace_bytes, int flags,
+                                               ic_stream_t stream, const int* tile_from_layer_host, const int* tile_channels_host,
+                                               int fill_sym, const int* layer_ends_host, int nlayers, const ic_pc_seg_t* segs_host);
 /* Concealment: what stands in the volumes where a tile could not be decoded (a damaged file; codec.py, salvage).  Stated on symbols,
  * so exact: for a damaged tile T and a channel c the candidates are the symbols of channel c directly above T's top row, below its
  * bottom row, left of its left column and right of its right column (no corners) that lie inside the volume and in a tile that
