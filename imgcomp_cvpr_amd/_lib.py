@@ -171,6 +171,14 @@ PROTOTYPES = {
     'ic_pc_decode_tiles_batch_layers_pertile_f32': (c_int, [c_void_p, c_longlong, c_void_p, c_int, c_void_p, c_int, POINTER(c_void_p), c_void_p,
                                                             c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_size_t,
                                                             c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p]),
+    'ic_pc_decode_tiles_batch_fronts_workspace_bytes': (c_size_t, [c_int] * 7),
+    'ic_pc_decode_tiles_batch_fronts_f32': (c_int, [c_void_p, c_longlong, c_void_p, c_int, c_void_p, c_int, POINTER(c_void_p), c_void_p,
+                                                    c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_size_t,
+                                                    c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p]),
+    'ic_pc_decode_tiles_batch_fronts_pertile_workspace_bytes': (c_size_t, [c_int] * 7),
+    'ic_pc_decode_tiles_batch_fronts_pertile_f32': (c_int, [c_void_p, c_longlong, c_void_p, c_int, c_void_p, c_int, POINTER(c_void_p), c_void_p,
+                                                            c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_size_t,
+                                                            c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p]),
     'ic_pc_decode_tiles_batch_layers_resume_workspace_bytes': (c_size_t, [c_int] * 7),
     'ic_pc_decode_tiles_batch_layers_resume_f32': (c_int, [c_void_p, c_longlong, c_void_p, c_int, c_void_p, c_int, POINTER(c_void_p), c_void_p,
                                                            c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_size_t,

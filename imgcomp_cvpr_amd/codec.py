@@ -1,9 +1,10 @@
 """Image codec: an image to a self-describing file and back.
 
     python -m imgcomp_cvpr_amd.codec compress   IN.png  OUT.icf [--ae_config cvpr/low] [--pc_config cvpr/res_shallow] [--weights synthetic|FILE.npz|CKPT]
-                                                                [--tile PIXELS [--checked | --wavefront | --layers a,b,.. | --progressive]]
+                                                                [--tile PIXELS [--checked | --wavefront | --layers a,b,.. | --progressive |
+                                                                                --front-layers a,b,.. | --front-progressive]]
     python -m imgcomp_cvpr_amd.codec decompress IN.icf  OUT.png [same options] [--salvage | --channels K | --partial | --recover]
-    python -m imgcomp_cvpr_amd.codec compress-dir   IN_DIR OUT_DIR [--tile PIXELS [--checked | --wavefront | --layers a,b,.. | --progressive]] [--batch N]   every *.png / *.jpg -> OUT_DIR/<stem>.icf
+    python -m imgcomp_cvpr_amd.codec compress-dir   IN_DIR OUT_DIR [--tile PIXELS [same choices]] [--batch N]   every *.png / *.jpg -> OUT_DIR/<stem>.icf
     python -m imgcomp_cvpr_amd.codec decompress-dir IN_DIR OUT_DIR [--batch N] [--salvage | --channels K | --partial | --recover]    every *.icf -> OUT_DIR/<stem>.png
     python -m imgcomp_cvpr_amd.codec verify PATH [PATH ...]         files or directories of *.icf: the checksums, without model or device
     python -m imgcomp_cvpr_amd.codec stream IN.icf OUT_DIR [model options] [--chunk BYTES]    a format-6 file fed chunk by chunk, a picture per gained layer
@@ -102,6 +103,17 @@ a channel limit per tile (ic_pc_decode_tiles_batch_layers_pertile_f32); then eve
 from the neighbouring tiles that hold that channel (ic_pc_conceal_tiles_channels: the most frequent symbol on the four edges, ties
 to the smallest), or with the fill symbol where no neighbour holds it -- if all tiles stop at one layer, that is --partial's image.
 The report names every tile with fewer than all layers.  --partial and --salvage read as before.
+--tile --front-layers a,b,.. / --tile --front-progressive (Codec(tile=(th, tw), front_layers=[..] | 'default')): format 8, "front-layered
+tiles" -- the bytes of format 6 (G, ends, first symbols, a length and a CRC per segment, header CRC, segments layer first, file CRC) with
+version 8 (7 is not used and is refused); only the meaning of a segment differs, as format 5 reuses format 4's layout.  A tile's
+symbols are coded in the wavefront order of format 5 and that stream is cut at FRONTS, not at channel planes (which are no prefix of
+it): for a tile of extent (C, th', tw'), segment g holds the symbols of wavefront_order(C, th', tw') with index in [n_{g-1}, n_g),
+n_g = wavefront_prefix_count(C, th', tw', e_g), n_{-1} = 0 (front_layer_cuts; index 0 is the uncoded first symbol; edge tiles have their
+own cuts; e_0 = 1 on a 1 x 1 tile gives an empty segment, the one byte 0x80).  These are the symbols a --channels e_g decode of a
+format-5 file steps through, so the bytes [0, layer_prefix_bytes(g)) decode as that preview a front at a time
+(ic_pc_decode_tiles_batch_fronts_f32 restarts the coder at each cut).  The price: a layer's prefix also carries the symbols of later
+channels that share its fronts, so the early prefixes are longer than format 6's; nothing is coded twice.  decompress, --channels,
+--partial, --recover and verify read it as they read format 6; --salvage and stream do not.
 stream (Codec.open_stream -> StreamDecoder): a format-6 file that is still arriving.  feed(chunk) takes the bytes as they come, image()
 gives recover's picture and report of the bytes so far -- but the decoder goes on where the last image() stopped: the session
 (PredictionNetwork.open_layers) keeps every tile's decoder workspace on the device and ic_pc_decode_tiles_batch_layers_resume_f32
@@ -139,9 +151,12 @@ CheckedContainer = namedtuple('CheckedContainer', TiledContainer._fields + ('str
 FORMAT_VERSION_WAVEFRONT = 5                                         # the layout of 4, the streams in wavefront order
 WavefrontContainer = namedtuple('WavefrontContainer', CheckedContainer._fields)
 FORMAT_VERSION_LAYERED = 6                                           # raster tiles cut into layers, stored layer first
+FORMAT_VERSION_FRONTS = 8                                            # wavefront tiles cut into layers at fronts; 7 is not used
+_LAYERED_VERSIONS = (FORMAT_VERSION_LAYERED, FORMAT_VERSION_FRONTS)  # one layout, one container type: `version` tells them apart
 MAX_LAYERS = 16
 # streams[t] is tile t's list of G segments (what decode_tiles_batch(layer_ends=...) takes), segments[g][t] the same bytes layer-major
-# (the file's order), segment_crcs[g][t] their CRCs; a segment that parse_partial found incomplete is None in both views
+# (the file's order), segment_crcs[g][t] their CRCs; a segment that parse_partial found incomplete is None in both views.  version is
+# 6 (segments cut at channel planes of the raster order) or 8 (cut at fronts of the wavefront order, front_layer_cuts)
 LayeredContainer = namedtuple('LayeredContainer', TiledContainer._fields + ('layer_ends', 'segments', 'segment_crcs'))
 PartialReport = namedtuple('PartialReport', ['layers_total', 'layers_decoded', 'channels', 'file_crc_ok'])
 _TILED = (TiledContainer, CheckedContainer, WavefrontContainer, LayeredContainer)
@@ -388,12 +403,30 @@ def check_layer_ends(layer_ends, C):
     return ends
 
 
-def build_layered_container(ae_name, pc_name, H, W, C, h, w, L, resolution, fingerprint, th, tw, first_syms, layer_ends, segments):
+def front_layer_cuts(C, th, tw, layer_ends):
+    """the cuts of format 8 for a (C, th, tw) tile: [n_0 < n_1 < .. < n_{G-1} = C th tw], n_g = wavefront_prefix_count(C, th, tw, e_g).
+    Segment g holds the symbols of wavefront_order(C, th, tw) with index in [n_{g-1}, n_g), n_{-1} = 0 (index 0 is the uncoded first
+    symbol): all symbols up to the front of the last symbol of channel e_g - 1, so segments 0 .. g hold every symbol of the channels
+    below e_g -- and the symbols of later channels that share those fronts.  e_0 = 1 on a 1 x 1 tile: n_0 = 1, an empty segment 0."""
+    ends = check_layer_ends(layer_ends, C)
+    return [wavefront_prefix_count(C, th, tw, e) for e in ends]
+
+
+def build_front_layered_container(ae_name, pc_name, H, W, C, h, w, L, resolution, fingerprint, th, tw, first_syms, layer_ends, segments):
+    """format 8: the bytes of format 6 with version 8; segments[g][t] codes tile t's symbols of wavefront_order(C, th', tw') between
+    the cuts front_layer_cuts(C, th', tw', layer_ends)[g - 1] and [g]."""
+    return build_layered_container(ae_name, pc_name, H, W, C, h, w, L, resolution, fingerprint, th, tw, first_syms, layer_ends, segments,
+                                   version=FORMAT_VERSION_FRONTS)
+
+
+def build_layered_container(ae_name, pc_name, H, W, C, h, w, L, resolution, fingerprint, th, tw, first_syms, layer_ends, segments,
+                            version=FORMAT_VERSION_LAYERED):
     """format 6: segments[g][t] = the bytes of layer g of tile t (tiles in the order of tile_grid(h, w, th, tw))."""
+    assert version in _LAYERED_VERSIONS
     ends = check_layer_ends(layer_ends, C)
     segments = [[bytes(b) for b in layer] for layer in segments]
     assert len(segments) == len(ends) and all(len(layer) == len(first_syms) for layer in segments)
-    front = _tiled_head(FORMAT_VERSION_LAYERED, ae_name, pc_name, H, W, C, h, w, L, resolution, fingerprint, th, tw, [b''] * len(first_syms), 0)[:-8]
+    front = _tiled_head(version, ae_name, pc_name, H, W, C, h, w, L, resolution, fingerprint, th, tw, [b''] * len(first_syms), 0)[:-8]
     flat = [b for layer in segments for b in layer]
     head = b''.join([front, struct.pack('<H', len(ends)), struct.pack('<{}H'.format(len(ends)), *ends),
                      struct.pack('<{}H'.format(len(first_syms)), *first_syms)] +
@@ -443,7 +476,7 @@ def parse_container(data):
     if data[:4] != MAGIC:
         raise ValueError('wrong magic {!r}: not a codec file (expected {!r})'.format(data[:4], MAGIC))
     version, = struct.unpack('<H', data[4:6])
-    if version not in (FORMAT_VERSION, FORMAT_VERSION_TILED, FORMAT_VERSION_CHECKED, FORMAT_VERSION_WAVEFRONT, FORMAT_VERSION_LAYERED):
+    if version not in (FORMAT_VERSION, FORMAT_VERSION_TILED, FORMAT_VERSION_CHECKED, FORMAT_VERSION_WAVEFRONT) + _LAYERED_VERSIONS:
         raise ValueError(_unsupported(version))
     stored, = struct.unpack('<I', data[-4:])
     actual = zlib.crc32(data[:-4]) & 0xffffffff
@@ -451,8 +484,8 @@ def parse_container(data):
         raise ValueError('CRC mismatch: file says {:08x}, content gives {:08x} (corrupt or truncated file)'.format(stored, actual))
     r = _Reader(data[:-4])
     ae_name, pc_name, H, W, C, h, w = _parse_front(r)
-    if version == FORMAT_VERSION_LAYERED:
-        return _parse_layered(r, ae_name, pc_name, H, W, C, h, w, strict=True)[0]
+    if version in _LAYERED_VERSIONS:
+        return _parse_layered(r, ae_name, pc_name, H, W, C, h, w, strict=True, version=version)[0]
     if version != FORMAT_VERSION:
         return _parse_tiled(r, version, ae_name, pc_name, H, W, C, h, w)
     L, first_sym = r.unpack('<HH', 'L and first symbol')
@@ -467,8 +500,8 @@ def parse_container(data):
 
 def _unsupported(version):
     return ('unsupported format version {} (this codec reads versions {}, {} and {}) and the wavefront version {} and the layered '
-            'version {}'.format(version, FORMAT_VERSION, FORMAT_VERSION_TILED, FORMAT_VERSION_CHECKED, FORMAT_VERSION_WAVEFRONT,
-                                FORMAT_VERSION_LAYERED))
+            'version {} and the front-layered version {}'.format(version, FORMAT_VERSION, FORMAT_VERSION_TILED, FORMAT_VERSION_CHECKED,
+                                                                 FORMAT_VERSION_WAVEFRONT, FORMAT_VERSION_LAYERED, FORMAT_VERSION_FRONTS))
 
 
 def _parse_front(r):
@@ -554,8 +587,8 @@ def _parse_tiled(r, version, ae_name, pc_name, H, W, C, h, w):
     return cls(version, ae_name, pc_name, H, W, C, h, w, L, resolution, fingerprint, th, tw, first_syms, streams, payload, crcs)
 
 
-def _parse_layered(r, ae_name, pc_name, H, W, C, h, w, strict):
-    """the rest of a format-6 file after the symbol volume shape -> (LayeredContainer, layers_complete, payload complete).
+def _parse_layered(r, ae_name, pc_name, H, W, C, h, w, strict, version=FORMAT_VERSION_LAYERED):
+    """the rest of a format-6 / format-8 file after the symbol volume shape -> (LayeredContainer, layers_complete, payload complete).
     The header: every length against the bytes that remain, then its own CRC.  strict (parse_container; the CRC over the file has
     been checked): the payload length must equal what is left and every segment must match its CRC.  Not strict (parse_partial): the
     payload is what arrived of it; a segment that is not whole or fails its CRC is None."""
@@ -602,7 +635,7 @@ def _parse_layered(r, ae_name, pc_name, H, W, C, h, w, strict):
             complete = g + 1
         segments.append(layer)
     streams = [[segments[g][t] for g in range(G)] for t in range(ntiles)]
-    c = LayeredContainer(FORMAT_VERSION_LAYERED, ae_name, pc_name, H, W, C, h, w, L, resolution, fingerprint, th, tw, first_syms, streams,
+    c = LayeredContainer(version, ae_name, pc_name, H, W, C, h, w, L, resolution, fingerprint, th, tw, first_syms, streams,
                          payload, ends, segments, crcs)
     return c, complete, len(payload) == n
 
@@ -654,7 +687,7 @@ def _partial_open(data):
     if data[:4] != MAGIC:
         raise ValueError('header damaged: wrong magic {!r}: not a codec file (expected {!r})'.format(data[:4], MAGIC))
     version, = struct.unpack('<H', data[4:6])
-    if version != FORMAT_VERSION_LAYERED:
+    if version not in _LAYERED_VERSIONS:
         raise ValueError('header damaged: format version {} is not the layered version {}: only a layered file (--tile --layers / '
                          '--progressive) decodes from a prefix'.format(version, FORMAT_VERSION_LAYERED))
     return _Reader(data), version
@@ -667,10 +700,10 @@ def parse_partial(data):
     segment that is not whole or fails its CRC is None in the container; file_crc_ok says whether the CRC over the file is there
     and right.  Bytes behind the declared end are ignored."""
     data = bytes(data)
-    r, _ = _partial_open(data)
+    r, version = _partial_open(data)
     try:
         ae_name, pc_name, H, W, C, h, w = _parse_front(r)
-        c, complete, whole = _parse_layered(r, ae_name, pc_name, H, W, C, h, w, strict=False)
+        c, complete, whole = _parse_layered(r, ae_name, pc_name, H, W, C, h, w, strict=False, version=version)
     except ValueError as e:
         raise ValueError('header damaged: nothing can be decoded ({})'.format(e))
     end = _prefix_from_bytes(data, len(c.layer_ends))       # where the CRC over the file stands
@@ -739,6 +772,9 @@ def stream_header_bytes(data):
     if len(data) < 6:
         return None
     version, = struct.unpack('<H', data[4:6])
+    if version == FORMAT_VERSION_FRONTS:
+        raise ValueError('format version {} (front-layered tiles) is not streamed: a front-ordered decode is not resumed yet; decompress '
+                         '--recover (Codec.recover) reads what has arrived of such a file'.format(version))
     if version != FORMAT_VERSION_LAYERED:
         parse_recover(data + bytes(_MIN_SIZE))            # another format: its refusal, whatever the length so far
         raise ValueError('header damaged: format version {} is not the layered version {}'.format(version, FORMAT_VERSION_LAYERED))
@@ -776,7 +812,7 @@ def parse_salvage(data):
     if version in (FORMAT_VERSION, FORMAT_VERSION_TILED):
         raise ValueError('format version {} has nothing to salvage with: one CRC over the whole file, none per tile (only version {}, '
                          'written with --tile --checked, can be salvaged)'.format(version, FORMAT_VERSION_CHECKED))
-    if version == FORMAT_VERSION_LAYERED:
+    if version in _LAYERED_VERSIONS:
         raise ValueError('format version {} (layered tiles) is not salvaged: salvage of layered files is out of scope; '
                          'decompress --partial (Codec.decompress_partial) reads the complete layers of a cut file'.format(version))
     if version not in _WITH_CRCS:
@@ -845,10 +881,14 @@ class Codec(object):
     sequence of layer ends e_0 < .. < e_{G-1} = C writes format 6, every tile's raster stream cut into G segments and stored layer
     first, so that a prefix of the file decodes (decompress_partial); needs a tile extent, not with order='wavefront', carries the
     checksums whatever `checked` says; refused, like the wavefront order, for a context model of another width than k = 24.
+    front_layers: None as above; 'default' or a sequence of layer ends writes format 8, the layout of format 6 with every tile's
+    WAVEFRONT-ordered stream cut at fronts (front_layer_cuts): decoded a front at a time like format 5, read from a prefix like
+    format 6.  Needs a tile extent; not with layers or order='wavefront' (it is neither format 6 nor format 5: the order is implied);
+    refused for a model that either of those refuses.
     Reading needs no option: the file's version decides."""
 
     def __init__(self, ae_config, pc_config, weights, device='cuda', plan_flags=0, device_encode=True, tile=None, checked=False,
-                 order='raster', layers=None):
+                 order='raster', layers=None, front_layers=None):
         if tile is not None:
             tile = (int(tile[0]), int(tile[1]))
             if not (1 <= tile[0] <= 0xffff and 1 <= tile[1] <= 0xffff):
@@ -859,6 +899,8 @@ class Codec(object):
             raise ValueError("order is 'raster' or 'wavefront', got {!r}".format(order))
         if order == 'wavefront' and tile is None:
             raise ValueError("order='wavefront' needs a tile extent: format 5 is a tiled format")
+        if front_layers is not None:
+            self._check_front_layers(front_layers, tile, order, layers)
         if layers is not None:
             if tile is None:
                 raise ValueError('layers needs a tile extent: format 6 is a tiled format')
@@ -867,7 +909,9 @@ class Codec(object):
             layers = layers if isinstance(layers, str) else check_layer_ends(layers, ae_config.num_chan_bn)
             if isinstance(layers, str) and layers != 'default':
                 raise ValueError("layers is None, 'default' or a sequence of layer ends, got {!r}".format(layers))
-        self.tile, self.checked, self.order, self.layers = tile, bool(checked), order, layers
+        if front_layers is not None:
+            front_layers = front_layers if isinstance(front_layers, str) else check_layer_ends(front_layers, ae_config.num_chan_bn)
+        self.tile, self.checked, self.order, self.layers, self.front_layers = tile, bool(checked), order, layers, front_layers
         import torch
         from . import autoencoder, probclass
         self.device = torch.device(device)
@@ -886,6 +930,8 @@ class Codec(object):
                                                      'width k = 24, this one has k = {}'.format(k))
         if layers is not None and self.layered_refusal:
             raise ValueError(self.layered_refusal)
+        if front_layers is not None and (self.wavefront_refusal or self.layered_refusal):
+            raise ValueError(self.wavefront_refusal or self.layered_refusal)
         self.pred = probclass.PredictionNetwork(self.pc, pc_config, self.ae.get_centers_variable())
         self.ae_name, self.pc_name = config_name(ae_config), config_name(pc_config)
         self.factor = int(self.ae.get_subsampling_factor())
@@ -924,10 +970,39 @@ class Codec(object):
         ac.encode_sequence(flat[1:], freqs[1:], out)
         return out.kept, int(flat[0])
 
+    @staticmethod
+    def _check_front_layers(front_layers, tile, order, layers):
+        if tile is None:
+            raise ValueError('front_layers needs a tile extent: format 8 is a tiled format')
+        if layers is not None:
+            raise ValueError('front_layers does not go with layers: the one cuts the wavefront order at fronts (format 8), the other the '
+                             'raster order at channel planes (format 6)')
+        if order == 'wavefront':
+            raise ValueError("front_layers does not go with order='wavefront': format 8 implies the order, order='wavefront' writes the "
+                             "unlayered format 5")
+        if isinstance(front_layers, str) and front_layers != 'default':
+            raise ValueError("front_layers is None, 'default' or a sequence of layer ends, got {!r}".format(front_layers))
+
+    def _front_ends(self):
+        """the layer ends of the format-8 file compress writes, or None (the attributes may have been set after construction, as main does)"""
+        if getattr(self, 'front_layers', None) is None:
+            return None
+        self._check_front_layers(self.front_layers, self.tile, self.order, self.layers)
+        if self.wavefront_refusal or self.layered_refusal:
+            raise ValueError(self.wavefront_refusal or self.layered_refusal)
+        return default_layer_ends(self.C) if isinstance(self.front_layers, str) else check_layer_ends(self.front_layers, self.C)
+
     def compress(self, img_hwc_uint8):
         enc, (H, W) = self.encode_symbols(img_hwc_uint8)
         sym = enc.symbols[0]
         C, h, w = (int(v) for v in sym.shape)
+        fronts = self._front_ends()
+        if fronts is not None:
+            th, tw = self.tile
+            coded = self.pred.encode_tiles(sym, th, tw, front_ends=fronts)
+            return build_front_layered_container(self.ae_name, self.pc_name, H, W, C, h, w, self.L, self.pred.freqs_resolution,
+                                                 self.fingerprint, th, tw, [f for _, f in coded], fronts,
+                                                 [[segs[g] for segs, _ in coded] for g in range(len(fronts))])
         ends = self._layer_ends()
         if ends is not None:
             th, tw = self.tile
@@ -1002,7 +1077,9 @@ class Codec(object):
         if isinstance(c, WavefrontContainer) and self.wavefront_refusal:
             raise ValueError('format 5 cannot be read with this model: {}'.format(self.wavefront_refusal))
         if isinstance(c, LayeredContainer) and self.layered_refusal:
-            raise ValueError('format 6 cannot be read with this model: {}'.format(self.layered_refusal))
+            raise ValueError('format {} cannot be read with this model: {}'.format(c.version, self.layered_refusal))
+        if isinstance(c, LayeredContainer) and c.version == FORMAT_VERSION_FRONTS and self.wavefront_refusal:
+            raise ValueError('format {} cannot be read with this model: {}'.format(c.version, self.wavefront_refusal))
         for first_sym in (c.first_syms if isinstance(c, _TILED) else [c.first_sym]):
             if first_sym >= c.L:
                 raise ValueError('header mismatch: first symbol {} is not below L = {}'.format(first_sym, c.L))
@@ -1019,7 +1096,7 @@ class Codec(object):
         try:
             if isinstance(c, LayeredContainer):          # a batch of one: the layers are arguments of the batch entry
                 sym = self.pred.decode_tiles_batch([(c.streams, c.first_syms, (c.C, c.h, c.w))], c.th, c.tw, want='symbols',
-                                                   channels=channels, layer_ends=c.layer_ends)[0].cpu().numpy()
+                                                   channels=channels, **_ends_kw(c))[0].cpu().numpy()
             elif isinstance(c, WavefrontContainer):      # a batch of one: the order is a flag of the batch entry
                 sym = self.pred.decode_tiles_batch([(c.streams, c.first_syms, (c.C, c.h, c.w))], c.th, c.tw, want='symbols',
                                                    order='wavefront', channels=channels)[0].cpu().numpy()
@@ -1042,7 +1119,7 @@ class Codec(object):
         channels = c.layer_ends[complete - 1]
         try:
             sym = self.pred.decode_tiles_batch([(c.streams, c.first_syms, (c.C, c.h, c.w))], c.th, c.tw, want='symbols',
-                                               channels=channels, layer_ends=c.layer_ends)[0].cpu().numpy()
+                                               channels=channels, **_ends_kw(c))[0].cpu().numpy()
         except ValueError as e:
             raise ValueError('decoder status is not 0: {}'.format(e))
         return self._image(sym, c), PartialReport(len(c.layer_ends), complete, channels, file_crc_ok)
@@ -1117,14 +1194,16 @@ class Codec(object):
             xs.append(torch.as_tensor(np.ascontiguousarray(np.transpose(padded, (2, 0, 1)))[None]).to(self.device).float())
         syms = self._in_flight(xs, lambda ae, x: ae.encode(x, is_training=False).symbols[0])
         out = [None] * len(syms)
-        ends = self._layer_ends()
+        fronts = self._front_ends()
+        ends = fronts if fronts is not None else self._layer_ends()
         if ends is not None:
             th, tw = self.tile
-            for i, coded in enumerate(self.pred.encode_tiles_batch(syms, th, tw, layer_ends=ends)):
+            build = build_layered_container if fronts is None else build_front_layered_container
+            for i, coded in enumerate(self.pred.encode_tiles_batch(syms, th, tw, **({'layer_ends': ends} if fronts is None else {'front_ends': ends}))):
                 C, h, w = (int(v) for v in syms[i].shape)
-                out[i] = build_layered_container(self.ae_name, self.pc_name, sizes[i][0], sizes[i][1], C, h, w, self.L,
-                                                 self.pred.freqs_resolution, self.fingerprint, th, tw, [f for _, f in coded], ends,
-                                                 [[segs[g] for segs, _ in coded] for g in range(len(ends))])
+                out[i] = build(self.ae_name, self.pc_name, sizes[i][0], sizes[i][1], C, h, w, self.L,
+                               self.pred.freqs_resolution, self.fingerprint, th, tw, [f for _, f in coded], ends,
+                               [[segs[g] for segs, _ in coded] for g in range(len(ends))])
             return out
         if self.tile is not None:
             th, tw = self.tile
@@ -1157,7 +1236,8 @@ class Codec(object):
         nothing has reached the device.  The format-2 / format-4 files of the most frequent tile extent are decoded together
         (decode_tiles_batch: the tiles of all of them in one launch per workspace chunk, the centres q staying on the device) and
         go through the decoder up to IN_FLIGHT at a time; so are, in launches of their own (the order is a flag of the call), the
-        format-5 files of their most frequent extent, and the format-6 files of their most frequent (tile extent, layer ends);
+        format-5 files of their most frequent extent, and the format-6 and the format-8 files of their most frequent (tile extent,
+        layer ends) each;
         format-1 files and the other tiled files take the single-file path."""
         import torch
         channels = check_channels(channels, self.C)
@@ -1170,10 +1250,11 @@ class Codec(object):
                 raise ValueError('file {}: {}'.format(i, e))
             heads.append(c)
         out = [None] * len(datas)
-        kind = lambda c: 'layered' if isinstance(c, LayeredContainer) else 'wavefront' if isinstance(c, WavefrontContainer) else 'raster'
-        for order in ('raster', 'wavefront', 'layered'):
+        kind = lambda c: (('fronts' if c.version == FORMAT_VERSION_FRONTS else 'layered') if isinstance(c, LayeredContainer)
+                          else 'wavefront' if isinstance(c, WavefrontContainer) else 'raster')
+        for order in ('raster', 'wavefront', 'layered', 'fronts'):
             mine = [i for i, c in enumerate(heads) if isinstance(c, _TILED) and kind(c) == order]
-            extents = [(heads[i].th, heads[i].tw) + (tuple(heads[i].layer_ends) if order == 'layered' else ()) for i in mine]
+            extents = [(heads[i].th, heads[i].tw) + (tuple(heads[i].layer_ends) if order in ('layered', 'fronts') else ()) for i in mine]
             major = max(sorted(set(extents)), key=extents.count) if extents else None
             together = [i for i, e in zip(mine, extents) if e == major]
             if not together:
@@ -1182,7 +1263,8 @@ class Codec(object):
                 qs = self.pred.decode_tiles_batch([(heads[i].streams, heads[i].first_syms, (heads[i].C, heads[i].h, heads[i].w))
                                                    for i in together], major[0], major[1], want='q',
                                                   max_workspace_bytes=max_workspace_bytes, channels=channels,
-                                                  **({'layer_ends': list(major[2:])} if order == 'layered' else {'order': order}))
+                                                  **({'layer_ends': list(major[2:])} if order == 'layered' else
+                                                     {'front_ends': list(major[2:])} if order == 'fronts' else {'order': order}))
             except ValueError as e:
                 m = re.search(r'volume (\d+)', str(e))
                 where = 'file {}: '.format(together[int(m.group(1))]) if m else ''
@@ -1268,8 +1350,8 @@ class Codec(object):
         the tiles with fewer than C channels)"""
         c0 = heads[0][0]
         return self.pred.decode_tiles_batch([(c.streams, c.first_syms, (c.C, c.h, c.w)) for c, _, _, _ in heads], c0.th, c0.tw, want=want,
-                                            max_workspace_bytes=max_workspace_bytes, layer_ends=c0.layer_ends,
-                                            tile_layers=[layers for _, layers, _, _ in heads])
+                                            max_workspace_bytes=max_workspace_bytes,
+                                            tile_layers=[layers for _, layers, _, _ in heads], **_ends_kw(c0))
 
     def _recover_report(self, head, held):
         """held: [(tile, layers_read, channels, reason)] of decode_tiles_batch(tile_layers=...); the reader's reason where it has one"""
@@ -1314,7 +1396,7 @@ class Codec(object):
             except ValueError as e:
                 raise ValueError('file {}: {}'.format(i, e))
         out = [None] * len(datas)
-        kind = lambda c: (c.th, c.tw) + tuple(c.layer_ends)
+        kind = lambda c: (c.version, c.th, c.tw) + tuple(c.layer_ends)
         for group in sorted(set(kind(h[0]) for h in heads)):
             members = [i for i, h in enumerate(heads) if kind(h[0]) == group]
             qs, held = self._recover_decode([heads[i] for i in members], 'q', max_workspace_bytes)
@@ -1343,6 +1425,11 @@ class Codec(object):
         img = self.decompress(data, channels=channels)
         Image.fromarray(img).save(image_path)
         return img
+
+
+def _ends_kw(c):
+    """the keyword decode_tiles_batch takes a LayeredContainer's layer ends through: plane cuts of format 6, front cuts of format 8"""
+    return {'front_ends': c.layer_ends} if c.version == FORMAT_VERSION_FRONTS else {'layer_ends': c.layer_ends}
 
 
 class StreamDecoder(object):
@@ -1451,7 +1538,8 @@ def _recover_line(path, report):
 
 
 def check_option_args(flags):
-    """--checked / --wavefront / --salvage / --channels / --layers / --progressive / --partial / --recover / --chunk against the command, --tile
+    """--checked / --wavefront / --salvage / --channels / --layers / --progressive / --front-layers / --front-progressive / --partial /
+    --recover / --chunk against the command, --tile
     and each other: decided before any model is built"""
     if getattr(flags, 'chunk', None) is not None:
         if flags.command != 'stream':
@@ -1499,6 +1587,24 @@ def check_option_args(flags):
             raise ValueError('--layers does not go with --progressive: the one names the layer ends, the other takes the default ones')
         if layers is not None:
             parse_layers_arg(layers)
+    front_layers, front_progressive = getattr(flags, 'front_layers', None), getattr(flags, 'front_progressive', False)
+    if front_layers is not None or front_progressive:
+        name = '--front-layers' if front_layers is not None else '--front-progressive'
+        if flags.command not in ('compress', 'compress-dir'):
+            raise ValueError('{} belongs to compress / compress-dir: a file says by itself what it is'.format(name))
+        if flags.tile is None:
+            raise ValueError('{} needs --tile: format 8 cuts every tile into layers'.format(name))
+        if getattr(flags, 'wavefront', False):
+            raise ValueError('{} does not go with --wavefront: format 8 implies the wavefront order, --wavefront writes the unlayered '
+                             'format 5'.format(name))
+        if layers is not None or progressive:
+            raise ValueError('{} does not go with {}: the one cuts the wavefront order at fronts (format 8), the other the raster order '
+                             'at channel planes (format 6)'.format(name, '--layers' if layers is not None else '--progressive'))
+        if front_layers is not None and front_progressive:
+            raise ValueError('--front-layers does not go with --front-progressive: the one names the layer ends, the other takes the '
+                             'default ones')
+        if front_layers is not None:
+            parse_layers_arg(front_layers, '--front-layers')
     if getattr(flags, 'partial', False):
         if flags.command not in ('decompress', 'decompress-dir'):
             raise ValueError('--partial belongs to decompress / decompress-dir: it reads a prefix of a layered file')
@@ -1518,14 +1624,14 @@ def check_option_args(flags):
             raise ValueError('--recover does not go with --channels: what every tile still holds decides its channels')
 
 
-def parse_layers_arg(text):
+def parse_layers_arg(text, option='--layers'):
     """'4,8,16,32' -> [4, 8, 16, 32]; a ValueError for anything but comma-separated positive integers (C is checked by the codec)"""
     try:
         ends = [int(v) for v in str(text).split(',')]
     except ValueError:
-        raise ValueError('--layers {!r} is not a comma-separated list of integers'.format(text))
+        raise ValueError('{} {!r} is not a comma-separated list of integers'.format(option, text))
     if not 1 <= len(ends) <= MAX_LAYERS or ends[0] < 1 or any(b <= a for a, b in zip(ends, ends[1:])):
-        raise ValueError('--layers {!r}: 1 to {} increasing layer ends from at least 1, the last one C'.format(text, MAX_LAYERS))
+        raise ValueError('{} {!r}: 1 to {} increasing layer ends from at least 1, the last one C'.format(option, text, MAX_LAYERS))
     return ends
 
 
@@ -1535,6 +1641,13 @@ def _layers_option(flags, C):
     if getattr(flags, 'layers', None) is not None:
         return check_layer_ends(parse_layers_arg(flags.layers), C)
     return 'default' if getattr(flags, 'progressive', False) else None
+
+
+def _front_layers_option(flags, C):
+    """the `front_layers` argument of Codec for a command line, as _layers_option"""
+    if getattr(flags, 'front_layers', None) is not None:
+        return check_layer_ends(parse_layers_arg(flags.front_layers, '--front-layers'), C)
+    return 'default' if getattr(flags, 'front_progressive', False) else None
 
 
 def check_dir_args(flags, factor):
@@ -1561,13 +1674,14 @@ def _main_dir(flags, ae_config, pc_config):
     from . import autoencoder, val, weights as _weights
     jobs, tile = check_dir_args(flags, int(autoencoder.get_network_cls(ae_config).get_subsampling_factor()))
     layers = _layers_option(flags, ae_config.num_chan_bn) if tile is not None else None
+    front_layers = _front_layers_option(flags, ae_config.num_chan_bn) if tile is not None else None
     if flags.weights == 'synthetic':
         wts = _weights.synthetic_weights(ae_config, pc_config, seed=flags.synthetic_seed)
     else:
         wts = val.load_weights_for_job(None, flags.weights, ae_config, pc_config)
     codec = Codec(ae_config, pc_config, wts, flags.device, tile=tile, checked=flags.checked,
                   order='wavefront' if flags.wavefront and tile is not None else 'raster',
-                  layers=layers)
+                  layers=layers, front_layers=front_layers)
     channels = check_channels(getattr(flags, 'channels', None), codec.C)
     os.makedirs(flags.output, exist_ok=True)
     total_in = total_out = total_pixels = 0
@@ -1737,7 +1851,7 @@ def verify_file(data):
                 c.version, len(data), G, ','.join(str(e) for e in c.layer_ends), ','.join(str(layer_prefix_bytes(c, g)) for g in range(G + 1)))
         return True, 'ok (format {}, {} bytes)'.format(c.version, len(data))
     except ValueError as strict:
-        if len(data) >= 6 and data[:4] == MAGIC and struct.unpack('<H', data[4:6])[0] == FORMAT_VERSION_LAYERED:
+        if len(data) >= 6 and data[:4] == MAGIC and struct.unpack('<H', data[4:6])[0] in _LAYERED_VERSIONS:
             try:
                 c, complete, _ = parse_partial(data)
             except ValueError as e:
@@ -1831,7 +1945,13 @@ def main(argv=None):
                    help='compress / compress-dir with --tile: layered tiles (format 6) with these layer ends, increasing, the last one C: '
                         'a prefix of the file decodes as a preview; not with --wavefront')
     p.add_argument('--progressive', action='store_true', help='compress / compress-dir with --tile: --layers with the default ends C/8, C/4, C/2, C')
-    p.add_argument('--partial', action='store_true', help='decompress / decompress-dir: decode the complete layers of a (cut) format-6 file and '
+    p.add_argument('--front-layers', dest='front_layers', default=None, metavar='a,b,..',
+                   help='compress / compress-dir with --tile: front-layered tiles (format 8) with these layer ends: every tile coded front by '
+                        'front as with --wavefront and cut at fronts, so that a prefix of the file decodes as a preview, a front at a time; '
+                        'not with --wavefront, --layers or --progressive')
+    p.add_argument('--front-progressive', dest='front_progressive', action='store_true',
+                   help='compress / compress-dir with --tile: --front-layers with the default ends C/8, C/4, C/2, C')
+    p.add_argument('--partial', action='store_true', help='decompress / decompress-dir: decode the complete layers of a (cut) format-6 / format-8 file and '
                                                           'print how many of them; not with --salvage or --channels')
     p.add_argument('--recover', action='store_true', help='decompress / decompress-dir: read what a damaged or cut format-6 file still holds, every '
                                                           'tile up to its own intact leading layers, the rest filled from the neighbours '
@@ -1852,6 +1972,7 @@ def main(argv=None):
             return _main_dir(flags, ae_config, pc_config)
         check_option_args(flags)
         layers = _layers_option(flags, ae_config.num_chan_bn)
+        front_layers = _front_layers_option(flags, ae_config.num_chan_bn)
         if flags.weights == 'synthetic':
             wts = _weights.synthetic_weights(ae_config, pc_config, seed=flags.synthetic_seed)
         else:
@@ -1865,6 +1986,7 @@ def main(argv=None):
                 codec.checked = flags.checked
                 codec.order = 'wavefront' if flags.wavefront else 'raster'
                 codec.layers = layers
+                codec.front_layers = front_layers
             data, pixels = codec.compress_file(flags.input, flags.output)
             print(_compress_line(flags.output, data, pixels))
         elif flags.command == 'stream':

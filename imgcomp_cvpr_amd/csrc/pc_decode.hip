@@ -6,7 +6,9 @@
 // ic_pc_decode_channels_f32 and ic_pc_decode_tiles_batch_channels_f32 decode only the first channels of every stream (preview);
 // ic_pc_decode_tiles_batch_layers_f32 reads every tile's stream as segments cut at channel planes (container format 6);
 // ic_pc_decode_tiles_batch_layers_pertile_f32 does so with a channel limit per tile (recovery of damaged or cut layered files);
-// ic_pc_decode_tiles_batch_layers_resume_f32 continues every tile at the layer where an earlier call on the same workspace stopped.
+// ic_pc_decode_tiles_batch_layers_resume_f32 continues every tile at the layer where an earlier call on the same workspace stopped;
+// ic_pc_decode_tiles_batch_fronts_f32 and ic_pc_decode_tiles_batch_fronts_pertile_f32 read every tile's wavefront-ordered stream as
+// segments cut at fronts (container format 8), with one channel limit or one per tile.
 #include "common.h"
 #include "pc_table.h"
 #include "pc_internal.h"
@@ -780,10 +782,26 @@ __device__ __forceinline__ void pc_wave_chain(const float* __restrict__ in, int 
 // in between the others: the range decoder steps through them like through any symbol, their centres go into V (later fronts of
 // the wanted channels have them in their context) and every cache phase keeps its full depth range; they are only not stored
 // through out.  The symbols stepped through are the first codec.wavefront_prefix_count(C, h, w, cdec) of the stream's order.
-template <bool SYMS, bool LIM = false>
+// SEG = true (the *_fronts entries, container format 8): the stream is cut into nlayers segments, each a coder run of its own -- not at
+// channel planes, which are no prefix of this order, but at FRONTS: segment g ends with the last symbol of front
+// t_g = (w - 1) + 2 (h - 1) + 4 (ends[g] - 1), the front of the last symbol of channel ends[g] - 1 (this tile's own h, w), so the segments
+// 0 .. g are exactly what a LIM sweep with cdec = ends[g] steps through.  bits / nbytes are segment 0; segment g >= 1 is segs[g] (offsets
+// from seg_base).  When phase 4 first comes to a front above t_g -- T - 28 > t_g, before that front's first symbol -- wave 0 folds
+// s.error into a sticky word, re-initialises the coder state on segment g + 1 and reads the 32 code bits, exactly as at the start of
+// a stream: a wave-uniform branch between the barrier behind phase 3 and the one behind the chunk's logits, where wave 0 has no other
+// work that anyone waits for.  The cuts lie at least four fronts apart (the ends increase), a step advances one front: one cut per
+// step at the most.  The fronts, the caches and the context know nothing of it; LDS does not grow.  Past its end a segment reads as
+// zeros (its own nbytes bounds pc_dec_bit).  segs and ends are the tile's rows of device tables that no kernel writes, read through
+// the constant address space with uniform indices: scalar loads.  With LIM the loop ends at T_stop(cdec) before it comes to a front
+// above t_g of any layer that ends at or above cdec: only the segments of layers that begin below cdec are read.  Everything a later
+// front needs -- V and the three caches -- is in the slot and the coder starts afresh at each cut, so a sweep that stopped at a layer
+// end could be continued by a later launch, as the raster FROM sweep is.  SEG = false reads none of this and is the decoder as before.
+template <bool SYMS, bool LIM = false, bool SEG = false>
 __device__ __forceinline__ void pc_dec_wave_body(const PcCachedArgs& f, const unsigned char* bits, long long nbytes, int h, int w, int first_sym,
                                                  float* vol, float* c0, float* c1, float* c2, int* status,
-                                                 long long* __restrict__ out, long long out_cs, int out_rs, int cdec = 0) {
+                                                 long long* __restrict__ out, long long out_cs, int out_rs, int cdec = 0,
+                                                 const unsigned char* seg_base = nullptr, const ic_pc_seg_t* __restrict__ segs = nullptr,
+                                                 const int* __restrict__ ends = nullptr, int nlayers = 0) {
     constexpr int K = 24, G = K / 4, CH = 64;             // CH: candidates of a front whose logits are in LDS at once
     __shared__ float s_logits[CH][16];
     __shared__ float s_centers[16];
@@ -798,6 +816,13 @@ __device__ __forceinline__ void pc_dec_wave_body(const PcCachedArgs& f, const un
     const int PH = h + 8, PW = w + 8;
     const int N0i = h + 6, N0j = w + 6, N1i = h + 4, N1j = w + 4, N2i = h + 2, N2j = w + 2;
     const int T_last = (w + 3) + 2 * (h + 3) + 4 * ((LIM ? cdec : C) + 3);    // the last symbol's front (LIM: of channel cdec - 1)
+    // SEG: the segment that comes next, the last front of the one being read (in the loop's terms, T = front + 28; none left: beyond the
+    // sweep), and the sticky error of the segments done
+    typedef const __attribute__((address_space(4))) ic_pc_seg_t* seg_cptr;
+    typedef const __attribute__((address_space(4))) int* int_cptr;
+    const int T_base = (w - 1) + 2 * (h - 1) - 4 + 28;                        // T of front t_g is T_base + 4 ends[g]
+    int seg_next = 1, T_cut = 0x7fffffff, sticky = 0;
+    if constexpr (SEG) T_cut = nlayers > 1 ? T_base + 4 * ((int_cptr)ends)[0] : 0x7fffffff;
     __syncthreads();
     for (int T = 7; T <= T_last; ++T) {
         {   // ---- 1: A0, first mask (13 live taps = TF taps 0..12), + bias, ReLU ----
@@ -860,6 +885,18 @@ __device__ __forceinline__ void pc_dec_wave_body(const PcCachedArgs& f, const un
         // ---- 4: the symbols (c, y, x) with x + 2 y + 4 c == T - 28: logits, then the range decoder in (c, y, x) order ----
         const PcFront fr = pc_front(T - 28, C, h, w);
         const int ncand = fr.nd * fr.iw;
+        if constexpr (SEG) {
+            if (wave == 0 && T > T_cut) {                 // the cut: this front's symbols are the first of segment seg_next
+                seg_next = __builtin_amdgcn_readfirstlane(seg_next);
+                const long long seg_off = ((seg_cptr)segs)[seg_next].off, seg_bytes = ((seg_cptr)segs)[seg_next].nbytes;
+                sticky |= s.error;
+                bits = seg_base + seg_off; nbytes = seg_bytes;
+                pc_dec_state_init(s, bits, nbytes);
+                for (int i = 0; i < PC_AC_BITS; ++i) s.code = (s.code << 1) | (unsigned)pc_dec_bit(bits, nbytes, s);
+                ++seg_next;
+                T_cut = seg_next < nlayers ? T_base + 4 * ((int_cptr)ends)[seg_next - 1] : 0x7fffffff;
+            }
+        }
         for (int cb = 0; cb < ncand; cb += CH) {
             const int nc = min(CH, ncand - cb);
             for (int n = tid; n < nc * L; n += 256) {
@@ -890,7 +927,7 @@ __device__ __forceinline__ void pc_dec_wave_body(const PcCachedArgs& f, const un
             __syncthreads();                              // V of this front before the next step's conv0; s_logits free again
         }
     }
-    if (tid == 0) *status = s.error;
+    if (tid == 0) *status = SEG ? (sticky | s.error) : s.error;
 }
 
 // ---- tiles: one work-group per tile, the tiles of all volumes in one launch ---------------------------------------------------
@@ -926,8 +963,10 @@ struct PcTilesBatchArgs {
     int* done;                        //   and the channels the workspace holds of every tile (ntiles; written by the kernel alone)
 };
 
-// SEG (ic_pc_decode_tiles_batch_layers_f32, raster only): the tile's stream is its nlayers segments, segs[blockIdx.x * nlayers + g];
-// the descriptor's stream_off / stream_bytes are not read.
+// SEG: the tile's stream is its nlayers segments, segs[blockIdx.x * nlayers + g]; the descriptor's stream_off / stream_bytes are not
+// read.  Raster (ic_pc_decode_tiles_batch_layers_f32): cut at channel planes.  WAVE (ic_pc_decode_tiles_batch_fronts_f32): cut at fronts
+// -- the two bodies each know one kind of cut; a channel plane is no prefix of a wavefront-ordered stream, so there is no WAVE decoder
+// of plane cuts and none is selected by any flag.
 // PER (ic_pc_decode_tiles_batch_layers_pertile_f32): the channel limit is the tile's own, tile_channels[blockIdx.x] in 1 .. C, in
 // place of the launch's cdec.  A uniform index into a table that no kernel writes, read like the segment table through the constant
 // address space: one scalar load per tile, a uniform value as cdec is, and nothing of it in the body's per-symbol path.  A tile whose
@@ -941,9 +980,8 @@ struct PcTilesBatchArgs {
 // Still nothing passes between work-groups: a work-group reads its own slot and its own done word.
 template <bool WAVE, bool SYMS, bool LIM = false, bool SEG = false, bool PER = false, bool FROM = false>
 __global__ __launch_bounds__(256) void pc_dec_tiles_batch_kernel(const PcTilesBatchArgs t) {
-    static_assert(!(WAVE && SEG), "a layer is no prefix of a wavefront-ordered stream");
-    static_assert(!PER || (LIM && SEG && !WAVE), "the limit per tile belongs to the layered raster decoder");
-    static_assert(!FROM || PER, "a sweep continues where a sweep with a limit per tile stopped");
+    static_assert(!PER || (LIM && SEG), "the limit per tile belongs to the segmented decoders: a limited sweep over a tile's segments");
+    static_assert(!FROM || (PER && !WAVE), "a sweep continues where a raster sweep with a limit per tile stopped; front-cut sweeps are not continued yet");
     const ic_pc_tile_t tl = t.tiles[blockIdx.x];
     // v = volumes ? volumes[tl.volume] : one, as a uniform branch around a scalar load.  (Written as a select, it becomes a select
     // between the two ADDRESSES, kernel arguments or global memory, and a load through a flat pointer into vector registers:
@@ -977,6 +1015,14 @@ __global__ __launch_bounds__(256) void pc_dec_tiles_batch_kernel(const PcTilesBa
                                                        t.bits, segs, t.ends, t.nlayers, gfrom);
         else if (threadIdx.x == 0) t.status[blockIdx.x] = 0;
         if (threadIdx.x == 0) t.done[blockIdx.x] = t.status[blockIdx.x] == 0 ? cdec : -1;       // (thread 0 stored the status)
+    } else if constexpr (WAVE && SEG) {
+        const ic_pc_seg_t* segs = t.segs + (size_t)blockIdx.x * t.nlayers;
+        typedef const __attribute__((address_space(4))) ic_pc_seg_t* seg_cptr;      // (a table no kernel writes: see the body)
+        const long long off0 = ((seg_cptr)segs)[0].off, nbytes0 = ((seg_cptr)segs)[0].nbytes;
+        pc_dec_wave_body<SYMS, LIM, true>(t.f, t.bits + off0, nbytes0, tl.th, tl.tw, tl.first_sym, (float*)slot,
+                                          (float*)(slot + t.off_c0), (float*)(slot + t.off_c1), (float*)(slot + t.off_c2), t.status + blockIdx.x,
+                                          SYMS ? t.symbols + v.symbols_off + corner : nullptr, plane, v.w, cdec,
+                                          t.bits, segs, t.ends, t.nlayers);
     } else if constexpr (WAVE)
         pc_dec_wave_body<SYMS, LIM>(t.f, t.bits + tl.stream_off, tl.stream_bytes, tl.th, tl.tw, tl.first_sym, (float*)slot,
                                     (float*)(slot + t.off_c0), (float*)(slot + t.off_c1), (float*)(slot + t.off_c2), t.status + blockIdx.x,
@@ -1266,7 +1312,7 @@ static int pc_decode_tiles_impl(const uint8_t* bitstreams, const ic_pc_tile_t* t
         } else {
             a.one = volumes_host[0];
         }
-        if (nlayers) {                // the layers entry (k = 24, flags 0): segment table and layer ends behind the two tables
+        if (nlayers) {                // the layers and fronts entries (k = 24): segment table and layer ends behind the two tables
             ic_pc_seg_t* segs_dev = (ic_pc_seg_t*)p; p += pc_dec_align((size_t)ntiles * nlayers * sizeof(ic_pc_seg_t));
             int* ends_dev = (int*)p; p += pc_dec_align((size_t)nlayers * sizeof(int));
             if (hipMemcpyAsync(segs_dev, segs_host, (size_t)ntiles * nlayers * sizeof(ic_pc_seg_t), hipMemcpyHostToDevice, st) != hipSuccess) return IC_ERR_ARG;
@@ -1309,7 +1355,12 @@ static int pc_decode_tiles_impl(const uint8_t* bitstreams, const ic_pc_tile_t* t
         const auto seg_lim = symbols ? pc_dec_tiles_batch_kernel<false, true, true, true> : pc_dec_tiles_batch_kernel<false, false, true, true>;
         const auto seg_per = symbols ? pc_dec_tiles_batch_kernel<false, true, true, true, true> : pc_dec_tiles_batch_kernel<false, false, true, true, true>;
         const auto seg_resume = symbols ? pc_dec_tiles_batch_kernel<false, true, true, true, true, true> : pc_dec_tiles_batch_kernel<false, false, true, true, true, true>;
-        const auto kernel = tile_from_host ? seg_resume : tile_channels_host ? seg_per : nlayers ? (channels < C ? seg_lim : seg_full) : (channels < C ? lim : full);
+        const auto front_full = symbols ? pc_dec_tiles_batch_kernel<true, true, false, true> : pc_dec_tiles_batch_kernel<true, false, false, true>;
+        const auto front_lim = symbols ? pc_dec_tiles_batch_kernel<true, true, true, true> : pc_dec_tiles_batch_kernel<true, false, true, true>;
+        const auto front_per = symbols ? pc_dec_tiles_batch_kernel<true, true, true, true, true> : pc_dec_tiles_batch_kernel<true, false, true, true, true>;
+        const auto kernel = tile_from_host ? seg_resume
+                          : (wavefront && nlayers) ? (tile_channels_host ? front_per : channels < C ? front_lim : front_full)
+                          : tile_channels_host ? seg_per : nlayers ? (channels < C ? seg_lim : seg_full) : (channels < C ? lim : full);
         hipLaunchKernelGGL(kernel, dim3((unsigned)ntiles), dim3(256), 0, st, a);
         IC_LAUNCH_CHECK();
         return IC_OK;
@@ -1427,12 +1478,14 @@ extern "C" size_t ic_pc_decode_tiles_batch_layers_workspace_bytes(int C, int th_
     return base ? base + pc_dec_layers_tables_bytes(ntiles, nlayers) : 0;
 }
 
-extern "C" int ic_pc_decode_tiles_batch_layers_f32(const uint8_t* bitstreams, long long total_bytes, const ic_pc_tile_t* tiles_host, int ntiles,
-                                                   const ic_pc_volume_t* volumes_host, int nvolumes, const float* const* wtab_host,
-                                                   const float* centers, int k, int L, float resolution, int64_t* symbols, float* q,
-                                                   int* status, int C, void* workspace, size_t workspace_bytes, int flags,
-                                                   ic_stream_t stream, int channels, int fill_sym,
-                                                   const int* layer_ends_host, int nlayers, const ic_pc_seg_t* segs_host) {
+// the layers entry and the fronts entry: one set of checks; `order` is what the decoder is told, 0 (raster, plane cuts) or
+// IC_PC_DECODE_WAVEFRONT (front cuts) -- the caller's own flags must be 0 for both
+static int pc_decode_tiles_segments(const uint8_t* bitstreams, long long total_bytes, const ic_pc_tile_t* tiles_host, int ntiles,
+                                    const ic_pc_volume_t* volumes_host, int nvolumes, const float* const* wtab_host,
+                                    const float* centers, int k, int L, float resolution, int64_t* symbols, float* q,
+                                    int* status, int C, void* workspace, size_t workspace_bytes, int flags,
+                                    ic_stream_t stream, int channels, int fill_sym,
+                                    const int* layer_ends_host, int nlayers, const ic_pc_seg_t* segs_host, int order) {
     // everything about the four tables is decided here, on the host, before the first HIP call
     IC_CHECK_ARG(bitstreams && tiles_host && volumes_host && wtab_host && centers && (symbols || q) && status && workspace);
     IC_CHECK_ARG(layer_ends_host && segs_host);
@@ -1461,8 +1514,19 @@ extern "C" int ic_pc_decode_tiles_batch_layers_f32(const uint8_t* bitstreams, lo
     if (L > 16 || k != 24 || flags != 0) return IC_ERR_UNSUPPORTED;
     if (workspace_bytes < ic_pc_decode_tiles_batch_layers_workspace_bytes(C, th_max, tw_max, ntiles, nvolumes, k, nlayers)) return IC_ERR_WORKSPACE;
     return pc_decode_tiles_impl(bitstreams, tiles_host, ntiles, th_max, tw_max, volumes_host, nvolumes, wtab_host, centers, k, L,
-                                resolution, symbols, q, status, C, workspace, flags, channels, fill_sym, stream,
+                                resolution, symbols, q, status, C, workspace, order, channels, fill_sym, stream,
                                 layer_ends_host, nlayers, segs_host);
+}
+
+extern "C" int ic_pc_decode_tiles_batch_layers_f32(const uint8_t* bitstreams, long long total_bytes, const ic_pc_tile_t* tiles_host, int ntiles,
+                                                   const ic_pc_volume_t* volumes_host, int nvolumes, const float* const* wtab_host,
+                                                   const float* centers, int k, int L, float resolution, int64_t* symbols, float* q,
+                                                   int* status, int C, void* workspace, size_t workspace_bytes, int flags,
+                                                   ic_stream_t stream, int channels, int fill_sym,
+                                                   const int* layer_ends_host, int nlayers, const ic_pc_seg_t* segs_host) {
+    return pc_decode_tiles_segments(bitstreams, total_bytes, tiles_host, ntiles, volumes_host, nvolumes, wtab_host, centers, k, L, resolution,
+                                    symbols, q, status, C, workspace, workspace_bytes, flags, stream, channels, fill_sym,
+                                    layer_ends_host, nlayers, segs_host, 0);
 }
 
 // ---- layered tiles with a channel limit per tile: what a damaged or cut format-6 file still holds of every tile ---------------
@@ -1471,12 +1535,12 @@ extern "C" size_t ic_pc_decode_tiles_batch_layers_pertile_workspace_bytes(int C,
     return base ? base + pc_dec_align((size_t)ntiles * sizeof(int)) : 0;
 }
 
-extern "C" int ic_pc_decode_tiles_batch_layers_pertile_f32(const uint8_t* bitstreams, long long total_bytes, const ic_pc_tile_t* tiles_host, int ntiles,
-                                                           const ic_pc_volume_t* volumes_host, int nvolumes, const float* const* wtab_host,
-                                                           const float* centers, int k, int L, float resolution, int64_t* symbols, float* q,
-                                                           int* status, int C, void* workspace, size_t workspace_bytes, int flags,
-                                                           ic_stream_t stream, const int* tile_channels_host, int fill_sym,
-                                                           const int* layer_ends_host, int nlayers, const ic_pc_seg_t* segs_host) {
+static int pc_decode_tiles_segments_pertile(const uint8_t* bitstreams, long long total_bytes, const ic_pc_tile_t* tiles_host, int ntiles,
+                                            const ic_pc_volume_t* volumes_host, int nvolumes, const float* const* wtab_host,
+                                            const float* centers, int k, int L, float resolution, int64_t* symbols, float* q,
+                                            int* status, int C, void* workspace, size_t workspace_bytes, int flags,
+                                            ic_stream_t stream, const int* tile_channels_host, int fill_sym,
+                                            const int* layer_ends_host, int nlayers, const ic_pc_seg_t* segs_host, int order) {
     // everything about the five tables is decided here, on the host, before the first HIP call
     IC_CHECK_ARG(bitstreams && tiles_host && volumes_host && wtab_host && centers && (symbols || q) && status && workspace);
     IC_CHECK_ARG(tile_channels_host && layer_ends_host && segs_host);
@@ -1507,8 +1571,51 @@ extern "C" int ic_pc_decode_tiles_batch_layers_pertile_f32(const uint8_t* bitstr
     if (L > 16 || k != 24 || flags != 0) return IC_ERR_UNSUPPORTED;
     if (workspace_bytes < ic_pc_decode_tiles_batch_layers_pertile_workspace_bytes(C, th_max, tw_max, ntiles, nvolumes, k, nlayers)) return IC_ERR_WORKSPACE;
     return pc_decode_tiles_impl(bitstreams, tiles_host, ntiles, th_max, tw_max, volumes_host, nvolumes, wtab_host, centers, k, L,
-                                resolution, symbols, q, status, C, workspace, flags, C, fill_sym, stream,
+                                resolution, symbols, q, status, C, workspace, order, C, fill_sym, stream,
                                 layer_ends_host, nlayers, segs_host, tile_channels_host);
+}
+
+extern "C" int ic_pc_decode_tiles_batch_layers_pertile_f32(const uint8_t* bitstreams, long long total_bytes, const ic_pc_tile_t* tiles_host, int ntiles,
+                                                           const ic_pc_volume_t* volumes_host, int nvolumes, const float* const* wtab_host,
+                                                           const float* centers, int k, int L, float resolution, int64_t* symbols, float* q,
+                                                           int* status, int C, void* workspace, size_t workspace_bytes, int flags,
+                                                           ic_stream_t stream, const int* tile_channels_host, int fill_sym,
+                                                           const int* layer_ends_host, int nlayers, const ic_pc_seg_t* segs_host) {
+    return pc_decode_tiles_segments_pertile(bitstreams, total_bytes, tiles_host, ntiles, volumes_host, nvolumes, wtab_host, centers, k, L,
+                                            resolution, symbols, q, status, C, workspace, workspace_bytes, flags, stream, tile_channels_host,
+                                            fill_sym, layer_ends_host, nlayers, segs_host, 0);
+}
+
+// ---- front-layered tiles (container format 8): every tile's wavefront-ordered stream as nlayers segments cut at fronts ------------
+// The arguments, the checks and the workspace of the two layered entries; only the meaning of a segment differs (pc_dec_wave_body, SEG).
+extern "C" size_t ic_pc_decode_tiles_batch_fronts_workspace_bytes(int C, int th_max, int tw_max, int ntiles, int nvolumes, int k, int nlayers) {
+    return ic_pc_decode_tiles_batch_layers_workspace_bytes(C, th_max, tw_max, ntiles, nvolumes, k, nlayers);
+}
+
+extern "C" int ic_pc_decode_tiles_batch_fronts_f32(const uint8_t* bitstreams, long long total_bytes, const ic_pc_tile_t* tiles_host, int ntiles,
+                                                   const ic_pc_volume_t* volumes_host, int nvolumes, const float* const* wtab_host,
+                                                   const float* centers, int k, int L, float resolution, int64_t* symbols, float* q,
+                                                   int* status, int C, void* workspace, size_t workspace_bytes, int flags,
+                                                   ic_stream_t stream, int channels, int fill_sym,
+                                                   const int* layer_ends_host, int nlayers, const ic_pc_seg_t* segs_host) {
+    return pc_decode_tiles_segments(bitstreams, total_bytes, tiles_host, ntiles, volumes_host, nvolumes, wtab_host, centers, k, L, resolution,
+                                    symbols, q, status, C, workspace, workspace_bytes, flags, stream, channels, fill_sym,
+                                    layer_ends_host, nlayers, segs_host, IC_PC_DECODE_WAVEFRONT);
+}
+
+extern "C" size_t ic_pc_decode_tiles_batch_fronts_pertile_workspace_bytes(int C, int th_max, int tw_max, int ntiles, int nvolumes, int k, int nlayers) {
+    return ic_pc_decode_tiles_batch_layers_pertile_workspace_bytes(C, th_max, tw_max, ntiles, nvolumes, k, nlayers);
+}
+
+extern "C" int ic_pc_decode_tiles_batch_fronts_pertile_f32(const uint8_t* bitstreams, long long total_bytes, const ic_pc_tile_t* tiles_host, int ntiles,
+                                                           const ic_pc_volume_t* volumes_host, int nvolumes, const float* const* wtab_host,
+                                                           const float* centers, int k, int L, float resolution, int64_t* symbols, float* q,
+                                                           int* status, int C, void* workspace, size_t workspace_bytes, int flags,
+                                                           ic_stream_t stream, const int* tile_channels_host, int fill_sym,
+                                                           const int* layer_ends_host, int nlayers, const ic_pc_seg_t* segs_host) {
+    return pc_decode_tiles_segments_pertile(bitstreams, total_bytes, tiles_host, ntiles, volumes_host, nvolumes, wtab_host, centers, k, L,
+                                            resolution, symbols, q, status, C, workspace, workspace_bytes, flags, stream, tile_channels_host,
+                                            fill_sym, layer_ends_host, nlayers, segs_host, IC_PC_DECODE_WAVEFRONT);
 }
 
 // ---- layered tiles, continued: every tile from the layer where an earlier call on the same workspace stopped --------------------

@@ -431,6 +431,25 @@ class PredictionNetwork(object):
             res.append(([bytes(host[n, g, :nbytes[n * G + g]]) for g in range(G)], int(sym[n, 0, 0, 0])))
         return res
 
+    def _encode_fronts(self, symbols, layer_ends, capacity=None):
+        """a batch (N,C,h,w) of volumes of one shape, each coded in wavefront order and cut at fronts (container format 8): logits and
+        symbols gathered through codec.wavefront_order(C, h, w) on the device, as encode_stream(order='wavefront') does it, then ONE
+        ic_pc_encode_segments_f32 launch with the cuts codec.front_layer_cuts(C, h, w, layer_ends) -> [([segment bytes per layer],
+        first_sym)].  Segment g is arithmetic_coding.encode_sequence over the permuted symbols and tables [max(1, n_{g-1}), n_g)."""
+        from .codec import wavefront_order, front_layer_cuts
+        dev = self.centers.device
+        sym = symbols.to(dev).long().contiguous()
+        N, C, h, w = (int(v) for v in sym.shape)
+        cuts = front_layer_cuts(C, h, w, layer_ends)
+        pad = self.pc_class.get_context_size(self.config) // 2
+        q = self.centers[torch.nn.functional.pad(sym, (pad, pad, pad, pad, pad, 0))].contiguous()    # (N,C+4,h+8,w+8), symbol 0 around
+        logits = self.pc.logits(q, is_training=False)                  # (N,C,h,w,L)
+        count = C * h * w
+        perm = torch.as_tensor(np.array(wavefront_order(C, h, w))).to(dev)           # (a copy: the cached order is read-only)
+        logits = logits.view(N, count, self.pc.L).index_select(1, perm).contiguous()
+        coded = sym.view(N, count).index_select(1, perm).contiguous()
+        return self._encode_segments(logits, coded.view(N, count, 1, 1), N, count, cuts, capacity)
+
     def _preview(self, channels, C):
         """channels=None -> None (the full decode, the old entries); else (channels, fill symbol) for the *_channels entries, which
         exist for the k = 24 kernels only"""
@@ -468,14 +487,18 @@ class PredictionNetwork(object):
             raise ValueError('Cannot decode symbol because total is too large')
         return out.cpu().numpy()
 
-    def encode_tiles(self, symbols, th, tw, order='raster', layer_ends=None):
+    def encode_tiles(self, symbols, th, tw, order='raster', layer_ends=None, front_ends=None):
         """symbols: un-padded (C,h,w) -> [(stream_bytes, first_sym)] for the tiles of codec.tile_grid(h, w, th, tw), in grid order.
         Every tile is coded as a volume of its own: its stream is encode_stream(symbols[:, y0:y0+th', x0:x0+tw']) byte for byte.
         Tiles of one shape (at most four: interior, right column, bottom row, corner) are one encode_stream batch, one launch.
         order='wavefront': every tile's stream in the wavefront order of its own extent (encode_stream).
         layer_ends=[e_0 < ... = C] (raster only, container format 6): every tile's stream cut at these channel planes into segments
-        (encode_stream(seg_ends=[e th' tw' ...])) -> [([segment bytes per layer], first_sym)]."""
+        (encode_stream(seg_ends=[e th' tw' ...])) -> [([segment bytes per layer], first_sym)].
+        front_ends=[e_0 < ... = C] (container format 8; not with layer_ends or order='wavefront', the order is implied): every tile's
+        stream in the wavefront order of its own extent, cut at that extent's fronts codec.front_layer_cuts(C, th', tw', front_ends)
+        (_encode_fronts) -> [([segment bytes per layer], first_sym)]."""
         from .codec import tile_grid
+        self._check_front_ends(front_ends, order, layer_ends)
         sym = symbols if torch.is_tensor(symbols) else torch.as_tensor(np.ascontiguousarray(symbols))
         assert sym.dim() == 3, 'Expected CHW symbols'
         sym = sym.to(self.centers.device).long()
@@ -487,9 +510,16 @@ class PredictionNetwork(object):
         for (a, b), members in by_shape.items():
             batch = torch.stack([sym[:, grid[t][0]:grid[t][0] + a, grid[t][1]:grid[t][1] + b] for t in members])
             seg_ends = None if layer_ends is None else [int(e) * a * b for e in layer_ends]
-            for t, r in zip(members, self.encode_stream(batch, order=order, seg_ends=seg_ends)):
+            coded = self._encode_fronts(batch, front_ends) if front_ends is not None else self.encode_stream(batch, order=order, seg_ends=seg_ends)
+            for t, r in zip(members, coded):
                 res[t] = r
         return res
+
+    @staticmethod
+    def _check_front_ends(front_ends, order, layer_ends):
+        if front_ends is not None and (layer_ends is not None or order != 'raster'):
+            raise ValueError("front_ends cuts the wavefront order at fronts by itself: not with layer_ends (plane cuts of the raster "
+                             "order) or order={!r}".format(order))
 
     def decode_tiles(self, streams, first_syms, symbols_shape, th, tw, flags=0, channels=None):
         """The mirror of encode_tiles: all tiles of a volume decoded by ONE launch, one work-group per tile
@@ -524,12 +554,14 @@ class PredictionNetwork(object):
                 raise ValueError('Cannot decode symbol because total is too large (tile {} at ({}, {}))'.format(t, grid[t][0], grid[t][1]))
         return out.cpu().numpy()
 
-    def encode_tiles_batch(self, volumes, th, tw, order='raster', layer_ends=None):
+    def encode_tiles_batch(self, volumes, th, tw, order='raster', layer_ends=None, front_ends=None):
         """encode_tiles for a list of un-padded (C,h,w) symbol volumes of any mix of (h, w): -> per volume the list encode_tiles
         gives for it, byte for byte.  The tiles of ALL volumes are grouped by tile shape -- for a folder of equal-sized images the
         same four shapes as for one -- and each group is one encode_stream batch, one ic_pc_encode_f32 launch.
-        layer_ends: as encode_tiles, the ends converted to symbol counts per tile shape (raster only)."""
+        layer_ends: as encode_tiles, the ends converted to symbol counts per tile shape (raster only).
+        front_ends: as encode_tiles, every tile shape by its own cuts."""
         from .codec import tile_grid
+        self._check_front_ends(front_ends, order, layer_ends)
         dev = self.centers.device
         syms, grids = [], []
         for v in volumes:
@@ -545,12 +577,13 @@ class PredictionNetwork(object):
         for (_, a, b), members in by_shape.items():
             batch = torch.stack([syms[n][:, grids[n][t][0]:grids[n][t][0] + a, grids[n][t][1]:grids[n][t][1] + b] for n, t in members])
             seg_ends = None if layer_ends is None else [int(e) * a * b for e in layer_ends]
-            for (n, t), r in zip(members, self.encode_stream(batch, order=order, seg_ends=seg_ends)):
+            coded = self._encode_fronts(batch, front_ends) if front_ends is not None else self.encode_stream(batch, order=order, seg_ends=seg_ends)
+            for (n, t), r in zip(members, coded):
                 res[n][t] = r
         return res
 
     def decode_tiles_batch(self, volumes, th, tw, want='q', max_workspace_bytes=1 << 31, flags=0, conceal=False, order='raster',
-                           channels=None, layer_ends=None, tile_layers=None):
+                           channels=None, layer_ends=None, tile_layers=None, front_ends=None):
         """The mirror of encode_tiles_batch: the tiles of ALL volumes decoded by one launch per chunk (ic_pc_decode_tiles_batch_f32,
         one work-group per tile).  volumes: [(streams, first_syms, (C,h,w))], each as decode_tiles takes them, one C throughout.
         want: 'q' -> per volume the (C,h,w) float32 DEVICE tensor centers[symbols] (what ae.decode consumes: the symbols never
@@ -576,8 +609,16 @@ class PredictionNetwork(object):
         ic_pc_conceal_tiles_channels launch fills every missing (tile, channel) from the neighbours that hold that channel (the
         fallback is the fill symbol, so a channel no neighbour holds is that of a preview).  The call returns (result as above, [per
         volume [(tile, layers_read, channels, reason)] in tile order for the tiles that hold fewer than C channels]); reason is
-        'decoder' or None (the caller's own limit)."""
+        'decoder' or None (the caller's own limit).
+        front_ends=[e_0 < ... = C] (container format 8, ic_pc_decode_tiles_batch_fronts_f32 / _fronts_pertile_f32): everything said of
+        layer_ends -- channels, tile_layers, what may be None, what is returned -- for streams[t] = the tile's G segments of its
+        wavefront order cut at fronts, as encode_tiles(front_ends=...) gives them.  Not with layer_ends or order='wavefront' (the
+        order is implied)."""
         from .codec import tile_grid, chunk_tiles, check_channels, check_layer_ends
+        fronts = front_ends is not None
+        if fronts:
+            self._check_front_ends(front_ends, order, layer_ends)
+            layer_ends = front_ends
         if layer_ends is not None:
             if conceal:
                 raise ValueError('layer_ends with conceal=True: salvage of layered tiles is not offered')
@@ -668,11 +709,17 @@ class PredictionNetwork(object):
         G = 0 if layer_ends is None else len(ends)
         vtable, offs, total = _lib.packed_volume_table(shapes)
 
+        kind = 'fronts' if fronts else 'layers'
+        entry_name, entry_per_name = 'ic_pc_decode_tiles_batch_{}_f32'.format(kind), 'ic_pc_decode_tiles_batch_{}_pertile_f32'.format(kind)
+        entry, entry_per = getattr(lib, entry_name), getattr(lib, entry_per_name)
+        entry_ws = getattr(lib, 'ic_pc_decode_tiles_batch_{}_workspace_bytes'.format(kind))
+        entry_per_ws = getattr(lib, 'ic_pc_decode_tiles_batch_{}_pertile_workspace_bytes'.format(kind))
+
         def need(th_max, tw_max, ntiles):
             if tile_layers is not None:
-                return int(lib.ic_pc_decode_tiles_batch_layers_pertile_workspace_bytes(C, th_max, tw_max, ntiles, len(shapes), k, G))
+                return int(entry_per_ws(C, th_max, tw_max, ntiles, len(shapes), k, G))
             if G:
-                return int(lib.ic_pc_decode_tiles_batch_layers_workspace_bytes(C, th_max, tw_max, ntiles, len(shapes), k, G))
+                return int(entry_ws(C, th_max, tw_max, ntiles, len(shapes), k, G))
             return int(lib.ic_pc_decode_tiles_batch_workspace_bytes(C, th_max, tw_max, ntiles, len(shapes), k))
 
         chunks = chunk_tiles([(a, b) for _, _, a, b, _, _, _, _ in tiles], need, int(max_workspace_bytes))
@@ -699,10 +746,9 @@ class PredictionNetwork(object):
                 seg_ptr = ctypes.c_void_p(ctypes.addressof(seg_table) + a * G * ctypes.sizeof(_lib.PcSeg))
             if tile_layers is not None:
                 lim_ptr = ctypes.c_void_p(ctypes.addressof(host_limits) + a * ctypes.sizeof(ctypes.c_int))
-                check(lib.ic_pc_decode_tiles_batch_layers_pertile_f32(*(args + (lim_ptr, self.conceal_fallback(), host_ends, G, seg_ptr))),
-                      'ic_pc_decode_tiles_batch_layers_pertile_f32')
+                check(entry_per(*(args + (lim_ptr, self.conceal_fallback(), host_ends, G, seg_ptr))), entry_per_name)
             elif G:
-                check(lib.ic_pc_decode_tiles_batch_layers_f32(*(args + layers + (host_ends, G, seg_ptr))), 'ic_pc_decode_tiles_batch_layers_f32')
+                check(entry(*(args + layers + (host_ends, G, seg_ptr))), entry_name)
             elif preview is None:
                 check(lib.ic_pc_decode_tiles_batch_f32(*args), 'ic_pc_decode_tiles_batch_f32')
             else:

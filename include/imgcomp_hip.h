@@ -392,6 +392,33 @@ int ic_pc_decode_tiles_batch_layers_pertile_f32(const uint8_t* bitstreams, long 
                                                 int* status, int C, void* workspace, size_t workspace_bytes, int flags,
                                                 ic_stream_t stream, const int* tile_channels_host, int fill_sym,
                                                 const int* layer_ends_host, int nlayers, const ic_pc_seg_t* segs_host);
+/* Front-layered tiles (container format 8): a tile's WAVEFRONT-ordered stream (IC_PC_DECODE_WAVEFRONT: symbols sorted by (T, c, y, x),
+ * T = x + 2 y + 4 c in the tile's own coordinates) cut into nlayers segments, each a coder run of its own.  A channel plane is no
+ * prefix of that order, a front is: segment g ends with the last symbol of front t_g = (tw - 1) + 2 (th - 1) + 4 (e_g - 1), the front of
+ * the last symbol of channel e_g - 1, every tile by its own extent.  Segments 0 .. g are what the wavefront preview decoder steps
+ * through for channels = e_g: every symbol of the channels below e_g and the symbols of later channels that share those fronts.  At the
+ * first front above t_g the decoder keeps its error flag, re-initialises the range decoder on segment g + 1 and primes it with 32
+ * bits; the fronts, the caches and the context cross the cuts.  Decoded a front at a time like format 5, a prefix of a file decodes
+ * like format 6.
+ * The two entries mirror ic_pc_decode_tiles_batch_layers_f32 and ic_pc_decode_tiles_batch_layers_pertile_f32 argument for argument --
+ * parameters, host-side checks, return codes, what is read of segs_host (only the layers that begin below the limit; the others may be
+ * {0, 0}), what is written (every position of every listed tile; the limit need not be a layer end), status (the error flag kept over
+ * the cuts) and workspace (the *_fronts_*workspace_bytes functions return the layered entries' sizes).  flags must be 0: the order is
+ * the entry's own.  Past its end a segment reads as zeros.  All refusals are decided on the host; a refused call writes nothing. */
+size_t ic_pc_decode_tiles_batch_fronts_workspace_bytes(int C, int th_max, int tw_max, int ntiles, int nvolumes, int k, int nlayers);
+int ic_pc_decode_tiles_batch_fronts_f32(const uint8_t* bitstreams, long long total_bytes, const ic_pc_tile_t* tiles_host, int ntiles,
+                                        const ic_pc_volume_t* volumes_host, int nvolumes, const float* const* wtab_host,
+                                        const float* centers, int k, int L, float resolution, int64_t* symbols, float* q,
+                                        int* status, int C, void* workspace, size_t workspace_bytes, int flags,
+                                        ic_stream_t stream, int channels, int fill_sym,
+                                        const int* layer_ends_host, int nlayers, const ic_pc_seg_t* segs_host);
+size_t ic_pc_decode_tiles_batch_fronts_pertile_workspace_bytes(int C, int th_max, int tw_max, int ntiles, int nvolumes, int k, int nlayers);
+int ic_pc_decode_tiles_batch_fronts_pertile_f32(const uint8_t* bitstreams, long long total_bytes, const ic_pc_tile_t* tiles_host, int ntiles,
+                                                const ic_pc_volume_t* volumes_host, int nvolumes, const float* const* wtab_host,
+                                                const float* centers, int k, int L, float resolution, int64_t* symbols, float* q,
+                                                int* status, int C, void* workspace, size_t workspace_bytes, int flags,
+                                                ic_stream_t stream, const int* tile_channels_host, int fill_sym,
+                                                const int* layer_ends_host, int nlayers, const ic_pc_seg_t* segs_host);
 /* Layered tiles, CONTINUED: every tile from the layer where an earlier call on the same workspace stopped (codec.py, stream: a picture
  * redrawn after each layer of a file that is still arriving decodes every plane once).  When a sweep with a limit ends, the tile's slot
  * of the workspace holds all that the next planes need -- the padded volume and the three activation caches up to the limit -- and the
