@@ -19,10 +19,12 @@
 //   * work-group = 4 waves = 4 channel tiles (one HALF of the output channels) of one segment.  Wave w loads and transforms the
 //     input of k-steps 4 j + w only; the B operands reach the other waves through a two-half LDS ring (72 KB), one barrier per
 //     4 k-steps.  Patch columns: every lane loads its own aligned 4 pixels per patch row, the two outer columns are the neighbour
-//     lanes' values (DPP row shifts; the two ends of the 16-lane tile row load one extra dword).
+//     lanes' column-transformed values (DPP row shifts; the two ends of the 16-lane tile row load one extra dword).
 //   * A operands (transformed filters, 36 x 128 x 128 floats = 2.36 MB per layer) are pre-packed in fragment order: 9 16-byte
 //     loads per k-step and lane, each 1 KB contiguous across the wave, L2 resident, streamed through a register ring.
-//   * zero padding is done by the memory system (raw buffer loads, out-of-range lane offsets), as in the F(2x2) kernels.
+//   * zero padding is done by the memory system (raw buffer loads): a column outside is an out-of-range lane offset, as in the
+//     F(2x2) kernels; a ROW outside is a zero-record descriptor chosen on the scalar unit, and the row step is the scalar offset.
+//   * accumulators: all 144 registers in the VGPR file, never cleared -- the first MFMA into each takes the literal 0 as addend.
 // Shapes: W % 4 == 0 (aligned 16-byte rows); anything else keeps the F(2x2) forms (ic_conv3x3_c128_auto_f32).
 //
 // Where the time goes (in-kernel shader-clock stamps, a build with -DW4_STAMPS, tools/w4prof.py; batch of 8 Kodak-sized maps, two
@@ -32,6 +34,25 @@
 // patch requested ahead of its transform 189 us; the transform of a turn cut into 26 pieces behind MFMAs (loop alone 75 k -> 57 k
 // clocks; no change at full load, where the other wave fills the pipe anyway); epilogue operands two channels ahead and in front
 // of the stores (epilogue 20 k -> 8.5 k clocks) 175 us.  F(2x2) plan on the same input: 242 us.
+//
+// VECTOR INSTRUCTIONS THAT COMPUTE NOTHING (tools/w4_count.py: static count per wave from the gfx950 assembly, loop blocks weighted by
+// their trip count; profiles/w4_vector_diet.md).  The fp32 MFMAs and the vector instructions of a SIMD do not overlap: every non-MFMA
+// vector instruction of either wave costs the SIMD 5-6 clocks of matrix issue (profiles/r05_w4_ablations.md read that way).  The Kodak
+// instantiation <WT, 1, 128, 128> had 2,453 of them per wave against 1,152 MFMAs; 1,882 now, the same operations on the same values
+// (bit-identical outputs: tests/test_gpu_wino4_small.py holds every instantiation family to the bits recorded before):
+//   * accumulators in the VGPR file (W4_ACC_A 0): no v_accvgpr_write to clear them, no v_accvgpr_read in front of the epilogue's
+//     arithmetic (-256).  All instantiations fit 247-256 registers at two waves per SIMD without scratch -- the h12 forms, which
+//     spilled 8-20 bytes with 32 accumulators in AGPRs, included;
+//   * no clear at all: the 36 MFMAs of k-step 0 of iteration 0 have the form `D = A B + 0` (`=&v`, literal 0), all others the tied
+//     form `D += A B` (`+v`); the first pair of iterations stands outside the loop for that;
+//   * patch loads without per-load vector arithmetic: row step in the scalar offset, row validity in the descriptor (load_patch),
+//     -23 per turn; SEG2 keeps one select per load (its row validity is per lane);
+//   * the outer patch columns come across the lanes TRANSFORMED (a tile's column 0 is its left neighbour's column 4): five column
+//     passes per turn instead of six (-12 per turn; transform_put, slice).
+// Measured (one box, libraries alternating): a lone Kodak launch 27.56 -> 27.18 us, 8 maps in one launch level (150.3-151.3 us both),
+// bench step four in flight 234.2 -> 237.0 Mpix/s (+1.2 %, ranges disjoint), one image at a time 174.0 -> 175.7 (+1.0 %).  A fifth of
+// the vector instructions for 1 %: the stamps show the prologue 2.6 k clocks shorter and the loop 1.7 k LONGER (a wave's 98 k clocks
+// unchanged) -- the loop's removed instructions sat in the shadow of MFMAs already; the 5-6-clock rule overstates what they cost.
 //
 // INLINE-ASM MFMAs AND THE COMPILER (round 5; experiment log: profiles/r05_w4_rootcause.md).  The MFMAs below are asm statements so that
 // the accumulator stays tied to the destination.  hipcc orders an asm statement by its operands but does not know it is an MFMA, so it
@@ -56,7 +77,9 @@
 
 #define W4_QUADS 9                                  // 36 positions in quads of 4
 #define W4_PACKED_FLOATS (36 * WN_C * WN_C)
-#define W4_ACC_A 32                                 // accumulators (of 36) kept in AGPRs
+#ifndef W4_ACC_A
+#define W4_ACC_A 0                                  // accumulators (of 36) kept in AGPRs: none -- all 144 registers in the VGPR file (below: "Accumulators")
+#endif
 // tuning knobs (defaults = the measured best, round 4: 4 waves, round 5: rings 9 / 3, turn at quad 6, transform 10 quads after its request)
 #ifndef W4_RA
 #define W4_RA 9                                     // filter-fragment ring, in quads (36 % W4_RA == 0); round 5: 6 -> 9 (below)
@@ -259,13 +282,19 @@ void wino4_3x3_kernel(const WnArgs a) {
     const int tx = SEG2 ? 8 * sx + (n16 & 7) : 16 * sx + n16;
     const int H = a.H, W = a.W, HW = H * W;
 
-    const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc((void*)(a.x + (size_t)n * CIN * HW), 0, CIN * HW * 4, 0x00020000);
+    // The input's descriptor starts ONE ROW above the image (and is one row longer): a patch row r in -1 .. H + 3 is the scalar offset
+    // (r + 1) W 4 >= 0, the lane offsets carry the column only.  (The row above is never read: row validity, below.)
+    const float* xb = a.x + (size_t)n * CIN * HW - W;
+    const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc((void*)xb, 0, (CIN * HW + W) * 4, 0x00020000);
+    const __amdgpu_buffer_rsrc_t xz = __builtin_amdgcn_make_buffer_rsrc((void*)xb, 0, 0, 0x00020000);      // no records: every load returns 0, no memory access
     const __amdgpu_buffer_rsrc_t fr = __builtin_amdgcn_make_buffer_rsrc((void*)a.wp, 0, 36 * CIN * COUT * 4, 0x00020000);
     // patch rows 4 ty - 1 .. 4 ty + 4: own aligned 4 pixels (columns 4 tx .. 4 tx + 3); the end lanes of a tile row also fetch the
     // column outside (first lane: 4 tx - 1, last lane: 4 tx + 4), every other lane gets an out-of-range offset there.
-    // Row validity is wave-uniform (SEG2: one value per half), column validity per lane: ONE lane offset for the patch's first row
-    // (out of range when the tile lies beyond the map) and one for the end column; a row outside the image swaps in the
-    // out-of-range offset by a scalar condition.
+    // Row validity is wave-uniform (SEG2: one value per half), column validity per lane.  The ROW lives on the scalar unit: its
+    // step in the scalar offset, its validity in the choice between the image's descriptor and a zero-record one (as the epilogue
+    // does for an absent residual) -- no vector instruction per load (rounds 4-6: an add and a select for each of the 12).  The two
+    // lane offsets, one for the own pixels (out of range when the tile lies beyond the map) and one for the end column, are the same
+    // for all six rows.  SEG2: a lane's row is 4 hrow further down (in its lane offsets) and valid by its half: one select per load.
     const bool col_ok = 4 * tx < W;
     const bool first_lane = SEG2 ? (n16 & 7) == 0 : n16 == 0, last_lane = SEG2 ? (n16 & 7) == 7 : n16 == 15;
     const bool mid_l = SEG2 && n16 == 8, mid_r = SEG2 && n16 == 7;       // lanes whose DPP neighbour belongs to the other tile row
@@ -274,23 +303,18 @@ void wino4_3x3_kernel(const WnArgs a) {
     const int tyr = SEG2 ? 2 * ty : ty;                           // (first) tile row of the segment: scalar
     const int r_first = 4 * tyr - 1;
     // (offsets are formed in int: r_first may be -1; the rows actually used are >= 0)
-    const int obase = (kq * HW + (r_first + 4 * hrow) * W + 4 * tx) * 4;
-    const int ebase = (kq * HW + (r_first + 4 * hrow) * W + ecol) * 4;
+    const unsigned obase = col_ok ? (unsigned)((kq * HW + 4 * hrow * W + 4 * tx) * 4) : WN_OOB;
+    const unsigned ebase = e_ok ? (unsigned)((kq * HW + 4 * hrow * W + ecol) * 4) : WN_OOB;
     const unsigned fo = (unsigned)lane * 16u;
 
     // Accumulators are tied to the MFMA's destination by inline asm: the builtin lets the allocator put the result into ANOTHER
     // tuple than the addend, which doubles the accumulator footprint for the duration and pushes the rings into scratch.
+    // Accumulators: all 36 (144 registers) in the VGPR file (W4_ACC_A 0; rounds 4-6 kept 32 of them in AGPRs, which cost a
+    // v_accvgpr_write per register to clear them and a v_accvgpr_read per register in the epilogue: 256 vector instructions per wave
+    // that compute nothing -- the MFMA takes its addend from either file, the epilogue's arithmetic only from this one).
+    // They are never cleared: the FIRST MFMA into each -- the 36 of k-step 0 of iteration 0 -- takes the literal 0 as its addend
+    // (`first` in iteration() below; 0 + a b accumulates exactly as 0-initialised registers would).
     f32x4 acc[36];
-#pragma unroll
-    for (int p = 0; p < 36; ++p) acc[p] = f32x4{0.f, 0.f, 0.f, 0.f};
-    // (at two waves per SIMD the compiler splits the 256 registers of a wave 128 : 128 between the two files: 32 of the 36
-    // accumulators sit in AGPRs, the last four in VGPRs -- the MFMA takes its addend from either file)
-#pragma unroll
-    for (int p = 0; p < 36; ++p) {
-        if (p < W4_ACC_A) asm volatile("" : "+a"(acc[p]));
-        else asm volatile("" : "+v"(acc[p]));
-    }
-    __builtin_amdgcn_sched_barrier(0);
 
     // B-operand reads of ring half 1 (byte offsets 0x9000 .. 0x12000): a ds_read's immediate offset has 16 bits, so the compiler keeps
     // one address register per 1 KB quad beyond 0x10000 -- eight of them through the whole loop (the 4-wave form has the room, the
@@ -306,43 +330,53 @@ void wino4_3x3_kernel(const WnArgs a) {
     f32x4 pr[6];            // own 4 pixels of the 6 patch rows
     float pe[6];            // the column outside (lanes 0 / 15 of a tile row)
     auto load_patch = [&](int ks) __attribute__((always_inline)) {
-        const int so = ks * 4 * HW * 4;                           // scalar: channels 4 ks ..
-        // the 12 lane offsets are re-derived from two registers at every call: hoisted out of the loop (which the compiler does
-        // on its own) they would sit in 12 registers next to 144 accumulators and spill
-        int ob = obase, eb = ebase;
-        asm volatile("" : "+v"(ob), "+v"(eb));
-        // (Round 5: a second path for segments whose six patch rows all lie inside the image -- row steps in the SCALAR offset, the two
-        // lane offsets carrying only the column's validity, no vector instruction per load instead of an add and a select -- was
-        // slower: one image at a time 163.2 against 171.0 Mpix/s, 8 Kodak maps 183.3 against 179.7 us.  Removed.)
+        const int so = (ks * 4 * HW + (r_first + 1) * W) * 4;     // scalar: channels 4 ks .., patch row 0 (counted from the row above the image)
+        // SEG2: the 12 selected lane offsets are re-derived from two registers at every call: hoisted out of the loop (which the
+        // compiler does on its own) they would sit in 12 registers next to 144 accumulators and spill
+        unsigned ob = obase, eb = ebase;
+        if (SEG2) asm volatile("" : "+v"(ob), "+v"(eb));
+        // (Round 5 had this form as a SECOND path, for segments whose six patch rows all lie inside the image, next to the one with an
+        // add and a select per load, and lost -- one image at a time 163.2 against 171.0 Mpix/s: two copies of the loop.  It is the
+        // only path now.)
 #pragma unroll
         for (int i = 0; i < 6; ++i) {
             const bool row_lo = r_first + i >= 0 && r_first + i < H;          // scalar
             const bool row_hi = r_first + 4 + i < H;                          // scalar: the same patch row of the segment's second tile row
-            const bool row_ok = SEG2 ? (hrow ? row_hi : row_lo) : row_lo;
-            const unsigned o1 = (row_ok && col_ok) ? (unsigned)(ob + i * W * 4) : WN_OOB;
-            const unsigned o2 = (row_ok && e_ok) ? (unsigned)(eb + i * W * 4) : WN_OOB;
-            pr[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(xr, o1, so, 0));
-            pe[i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(xr, o2, so, 0));
+            if (SEG2) {
+                const bool row_ok = hrow ? row_hi : row_lo;
+                pr[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(xr, row_ok ? ob : WN_OOB, so + i * W * 4, 0));
+                pe[i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(xr, row_ok ? eb : WN_OOB, so + i * W * 4, 0));
+            } else {
+                const __amdgpu_buffer_rsrc_t xi = row_lo ? xr : xz;
+                pr[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(xi, ob, so + i * W * 4, 0));
+                pe[i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(xi, eb, so + i * W * 4, 0));
+            }
         }
     };
     // Bt d B of this lane's patch -> ring[half][st = wave][quad][lane].  In place on 36 registers: columns first (each 6 -> 6),
     // then rows, a pair of rows = three position quads written as soon as it is complete; the phases are fenced so that the
     // scheduler does not interleave them (36 accumulators + rings leave ~50 registers for all of this)
     auto transform_put = [&](int half) __attribute__((always_inline)) {
+        // The two outer patch columns are the neighbour lanes' columns 4 and 1, and so are their column transforms: the lanes transform
+        // their own four columns and the end column (one pass serves both ends of the tile row), and the TRANSFORMED outer columns
+        // come across by DPP -- five column passes instead of six, the same operations on the same values.
         float u[6][6];
 #pragma unroll
-        for (int i = 0; i < 6; ++i) {
-            u[i][0] = dpp_from_left(pe[i], pr[i][3]);            // column 4 tx - 1 = the left neighbour's last pixel
-            u[i][5] = dpp_from_right(pe[i], pr[i][0]);           // column 4 tx + 4 = the right neighbour's first pixel
-            if (SEG2) { u[i][0] = mid_l ? pe[i] : u[i][0]; u[i][5] = mid_r ? pe[i] : u[i][5]; }     // the row's middle is an end too
-            u[i][1] = pr[i][0]; u[i][2] = pr[i][1]; u[i][3] = pr[i][2]; u[i][4] = pr[i][3];
-        }
+        for (int i = 0; i < 6; ++i) { u[i][1] = pr[i][0]; u[i][2] = pr[i][1]; u[i][3] = pr[i][2]; u[i][4] = pr[i][3]; }
+        w4_bt(pe[0], pe[1], pe[2], pe[3], pe[4], pe[5], pe[0], pe[1], pe[2], pe[3], pe[4], pe[5]);
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int j = 0; j < 6; ++j) {
+        for (int j = 1; j < 5; ++j) {
             w4_bt(u[0][j], u[1][j], u[2][j], u[3][j], u[4][j], u[5][j], u[0][j], u[1][j], u[2][j], u[3][j], u[4][j], u[5][j]);
             __builtin_amdgcn_sched_barrier(0);
         }
+#pragma unroll
+        for (int i = 0; i < 6; ++i) {
+            u[i][0] = dpp_from_left(pe[i], u[i][4]);             // column 4 tx - 1 = the left neighbour's last column
+            u[i][5] = dpp_from_right(pe[i], u[i][1]);            // column 4 tx + 4 = the right neighbour's first column
+            if (SEG2) { u[i][0] = mid_l ? pe[i] : u[i][0]; u[i][5] = mid_r ? pe[i] : u[i][5]; }     // the row's middle is an end too
+        }
+        __builtin_amdgcn_sched_barrier(0);
         f32x4* dst = &ring[((half * 4 + pw) * W4_QUADS) * 64 + lane];
 #pragma unroll
         for (int x = 0; x < 6; x += 2) {
@@ -360,7 +394,8 @@ void wino4_3x3_kernel(const WnArgs a) {
     // instructions placed directly behind an MFMA -- the matrix pipe works 8 passes (32 clocks) on it, the vector unit is free for 7
     // instructions of the same wave meanwhile.  As one block the ~200 instructions of a turn stop the wave's MFMA issue for ~2 k
     // clocks, 8 times per work-group (stamps: loop 75 k clocks with nothing else on the SIMD against 37 k of MFMA issue).
-    //   k = 0: the outer patch columns from the neighbour lanes;  k = 1 .. 6: Bt over columns 0, 5, 1, 2, 3, 4 (in place);
+    //   k = 0: Bt over the end column pe[] (in place);  k = 1, 2, 4, 5: Bt over the own columns 1, 4, 2, 3 (in place);
+    //   k = 3: the transformed outer columns 0 / 5 from the neighbour lanes' columns 4 / 1 (the end lanes: pe[]);  k = 6: nothing;
     //   k = 7 .. 12: Bt over row k - 7, written to the ring as soon as a position quad is complete.
     // Same operations in the same order per value as transform_put: bit-identical.
     // (Round 5: the same slices cut finer -- four parts of ~3 instructions, one behind EVERY MFMA of a quad instead of six behind two of
@@ -377,21 +412,27 @@ void wino4_3x3_kernel(const WnArgs a) {
     };
     auto slice = [&](int k, int part, int half) __attribute__((always_inline)) {
         if (k == 0) {
+            if (part == 0) {
+#pragma unroll
+                for (int i = 0; i < 6; ++i) { su[i][1] = pr[i][0]; su[i][2] = pr[i][1]; su[i][3] = pr[i][2]; su[i][4] = pr[i][3]; }
+                bt_first(pe[0], pe[1], pe[2], pe[3], pe[4]);
+            } else bt_second(pe[1], pe[3], pe[5], pe[0], pe[1], pe[2], pe[3], pe[4], pe[5]);
+        } else if (k == 3) {
 #pragma unroll
             for (int i = 0; i < 6; ++i) {
                 if (part == 0) {
-                    su[i][0] = dpp_from_left(pe[i], pr[i][3]);
+                    su[i][0] = dpp_from_left(pe[i], su[i][4]);
                     if (SEG2) su[i][0] = mid_l ? pe[i] : su[i][0];
                 } else {
-                    su[i][5] = dpp_from_right(pe[i], pr[i][0]);
+                    su[i][5] = dpp_from_right(pe[i], su[i][1]);
                     if (SEG2) su[i][5] = mid_r ? pe[i] : su[i][5];
-                    su[i][1] = pr[i][0]; su[i][2] = pr[i][1]; su[i][3] = pr[i][2]; su[i][4] = pr[i][3];
                 }
             }
-        } else if (k <= 6) {
-            const int c = k == 1 ? 0 : (k == 2 ? 5 : k - 2);
+        } else if (k < 6) {
+            const int c = k == 1 ? 1 : (k == 2 ? 4 : k - 2);
             if (part == 0) bt_first(su[0][c], su[1][c], su[2][c], su[3][c], su[4][c]);
             else bt_second(su[1][c], su[3][c], su[5][c], su[0][c], su[1][c], su[2][c], su[3][c], su[4][c], su[5][c]);
+        } else if (k == 6) {
         } else {
             const int x = k - 7;
             if (part == 0) bt_first(su[x][0], su[x][1], su[x][2], su[x][3], su[x][4]);
@@ -551,7 +592,8 @@ void wino4_3x3_kernel(const WnArgs a) {
 #pragma unroll
     for (int q0 = 0; q0 < W4_RB - 1; ++q0) bq[q0] = ring_rd(0, q0);
     // `produce`: this wave prepares its k-step of the next iteration in this one (always in the 4-wave form; WG8: the group of the next half)
-    auto iteration = [&](const int j, const int u2, const bool last, const bool produce) __attribute__((always_inline)) {      // reads ring half u2
+    // `first`: iteration 0, whose first k-step starts the accumulators (see "Accumulators" above)
+    auto iteration = [&](const int j, const int u2, const bool last, const bool produce, const bool first = false) __attribute__((always_inline)) {      // reads ring half u2
         if (WG8 && W4_WG8_FLAGS && j > 0) flag_wait(u2, 4u * ((unsigned)(j + 1) >> 1));       // RAW: this half is complete
         if (!W4_SOFT && j > 0) {
 #pragma unroll
@@ -564,7 +606,10 @@ void wino4_3x3_kernel(const WnArgs a) {
             const int sk = lq - (W4_TURN + W4_GAP);               // slice of the spread turn that rides on this quad
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                if (4 * q + i < W4_ACC_A) asm volatile("v_mfma_f32_16x16x4_f32 %0, %1, %2, %0" : "+a"(acc[4 * q + i]) : "v"(fa[lq % W4_RA][i]), "v"(bq[lq % W4_RB][i]));
+                if (first && lq < W4_QUADS) {                     // k-step 0 of iteration 0: the accumulator's first MFMA, addend 0 (early clobber: never on top of an operand)
+                    if (4 * q + i < W4_ACC_A) asm volatile("v_mfma_f32_16x16x4_f32 %0, %1, %2, 0" : "=&a"(acc[4 * q + i]) : "v"(fa[lq % W4_RA][i]), "v"(bq[lq % W4_RB][i]));
+                    else asm volatile("v_mfma_f32_16x16x4_f32 %0, %1, %2, 0" : "=&v"(acc[4 * q + i]) : "v"(fa[lq % W4_RA][i]), "v"(bq[lq % W4_RB][i]));
+                } else if (4 * q + i < W4_ACC_A) asm volatile("v_mfma_f32_16x16x4_f32 %0, %1, %2, %0" : "+a"(acc[4 * q + i]) : "v"(fa[lq % W4_RA][i]), "v"(bq[lq % W4_RB][i]));
                 else asm volatile("v_mfma_f32_16x16x4_f32 %0, %1, %2, %0" : "+v"(acc[4 * q + i]) : "v"(fa[lq % W4_RA][i]), "v"(bq[lq % W4_RB][i]));
                 if (WG8 && !last && sk == 0 && i == 0) kill_slices();       // (see kill_slices)
                 if (W4_SPREAD && produce && !(W4_ABL & 4) && i < (W4_SLICE1 ? 1 : 2) && sk >= 0 && sk < 13) {      // (W4_ABL & 4: no transform at all)
@@ -607,7 +652,10 @@ void wino4_3x3_kernel(const WnArgs a) {
     };
     // WG8: the group of the NEXT ring half produces in an iteration -- a scalar branch around each of its 13 slices and its patch request
     // (two copies of the loop, one per group, made the allocator spill 174 registers: tried)
-    for (int jj = 0; jj < IT - 2; jj += 2) {
+    // (the first pair of iterations stands outside the loop: its 36 first MFMAs have another form)
+    iteration(0, 0, false, !WG8 || grp == 1, true);
+    iteration(1, 1, false, !WG8 || grp == 0);
+    for (int jj = 2; jj < IT - 2; jj += 2) {
         iteration(jj, 0, false, !WG8 || grp == 1);
         iteration(jj + 1, 1, false, !WG8 || grp == 0);
     }
@@ -812,7 +860,8 @@ extern "C" long long ic_wino4_launch_stamps_count(void) { return g_w4_ls_launch.
 #endif
 
 extern "C" int ic_wino4_3x3_c128_supported(int N, int H, int W) {
-    return N > 0 && H > 0 && W > 0 && (W & 3) == 0 && (long long)WN_C * H * W * 4 < (1ll << 31);
+    // (one row more than the image: the input's descriptor starts a row above it, and every offset inside it must stay below WN_OOB)
+    return N > 0 && H > 0 && W > 0 && (W & 3) == 0 && ((long long)WN_C * H * W + W) * 4 < (1ll << 31);
 }
 
 // segments of 16 tiles: 1 x 16 (wide maps) or 2 x 8 -- whichever covers the map with fewer of them (a tie keeps 1 x 16)
@@ -931,7 +980,7 @@ extern "C" int ic_wino4_3x3_c128_bn_act_f32(const float* x, const float* w_packe
 // holds X[c][2 i + py][2 j + px]; h1 writes it that way on request, ic_space_to_depth2_f32 makes it from a plain tensor) -> y [N][128][H][W].
 // h12 (autoencoder.py:264): x [N][128][H][W] -> y [N][64][2H][2W], plain layouts.  W % 4 == 0; 10.07 GFLOP direct -> 3.62 executed.
 extern "C" int ic_wino4_conv5s2_supported(int N, int H, int W) {
-    return N > 0 && H > 0 && W > 0 && (W & 3) == 0 && (long long)256 * H * W * 4 < (1ll << 31);
+    return N > 0 && H > 0 && W > 0 && (W & 3) == 0 && ((long long)256 * H * W + W) * 4 < (1ll << 31);
 }
 extern "C" long long ic_wino4_conv5s2_workgroups(int N, int H, int W, int transposed) {
     if (!ic_wino4_conv5s2_supported(N, H, W)) return 0;
