@@ -183,6 +183,10 @@ PROTOTYPES = {
     'ic_pc_decode_tiles_batch_layers_resume_f32': (c_int, [c_void_p, c_longlong, c_void_p, c_int, c_void_p, c_int, POINTER(c_void_p), c_void_p,
                                                            c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_size_t,
                                                            c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p]),
+    'ic_pc_decode_tiles_batch_fronts_resume_workspace_bytes': (c_size_t, [c_int] * 7),
+    'ic_pc_decode_tiles_batch_fronts_resume_f32': (c_int, [c_void_p, c_longlong, c_void_p, c_int, c_void_p, c_int, POINTER(c_void_p), c_void_p,
+                                                           c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_size_t,
+                                                           c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p]),
     'ic_pc_encode_segments_f32': (c_int, [c_void_p, c_void_p, c_int, c_longlong, c_int, c_float, c_void_p, c_int, c_void_p, c_longlong,
                                           c_void_p, c_void_p, c_void_p]),
     'ic_pc_conceal_tiles_workspace_bytes': (c_size_t, [c_int, c_int, c_longlong]),

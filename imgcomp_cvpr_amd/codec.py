@@ -8,6 +8,7 @@
     python -m imgcomp_cvpr_amd.codec decompress-dir IN_DIR OUT_DIR [--batch N] [--salvage | --channels K | --partial | --recover]    every *.icf -> OUT_DIR/<stem>.png
     python -m imgcomp_cvpr_amd.codec verify PATH [PATH ...]         files or directories of *.icf: the checksums, without model or device
     python -m imgcomp_cvpr_amd.codec stream IN.icf OUT_DIR [model options] [--chunk BYTES]    a format-6 file fed chunk by chunk, a picture per gained layer
+    python -m imgcomp_cvpr_amd.codec stream IN.icf OUT_DIR --fronts [model options] [--chunk BYTES]    the same for a format-6 or a format-8 file
 
 compress:   pad to a multiple of the subsampling factor (val.add_padding) -> ae.encode -> PredictionNetwork.encode_stream (the
             range coder on the device, ic_pc_encode_f32) -> container.
@@ -113,7 +114,7 @@ own cuts; e_0 = 1 on a 1 x 1 tile gives an empty segment, the one byte 0x80).  T
 format-5 file steps through, so the bytes [0, layer_prefix_bytes(g)) decode as that preview a front at a time
 (ic_pc_decode_tiles_batch_fronts_f32 restarts the coder at each cut).  The price: a layer's prefix also carries the symbols of later
 channels that share its fronts, so the early prefixes are longer than format 6's; nothing is coded twice.  decompress, --channels,
---partial, --recover and verify read it as they read format 6; --salvage and stream do not.
+--partial, --recover and verify read it as they read format 6, and so does stream --fronts; --salvage and stream without it do not.
 stream (Codec.open_stream -> StreamDecoder): a format-6 file that is still arriving.  feed(chunk) takes the bytes as they come, image()
 gives recover's picture and report of the bytes so far -- but the decoder goes on where the last image() stopped: the session
 (PredictionNetwork.open_layers) keeps every tile's decoder workspace on the device and ic_pc_decode_tiles_batch_layers_resume_f32
@@ -121,6 +122,10 @@ continues each tile at the first layer it has gained (resume_plan), so a viewer 
 plane once, not once per redraw.  The command feeds IN.icf in chunks of --chunk bytes (default 16384), as a download would, and
 writes OUT_DIR/<stem>.<bytes fed, 9 digits>.png with a recover line each time a tile has gained a layer; the last picture of an intact
 file is decompress's.
+stream --fronts (Codec.open_stream(fronts=True)): a format-8 file is streamed too.  The session is opened with the file's ends as front
+ends and ic_pc_decode_tiles_batch_fronts_resume_f32 continues every tile's front sweep behind the last front of the layers it held, so
+every front is swept once: the 191 steps of a (32, 16, 16) tile in all, where a --recover per redraw at the four default layer ends
+takes 79 + 95 + 127 + 191.  Opt-in: without --fronts a format-8 file is refused as before.  A format-6 file streams the same either way.
 """
 import argparse
 import io
@@ -761,8 +766,9 @@ def resume_plan(done_layers, now_layers, layer_ends):
     return (done if done <= now else 0), int(layer_ends[now - 1])
 
 
-def stream_header_bytes(data):
-    """the length of the header of the format-6 file that begins with `data` (magic up to and including the header CRC), or None
+def stream_header_bytes(data, fronts=False):
+    """the length of the header of the format-6 file (fronts=True: format-6 or format-8 file, which share the layout) that begins with
+    `data` (magic up to and including the header CRC), or None
     while `data` is too short to tell.  A ValueError as soon as the bytes cannot be the beginning of a format-6 file: wrong magic,
     another format (parse_recover's words), a layer count or a tile count that does not fit the rest.  Nothing is checked that the
     whole header's own CRC covers: parse_recover does that once the header is there."""
@@ -772,10 +778,11 @@ def stream_header_bytes(data):
     if len(data) < 6:
         return None
     version, = struct.unpack('<H', data[4:6])
-    if version == FORMAT_VERSION_FRONTS:
-        raise ValueError('format version {} (front-layered tiles) is not streamed: a front-ordered decode is not resumed yet; decompress '
-                         '--recover (Codec.recover) reads what has arrived of such a file'.format(version))
-    if version != FORMAT_VERSION_LAYERED:
+    if version == FORMAT_VERSION_FRONTS and not fronts:
+        raise ValueError('format version {} (front-layered tiles) is not streamed without --fronts (open_stream(fronts=True)), which '
+                         'continues a front-ordered decode; decompress --recover (Codec.recover) also reads what has arrived of such '
+                         'a file'.format(version))
+    if version != FORMAT_VERSION_LAYERED and not (fronts and version == FORMAT_VERSION_FRONTS):
         parse_recover(data + bytes(_MIN_SIZE))            # another format: its refusal, whatever the length so far
         raise ValueError('header damaged: format version {} is not the layered version {}'.format(version, FORMAT_VERSION_LAYERED))
     if len(data) < 8:
@@ -1405,9 +1412,10 @@ class Codec(object):
                 out[i] = (self._crop(x, heads[i][0]), self._recover_report(heads[i], tiles))
         return out
 
-    def open_stream(self, max_workspace_bytes=1 << 31):
-        """a StreamDecoder: a format-6 file fed as it arrives, recover's picture of the bytes so far, every layer decoded once"""
-        return StreamDecoder(self, max_workspace_bytes)
+    def open_stream(self, max_workspace_bytes=1 << 31, fronts=False):
+        """a StreamDecoder: a format-6 file fed as it arrives, recover's picture of the bytes so far, every layer decoded once;
+        fronts=True: a format-8 file is taken as well, every front swept once"""
+        return StreamDecoder(self, max_workspace_bytes, fronts=fronts)
 
     def compress_file(self, image_path, out_path):
         from PIL import Image
@@ -1440,10 +1448,13 @@ class StreamDecoder(object):
     image(): (HWC uint8 image, RecoverReport), equal to Codec.recover(the bytes so far).  The first call opens the session
         (PredictionNetwork.open_layers); every call decodes, per tile, only the layers gained since the last one, conceals per (tile,
         channel) and runs one autoencoder pass.  ValueError('no complete layer ...') while no tile has a layer.  Without a new layer in
-        any tile the last picture is returned again and nothing is launched (the report is that of the bytes so far)."""
+        any tile the last picture is returned again and nothing is launched (the report is that of the bytes so far).
+    fronts=True: a format-8 file is streamed as well, its session opened with the file's ends as front ends
+        (ic_pc_decode_tiles_batch_fronts_resume_f32); a format-6 file streams as with fronts=False.  Without it a format-8 file is
+        refused by the feed that shows its version."""
 
-    def __init__(self, codec, max_workspace_bytes=1 << 31):
-        self.codec, self.max_workspace_bytes = codec, int(max_workspace_bytes)
+    def __init__(self, codec, max_workspace_bytes=1 << 31, fronts=False):
+        self.codec, self.max_workspace_bytes, self.fronts = codec, int(max_workspace_bytes), bool(fronts)
         self._buf = bytearray()
         self._header = None            # its length, once known
         self._ready = False
@@ -1460,7 +1471,7 @@ class StreamDecoder(object):
         if self._ready:
             return True
         if self._header is None:
-            self._header = stream_header_bytes(self._buf[:1 << 18])          # (the fields that give the length end below 2^18)
+            self._header = stream_header_bytes(self._buf[:1 << 18], fronts=self.fronts)      # (the fields that give the length end below 2^18)
         if self._header is None or len(self._buf) < self._header:
             return False
         self._parsed()                 # the header's CRC, the model checks: raises what recover raises
@@ -1486,7 +1497,7 @@ class StreamDecoder(object):
         codec = self.codec
         if self._last is None or self._last[0] != layers:
             if self._session is None:
-                self._session = codec.pred.open_layers([(c.C, c.h, c.w)], c.th, c.tw, c.layer_ends, self.max_workspace_bytes)
+                self._session = codec.pred.open_layers([(c.C, c.h, c.w)], c.th, c.tw, max_workspace_bytes=self.max_workspace_bytes, **_ends_kw(c))
             qs, held = self._session.advance([(c.streams, c.first_syms)], [layers], want='q')
             x_out = codec.ae.decode(qs[0][None], is_training=False).to(torch.uint8)      # tf.cast truncates (val.py)
             self._last = (layers, codec._crop(x_out[0], c), held[0])
@@ -1539,13 +1550,15 @@ def _recover_line(path, report):
 
 def check_option_args(flags):
     """--checked / --wavefront / --salvage / --channels / --layers / --progressive / --front-layers / --front-progressive / --partial /
-    --recover / --chunk against the command, --tile
+    --recover / --chunk / --fronts against the command, --tile
     and each other: decided before any model is built"""
     if getattr(flags, 'chunk', None) is not None:
         if flags.command != 'stream':
             raise ValueError('--chunk belongs to stream: the size of the pieces the file is fed in')
         if flags.chunk < 1:
             raise ValueError('--chunk {} is not at least 1'.format(flags.chunk))
+    if getattr(flags, 'fronts', False) and flags.command != 'stream':
+        raise ValueError('--fronts belongs to stream: it lets a front-layered file (format 8) be streamed as well')
     if flags.command == 'stream':
         for name in ('salvage', 'partial', 'recover'):
             if getattr(flags, name, False):
@@ -1901,7 +1914,7 @@ def _main_stream(flags, codec):
         data = f.read()
     chunk = STREAM_CHUNK if flags.chunk is None else flags.chunk
     stem = os.path.splitext(os.path.basename(flags.input))[0]
-    dec, shown = codec.open_stream(), None
+    dec, shown = codec.open_stream(fronts=getattr(flags, 'fronts', False)), None
     for pos in range(0, len(data), chunk):
         if not dec.feed(data[pos:pos + chunk]):
             continue
@@ -1963,6 +1976,8 @@ def main(argv=None):
                         'after them, the other channels get the centre nearest zero); not with --salvage')
     p.add_argument('--chunk', type=int, default=None, metavar='BYTES',
                    help='stream: feed the file in pieces of this many bytes (default {})'.format(STREAM_CHUNK))
+    p.add_argument('--fronts', action='store_true', help='stream: take a front-layered file (format 8) as well, every front of every tile '
+                                                         'swept once; without it such a file is refused')
     flags = p.parse_args(argv)
     from . import config_parser, val, weights as _weights
     try:

@@ -8,7 +8,8 @@
 // ic_pc_decode_tiles_batch_layers_pertile_f32 does so with a channel limit per tile (recovery of damaged or cut layered files);
 // ic_pc_decode_tiles_batch_layers_resume_f32 continues every tile at the layer where an earlier call on the same workspace stopped;
 // ic_pc_decode_tiles_batch_fronts_f32 and ic_pc_decode_tiles_batch_fronts_pertile_f32 read every tile's wavefront-ordered stream as
-// segments cut at fronts (container format 8), with one channel limit or one per tile.
+// segments cut at fronts (container format 8), with one channel limit or one per tile;
+// ic_pc_decode_tiles_batch_fronts_resume_f32 continues every tile's front sweep at the layer end where an earlier call stopped.
 #include "common.h"
 #include "pc_table.h"
 #include "pc_internal.h"
@@ -796,12 +797,28 @@ __device__ __forceinline__ void pc_wave_chain(const float* __restrict__ in, int 
 // above t_g of any layer that ends at or above cdec: only the segments of layers that begin below cdec are read.  Everything a later
 // front needs -- V and the three caches -- is in the slot and the coder starts afresh at each cut, so a sweep that stopped at a layer
 // end could be continued by a later launch, as the raster FROM sweep is.  SEG = false reads none of this and is the decoder as before.
-template <bool SYMS, bool LIM = false, bool SEG = false>
+// FROM = true (ic_pc_decode_tiles_batch_fronts_resume_f32; only with LIM && SEG): gfrom is the layer the tile continues with, uniform
+// like cdec.  gfrom == 0 is the sweep from the start.  gfrom > 0: an earlier launch has run this tile's loop up to T = T_base + 4 cfrom,
+// cfrom = ends[gfrom - 1] -- the T_cut of layer gfrom - 1 -- and has left V and the caches in the slot; this loop runs
+// T = T_base + 4 cfrom + 1 .. T_last(cdec).  Nothing of that launch's LDS or registers is needed.  s_logits is written and read within a
+// chunk and s_centers is loaded again.  A step reads V and the caches at fronts below its own only (T - 1, T - 7, T - 14, T - 21 and less):
+// phases 1 - 3 of the first step read voxels of earlier steps, which are in the slot whichever launch ran them, and write the voxels of
+// fronts T - 7, T - 14, T - 21, which no earlier step wrote.  The coder needs no state: the first step has T > T_cut, so the cut branch in
+// front of phase 4 initialises it on segment gfrom before the first symbol is decoded, exactly as in the middle of a sweep.  Until then
+// s holds a coder at rest, and no segment below gfrom -- segment 0 included -- is initialised from or read.
+// What the raster FROM sweep does not have to carry: the sweep to cfrom has stepped through symbols of channels >= cfrom (those that
+// share its fronts).  Their centres are in V, but they were not stored through out and this sweep does not come to them again.  So the
+// FROM sweeps keep every symbol they decode in `plane`, a byte per symbol in the slot's part of the workspace, (c, y, x) order of
+// the tile, and store nothing through out: the caller copies [cfrom, cdec) out of the plane behind the body.  A byte of the plane is
+// only ever copied out, never used as an index.  FROM = false reads none of this and is the decoder as before.
+template <bool SYMS, bool LIM = false, bool SEG = false, bool FROM = false>
 __device__ __forceinline__ void pc_dec_wave_body(const PcCachedArgs& f, const unsigned char* bits, long long nbytes, int h, int w, int first_sym,
                                                  float* vol, float* c0, float* c1, float* c2, int* status,
                                                  long long* __restrict__ out, long long out_cs, int out_rs, int cdec = 0,
                                                  const unsigned char* seg_base = nullptr, const ic_pc_seg_t* __restrict__ segs = nullptr,
-                                                 const int* __restrict__ ends = nullptr, int nlayers = 0) {
+                                                 const int* __restrict__ ends = nullptr, int nlayers = 0, int gfrom = 0,
+                                                 unsigned char* __restrict__ plane = nullptr) {
+    static_assert(!FROM || (LIM && SEG), "a sweep continues at a layer cut of a limited sweep");
     constexpr int K = 24, G = K / 4, CH = 64;             // CH: candidates of a front whose logits are in LDS at once
     __shared__ float s_logits[CH][16];
     __shared__ float s_centers[16];
@@ -809,10 +826,21 @@ __device__ __forceinline__ void pc_dec_wave_body(const PcCachedArgs& f, const un
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int L = a.L, C = a.C;
     if (tid < L) s_centers[tid] = a.centers[tid];
+    bool resumed = false;
+    int cfrom = 0;
+    if constexpr (FROM) {
+        resumed = gfrom > 0;
+        if (resumed) cfrom = ((const __attribute__((address_space(4))) int*)ends)[gfrom - 1];
+    }
     PcDecState s;                                         // wave 0 keeps the coder state, identical in all its lanes
-    pc_dec_state_init(s, bits, nbytes);
-    if (wave == 0)
-        for (int i = 0; i < PC_AC_BITS; ++i) s.code = (s.code << 1) | (unsigned)pc_dec_bit(bits, nbytes, s);
+    if (!resumed) {
+        pc_dec_state_init(s, bits, nbytes);
+        if (wave == 0)
+            for (int i = 0; i < PC_AC_BITS; ++i) s.code = (s.code << 1) | (unsigned)pc_dec_bit(bits, nbytes, s);
+    } else {                                              // a coder at rest: the first step's cut initialises it on segment gfrom
+        s.low = 0; s.high = (1ull << PC_AC_BITS) - 1; s.code = 0;
+        s.byte_pos = -1; s.bit_left = 0; s.cur_byte = 0; s.nxt_byte = 0; s.error = 0; s.next = 1;
+    }
     const int PH = h + 8, PW = w + 8;
     const int N0i = h + 6, N0j = w + 6, N1i = h + 4, N1j = w + 4, N2i = h + 2, N2j = w + 2;
     const int T_last = (w + 3) + 2 * (h + 3) + 4 * ((LIM ? cdec : C) + 3);    // the last symbol's front (LIM: of channel cdec - 1)
@@ -823,8 +851,10 @@ __device__ __forceinline__ void pc_dec_wave_body(const PcCachedArgs& f, const un
     const int T_base = (w - 1) + 2 * (h - 1) - 4 + 28;                        // T of front t_g is T_base + 4 ends[g]
     int seg_next = 1, T_cut = 0x7fffffff, sticky = 0;
     if constexpr (SEG) T_cut = nlayers > 1 ? T_base + 4 * ((int_cptr)ends)[0] : 0x7fffffff;
+    int T_first = 7;
+    if constexpr (FROM) if (resumed) { seg_next = gfrom; T_cut = T_base + 4 * cfrom; T_first = T_cut + 1; }
     __syncthreads();
-    for (int T = 7; T <= T_last; ++T) {
+    for (int T = T_first; T <= T_last; ++T) {
         {   // ---- 1: A0, first mask (13 live taps = TF taps 0..12), + bias, ReLU ----
             const PcFront fr = pc_front(T - 7, C + 3, N0i, N0j);
             for (int n = tid; n < fr.nd * fr.iw * G; n += 256) {
@@ -919,7 +949,8 @@ __device__ __forceinline__ void pc_dec_wave_body(const PcCachedArgs& f, const un
                                      : pc_dec_symbol_wave<0>(bits, nbytes, L, a.resolution, s, logit);
                     }
                     if (lane == 0) {
-                        if (SYMS && (!LIM || c < cdec)) out[(long long)c * out_cs + (long long)y * out_rs + x] = sym;
+                        if constexpr (FROM) plane[(c * h + y) * w + x] = (unsigned char)sym;
+                        else if (SYMS && (!LIM || c < cdec)) out[(long long)c * out_cs + (long long)y * out_rs + x] = sym;
                         vol[((size_t)(c + 4) * PH + y + 4) * PW + x + 4] = s_centers[sym];
                     }
                 }
@@ -961,6 +992,8 @@ struct PcTilesBatchArgs {
     const int* tile_channels;         // PER kernels only: device copy of the channel limit per tile (ntiles)
     const int* tile_from;             // FROM kernels only: device copy of the layer every tile continues with (ntiles),
     int* done;                        //   and the channels the workspace holds of every tile (ntiles; written by the kernel alone)
+    unsigned char* planes;            // WAVE FROM kernels only: a byte per symbol of every tile, plane_bytes per tile, (c, y, x) order
+    size_t plane_bytes;               //   of the tile's own extent (written and read by the kernel alone)
 };
 
 // SEG: the tile's stream is its nlayers segments, segs[blockIdx.x * nlayers + g]; the descriptor's stream_off / stream_bytes are not
@@ -978,10 +1011,18 @@ struct PcTilesBatchArgs {
 // of its slot or of done is touched.  Otherwise the body sweeps the channels [cfrom, cdec) (none if cfrom == cdec: a uniform branch
 // around it) and the copy loop writes those and the fill above cdec; the channels below cfrom are the earlier call's and stay.
 // Still nothing passes between work-groups: a work-group reads its own slot and its own done word.
+// WAVE && FROM (ic_pc_decode_tiles_batch_fronts_resume_f32): the same for front-cut streams, pc_dec_wave_body<.., FROM>.  A slot swept
+// in one order is of no use to the other -- the raster sweep fills the caches plane by plane, the front sweep front by front -- and the
+// two entries may be given the same workspace, so the done word tells them apart: the raster kernels write cdec >= 1, these write
+// -2 - cdec <= -3, both write -1 behind an error, and each takes only its own kind for a match.  The body stores no symbol through
+// `symbols`; it keeps every symbol it steps through in the tile's byte plane (see the body), and the copy loop writes the symbols of
+// [cfrom, cdec) from the plane next to q from V.  The plane of a tile holds every symbol of the channels below cdec after a sweep to
+// cdec, whichever launches decoded them: each lies on a front <= T_last(cdec), and every front is swept once.
 template <bool WAVE, bool SYMS, bool LIM = false, bool SEG = false, bool PER = false, bool FROM = false>
 __global__ __launch_bounds__(256) void pc_dec_tiles_batch_kernel(const PcTilesBatchArgs t) {
     static_assert(!PER || (LIM && SEG), "the limit per tile belongs to the segmented decoders: a limited sweep over a tile's segments");
-    static_assert(!FROM || (PER && !WAVE), "a sweep continues where a raster sweep with a limit per tile stopped; front-cut sweeps are not continued yet");
+    static_assert(!FROM || PER, "a sweep continues where a sweep with a limit per tile stopped");
+    constexpr int DONE_SIGN = (WAVE && FROM) ? -1 : 1, DONE_BASE = (WAVE && FROM) ? -2 : 0;     // done word of a status-0 sweep to c: DONE_BASE + DONE_SIGN * c
     const ic_pc_tile_t tl = t.tiles[blockIdx.x];
     // v = volumes ? volumes[tl.volume] : one, as a uniform branch around a scalar load.  (Written as a select, it becomes a select
     // between the two ADDRESSES, kernel arguments or global memory, and a load through a flat pointer into vector registers:
@@ -1001,20 +1042,27 @@ __global__ __launch_bounds__(256) void pc_dec_tiles_batch_kernel(const PcTilesBa
         long long off0 = 0, nbytes0 = 0;                   // segment 0 of a tile that continues is not looked at
         if (gfrom > 0) {
             cfrom = ((int_cptr)t.ends)[gfrom - 1];
-            if (t.done[blockIdx.x] != cfrom) {              // the slot does not hold this tile up to cfrom (uniform)
+            if (t.done[blockIdx.x] != DONE_BASE + DONE_SIGN * cfrom) {      // the slot does not hold this tile up to cfrom (uniform)
                 if (threadIdx.x == 0) t.status[blockIdx.x] = 2;
                 return;
             }
         } else {
             off0 = ((seg_cptr)segs)[0].off; nbytes0 = ((seg_cptr)segs)[0].nbytes;
         }
-        if (cfrom < cdec)
+        if constexpr (WAVE) {
+            if (cfrom < cdec)
+                pc_dec_wave_body<SYMS, true, true, true>(t.f, t.bits + off0, nbytes0, tl.th, tl.tw, tl.first_sym, (float*)slot,
+                                                         (float*)(slot + t.off_c0), (float*)(slot + t.off_c1), (float*)(slot + t.off_c2), t.status + blockIdx.x,
+                                                         nullptr, 0, 0, cdec, t.bits, segs, t.ends, t.nlayers, gfrom,
+                                                         t.planes + (size_t)blockIdx.x * t.plane_bytes);
+            else if (threadIdx.x == 0) t.status[blockIdx.x] = 0;
+        } else if (cfrom < cdec)
             pc_dec_cached_body<SYMS, true, true, true>(t.f, t.bits + off0, nbytes0, tl.th, tl.tw, tl.first_sym, (float*)slot,
                                                        (float*)(slot + t.off_c0), (float*)(slot + t.off_c1), (float*)(slot + t.off_c2), t.status + blockIdx.x,
                                                        SYMS ? t.symbols + v.symbols_off + corner : nullptr, plane, v.w, cdec,
                                                        t.bits, segs, t.ends, t.nlayers, gfrom);
         else if (threadIdx.x == 0) t.status[blockIdx.x] = 0;
-        if (threadIdx.x == 0) t.done[blockIdx.x] = t.status[blockIdx.x] == 0 ? cdec : -1;       // (thread 0 stored the status)
+        if (threadIdx.x == 0) t.done[blockIdx.x] = t.status[blockIdx.x] == 0 ? DONE_BASE + DONE_SIGN * cdec : -1;       // (thread 0 stored the status)
     } else if constexpr (WAVE && SEG) {
         const ic_pc_seg_t* segs = t.segs + (size_t)blockIdx.x * t.nlayers;
         typedef const __attribute__((address_space(4))) ic_pc_seg_t* seg_cptr;      // (a table no kernel writes: see the body)
@@ -1059,6 +1107,7 @@ __global__ __launch_bounds__(256) void pc_dec_tiles_batch_kernel(const PcTilesBa
             const long long o = (long long)c * plane + (long long)y * v.w + x;
             if (c < cdec) {
                 if (q) q[o] = vol[((size_t)(c + 4) * PH + y + 4) * PW + x + 4];
+                if constexpr (WAVE && FROM && SYMS) syms[o] = t.planes[(size_t)blockIdx.x * t.plane_bytes + i];
             } else {
                 if (q) q[o] = qfill;
                 if (SYMS) syms[o] = t.fill;
@@ -1294,7 +1343,8 @@ static int pc_decode_tiles_impl(const uint8_t* bitstreams, const ic_pc_tile_t* t
                                 int k, int L, float resolution, int64_t* symbols, float* q, int* status, int C, void* workspace,
                                 int flags, int channels, int fill_sym, ic_stream_t stream,
                                 const int* layer_ends_host = nullptr, int nlayers = 0, const ic_pc_seg_t* segs_host = nullptr,
-                                const int* tile_channels_host = nullptr, const int* tile_from_host = nullptr) {
+                                const int* tile_channels_host = nullptr, const int* tile_from_host = nullptr,
+                                size_t planes_off = 0) {
     const bool wavefront = (flags & IC_PC_DECODE_WAVEFRONT) != 0;
     hipStream_t st = (hipStream_t)stream;
     char* p = (char*)workspace;
@@ -1329,6 +1379,10 @@ static int pc_decode_tiles_impl(const uint8_t* bitstreams, const ic_pc_tile_t* t
             if (hipMemcpyAsync(from_dev, tile_from_host, (size_t)ntiles * sizeof(int), hipMemcpyHostToDevice, st) != hipSuccess) return IC_ERR_ARG;
             a.tile_from = from_dev;
             a.done = (int*)p; p += pc_dec_align((size_t)ntiles * sizeof(int));
+            if (wavefront) {          // the fronts resume entry: the symbol planes behind everything the layers resume entry lays out
+                a.planes = (unsigned char*)workspace + planes_off;
+                a.plane_bytes = pc_dec_align((size_t)C * th_max * tw_max);
+            }
         }
         a.f.d.centers = centers; a.f.d.C = C; a.f.d.L = L; a.f.d.resolution = resolution;
         a.f.w0 = wtab_host[0]; a.f.b0 = wtab_host[1]; a.f.w1 = wtab_host[2]; a.f.b1 = wtab_host[3];
@@ -1358,7 +1412,8 @@ static int pc_decode_tiles_impl(const uint8_t* bitstreams, const ic_pc_tile_t* t
         const auto front_full = symbols ? pc_dec_tiles_batch_kernel<true, true, false, true> : pc_dec_tiles_batch_kernel<true, false, false, true>;
         const auto front_lim = symbols ? pc_dec_tiles_batch_kernel<true, true, true, true> : pc_dec_tiles_batch_kernel<true, false, true, true>;
         const auto front_per = symbols ? pc_dec_tiles_batch_kernel<true, true, true, true, true> : pc_dec_tiles_batch_kernel<true, false, true, true, true>;
-        const auto kernel = tile_from_host ? seg_resume
+        const auto front_resume = symbols ? pc_dec_tiles_batch_kernel<true, true, true, true, true, true> : pc_dec_tiles_batch_kernel<true, false, true, true, true, true>;
+        const auto kernel = tile_from_host ? (wavefront ? front_resume : seg_resume)
                           : (wavefront && nlayers) ? (tile_channels_host ? front_per : channels < C ? front_lim : front_full)
                           : tile_channels_host ? seg_per : nlayers ? (channels < C ? seg_lim : seg_full) : (channels < C ? lim : full);
         hipLaunchKernelGGL(kernel, dim3((unsigned)ntiles), dim3(256), 0, st, a);
@@ -1624,12 +1679,18 @@ extern "C" size_t ic_pc_decode_tiles_batch_layers_resume_workspace_bytes(int C, 
     return base ? base + 2 * pc_dec_align((size_t)ntiles * sizeof(int)) : 0;       // from, done
 }
 
-extern "C" int ic_pc_decode_tiles_batch_layers_resume_f32(const uint8_t* bitstreams, long long total_bytes, const ic_pc_tile_t* tiles_host, int ntiles,
-                                                          const ic_pc_volume_t* volumes_host, int nvolumes, const float* const* wtab_host,
-                                                          const float* centers, int k, int L, float resolution, int64_t* symbols, float* q,
-                                                          int* status, int C, void* workspace, size_t workspace_bytes, int flags,
-                                                          ic_stream_t stream, const int* tile_from_layer_host, const int* tile_channels_host,
-                                                          int fill_sym, const int* layer_ends_host, int nlayers, const ic_pc_seg_t* segs_host) {
+// the symbol planes of the fronts resume entry: a byte per symbol of the largest tile, per tile
+static size_t pc_dec_planes_bytes(int C, int th_max, int tw_max, int ntiles) {
+    return (size_t)ntiles * pc_dec_align((size_t)C * th_max * tw_max);
+}
+
+// the two resume entries: one set of checks; `order` as in pc_decode_tiles_segments
+static int pc_decode_tiles_segments_resume(const uint8_t* bitstreams, long long total_bytes, const ic_pc_tile_t* tiles_host, int ntiles,
+                                           const ic_pc_volume_t* volumes_host, int nvolumes, const float* const* wtab_host,
+                                           const float* centers, int k, int L, float resolution, int64_t* symbols, float* q,
+                                           int* status, int C, void* workspace, size_t workspace_bytes, int flags,
+                                           ic_stream_t stream, const int* tile_from_layer_host, const int* tile_channels_host,
+                                           int fill_sym, const int* layer_ends_host, int nlayers, const ic_pc_seg_t* segs_host, int order) {
     // everything about the six tables is decided here, on the host, before the first HIP call
     IC_CHECK_ARG(bitstreams && tiles_host && volumes_host && wtab_host && centers && (symbols || q) && status && workspace);
     IC_CHECK_ARG(tile_from_layer_host && tile_channels_host && layer_ends_host && segs_host);
@@ -1661,8 +1722,37 @@ extern "C" int ic_pc_decode_tiles_batch_layers_resume_f32(const uint8_t* bitstre
         tw_max = d.tw > tw_max ? d.tw : tw_max;
     }
     if (L > 16 || k != 24 || flags != 0) return IC_ERR_UNSUPPORTED;
-    if (workspace_bytes < ic_pc_decode_tiles_batch_layers_resume_workspace_bytes(C, th_max, tw_max, ntiles, nvolumes, k, nlayers)) return IC_ERR_WORKSPACE;
+    const size_t planes_off = ic_pc_decode_tiles_batch_layers_resume_workspace_bytes(C, th_max, tw_max, ntiles, nvolumes, k, nlayers);
+    if (workspace_bytes < planes_off + (order ? pc_dec_planes_bytes(C, th_max, tw_max, ntiles) : 0)) return IC_ERR_WORKSPACE;
     return pc_decode_tiles_impl(bitstreams, tiles_host, ntiles, th_max, tw_max, volumes_host, nvolumes, wtab_host, centers, k, L,
-                                resolution, symbols, q, status, C, workspace, flags, C, fill_sym, stream,
-                                layer_ends_host, nlayers, segs_host, tile_channels_host, tile_from_layer_host);
+                                resolution, symbols, q, status, C, workspace, order, C, fill_sym, stream,
+                                layer_ends_host, nlayers, segs_host, tile_channels_host, tile_from_layer_host, planes_off);
+}
+
+extern "C" int ic_pc_decode_tiles_batch_layers_resume_f32(const uint8_t* bitstreams, long long total_bytes, const ic_pc_tile_t* tiles_host, int ntiles,
+                                                          const ic_pc_volume_t* volumes_host, int nvolumes, const float* const* wtab_host,
+                                                          const float* centers, int k, int L, float resolution, int64_t* symbols, float* q,
+                                                          int* status, int C, void* workspace, size_t workspace_bytes, int flags,
+                                                          ic_stream_t stream, const int* tile_from_layer_host, const int* tile_channels_host,
+                                                          int fill_sym, const int* layer_ends_host, int nlayers, const ic_pc_seg_t* segs_host) {
+    return pc_decode_tiles_segments_resume(bitstreams, total_bytes, tiles_host, ntiles, volumes_host, nvolumes, wtab_host, centers, k, L,
+                                           resolution, symbols, q, status, C, workspace, workspace_bytes, flags, stream, tile_from_layer_host,
+                                           tile_channels_host, fill_sym, layer_ends_host, nlayers, segs_host, 0);
+}
+
+// ---- front-layered tiles, continued: every tile's front sweep from the layer end where an earlier call on the same workspace stopped ---
+extern "C" size_t ic_pc_decode_tiles_batch_fronts_resume_workspace_bytes(int C, int th_max, int tw_max, int ntiles, int nvolumes, int k, int nlayers) {
+    const size_t base = ic_pc_decode_tiles_batch_layers_resume_workspace_bytes(C, th_max, tw_max, ntiles, nvolumes, k, nlayers);
+    return base ? base + pc_dec_planes_bytes(C, th_max, tw_max, ntiles) : 0;
+}
+
+extern "C" int ic_pc_decode_tiles_batch_fronts_resume_f32(const uint8_t* bitstreams, long long total_bytes, const ic_pc_tile_t* tiles_host, int ntiles,
+                                                          const ic_pc_volume_t* volumes_host, int nvolumes, const float* const* wtab_host,
+                                                          const float* centers, int k, int L, float resolution, int64_t* symbols, float* q,
+                                                          int* status, int C, void* workspace, size_t workspace_bytes, int flags,
+                                                          ic_stream_t stream, const int* tile_from_layer_host, const int* tile_channels_host,
+                                                          int fill_sym, const int* layer_ends_host, int nlayers, const ic_pc_seg_t* segs_host) {
+    return pc_decode_tiles_segments_resume(bitstreams, total_bytes, tiles_host, ntiles, volumes_host, nvolumes, wtab_host, centers, k, L,
+                                           resolution, symbols, q, status, C, workspace, workspace_bytes, flags, stream, tile_from_layer_host,
+                                           tile_channels_host, fill_sym, layer_ends_host, nlayers, segs_host, IC_PC_DECODE_WAVEFRONT);
 }

@@ -782,11 +782,17 @@ class PredictionNetwork(object):
         res = cut(q) if want == 'q' else cut(sym) if want == 'symbols' else list(zip(cut(q), cut(sym)))
         return (res, damage) if conceal else res
 
-    def open_layers(self, volumes_geometry, th, tw, layer_ends, max_workspace_bytes=1 << 31):
+    def open_layers(self, volumes_geometry, th, tw, layer_ends=None, max_workspace_bytes=1 << 31, front_ends=None):
         """a LayerSession over the volumes [(C,h,w)] cut into th x tw tiles of layered streams (container format 6): the decoder's
         workspace, symbols and q stay on the device between its advance() calls, so that every layer of every tile is decoded once
-        however often the caller looks at what has arrived (ic_pc_decode_tiles_batch_layers_resume_f32)"""
-        return LayerSession(self, volumes_geometry, th, tw, layer_ends, max_workspace_bytes)
+        however often the caller looks at what has arrived (ic_pc_decode_tiles_batch_layers_resume_f32).
+        front_ends in place of layer_ends (exactly one of the two): the same session over front-layered streams (container format 8,
+        ic_pc_decode_tiles_batch_fronts_resume_f32): every front of every tile is swept once"""
+        if (layer_ends is None) == (front_ends is None):
+            raise ValueError('a session is opened with layer_ends (plane cuts, format 6) or with front_ends (front cuts, format 8): '
+                             'exactly one of the two')
+        return LayerSession(self, volumes_geometry, th, tw, layer_ends if front_ends is None else front_ends, max_workspace_bytes,
+                            fronts=front_ends is not None)
 
     def conceal_fallback(self):
         """the symbol a tile gets that has no intact neighbour: the centre of smallest magnitude (ties: the smallest index), what
@@ -861,9 +867,12 @@ class LayerSession(object):
     (number of tiles, largest tile), so a tile continues only while both are what they were when its slot was written and starts
     afresh otherwise: in a format-6 file, which stores layer 0 of all tiles first, the launches change shape only while layer 0
     arrives, when there is nothing to continue.  A tile whose status is not 0 is reported with reason 'decoder' and starts afresh in
-    the next call, as does a tile that is given fewer layers than its slot holds."""
+    the next call, as does a tile that is given fewer layers than its slot holds.
+    fronts=True (open_layers(front_ends=...)): the streams are front-layered (container format 8) and the launch is
+    ic_pc_decode_tiles_batch_fronts_resume_f32, with its larger workspace; advance() then returns what
+    decode_tiles_batch(front_ends=..., tile_layers=...) returns.  Everything else is the same object."""
 
-    def __init__(self, pred, volumes_geometry, th, tw, layer_ends, max_workspace_bytes=1 << 31):
+    def __init__(self, pred, volumes_geometry, th, tw, layer_ends, max_workspace_bytes=1 << 31, fronts=False):
         from .codec import tile_grid, check_layer_ends
         self.pred = pred
         self.shapes = [tuple(int(v) for v in shape) for shape in volumes_geometry]
@@ -876,6 +885,8 @@ class LayerSession(object):
         if pred.pc._k != 24:
             raise ValueError('layered tiles need a context model of width k = 24, this one has k = {}'.format(pred.pc._k))
         self.ends = check_layer_ends(layer_ends, C)
+        self.fronts = bool(fronts)
+        self.entry = 'ic_pc_decode_tiles_batch_fronts_resume_f32' if self.fronts else 'ic_pc_decode_tiles_batch_layers_resume_f32'
         self.th, self.tw = int(th), int(tw)
         self.grids = [tile_grid(h, w, self.th, self.tw) for _, h, w in self.shapes]
         self.vtable, self.offs, self.total = _lib.packed_volume_table(self.shapes)
@@ -893,8 +904,9 @@ class LayerSession(object):
         self.launches = 0
 
     def _need(self, th_max, tw_max, ntiles):
-        return int(lib.ic_pc_decode_tiles_batch_layers_resume_workspace_bytes(self.shapes[0][0], th_max, tw_max, ntiles, len(self.shapes),
-                                                                              self.pred.pc._k, len(self.ends)))
+        size = (lib.ic_pc_decode_tiles_batch_fronts_resume_workspace_bytes if self.fronts
+                else lib.ic_pc_decode_tiles_batch_layers_resume_workspace_bytes)
+        return int(size(self.shapes[0][0], th_max, tw_max, ntiles, len(self.shapes), self.pred.pc._k, len(self.ends)))
 
     def advance(self, volumes_segments, tile_layers, want='q'):
         from .codec import resume_plan
@@ -950,10 +962,10 @@ class LayerSession(object):
             host_ends, host_from, host_limits = (ctypes.c_int * G)(*ends), (ctypes.c_int * len(froms))(*froms), (ctypes.c_int * len(limits))(*limits)
             data = torch.frombuffer(bytearray(b''.join(blobs)) or bytearray(1), dtype=torch.uint8).to(dev)
             status = torch.zeros(len(tiles), dtype=torch.int32, device=dev)
-            check(lib.ic_pc_decode_tiles_batch_layers_resume_f32(
+            check(getattr(lib, self.entry)(
                 ptr(data), pos, table, len(tiles), self.vtable, len(self.shapes), pred.pc._tab, ptr(centers), pred.pc._k, pred.pc.L,
                 pred.freqs_resolution, ptr(self.sym), ptr(self.q), ptr(status), C, ptr(self.ws), need, 0, _lib.current_stream(dev),
-                host_from, host_limits, pred.conceal_fallback(), host_ends, G, seg_table), 'ic_pc_decode_tiles_batch_layers_resume_f32')
+                host_from, host_limits, pred.conceal_fallback(), host_ends, G, seg_table), self.entry)
             self.launches += 1
             for (n, t, _, _, _, _, _, g_t, _), i, st in zip(listed, range(len(listed)), status.tolist()):      # (the host waits here)
                 if st != 0:

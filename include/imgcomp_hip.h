@@ -455,6 +455,30 @@ int ic_pc_decode_tiles_batch_layers_resume_f32(const uint8_t* bitstreams, long l
                                                int* status, int C, void* workspace, size_t workspace_bytes, int flags,
                                                ic_stream_t stream, const int* tile_from_layer_host, const int* tile_channels_host,
                                                int fill_sym, const int* layer_ends_host, int nlayers, const ic_pc_seg_t* segs_host);
+/* Front-layered tiles, CONTINUED: ic_pc_decode_tiles_batch_layers_resume_f32 for the front-cut streams of container format 8 (codec.py,
+ * stream --fronts).  A front sweep that ended at a layer end e has run every front up to t = (tw - 1) + 2 (th - 1) + 4 (e - 1); the slot
+ * holds V and the three caches of those fronts, the coder starts afresh behind the cut, and the next call runs the fronts above t only.
+ * The entry mirrors the layers resume entry argument for argument: parameters, host-side checks and return codes, the rows of segs_host
+ * that are checked (g >= from[t] that begin below tile_channels[t]; a tile that continues does not need segment 0), what is written
+ * ([cfrom, limit) decoded, [limit, C) filled, nothing below cfrom), status 0 / 1 / 2, flags == 0.  What differs:
+ *   - a segment is a run of fronts, as in ic_pc_decode_tiles_batch_fronts_pertile_f32; with every from[t] == 0 the result is that
+ *     entry's, bit for bit.
+ *   - a sweep to cfrom has already stepped through the symbols of channels >= cfrom that share its fronts.  The kernel keeps every
+ *     symbol it decodes in a byte plane per tile in the workspace and writes `symbols` of [cfrom, limit) from it, so a call delivers
+ *     those channels complete whichever call decoded a symbol.  The plane is only ever copied out.
+ *   - the `done` word tells the two orders apart (a raster sweep leaves the caches filled plane by plane): this entry writes
+ *     -2 - channels behind a status-0 sweep where the layers resume entry writes channels, both -1 behind an error.  A slot left by
+ *     one entry gets status 2 from the other.  0 and -1 match no cfrom here either.
+ *   workspace: ic_pc_decode_tiles_batch_fronts_resume_workspace_bytes: the layers resume entry's size -- with the same layout, so the
+ *   done words of the two lie at the same place -- and behind it ntiles planes of C * th_max * tw_max bytes, each rounded up to 256.
+ *   0 where the layers resume function returns 0. */
+size_t ic_pc_decode_tiles_batch_fronts_resume_workspace_bytes(int C, int th_max, int tw_max, int ntiles, int nvolumes, int k, int nlayers);
+int ic_pc_decode_tiles_batch_fronts_resume_f32(const uint8_t* bitstreams, long long total_bytes, const ic_pc_tile_t* tiles_host, int ntiles,
+                                               const ic_pc_volume_t* volumes_host, int nvolumes, const float* const* wtab_host,
+                                               const float* centers, int k, int L, float resolution, int64_t* symbols, float* q,
+                                               int* status, int C, void* workspace, size_t workspace_bytes, int flags,
+                                               ic_stream_t stream, const int* tile_from_layer_host, const int* tile_channels_host,
+                                               int fill_sym, const int* layer_ends_host, int nlayers, const ic_pc_seg_t* segs_host);
 /* Concealment: what stands in the volumes where a tile could not be decoded (a damaged file; codec.py, salvage).  Stated on symbols,
  * so exact: for a damaged tile T and a channel c the candidates are the symbols of channel c directly above T's top row, below its
  * bottom row, left of its left column and right of its right column (no corners) that lie inside the volume and in a tile that
