@@ -135,6 +135,8 @@ PROTOTYPES = {
                                 c_longlong, c_void_p]),
     'ic_heatmap_quantize_f32': (c_int, [c_void_p, c_void_p, c_int, c_float] + [c_void_p] * 6 +
                                 [c_int] * 4 + [c_void_p]),
+    'ic_heatmap_quantize_cap_f32': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_float] + [c_void_p] * 6 +
+                                    [c_int] * 4 + [c_void_p]),
     'ic_pc_workspace_bytes': (c_size_t, [c_int] * 5),
     'ic_pc_packed_floats': (c_size_t, [c_int, c_int]),
     'ic_pc_mid_tile': (c_int, [c_int, c_int, c_int]),
@@ -203,6 +205,8 @@ PROTOTYPES = {
     'ic_ae_res_stack_sync_pos_bytes': (c_size_t, [c_int] * 3),
     'ic_ae_encode_f32': (c_int, [c_void_p, POINTER(c_void_p)] + [c_int] * 5 + [c_void_p] * 6 +
                          [c_int] * 3 + [c_void_p, c_size_t, c_int, c_void_p]),
+    'ic_ae_encode_cap_f32': (c_int, [c_void_p, POINTER(c_void_p)] + [c_int] * 5 + [c_void_p] * 6 +
+                             [c_int] * 3 + [c_void_p, c_size_t, c_int, c_void_p, c_void_p, c_void_p]),
     'ic_ae_decode_f32': (c_int, [c_void_p, POINTER(c_void_p)] + [c_int] * 3 + [c_void_p] +
                          [c_int] * 3 + [c_void_p, c_size_t, c_int, c_void_p]),
     'ic_ae_res_stack_workspace_bytes': (c_size_t, [c_int] * 3),

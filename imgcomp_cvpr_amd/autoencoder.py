@@ -293,6 +293,79 @@ class _CVPR(_Network):
         self._last_qsoft = qsoft
         return EncoderOutput(qbar, qhard, symbols, z, heatmap)
 
+    # -- importance-map cap (not in the reference): an upper bound on heatmap2D per latent position, inference only --------
+
+    def _check_cap(self, cap, shape, device, what='cap'):
+        """cap: float32 device tensor of `shape`, 0 <= cap <= +inf -> contiguous; every refusal is a ValueError"""
+        if not bool(self.config.heatmap):
+            raise ValueError('{}: this config has no importance map (heatmap = False): there is nothing to cap'.format(what))
+        if not self.quantize:
+            raise ValueError('{}: this network was built with quantize=False'.format(what))
+        if not isinstance(cap, torch.Tensor) or cap.dtype != torch.float32 or cap.device != device or tuple(cap.shape) != tuple(shape):
+            raise ValueError('{}: expected a float32 tensor of shape {} on {}, got {}'.format(
+                what, tuple(shape), device, '{} {} on {}'.format(cap.dtype, tuple(cap.shape), cap.device) if isinstance(cap, torch.Tensor) else type(cap).__name__))
+        if not bool((cap >= 0).all()):            # (a NaN compares false)
+            raise ValueError('{}: entries must be in [0, +inf], got a negative or NaN entry'.format(what))
+        return cap.contiguous()
+
+    def encode_capped(self, x, cap=None, keep_bottleneck=False, plan_flags=0):
+        """encode(x, is_training=False) with h2 = min(heatmap2D, cap) in the importance map (ic_ae_encode_cap_f32).
+        cap: None, or (N, H/8, W/8) float32 on x's device, 0 <= cap <= +inf; cap >= C everywhere is encode itself, bit for bit.
+        -> (EncoderOutput, bottleneck (N, C+1, H/8, W/8) if keep_bottleneck else None): requantize(bottleneck, caps) quantises the
+        same image under other caps without running the encoder again."""
+        assert x.dtype == torch.float32, 'Expected float32 for x, got {}'.format(x.dtype)
+        self._sync_with_training_graph()
+        self._require_weights()
+        _lib.require_cuda(x, 'x')
+        x = x.contiguous()
+        N, three, H, W = x.shape
+        assert three == 3, 'Expected N3HW, got {}'.format(tuple(x.shape))
+        f = self.get_subsampling_factor()
+        if H % f or W % f:
+            raise ValueError('H and W must be multiples of {} (val.py pads images first), got {}x{}'.format(f, H, W))
+        C, hh, ww = self._C, H // f, W // f
+        if not bool(self.config.heatmap) or not self.quantize:
+            raise ValueError('encode_capped: this config has no importance map (heatmap = False) or no quantiser: use encode')
+        if cap is not None:
+            cap = self._check_cap(cap, (N, hh, ww), x.device)
+        mk = lambda: torch.empty((N, C, hh, ww), dtype=torch.float32, device=x.device)
+        z, qsoft, qhard, qbar, heatmap = mk(), mk(), mk(), mk(), mk()
+        symbols = torch.empty((N, C, hh, ww), dtype=torch.int64, device=x.device)
+        bott = torch.empty((N, C + 1, hh, ww), dtype=torch.float32, device=x.device) if keep_bottleneck else None
+        ws, need = self._workspace(N, H, W)
+        check(lib.ic_ae_encode_cap_f32(ptr(x), self._enc_tab, self._B, C, self._L, 1, int(self.config.normalization == 'FIXED'),
+                                       ptr(heatmap), ptr(z), ptr(qsoft), ptr(qhard), ptr(qbar), ptr(symbols),
+                                       N, H, W, ptr(ws), need, self._abi_flags(int(plan_flags) | int(self.plan_flags)),
+                                       _lib.current_stream(x.device), ptr(cap), ptr(bott)), 'ic_ae_encode_cap_f32')
+        self._last_qsoft = qsoft
+        return EncoderOutput(qbar, qhard, symbols, z, heatmap), bott
+
+    def requantize(self, bottleneck, caps, hard_only=False):
+        """bottleneck (N, C+1, h, w) of encode_capped(keep_bottleneck=True); caps (N, T, h, w) or (N, h, w) (T = 1), 1 <= T <= 16
+        -> EncoderOutput of batch N * T, image n * T + t under caps[n, t]: one launch of ic_heatmap_quantize_cap_f32 that reads the
+        bottleneck once for all T.  hard_only: qhard and symbols alone (the rest None), which is all a rate search reads."""
+        self._require_weights()
+        _lib.require_cuda(bottleneck, 'bottleneck')
+        C = self._C
+        if bottleneck.dtype != torch.float32 or bottleneck.dim() != 4 or bottleneck.shape[1] != C + 1:
+            raise ValueError('bottleneck: expected float32 (N, {}, h, w), got {} {}'.format(C + 1, bottleneck.dtype, tuple(bottleneck.shape)))
+        bottleneck = bottleneck.contiguous()
+        N, _, hh, ww = bottleneck.shape
+        if isinstance(caps, torch.Tensor) and caps.dim() == 3:
+            caps = caps[:, None]
+        T = int(caps.shape[1]) if isinstance(caps, torch.Tensor) and caps.dim() == 4 else 0
+        if isinstance(caps, torch.Tensor) and caps.dim() == 4 and not 1 <= T <= 16:
+            raise ValueError('caps: 1 .. 16 levels per launch, got {}'.format(T))
+        caps = self._check_cap(caps, (N, max(T, 1), hh, ww), bottleneck.device, 'caps')
+        mk = lambda: torch.empty((N * T, C, hh, ww), dtype=torch.float32, device=bottleneck.device)
+        qhard = mk()
+        z, qsoft, qbar, heatmap = (None,) * 4 if hard_only else (mk(), mk(), mk(), mk())
+        symbols = torch.empty((N * T, C, hh, ww), dtype=torch.int64, device=bottleneck.device)
+        check(lib.ic_heatmap_quantize_cap_f32(ptr(bottleneck), ptr(caps), T, ptr(self._centers), self._L, 1.0,
+                                              ptr(heatmap), ptr(z), ptr(qsoft), ptr(qhard), ptr(qbar), ptr(symbols),
+                                              N, C, hh, ww, _lib.current_stream(bottleneck.device)), 'ic_heatmap_quantize_cap_f32')
+        return EncoderOutput(qbar, qhard, symbols, z, heatmap)
+
     def _decode(self, q, is_training, plan_flags=0):
         assert not is_training
         _lib.require_cuda(q, 'q')

@@ -3,8 +3,9 @@
     python -m imgcomp_cvpr_amd.codec compress   IN.png  OUT.icf [--ae_config cvpr/low] [--pc_config cvpr/res_shallow] [--weights synthetic|FILE.npz|CKPT]
                                                                 [--tile PIXELS [--checked | --wavefront | --layers a,b,.. | --progressive |
                                                                                 --front-layers a,b,.. | --front-progressive]]
+                                                                [--cap T | --max-bytes N | --bpp B] [--roi X,Y,W,H ... [--background T]]
     python -m imgcomp_cvpr_amd.codec decompress IN.icf  OUT.png [same options] [--salvage | --channels K | --partial | --recover]
-    python -m imgcomp_cvpr_amd.codec compress-dir   IN_DIR OUT_DIR [--tile PIXELS [same choices]] [--batch N]   every *.png / *.jpg -> OUT_DIR/<stem>.icf
+    python -m imgcomp_cvpr_amd.codec compress-dir   IN_DIR OUT_DIR [--tile PIXELS [same choices]] [--batch N] [--cap T | --max-bytes N | --bpp B]   every *.png / *.jpg -> OUT_DIR/<stem>.icf
     python -m imgcomp_cvpr_amd.codec decompress-dir IN_DIR OUT_DIR [--batch N] [--salvage | --channels K | --partial | --recover]    every *.icf -> OUT_DIR/<stem>.png
     python -m imgcomp_cvpr_amd.codec verify PATH [PATH ...]         files or directories of *.icf: the checksums, without model or device
     python -m imgcomp_cvpr_amd.codec stream IN.icf OUT_DIR [model options] [--chunk BYTES]    a format-6 file fed chunk by chunk, a picture per gained layer
@@ -126,6 +127,14 @@ stream --fronts (Codec.open_stream(fronts=True)): a format-8 file is streamed to
 ends and ic_pc_decode_tiles_batch_fronts_resume_f32 continues every tile's front sweep behind the last front of the layers it held, so
 every front is swept once: the 191 steps of a (32, 16, 16) tile in all, where a --recover per redraw at the four default layer ends
 takes 79 + 95 + 127 + 191.  Opt-in: without --fronts a format-8 file is refused as before.  A format-6 file streams the same either way.
+--cap / --roi / --background / --max-bytes / --bpp (Codec.compress(cap=, rois=, background=), compress_to_budget): the encoder's rate
+knob.  The importance map heatmap2D = sigmoid(z0) C says per latent position how many of the C channels carry information; a cap is
+an upper bound on it, one float per position (cap_plane): the same level everywhere is a rate below the trained point, a plane that
+is high inside rectangles and low outside is region-of-interest coding, a search over the level (cap_levels: the grid k C / 256;
+budget_search: the contract, established on real files) is a byte budget.  A capped channel quantises to the centre nearest zero,
+the value every decoder path already knows as "nothing here" (fill_symbol), so the file format does not change, the cap is not
+recorded in the file and reading needs no option.  The budget search runs the encoder once and requantises its bottleneck per
+level (ic_heatmap_quantize_cap_f32: up to 16 levels a launch, costed by the context model as one batch for the estimate).
 """
 import argparse
 import io
@@ -186,6 +195,99 @@ def tile_grid(h, w, th, tw):
     if h < 1 or w < 1 or th < 1 or tw < 1:
         raise ValueError('tile grid: plane {} x {} and tile {} x {} must all be at least 1'.format(h, w, th, tw))
     return [(y0, x0, min(th, h - y0), min(tw, w - x0)) for y0 in range(0, h, th) for x0 in range(0, w, tw)]
+
+
+CAP_STEPS = 256                                                      # cap_levels: the grid a budget is searched on
+
+
+def cap_levels(C):
+    """the CAP_STEPS + 1 levels fl32(k C / CAP_STEPS), k = 0 .. CAP_STEPS, of an importance-map cap: 0 (every channel masked) up
+    to C (no cap); for C = 32 the step is 0.125"""
+    return (np.arange(CAP_STEPS + 1, dtype=np.float64) * int(C) / CAP_STEPS).astype(np.float32)
+
+
+def _check_level(value, what):
+    try:
+        v = float(value)
+    except (TypeError, ValueError):
+        raise ValueError('{} {!r} is not a number'.format(what, value))
+    if not v >= 0.0:                                                 # (a NaN compares false)
+        raise ValueError('{} {} is not in [0, +inf]'.format(what, value))
+    return v
+
+
+def cap_plane(H, W, factor, level=None, rois=(), background=None):
+    """the (h, w) float32 cap of an H x W image for Codec.compress(cap=...): `level` (None: +inf, no cap) in every latent cell, or,
+    with rectangles rois = [(x, y, w, h), ..] in pixels of the image, `level` in the cells whose factor x factor block of the
+    padded image (val.add_padding pads centred: top ((-H) % factor) // 2, left likewise) intersects a rectangle and `background` in
+    the others.  A ValueError for a level outside [0, +inf], a rectangle of no extent or one that misses the image, rectangles
+    without a background."""
+    H, W, f = int(H), int(W), int(factor)
+    if H < 1 or W < 1 or f < 1:
+        raise ValueError('cap_plane: image {} x {}, factor {}'.format(H, W, f))
+    h, w = (H + f - 1) // f, (W + f - 1) // f
+    inside = np.float32(np.inf if level is None else _check_level(level, 'level'))
+    rois = list(rois) if rois is not None else []
+    if not rois:
+        if background is not None:
+            raise ValueError('background {} without a rectangle: the level alone is the cap of every cell'.format(background))
+        return np.full((h, w), inside, dtype=np.float32)
+    if background is None:
+        raise ValueError('a region of interest needs a background: the level of the cells outside the rectangles')
+    plane = np.full((h, w), np.float32(_check_level(background, 'background')), dtype=np.float32)
+    top, left = ((-H) % f) // 2, ((-W) % f) // 2
+    for r in rois:
+        try:
+            x, y, rw, rh = (int(v) for v in r)
+        except (TypeError, ValueError):
+            raise ValueError('rectangle {!r} is not (x, y, w, h) in pixels'.format(r))
+        if rw < 1 or rh < 1:
+            raise ValueError('rectangle {}: the extent {} x {} is not positive'.format((x, y, rw, rh), rw, rh))
+        x0, y0, x1, y1 = max(x, 0), max(y, 0), min(x + rw, W), min(y + rh, H)
+        if x0 >= x1 or y0 >= y1:
+            raise ValueError('rectangle {} does not intersect the {} x {} image'.format((x, y, rw, rh), W, H))
+        plane[(y0 + top) // f:(y1 - 1 + top) // f + 1, (x0 + left) // f:(x1 - 1 + left) // f + 1] = inside
+    return plane
+
+
+def budget_search(fits, estimate_index):
+    """the largest-level search behind a byte budget, over the indices 0 .. CAP_STEPS of cap_levels.  fits(k) -> bool is one real
+    coding at level k; estimate_index is advice.  -> (k, probes) with fits(k) true and k == CAP_STEPS or fits(k + 1) false, BOTH
+    established by calls of fits: sizes need not be monotone in the level (tile borders, the context model), so the bisection
+    keeps fits(lo) and not fits(hi) and ends on an adjacent pair whatever lies between.  Order: CAP_STEPS (returned if it fits);
+    the estimate and, if it fits, its successor; 0 if no fitting index is known yet; then bisection of the side that remains --
+    at most 1 + 2 + 1 + 8 calls, none repeated.  A ValueError if 0 does not fit."""
+    probes = [0]
+
+    def probe(k):
+        probes[0] += 1
+        return bool(fits(k))
+
+    hi = CAP_STEPS
+    if probe(hi):
+        return hi, probes[0]
+    lo = None
+    e = min(max(int(estimate_index), 0), CAP_STEPS - 1)
+    if probe(e):
+        lo = e
+        if e + 1 < hi:
+            if probe(e + 1):
+                lo = e + 1
+            else:
+                hi = e + 1
+    else:
+        hi = e
+    if lo is None:
+        if hi == 0 or not probe(0):
+            raise ValueError('no level fits: the smallest file, at level 0, is over the budget in bytes')
+        lo = 0
+    while hi - lo > 1:
+        mid = (lo + hi) // 2
+        if probe(mid):
+            lo = mid
+        else:
+            hi = mid
+    return lo, probes[0]
 
 
 def wavefront_dependencies(masks, num_layers):
@@ -951,16 +1053,8 @@ class Codec(object):
 
     def encode_symbols(self, img_hwc_uint8):
         """HWC uint8 -> (EncoderOutput of the padded image, (H, W))."""
-        import torch
-        from . import val
-        img = np.asarray(img_hwc_uint8)
-        if img.ndim != 3 or img.shape[2] not in (3, 4) or img.dtype != np.uint8:
-            raise ValueError('expected an HWC uint8 image with 3 channels, got {} {}'.format(img.shape, img.dtype))
-        img = img[:, :, :3]
-        H, W = int(img.shape[0]), int(img.shape[1])
-        padded, _ = val.add_padding(img, self.factor)
-        x = torch.as_tensor(np.ascontiguousarray(np.transpose(padded, (2, 0, 1)))[None]).to(self.device).float()
-        return self.ae.encode(x, is_training=False), (H, W)
+        x, size = self._image_tensor(img_hwc_uint8)
+        return self.ae.encode(x, is_training=False), size
 
     def _host_encode_stream(self, symbols_chw):
         """the parent path: all tables to the host, the Python coder over them.  Same bytes as encode_stream."""
@@ -999,9 +1093,107 @@ class Codec(object):
             raise ValueError(self.wavefront_refusal or self.layered_refusal)
         return default_layer_ends(self.C) if isinstance(self.front_layers, str) else check_layer_ends(self.front_layers, self.C)
 
-    def compress(self, img_hwc_uint8):
-        enc, (H, W) = self.encode_symbols(img_hwc_uint8)
-        sym = enc.symbols[0]
+    def compress(self, img_hwc_uint8, cap=None, rois=None, background=None):
+        """HWC uint8 -> container bytes.  cap: None, a level, or an (h, w) plane bounding the importance map (cap_plane; rois and
+        background as there, the level inside the rectangles); without any of them the encoder's own operating point."""
+        if cap is None and not rois and background is None:
+            enc, (H, W) = self.encode_symbols(img_hwc_uint8)
+        else:
+            enc, _, (H, W) = self.encode_symbols_capped(img_hwc_uint8, cap, rois, background)
+        return self._container(enc.symbols[0], H, W)
+
+    def _image_tensor(self, img_hwc_uint8, what=''):
+        """HWC uint8 -> ((1, 3, H', W') float32 device tensor of the padded image, (H, W))"""
+        import torch
+        from . import val
+        img = np.asarray(img_hwc_uint8)
+        if img.ndim != 3 or img.shape[2] not in (3, 4) or img.dtype != np.uint8:
+            raise ValueError('{}expected an HWC uint8 image with 3 channels, got {} {}'.format(what, img.shape, img.dtype))
+        img = img[:, :, :3]
+        padded, _ = val.add_padding(img, self.factor)
+        x = torch.as_tensor(np.ascontiguousarray(np.transpose(padded, (2, 0, 1)))[None]).to(self.device).float()
+        return x, (int(img.shape[0]), int(img.shape[1]))
+
+    def cap_plane(self, H, W, cap=None, rois=None, background=None):
+        """compress's cap argument for an H x W image -> the (h, w) float32 plane: a plane is checked, a level goes through cap_plane"""
+        if cap is not None and np.ndim(cap) > 0:
+            f = self.factor
+            plane = np.asarray(cap)
+            if plane.shape != ((H + f - 1) // f, (W + f - 1) // f):
+                raise ValueError('cap plane of shape {} for a {} x {} image: expected {}'.format(plane.shape, H, W, ((H + f - 1) // f, (W + f - 1) // f)))
+            if rois or background is not None:
+                raise ValueError('rois / background do not go with a cap plane: they are a way of making one (cap_plane)')
+            plane = plane.astype(np.float32)
+            if not bool((plane >= 0).all()):
+                raise ValueError('cap plane: entries must be in [0, +inf], got a negative or NaN entry')
+            return np.ascontiguousarray(plane)
+        return cap_plane(H, W, self.factor, level=cap, rois=rois or (), background=background)
+
+    def encode_symbols_capped(self, img_hwc_uint8, cap=None, rois=None, background=None, keep_bottleneck=False):
+        """encode_symbols under a cap (compress's arguments) -> (EncoderOutput, bottleneck or None, (H, W))"""
+        import torch
+        x, (H, W) = self._image_tensor(img_hwc_uint8)
+        plane = torch.as_tensor(self.cap_plane(H, W, cap, rois, background)[None]).to(self.device)
+        enc, bott = self.ae.encode_capped(x, plane, keep_bottleneck=keep_bottleneck)
+        return enc, bott, (H, W)
+
+    def compress_to_budget(self, img_hwc_uint8, max_bytes, rois=None):
+        """the largest level of cap_levels(C) whose file has at most max_bytes bytes -> (data, level, probes): data is byte for byte
+        compress(img, cap=level), or with rois compress(img, rois=rois, background=level) (the rectangles stay uncapped, the budget
+        is met by the background); probes is the number of real codings.  The encoder runs once; every level after that is a
+        requantisation of its bottleneck.  An estimate from the context model's bit costs (up to 16 levels a launch, one
+        readback a round) starts budget_search, whose contract holds on the real files: data fits, and the next level's file
+        does not (or level == C).  A ValueError if the file of level 0 is over the budget."""
+        import torch
+        from ._lib import lib, check, ptr, current_stream
+        max_bytes = int(max_bytes)
+        x, (H, W) = self._image_tensor(img_hwc_uint8)
+        _, bott = self.ae.encode_capped(x, None, keep_bottleneck=True)
+        levels = cap_levels(self.C)
+        h, w = int(bott.shape[2]), int(bott.shape[3])
+        roi = torch.as_tensor(np.isinf(cap_plane(H, W, self.factor, rois=rois, background=0.0))).to(self.device) if rois else None
+        lv = torch.as_tensor(levels).to(self.device)
+        inf = torch.full((), float('inf'), dtype=torch.float32, device=self.device)
+
+        def planes(ks):                                               # (1, T, h, w): level k outside the rectangles, +inf inside
+            p = lv[torch.as_tensor(list(ks), device=self.device)][:, None, None].expand(len(ks), h, w)
+            return (p if roi is None else torch.where(roi[None], inf, p))[None].contiguous()
+
+        files = {}
+
+        def coded(k):
+            if k not in files:
+                files[k] = self._container(self.ae.requantize(bott, planes([k]), hard_only=True).symbols[0], H, W)
+            return files[k]
+
+        def estimate(ks):                                             # bytes of the whole-volume pass per level, one readback
+            enc = self.ae.requantize(bott, planes(ks), hard_only=True)
+            bits = self.pc.bitcost(enc.qhard, enc.symbols, is_training=False, pad_value=self.pc.auto_pad_value(self.ae))
+            buf = torch.empty(1024 + len(ks), dtype=torch.float32, device=self.device)
+            check(lib.ic_mean_rows_f32(ptr(bits), len(ks), bits.numel() // len(ks), 8.0, ptr(buf), ptr(buf[1024:]),
+                                       current_stream(self.device)), 'ic_mean_rows_f32')
+            return [float(v) for v in buf[1024:].cpu().numpy()]
+
+        guess = CAP_STEPS
+        if len(coded(CAP_STEPS)) > max_bytes:
+            # the container and the streams' ends cost the same at every level, to first order: take them from the one real file
+            ks = list(range(16, CAP_STEPS + 1, 16))
+            est = estimate(ks)
+            room = max_bytes - (len(files[CAP_STEPS]) - est[-1])
+            below = [k for k, b in zip(ks, est) if b <= room]
+            ks = list(range(1, 16)) if not below else list(range(below[-1] + 1, min(below[-1] + 16, CAP_STEPS)))
+            guess = below[-1] if below else 0
+            if ks:
+                fit = [k for k, b in zip(ks, estimate(ks)) if b <= room]
+                guess = fit[-1] if fit else guess
+        try:
+            k, probes = budget_search(lambda k: len(coded(k)) <= max_bytes, guess)
+        except ValueError:
+            raise ValueError('budget of {} bytes: the smallest file, at level 0, has {} bytes'.format(max_bytes, len(coded(0))))
+        return files[k], float(levels[k]), probes
+
+    def _container(self, sym, H, W):
+        """the symbols (C, h, w) of an H x W image, on the device -> container bytes in this Codec's format"""
         C, h, w = (int(v) for v in sym.shape)
         fronts = self._front_ends()
         if fronts is not None:
@@ -1182,24 +1374,25 @@ class Codec(object):
             cur.wait_stream(st)
         return outs
 
-    def compress_many(self, images):
+    def compress_many(self, images, caps=None):
         """[HWC uint8] of any mix of shapes -> [container bytes], element i byte for byte compress(images[i]).  Every image goes
         through the encoder on its own (batch 1, the plan flags of compress: the kernel form of a layer depends on the batch size,
-        the bytes must not), up to IN_FLIGHT at a time; then the tiles of all images are coded by one launch per tile shape."""
+        the bytes must not), up to IN_FLIGHT at a time; then the tiles of all images are coded by one launch per tile shape.
+        caps: None, or one entry per image -- None, a level or a plane, as compress's cap: element i is compress(images[i], cap=caps[i])."""
         import torch
-        from . import val
+        images = list(images)
+        caps = [None] * len(images) if caps is None else list(caps)
+        if len(caps) != len(images):
+            raise ValueError('caps: {} entries for {} images'.format(len(caps), len(images)))
         if not self.device_encode:
-            return [self.compress(img) for img in images]
+            return [self.compress(img, cap=cap) for img, cap in zip(images, caps)]
         xs, sizes = [], []
-        for i, img in enumerate(images):
-            img = np.asarray(img)
-            if img.ndim != 3 or img.shape[2] not in (3, 4) or img.dtype != np.uint8:
-                raise ValueError('image {}: expected an HWC uint8 image with 3 channels, got {} {}'.format(i, img.shape, img.dtype))
-            img = img[:, :, :3]
-            sizes.append((int(img.shape[0]), int(img.shape[1])))
-            padded, _ = val.add_padding(img, self.factor)
-            xs.append(torch.as_tensor(np.ascontiguousarray(np.transpose(padded, (2, 0, 1)))[None]).to(self.device).float())
-        syms = self._in_flight(xs, lambda ae, x: ae.encode(x, is_training=False).symbols[0])
+        for i, (img, cap) in enumerate(zip(images, caps)):
+            x, size = self._image_tensor(img, 'image {}: '.format(i))
+            sizes.append(size)
+            xs.append((x, None if cap is None else torch.as_tensor(self.cap_plane(size[0], size[1], cap)[None]).to(self.device)))
+        syms = self._in_flight(xs, lambda ae, xc: (ae.encode(xc[0], is_training=False) if xc[1] is None else
+                                                   ae.encode_capped(xc[0], xc[1])[0]).symbols[0])
         out = [None] * len(syms)
         fronts = self._front_ends()
         ends = fronts if fronts is not None else self._layer_ends()
@@ -1417,10 +1610,10 @@ class Codec(object):
         fronts=True: a format-8 file is taken as well, every front swept once"""
         return StreamDecoder(self, max_workspace_bytes, fronts=fronts)
 
-    def compress_file(self, image_path, out_path):
+    def compress_file(self, image_path, out_path, **cap_args):
         from PIL import Image
         img = np.asarray(Image.open(image_path).convert('RGB'), dtype=np.uint8)     # as val.load_image_chw reads it
-        data = self.compress(img)
+        data = self.compress(img, **cap_args)
         with open(out_path, 'wb') as f:
             f.write(data)
         return data, img.shape[0] * img.shape[1]
@@ -1550,8 +1743,38 @@ def _recover_line(path, report):
 
 def check_option_args(flags):
     """--checked / --wavefront / --salvage / --channels / --layers / --progressive / --front-layers / --front-progressive / --partial /
-    --recover / --chunk / --fronts against the command, --tile
+    --recover / --chunk / --fronts / --cap / --roi / --background / --max-bytes / --bpp against the command, --tile
     and each other: decided before any model is built"""
+    cap, background, rois = getattr(flags, 'cap', None), getattr(flags, 'background', None), getattr(flags, 'roi', None) or []
+    max_bytes, bpp = getattr(flags, 'max_bytes', None), getattr(flags, 'bpp', None)
+    for name, value in (('--cap', cap), ('--background', background), ('--max-bytes', max_bytes), ('--bpp', bpp)):
+        if value is not None and flags.command not in ('compress', 'compress-dir'):
+            raise ValueError('{} belongs to compress / compress-dir: the cap on the importance map is the encoder\'s, a file is read '
+                             'without it'.format(name))
+    if rois and flags.command != 'compress':
+        raise ValueError('--roi belongs to compress: a rectangle is in the pixels of one image' if flags.command == 'compress-dir' else
+                         '--roi belongs to compress: the cap on the importance map is the encoder\'s, a file is read without it')
+    if max_bytes is not None and bpp is not None:
+        raise ValueError('--max-bytes does not go with --bpp: the one names the budget in bytes, the other per pixel')
+    if cap is not None and (max_bytes is not None or bpp is not None):
+        raise ValueError('--cap does not go with {}: the one names the level, the other searches for it'.format(
+            '--max-bytes' if max_bytes is not None else '--bpp'))
+    if rois and background is None and max_bytes is None and bpp is None:
+        raise ValueError('--roi needs --background or a budget (--max-bytes / --bpp): the level of the cells outside the rectangles')
+    if background is not None and not rois:
+        raise ValueError('--background needs --roi: without a rectangle --cap is the level of every cell')
+    if background is not None and (max_bytes is not None or bpp is not None):
+        raise ValueError('--background does not go with {}: with --roi the budget searches for the background'.format(
+            '--max-bytes' if max_bytes is not None else '--bpp'))
+    for name, value in (('--cap', cap), ('--background', background)):
+        if value is not None:
+            _check_level(value, name)
+    if max_bytes is not None and max_bytes < 1:
+        raise ValueError('--max-bytes {} is not at least 1'.format(max_bytes))
+    if bpp is not None and not bpp > 0:
+        raise ValueError('--bpp {} is not above 0'.format(bpp))
+    for r in rois:
+        parse_roi_arg(r)
     if getattr(flags, 'chunk', None) is not None:
         if flags.command != 'stream':
             raise ValueError('--chunk belongs to stream: the size of the pieces the file is fed in')
@@ -1637,6 +1860,30 @@ def check_option_args(flags):
             raise ValueError('--recover does not go with --channels: what every tile still holds decides its channels')
 
 
+def parse_roi_arg(text):
+    """'X,Y,W,H' -> (x, y, w, h); a ValueError for anything but four integers with a positive extent (the image is checked by cap_plane)"""
+    try:
+        x, y, w, h = (int(v) for v in str(text).split(','))
+    except ValueError:
+        raise ValueError('--roi {!r} is not X,Y,W,H in pixels'.format(text))
+    if w < 1 or h < 1:
+        raise ValueError('--roi {!r}: the extent {} x {} is not positive'.format(text, w, h))
+    return x, y, w, h
+
+
+def _budget_of(flags, H, W):
+    """--max-bytes, or --bpp over the H x W pixels of one image, or None"""
+    if getattr(flags, 'max_bytes', None) is not None:
+        return int(flags.max_bytes)
+    if getattr(flags, 'bpp', None) is not None:
+        return int(flags.bpp * H * W // 8)
+    return None
+
+
+def _budget_note(level, probes):
+    return ', cap level {:g} after {} codings'.format(level, probes)
+
+
 def parse_layers_arg(text, option='--layers'):
     """'4,8,16,32' -> [4, 8, 16, 32]; a ValueError for anything but comma-separated positive integers (C is checked by the codec)"""
     try:
@@ -1708,10 +1955,16 @@ def _main_dir(flags, ae_config, pc_config):
         part = jobs[start:start + flags.batch]
         if flags.command == 'compress-dir':
             imgs = [np.asarray(Image.open(src).convert('RGB'), dtype=np.uint8) for src, _ in part]     # as compress_file reads them
-            for (src, dst), img, data in zip(part, imgs, codec.compress_many(imgs)):
+            notes = [''] * len(imgs)
+            if _budget_of(flags, 1, 1) is not None:              # a budget per file: a search per file, one after the other
+                found = [codec.compress_to_budget(img, _budget_of(flags, img.shape[0], img.shape[1])) for img in imgs]
+                datas, notes = [d for d, _, _ in found], [_budget_note(level, probes) for _, level, probes in found]
+            else:
+                datas = codec.compress_many(imgs, caps=None if getattr(flags, 'cap', None) is None else [flags.cap] * len(imgs))
+            for (src, dst), img, data, note in zip(part, imgs, datas, notes):
                 with open(dst, 'wb') as f:
                     f.write(data)
-                print(_compress_line(dst, data, img.shape[0] * img.shape[1]))
+                print(_compress_line(dst, data, img.shape[0] * img.shape[1]) + note)
                 total_in, total_out, total_pixels = total_in + os.path.getsize(src), total_out + len(data), total_pixels + img.shape[0] * img.shape[1]
         else:
             datas = []
@@ -1978,6 +2231,16 @@ def main(argv=None):
                    help='stream: feed the file in pieces of this many bytes (default {})'.format(STREAM_CHUNK))
     p.add_argument('--fronts', action='store_true', help='stream: take a front-layered file (format 8) as well, every front of every tile '
                                                          'swept once; without it such a file is refused')
+    p.add_argument('--cap', type=float, default=None, metavar='T',
+                   help='compress / compress-dir: an upper bound T in [0, C] on the importance map, the same in every latent cell: a rate '
+                        'below the model\'s own (0: every channel masked; C or more: no cap); the file format is unchanged')
+    p.add_argument('--roi', action='append', default=None, metavar='X,Y,W,H',
+                   help='compress: a rectangle in image pixels that keeps --cap (or no cap) while the rest gets --background; repeatable')
+    p.add_argument('--background', type=float, default=None, metavar='T', help='compress with --roi: the cap outside the rectangles')
+    p.add_argument('--max-bytes', dest='max_bytes', type=int, default=None, metavar='N',
+                   help='compress / compress-dir: the largest cap level (of the grid k C / 256) whose file has at most N bytes; with --roi '
+                        'the rectangles stay uncapped and the level is the background\'s; prints the level and the number of codings')
+    p.add_argument('--bpp', type=float, default=None, metavar='B', help='compress / compress-dir: --max-bytes floor(B H W / 8), per image')
     flags = p.parse_args(argv)
     from . import config_parser, val, weights as _weights
     try:
@@ -2002,8 +2265,20 @@ def main(argv=None):
                 codec.order = 'wavefront' if flags.wavefront else 'raster'
                 codec.layers = layers
                 codec.front_layers = front_layers
-            data, pixels = codec.compress_file(flags.input, flags.output)
-            print(_compress_line(flags.output, data, pixels))
+            rois = [parse_roi_arg(r) for r in flags.roi or []]
+            if flags.max_bytes is not None or flags.bpp is not None:
+                from PIL import Image
+                img = np.asarray(Image.open(flags.input).convert('RGB'), dtype=np.uint8)     # as compress_file reads it
+                data, level, probes = codec.compress_to_budget(img, _budget_of(flags, img.shape[0], img.shape[1]), rois=rois or None)
+                with open(flags.output, 'wb') as f:
+                    f.write(data)
+                print(_compress_line(flags.output, data, img.shape[0] * img.shape[1]) + _budget_note(level, probes))
+            elif flags.cap is not None or rois:
+                data, pixels = codec.compress_file(flags.input, flags.output, cap=flags.cap, rois=rois or None, background=flags.background)
+                print(_compress_line(flags.output, data, pixels))
+            else:
+                data, pixels = codec.compress_file(flags.input, flags.output)
+                print(_compress_line(flags.output, data, pixels))
         elif flags.command == 'stream':
             _main_stream(flags, codec)
         elif flags.partial:

@@ -24,7 +24,9 @@ Control flow: the scan is linear, a backward branch is followed across its back 
 the 8-wave form skips its transform slices behind scalar branches -- the instructions skipped must not be counted as wait states),
 each with a copy of the state, for as many wait states as a hazard can span.
 
-usage: isa_audit.py file.s [--max-scratch BYTES] [--allow-scratch NAME-REGEX]   (exit 1 on a finding; BYTES per kernel, default 0)
+usage: isa_audit.py file.s [--max-scratch BYTES] [--allow-scratch NAME-REGEX] [--scratch-all]   (exit 1 on a finding; BYTES per kernel, default 0)
+--scratch-all: rule (S) for EVERY kernel of the file, those without MFMAs too (quantize.hip: HBM-streaming kernels that keep their centres
+and distances in registers -- an array the compiler indexes dynamically would move to scratch and halve them without failing a test).
 Wait states are counted the way LLVM does: every instruction 1, `s_nop N` N + 1."""
 import re, sys
 
@@ -139,6 +141,7 @@ def main():
     ap.add_argument('path')
     ap.add_argument('--max-scratch', type=int, default=0)
     ap.add_argument('--allow-scratch', default=None)
+    ap.add_argument('--scratch-all', action='store_true')
     a = ap.parse_args()
     path = a.path
     bad = 0
@@ -146,7 +149,7 @@ def main():
     scratch = scratch_of(path)
     for name, body in kernels(path):
         n_mfma, findings = audit_kernel(name, body)
-        if not n_mfma: continue
+        if not n_mfma and not a.scratch_all: continue
         audited += 1
         priv, spilled = scratch.get(name, (0, 0))
         if (priv > a.max_scratch or spilled) and not (a.allow_scratch and re.search(a.allow_scratch, name)):
@@ -156,7 +159,7 @@ def main():
             for f in of_rule[:6]: print('%s: %s: %s' % (path, name, f))
             if len(of_rule) > 6: print('%s: %s: ... %d more of %s' % (path, name, len(of_rule) - 6, rule))
         bad += len(findings)
-    print('isa_audit: %s: %d kernel(s) with MFMAs audited, %d finding(s)' % (path, audited, bad))
+    print('isa_audit: %s: %d kernel(s) %s audited, %d finding(s)' % (path, audited, 'in all' if a.scratch_all else 'with MFMAs', bad))
     sys.exit(1 if bad else 0)
 
 

@@ -183,12 +183,15 @@ extern "C" int ic_pack_conv5s2_both_f32(const float* w_tf, float* w_packed, int 
     return ic_pack_wino4_conv5s2_f32(w_tf, w_packed + ic_conv2d_mfma_packed_floats(5, 5, cin, cout, 2, tr), tr, stream);
 }
 
-extern "C" int ic_ae_encode_f32(const float* x, const void* const* tab, int B, int C, int L, int heatmap_on,
-                                int normalize_on, float* heatmap, float* z, float* qsoft, float* qhard, float* qbar,
-                                int64_t* symbols, int N, int H, int W,
-                                void* workspace, size_t workspace_bytes, int flags, ic_stream_t stream) {
+// cap, bottleneck_out: the two additions of ic_ae_encode_cap_f32; with both null this is ic_ae_encode_f32 launch for launch
+static int ae_encode(const float* x, const void* const* tab, int B, int C, int L, int heatmap_on,
+                     int normalize_on, float* heatmap, float* z, float* qsoft, float* qhard, float* qbar,
+                     int64_t* symbols, int N, int H, int W,
+                     void* workspace, size_t workspace_bytes, int flags, ic_stream_t stream,
+                     const float* cap, float* bottleneck_out) {
     IC_CHECK_ARG(x && tab && workspace && N > 0 && H > 0 && W > 0 && B >= 0 && C > 0 && L > 0);
     if (H % 8 || W % 8) return IC_ERR_UNSUPPORTED;          // callers pad to the subsampling factor (val.py:157)
+    if (cap && !heatmap_on) return IC_ERR_UNSUPPORTED;      // the cap bounds the importance map: no map, nothing to bound
     if (workspace_bytes < ic_ae_workspace_bytes(N, H, W, C)) return IC_ERR_WORKSPACE;
     const int nconv = 6 * B + 2;
     for (int i = 0; i < 3 * (nconv + 3) + 1; ++i) IC_CHECK_ARG(tab[i] != nullptr);
@@ -226,6 +229,13 @@ extern "C" int ic_ae_encode_f32(const float* x, const void* const* tab, int B, i
     if ((rc = ic_conv2d_mfma_bn_act_f32(bufs[o], tb[0], tb[1], tb[2], bott, N, 128, H / 4, W / 4, Cb, 5, 5, 2, 0, 0, st)))
         return rc;
     const float* centers = tb[3];
+    if (bottleneck_out) {
+        hipError_t e = hipMemcpyAsync(bottleneck_out, bott, (size_t)N * Cb * (H / 8) * (W / 8) * sizeof(float), hipMemcpyDeviceToDevice, st);
+        if (e != hipSuccess) return (int)e;
+    }
+    if (heatmap_on && cap)
+        return ic_heatmap_quantize_cap_f32(bott, cap, 1, centers, L, 1.0f, heatmap, z, qsoft, qhard, qbar, symbols,
+                                           N, C, H / 8, W / 8, stream);
     if (heatmap_on)
         return ic_heatmap_quantize_f32(bott, centers, L, 1.0f, heatmap, z, qsoft, qhard, qbar, symbols,
                                        N, C, H / 8, W / 8, stream);
@@ -238,6 +248,23 @@ extern "C" int ic_ae_encode_f32(const float* x, const void* const* tab, int B, i
     if (qbar) return IC_ERR_UNSUPPORTED;   // qbar == qhard in value; request qhard instead
     if (!qsoft && !qhard && !symbols) return IC_OK;      // a network built with quantize=False (autoencoder.py:127-129): z only
     return ic_quantize_f32(bott, centers, L, 1.0f, qsoft, qhard, symbols, cnt, stream);
+}
+
+extern "C" int ic_ae_encode_f32(const float* x, const void* const* tab, int B, int C, int L, int heatmap_on,
+                                int normalize_on, float* heatmap, float* z, float* qsoft, float* qhard, float* qbar,
+                                int64_t* symbols, int N, int H, int W,
+                                void* workspace, size_t workspace_bytes, int flags, ic_stream_t stream) {
+    return ae_encode(x, tab, B, C, L, heatmap_on, normalize_on, heatmap, z, qsoft, qhard, qbar, symbols, N, H, W,
+                     workspace, workspace_bytes, flags, stream, nullptr, nullptr);
+}
+
+extern "C" int ic_ae_encode_cap_f32(const float* x, const void* const* tab, int B, int C, int L, int heatmap_on,
+                                    int normalize_on, float* heatmap, float* z, float* qsoft, float* qhard, float* qbar,
+                                    int64_t* symbols, int N, int H, int W,
+                                    void* workspace, size_t workspace_bytes, int flags, ic_stream_t stream,
+                                    const float* cap, float* bottleneck_out) {
+    return ae_encode(x, tab, B, C, L, heatmap_on, normalize_on, heatmap, z, qsoft, qhard, qbar, symbols, N, H, W,
+                     workspace, workspace_bytes, flags, stream, cap, bottleneck_out);
 }
 
 extern "C" int ic_ae_decode_f32(const float* q, const void* const* tab, int B, int C, int normalize_on,

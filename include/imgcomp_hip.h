@@ -226,6 +226,17 @@ int ic_quantize_f32(const float* z, const float* centers, int L, float sigma,
 int ic_heatmap_quantize_f32(const float* bottleneck, const float* centers, int L, float sigma,
                             float* heatmap, float* z, float* qsoft, float* qhard, float* qbar,
                             int64_t* symbols, int N, int C, int h, int w, ic_stream_t stream);
+/* ic_heatmap_quantize_f32 with a caller's upper bound on heatmap2D = sigmoid(z0) * C, one float per latent position, and T bounds
+ * ("levels", 1 <= T <= 16) per image in ONE launch that reads every bottleneck value once:
+ *   cap (N*T,h,w), 0 <= cap <= +inf;  h2' = min(h2, cap[n*T + t, p]);  heatmap = max(min(h2' - ch, 1), 0);  z = heatmap * zc;
+ *   the rest as above.  Outputs (N*T,C,h,w), image n*T + t, each nullable (without qsoft and qbar no softmax is evaluated).
+ * cap >= C everywhere (+inf included) gives the bytes of ic_heatmap_quantize_f32; an integer cap K leaves channels < K as they
+ * were and puts heatmap 0, z = +-0 and the symbol of the centre nearest zero into the others.  Channels masked this way are
+ * what the decoders' channel previews assume, so the bound needs no place in a file.
+ * T outside 1..16: IC_ERR_UNSUPPORTED; cap NULL: IC_ERR_ARG. */
+int ic_heatmap_quantize_cap_f32(const float* bottleneck, const float* cap, int T, const float* centers, int L, float sigma,
+                                float* heatmap, float* z, float* qsoft, float* qhard, float* qbar,
+                                int64_t* symbols, int N, int C, int h, int w, ic_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Context model (res_shallow): probclass.py:63-106 (bitcost), :130-135 (logits), :214-221
@@ -575,6 +586,15 @@ int ic_ae_encode_f32(const float* x, const void* const* enc_tab_host, int B, int
                      int normalize_on, float* heatmap, float* z, float* qsoft, float* qhard, float* qbar,
                      int64_t* symbols, int N, int H, int W,
                      void* workspace, size_t workspace_bytes, int flags, ic_stream_t stream);
+/* ic_ae_encode_f32 with two more (nullable) pointers; with both NULL it is that call.
+ *   cap (N,H/8,W/8): the bound of ic_heatmap_quantize_cap_f32 (T = 1) on the importance map; needs heatmap_on (else IC_ERR_UNSUPPORTED).
+ *   bottleneck_out (N,C+1,H/8,W/8) ((N,C,..) without importance map): to_bn's output, copied out of the workspace on `stream` --
+ *   what ic_heatmap_quantize_cap_f32 needs to quantise the same image under other bounds without running the encoder again. */
+int ic_ae_encode_cap_f32(const float* x, const void* const* enc_tab_host, int B, int C, int L, int heatmap_on,
+                         int normalize_on, float* heatmap, float* z, float* qsoft, float* qhard, float* qbar,
+                         int64_t* symbols, int N, int H, int W,
+                         void* workspace, size_t workspace_bytes, int flags, ic_stream_t stream,
+                         const float* cap, float* bottleneck_out);
 int ic_ae_decode_f32(const float* q, const void* const* dec_tab_host, int B, int C, int normalize_on,
                      float* x_out, int N, int H, int W,
                      void* workspace, size_t workspace_bytes, int flags, ic_stream_t stream);
