@@ -373,7 +373,7 @@ extern "C" int ic_msssim_loss_grad_f32(const float* x, const float* x_out, int N
     if (!p.ok) return IC_ERR_UNSUPPORTED;
     const size_t planes = (size_t)N * C;
     const MsWs w = ms_workspace(p, planes);
-    IC_CHECK_ARG(workspace_bytes >= w.total);
+    if (workspace_bytes < w.total) return IC_ERR_WORKSPACE;
     if (planes * (size_t)H * W >= ((size_t)1 << 31)) return IC_ERR_UNSUPPORTED;
     hipStream_t st = (hipStream_t)stream;
     char* ws = (char*)workspace;

@@ -124,7 +124,10 @@ extern "C" size_t ic_pc_bwd_data_workspace_bytes(int N, int Cin, int Cout, int O
 }
 
 // workspace: ic_pc_bwd_data_workspace_bytes(...) bytes select the matrix-core path ("other" mask, Cin = 24 or 64); NULL or
-// 0 bytes (or a shape it does not cover) run the any-shape VALU kernel.
+// 0 bytes (or a shape it does not cover, or the first mask) run the any-shape VALU kernel.  A workspace that is given (non-NULL,
+// workspace_bytes > 0) but smaller than the query's answer is IC_ERR_WORKSPACE, decided before anything is enqueued: asking for the
+// matrix-core path and getting the other kernel's rounding would be a silent change.  "No workspace" is either half of the pair:
+// a non-NULL pointer with 0 bytes and a NULL pointer with any byte count both mean the VALU kernel, never a refusal.
 extern "C" int ic_pc_bwd_data_f32(const float* g, const float* w, const float* res, const float* act, float* dx,
                                   int N, int Cin, int Cout, int OD, int OH, int OW, int first_mask, int relu_mask,
                                   void* workspace, size_t workspace_bytes, ic_stream_t stream) {
@@ -136,6 +139,7 @@ extern "C" int ic_pc_bwd_data_f32(const float* g, const float* w, const float* r
     const int ivol = (OD + 1) * (OH + 2) * (OW + 2);
     hipStream_t st = (hipStream_t)stream;
     const size_t need = first_mask ? 0 : ic_pc_bwd_data_workspace_bytes(N, Cin, Cout, OD, OH, OW);
+    if (workspace && workspace_bytes && need && workspace_bytes < need) return IC_ERR_WORKSPACE;
     if (workspace && need && workspace_bytes >= need) {
         float* zero = (float*)((char*)workspace + need - 64 * sizeof(float));
         if (hipMemsetAsync(zero, 0, 64 * sizeof(float), st) != hipSuccess) return IC_ERR_ARG;

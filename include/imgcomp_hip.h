@@ -699,7 +699,8 @@ int ic_pc_dlogits_f32(const float* logits, const int64_t* symbols, const float* 
                       int N, int vol, int L, ic_stream_t stream);
 /* data gradient of one masked conv3d layer: dx = (sum_taps w^T g (+ res embedded at (2,2,2))) * [act > 0].
  * workspace = ic_pc_bwd_data_workspace_bytes(...) bytes runs it on the matrix cores (the layer's adjoint: mirrored taps,
- * transposed filter, zero-padded gradient); NULL / 0 or an uncovered shape (size query returns 0) runs the VALU kernel. */
+ * transposed filter, zero-padded gradient); NULL / 0 or an uncovered shape (size query returns 0) runs the VALU kernel; a
+ * workspace that is given but smaller than the query's answer is IC_ERR_WORKSPACE (nothing is written). */
 size_t ic_pc_bwd_data_workspace_bytes(int N, int Cin, int Cout, int OD, int OH, int OW);
 int ic_pc_bwd_data_f32(const float* g, const float* w, const float* res, const float* act, float* dx,
                        int N, int Cin, int Cout, int OD, int OH, int OW, int first_mask, int relu_mask,
@@ -833,7 +834,8 @@ int ic_val_metrics_per_image_u8_f64(const unsigned char* x, const unsigned char*
  * Gaussian 'VALID' blur with REFLECT pads on small scales, 2x2 box between scales), train.py:352-394
  * (d_loss_scaled = K_ms_ssim * (1 - MS-SSIM(x, x_out)); TensorFlow derives d / d x_out, here it is written out).
  * The blur matrices of a shape are computed once on the HOST (ic_msssim_plan_fill -> a plain buffer the caller uploads) and
- * passed as a device pointer with every call.  IC_ERR_UNSUPPORTED / 0 bytes: an image too small for five scales.
+ * passed as a device pointer with every call.  IC_ERR_UNSUPPORTED / 0 bytes: an image too small for five scales; a workspace
+ * smaller than ic_msssim_workspace_bytes: IC_ERR_WORKSPACE.
  * --------------------------------------------------------------------------------------------- */
 size_t ic_msssim_plan_bytes(int H, int W);
 int ic_msssim_plan_fill(int H, int W, void* host_buf, size_t bytes);          /* CPU arithmetic only */

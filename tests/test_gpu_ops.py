@@ -669,6 +669,35 @@ def test_error_codes(cuda):
     with pytest.raises(L.HipLibraryError):
         from imgcomp_cvpr_amd import quantizer
         quantizer.quantize(torch.zeros(1, 1, 2, 2), torch.zeros(6), 1.0)     # CPU tensors: no fallback
+    # a workspace one byte short of the size query's answer: IC_ERR_WORKSPACE (-3), decided on the host before any launch
+    st = L.current_stream()
+    f = lambda *shape: torch.zeros(shape, device=cuda)
+    ws = lambda n: torch.zeros(n, dtype=torch.uint8, device=cuda)
+    u8 = torch.zeros((1, 3, 17, 23), dtype=torch.uint8, device=cuda)
+    need = L.lib.ic_val_metrics_workspace_bytes(1, 3, 17, 23)
+    out6 = torch.zeros(6, dtype=torch.float64, device=cuda)
+    assert need > 0 and L.lib.ic_val_metrics_u8_f64(L.ptr(u8), L.ptr(u8), 1, 3, 17, 23, L.ptr(out6), L.ptr(ws(need)), need - 1, st) == -3
+    need, nplan = L.lib.ic_msssim_workspace_bytes(1, 2, 17, 19), L.lib.ic_msssim_plan_bytes(17, 19)
+    assert need > 0 and nplan > 0
+    assert L.lib.ic_msssim_loss_grad_f32(L.ptr(f(1, 2, 17, 19)), L.ptr(f(1, 2, 17, 19)), 1, 2, 17, 19, 1.0, L.ptr(ws(nplan)), None, L.ptr(f(16)),
+                                         L.ptr(ws(need)), need - 1, st) == -3
+    need = L.lib.ic_conv2d_wgrad_workspace_bytes(1, 3, 3, 5, 6, 3, 3)
+    assert need > 0 and L.lib.ic_conv2d_wgrad_f32(L.ptr(f(1, 3, 5, 6)), L.ptr(f(1, 3, 5, 6)), L.ptr(f(3, 3, 3, 3)), 1, 3, 5, 6, 3, 3, 3, 1, None, 0.0,
+                                                  L.ptr(ws(need)), need - 1, st) == -3
+    need = L.lib.ic_conv3x3_c128_wgrad_workspace_bytes(1, 8, 16)
+    assert need > 0 and L.lib.ic_conv3x3_c128_wgrad_f32(L.ptr(f(1, 128, 8, 16)), L.ptr(f(1, 128, 8, 16)), L.ptr(f(3, 3, 128, 128)), 1, 8, 16, None, 0.0,
+                                                        L.ptr(ws(need)), need - 1, st) == -3
+    need = L.lib.ic_pc_bwd_data_workspace_bytes(1, 24, 24, 1, 1, 1)
+    assert need > 0 and L.lib.ic_pc_bwd_data_f32(L.ptr(f(1, 24, 1, 1, 1)), L.ptr(f(2, 3, 3, 24, 24)), None, None, L.ptr(f(1, 24, 2, 3, 3)), 1, 24, 24,
+                                                 1, 1, 1, 0, 0, L.ptr(ws(need)), need - 1, st) == -3
+    need = L.lib.ic_pc_wgrad_workspace_bytes(1, 24, 6, 1, 2, 2)
+    assert need > 0 and L.lib.ic_pc_wgrad_f32(L.ptr(f(1, 24, 2, 4, 4)), None, 0.0, L.ptr(f(1, 6, 1, 2, 2)), L.ptr(f(2, 3, 3, 24, 6)), 1, 24, 6, 1, 2, 2, 0,
+                                              L.ptr(ws(need)), need - 1, st) == -3
+    need = L.lib.ic_ae_res_stack_workspace_bytes(1, 5, 7)
+    wp, one = f(L.lib.ic_conv3x3_c128_both_packed_floats()), torch.ones(128, device=cuda)
+    assert need > 0 and L.lib.ic_ae_res_stack_f32(L.ptr(f(1, 128, 5, 7)), L.ptr_table([wp, one, one] * 2), 0, L.ptr(f(1, 128, 5, 7)), 1, 5, 7,
+                                                  L.ptr(ws(need)), need - 1, 0, st) == -3
+    torch.cuda.synchronize()
 
 
 def test_conv3x3_c128_forms_agree_on_random_shapes(cuda):
