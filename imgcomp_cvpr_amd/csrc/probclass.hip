@@ -877,6 +877,8 @@ int icx_pc_bwd_data_mfma(const float* g, const float* w, float* dx_raw, int N, i
                          const float* zero_bias, void* workspace, size_t workspace_bytes, hipStream_t st) {
     const int KP = CoutF <= 24 ? 24 : 64;
     if (CoutF > 64 || CinF > 64 || (CinF != 24 && CinF != 64)) return IC_ERR_UNSUPPORTED;
+    // the KP = 64 kernel's two row waves (WM = 2) index the fragments as two 32-row tiles; 24 rows pack into one
+    if (KP == 64 && CinF != 64) return IC_ERR_UNSUPPORTED;
     if ((size_t)KP * (OD + 2) * (OH + 4) * (OW + 4) * 4 >= (1ull << 31)) return IC_ERR_UNSUPPORTED;
     const size_t gp_floats = (size_t)N * KP * (OD + 2) * (OH + 4) * (OW + 4);
     const size_t pk_floats = pc_packed_floats(KP, CinF);
@@ -905,6 +907,7 @@ int icx_pc_bwd_data_mfma(const float* g, const float* w, float* dx_raw, int N, i
 size_t icx_pc_bwd_data_mfma_workspace(int N, int CinF, int CoutF, int OD, int OH, int OW) {
     if (CoutF > 64 || (CinF != 24 && CinF != 64)) return 0;
     const int KP = CoutF <= 24 ? 24 : 64;
+    if (KP == 64 && CinF != 64) return 0;             // (as in icx_pc_bwd_data_mfma: the any-shape kernel serves Cin = 24, Cout > 24)
     if ((size_t)KP * (OD + 2) * (OH + 4) * (OW + 4) * 4 >= (1ull << 31)) return 0;
     return ((size_t)N * KP * (OD + 2) * (OH + 4) * (OW + 4) + pc_packed_floats(KP, CinF)) * sizeof(float);
 }

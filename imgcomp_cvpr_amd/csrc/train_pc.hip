@@ -123,7 +123,8 @@ extern "C" size_t ic_pc_bwd_data_workspace_bytes(int N, int Cin, int Cout, int O
     return b ? b + 64 * sizeof(float) : 0;
 }
 
-// workspace: ic_pc_bwd_data_workspace_bytes(...) bytes select the matrix-core path ("other" mask, Cin = 24 or 64); NULL or
+// workspace: ic_pc_bwd_data_workspace_bytes(...) bytes select the matrix-core path ("other" mask; Cin = 24 with Cout <= 24, or
+// Cin = 64 with Cout <= 64 -- the query is 0 for every other shape, Cin = 24 with Cout 25 .. 64 among them); NULL or
 // 0 bytes (or a shape it does not cover, or the first mask) run the any-shape VALU kernel.  A workspace that is given (non-NULL,
 // workspace_bytes > 0) but smaller than the query's answer is IC_ERR_WORKSPACE, decided before anything is enqueued: asking for the
 // matrix-core path and getting the other kernel's rounding would be a silent change.  "No workspace" is either half of the pair:

@@ -700,7 +700,10 @@ int ic_pc_dlogits_f32(const float* logits, const int64_t* symbols, const float* 
 /* data gradient of one masked conv3d layer: dx = (sum_taps w^T g (+ res embedded at (2,2,2))) * [act > 0].
  * workspace = ic_pc_bwd_data_workspace_bytes(...) bytes runs it on the matrix cores (the layer's adjoint: mirrored taps,
  * transposed filter, zero-padded gradient); NULL / 0 or an uncovered shape (size query returns 0) runs the VALU kernel; a
- * workspace that is given but smaller than the query's answer is IC_ERR_WORKSPACE (nothing is written). */
+ * workspace that is given but smaller than the query's answer is IC_ERR_WORKSPACE (nothing is written).
+ * The matrix cores take first_mask = 0 with Cin = 24 and Cout <= 24, or Cin = 64 and Cout <= 64 (the k -> k and k -> L layers of
+ * k = 24 and k = 64).  Every other shape -- another Cin, Cout > 64, Cin = 24 with Cout in 25 .. 64 -- has a query of 0 and gets
+ * the VALU kernel whatever workspace is passed; so does first_mask = 1 (the query does not take the mask). */
 size_t ic_pc_bwd_data_workspace_bytes(int N, int Cin, int Cout, int OD, int OH, int OW);
 int ic_pc_bwd_data_f32(const float* g, const float* w, const float* res, const float* act, float* dx,
                        int N, int Cin, int Cout, int OD, int OH, int OW, int first_mask, int relu_mask,
