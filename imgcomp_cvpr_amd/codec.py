@@ -10,6 +10,9 @@
     python -m imgcomp_cvpr_amd.codec verify PATH [PATH ...]         files or directories of *.icf: the checksums, without model or device
     python -m imgcomp_cvpr_amd.codec stream IN.icf OUT_DIR [model options] [--chunk BYTES]    a format-6 file fed chunk by chunk, a picture per gained layer
     python -m imgcomp_cvpr_amd.codec stream IN.icf OUT_DIR --fronts [model options] [--chunk BYTES]    the same for a format-6 or a format-8 file
+    python -m imgcomp_cvpr_amd.codec transcode IN.icf OUT.icf [model options] [--tile PIXELS [the choices of compress]]
+                                                              [--cap K | --max-bytes N | --bpp B] [--roi X,Y,W,H ... [--background K]] [--salvage | --recover]
+    python -m imgcomp_cvpr_amd.codec transcode-dir IN_DIR OUT_DIR [the same, without --roi] [--batch N]     every *.icf -> OUT_DIR/<stem>.icf
 
 compress:   pad to a multiple of the subsampling factor (val.add_padding) -> ae.encode -> PredictionNetwork.encode_stream (the
             range coder on the device, ic_pc_encode_f32) -> container.
@@ -135,6 +138,16 @@ budget_search: the contract, established on real files) is a byte budget.  A cap
 the value every decoder path already knows as "nothing here" (fill_symbol), so the file format does not change, the cap is not
 recorded in the file and reading needs no option.  The budget search runs the encoder once and requantises its bottleneck per
 level (ic_heatmap_quantize_cap_f32: up to 16 levels a launch, costed by the context model as one batch for the estimate).
+transcode / transcode-dir (Codec.transcode, transcode_many, transcode_to_budget, repair): a file to a file, without its image.  A file
+is a symbol volume plus a choice of entropy-coding layout; the symbols are the autoencoder's, so they are decoded, left on the device
+and coded again in the format this Codec writes -- byte for byte the file compress would have written from the image, where
+compress(decompress(data)) runs the autoencoder twice and yields other symbols.  No new format, no new entry point: the decoders and
+encoders above, and between them at most one torch.where.  An INTEGER cap K gives exactly preview_symbols(plain, K, fill) (the
+quantiser's contract), so --cap / --roi / --background at integer levels and --max-bytes / --bpp over the levels 0 .. C
+(budget_search(steps=C)) apply to a file as they apply to an image: cap_symbols is the rule, cell p keeps the channels below its
+level.  A fractional level rescales z and needs the bottleneck: refused here, it is compress's.  --salvage / --recover (repair) write
+what a damaged format-4 / 5 (salvage's reader and concealment) or a damaged or cut format-6 / 8 file (recover's) still holds as an
+intact file, with the reader's report; formats 1 and 2 carry no checksums to read a damaged file by.
 """
 import argparse
 import io
@@ -250,24 +263,29 @@ def cap_plane(H, W, factor, level=None, rois=(), background=None):
     return plane
 
 
-def budget_search(fits, estimate_index):
+def budget_search(fits, estimate_index, steps=CAP_STEPS):
     """the largest-level search behind a byte budget, over the indices 0 .. CAP_STEPS of cap_levels.  fits(k) -> bool is one real
     coding at level k; estimate_index is advice.  -> (k, probes) with fits(k) true and k == CAP_STEPS or fits(k + 1) false, BOTH
     established by calls of fits: sizes need not be monotone in the level (tile borders, the context model), so the bisection
     keeps fits(lo) and not fits(hi) and ends on an adjacent pair whatever lies between.  Order: CAP_STEPS (returned if it fits);
     the estimate and, if it fits, its successor; 0 if no fitting index is known yet; then bisection of the side that remains --
-    at most 1 + 2 + 1 + 8 calls, none repeated.  A ValueError if 0 does not fit."""
+    at most 1 + 2 + 1 + 8 calls, none repeated.  A ValueError if 0 does not fit.
+    steps=S >= 1: the same search over the indices 0 .. S (Codec.transcode_to_budget: the integer levels 0 .. C), at most
+    1 + 2 + 1 + ceil(log2 S) calls."""
+    steps = int(steps)
+    if steps < 1:
+        raise ValueError('budget search: {} steps, at least 1 is needed'.format(steps))
     probes = [0]
 
     def probe(k):
         probes[0] += 1
         return bool(fits(k))
 
-    hi = CAP_STEPS
+    hi = steps
     if probe(hi):
         return hi, probes[0]
     lo = None
-    e = min(max(int(estimate_index), 0), CAP_STEPS - 1)
+    e = min(max(int(estimate_index), 0), steps - 1)
     if probe(e):
         lo = e
         if e + 1 < hi:
@@ -369,6 +387,39 @@ def preview_symbols(symbols_chw, channels, fill):
     return out
 
 
+def cap_channels(plane, C):
+    """a cap plane that can be applied to symbols -> the (h, w) int64 plane of channels kept per cell, 0 .. C.  Every entry is an
+    integer value in [0, C] or anything at or above C (+inf: no cap); a ValueError for a negative or NaN entry (as _check_level)
+    and for a fractional one below C."""
+    C = int(C)
+    p = np.asarray(plane, dtype=np.float64)
+    if p.ndim != 2:
+        raise ValueError('cap plane of shape {}: expected (h, w)'.format(p.shape))
+    if not bool((p >= 0).all()):                                     # (a NaN compares false)
+        raise ValueError('cap {} is not in [0, +inf]'.format(float(p[~(p >= 0)].flat[0])))
+    low = np.minimum(p, C)
+    if not bool((low == np.floor(low)).all()):
+        raise ValueError('cap {:g} is not an integer: a fractional cap rescales z and needs the bottleneck, so it belongs to compress '
+                         'from the image; symbols take the integer levels 0 .. C = {}'.format(float(low[low != np.floor(low)].flat[0]), C))
+    return low.astype(np.int64)
+
+
+def cap_symbols(symbols_chw, plane, fill):
+    """an integer cap applied to a (C, h, w) symbol volume: a copy with out[c, y, x] = symbols[c, y, x] if c < plane[y, x] else fill.
+    plane: (h, w), as cap_channels takes it.  This is what the quantiser writes under that cap (an integer level cuts at a channel
+    plane and leaves the channels below it as they are), so a file can be capped without its image: with a constant plane K it is
+    preview_symbols(symbols, K, fill)."""
+    sym = np.asarray(symbols_chw)
+    if sym.ndim != 3:
+        raise ValueError('cap_symbols: a (C, h, w) symbol volume is expected, got shape {}'.format(sym.shape))
+    keep = cap_channels(plane, sym.shape[0])
+    if keep.shape != sym.shape[1:]:
+        raise ValueError('cap plane of shape {} for a symbol volume of {} x {} cells'.format(keep.shape, sym.shape[1], sym.shape[2]))
+    out = np.array(sym, copy=True)
+    out[np.arange(sym.shape[0])[:, None, None] >= keep[None]] = fill
+    return out
+
+
 def check_channels(channels, C):
     """the channels argument of the decompress calls: None (all of them) or an integer in 1 .. C; else a ValueError naming C"""
     if channels is None:
@@ -424,7 +475,8 @@ def list_dir_jobs(in_dir, out_dir, command):
     """the files a -dir command works on: [(input path, output path)] sorted by file name.  compress-dir: every *.png / *.jpg of
     in_dir -> out_dir/<stem>.icf; decompress-dir: every *.icf -> out_dir/<stem>.png.  Two inputs with one stem (a.png, a.jpg) would
     write one output: a ValueError, as is a missing directory or one without such files."""
-    exts, out_ext = {'compress-dir': (('.png', '.jpg'), '.icf'), 'decompress-dir': (('.icf',), '.png')}[command]
+    exts, out_ext = {'compress-dir': (('.png', '.jpg'), '.icf'), 'decompress-dir': (('.icf',), '.png'),
+                     'transcode-dir': (('.icf',), '.icf')}[command]
     if not os.path.isdir(in_dir):
         raise ValueError('{}: {!r} is not a directory'.format(command, in_dir))
     names = sorted(n for n in os.listdir(in_dir)
@@ -1393,6 +1445,15 @@ class Codec(object):
             xs.append((x, None if cap is None else torch.as_tensor(self.cap_plane(size[0], size[1], cap)[None]).to(self.device)))
         syms = self._in_flight(xs, lambda ae, xc: (ae.encode(xc[0], is_training=False) if xc[1] is None else
                                                    ae.encode_capped(xc[0], xc[1])[0]).symbols[0])
+        return self._containers(syms, sizes)
+
+    def _containers(self, syms, sizes):
+        """[(C, h, w) device symbols], [(H, W)] -> [container bytes], element i byte for byte _container(syms[i], H, W): the tiles of
+        all volumes coded by one launch per tile shape (format 1: the volumes of one shape by one launch).  The tail of
+        compress_many and of transcode_many."""
+        import torch
+        if not self.device_encode:
+            return [self._container(sym, H, W) for sym, (H, W) in zip(syms, sizes)]
         out = [None] * len(syms)
         fronts = self._front_ends()
         ends = fronts if fronts is not None else self._layer_ends()
@@ -1429,6 +1490,31 @@ class Codec(object):
         t, l = ((-c.H) % f) // 2, ((-c.W) % f) // 2                               # val.add_padding's offsets
         return np.ascontiguousarray(img[t:t + c.H, l:l + c.W, :])
 
+    def _decode_together(self, heads, want, max_workspace_bytes=1 << 31, channels=None):
+        """the batched part of decompress_many / transcode_many over parsed and checked containers: per kind (raster, wavefront,
+        layered, front-layered) the tiled files of the most frequent tile extent (and layer ends) in one decode_tiles_batch call ->
+        yields (their indices, per file q or symbols on the device); the other files are the caller's, one by one"""
+        kind = lambda c: (('fronts' if c.version == FORMAT_VERSION_FRONTS else 'layered') if isinstance(c, LayeredContainer)
+                          else 'wavefront' if isinstance(c, WavefrontContainer) else 'raster')
+        for order in ('raster', 'wavefront', 'layered', 'fronts'):
+            mine = [i for i, c in enumerate(heads) if isinstance(c, _TILED) and kind(c) == order]
+            extents = [(heads[i].th, heads[i].tw) + (tuple(heads[i].layer_ends) if order in ('layered', 'fronts') else ()) for i in mine]
+            major = max(sorted(set(extents)), key=extents.count) if extents else None
+            together = [i for i, e in zip(mine, extents) if e == major]
+            if not together:
+                continue
+            try:
+                got = self.pred.decode_tiles_batch([(heads[i].streams, heads[i].first_syms, (heads[i].C, heads[i].h, heads[i].w))
+                                                    for i in together], major[0], major[1], want=want,
+                                                   max_workspace_bytes=max_workspace_bytes, channels=channels,
+                                                   **({'layer_ends': list(major[2:])} if order == 'layered' else
+                                                      {'front_ends': list(major[2:])} if order == 'fronts' else {'order': order}))
+            except ValueError as e:
+                m = re.search(r'volume (\d+)', str(e))
+                where = 'file {}: '.format(together[int(m.group(1))]) if m else ''
+                raise ValueError('{}decoder status is not 0: {}'.format(where, e))
+            yield together, got
+
     def decompress_many(self, datas, max_workspace_bytes=1 << 31, channels=None):
         """[container bytes] of either format, any mix of shapes -> [HWC uint8], element i equal to decompress(datas[i]); with
         channels=K to decompress(datas[i], channels=K), one K for the call.
@@ -1450,25 +1536,7 @@ class Codec(object):
                 raise ValueError('file {}: {}'.format(i, e))
             heads.append(c)
         out = [None] * len(datas)
-        kind = lambda c: (('fronts' if c.version == FORMAT_VERSION_FRONTS else 'layered') if isinstance(c, LayeredContainer)
-                          else 'wavefront' if isinstance(c, WavefrontContainer) else 'raster')
-        for order in ('raster', 'wavefront', 'layered', 'fronts'):
-            mine = [i for i, c in enumerate(heads) if isinstance(c, _TILED) and kind(c) == order]
-            extents = [(heads[i].th, heads[i].tw) + (tuple(heads[i].layer_ends) if order in ('layered', 'fronts') else ()) for i in mine]
-            major = max(sorted(set(extents)), key=extents.count) if extents else None
-            together = [i for i, e in zip(mine, extents) if e == major]
-            if not together:
-                continue
-            try:
-                qs = self.pred.decode_tiles_batch([(heads[i].streams, heads[i].first_syms, (heads[i].C, heads[i].h, heads[i].w))
-                                                   for i in together], major[0], major[1], want='q',
-                                                  max_workspace_bytes=max_workspace_bytes, channels=channels,
-                                                  **({'layer_ends': list(major[2:])} if order == 'layered' else
-                                                     {'front_ends': list(major[2:])} if order == 'fronts' else {'order': order}))
-            except ValueError as e:
-                m = re.search(r'volume (\d+)', str(e))
-                where = 'file {}: '.format(together[int(m.group(1))]) if m else ''
-                raise ValueError('{}decoder status is not 0: {}'.format(where, e))
+        for together, qs in self._decode_together(heads, 'q', max_workspace_bytes, channels):
             imgs = self._in_flight(qs, lambda ae, q: ae.decode(q[None], is_training=False).to(torch.uint8)[0])    # tf.cast truncates (val.py)
             for i, x in zip(together, imgs):
                 out[i] = self._crop(x, heads[i])
@@ -1604,6 +1672,168 @@ class Codec(object):
             for i, x, tiles in zip(members, imgs, held):
                 out[i] = (self._crop(x, heads[i][0]), self._recover_report(heads[i], tiles))
         return out
+
+    # -- a file to a file: another format, a lower rate, no image and no autoencoder --
+
+    def _check_target(self):
+        """the refusals of the format this Codec writes, before anything is decoded"""
+        self._front_ends()
+        self._layer_ends()
+        self._order()
+        if self.checked and self.tile is None:
+            raise ValueError('checked=True needs a tile extent: the checksums of format 4 are per tile')
+
+    def _keep_plane(self, c, cap=None, rois=None, background=None):
+        """transcode's cap arguments for the file of container c -> None (no cap) or the (h, w) int64 plane of channels kept per
+        cell (cap_plane on the header's H, W, then cap_channels: integer levels only)"""
+        if cap is None and not rois and background is None:
+            return None
+        return cap_channels(self.cap_plane(c.H, c.W, cap, rois, background), c.C)
+
+    def _capped(self, sym, keep):
+        """cap_symbols on the device: sym (C, h, w) int64, keep None or the (h, w) int64 plane of _keep_plane"""
+        import torch
+        if keep is None or int(keep.min()) >= int(sym.shape[0]):
+            return sym
+        k = torch.as_tensor(keep).to(sym.device)
+        below = torch.arange(int(sym.shape[0]), device=sym.device)[:, None, None] < k[None]
+        return torch.where(below, sym, torch.full_like(sym, self.pred.conceal_fallback()))
+
+    def _decode_device(self, c):
+        """a parsed and checked container -> its (C, h, w) int64 symbols, left on the device"""
+        shape = (c.C, c.h, c.w)
+        try:
+            if isinstance(c, LayeredContainer):
+                return self.pred.decode_tiles_batch([(c.streams, c.first_syms, shape)], c.th, c.tw, want='symbols', **_ends_kw(c))[0]
+            if isinstance(c, _TILED):
+                return self.pred.decode_tiles_batch([(c.streams, c.first_syms, shape)], c.th, c.tw, want='symbols',
+                                                    order='wavefront' if isinstance(c, WavefrontContainer) else 'raster')[0]
+            return self.pred.decode_stream(c.payload, shape, c.first_sym, on_device=True)
+        except ValueError as e:
+            raise ValueError('decoder status is not 0: {}'.format(str(e).replace('(volume 0, tile ', '(tile ')))
+
+    def transcode(self, data, cap=None, rois=None, background=None):
+        """container bytes of any format -> container bytes in the format THIS Codec writes (tile, checked, order, layers,
+        front_layers), byte for byte what compress would have written for the image: the symbols are decoded and left on the device,
+        then coded again; the autoencoder is not run, so nothing is lost a second time.  cap, rois, background: as compress takes them,
+        but at integer levels only (cap_channels: a fractional cap needs the bottleneck) -- cell p keeps the channels below its level,
+        the others get the fill symbol (cap_symbols), which is compress(img, cap=...) of the same levels.  The file is parsed and
+        checked as decompress does it; every refusal, the target format's included, comes before any device work."""
+        self._check_target()
+        c = parse_container(data)
+        self.check_container(c)
+        keep = self._keep_plane(c, cap, rois, background)
+        return self._container(self._capped(self._decode_device(c), keep), c.H, c.W)
+
+    def transcode_many(self, datas, caps=None, max_workspace_bytes=1 << 31):
+        """[container bytes] of any mix of formats and shapes -> [container bytes], element i equal to transcode(datas[i], cap=caps[i])
+        (caps: None, or one entry per file -- None, an integer level or a plane).  Every file is parsed and checked first: the first
+        refusal raises its ValueError with 'file i: ' in front and nothing has reached the device.  The sources are grouped as
+        decompress_many groups them (per kind the files of the most frequent tile extent / layer ends in one decode launch per
+        workspace chunk, the others file by file), the symbols stay on the device, and the targets are coded as compress_many codes
+        them: the tiles of all files in one launch per tile shape."""
+        datas = list(datas)
+        caps = [None] * len(datas) if caps is None else list(caps)
+        if len(caps) != len(datas):
+            raise ValueError('caps: {} entries for {} files'.format(len(caps), len(datas)))
+        self._check_target()
+        heads, keeps = [], []
+        for i, (data, cap) in enumerate(zip(datas, caps)):
+            try:
+                c = parse_container(data)
+                self.check_container(c)
+                keeps.append(self._keep_plane(c, cap))
+            except ValueError as e:
+                raise ValueError('file {}: {}'.format(i, e))
+            heads.append(c)
+        syms = [None] * len(datas)
+        for together, got in self._decode_together(heads, 'symbols', max_workspace_bytes):
+            for i, sym in zip(together, got):
+                syms[i] = sym
+        for i, c in enumerate(heads):
+            if syms[i] is None:
+                try:
+                    syms[i] = self._decode_device(c)
+                except ValueError as e:
+                    raise ValueError('file {}: {}'.format(i, e))
+        return self._containers([self._capped(sym, keep) for sym, keep in zip(syms, keeps)], [(c.H, c.W) for c in heads])
+
+    def transcode_to_budget(self, data, max_bytes, rois=None):
+        """the largest integer level K in 0 .. C whose file has at most max_bytes bytes -> (out, K, probes): out is byte for byte
+        transcode(data, cap=K), or with rois transcode(data, rois=rois, background=K) (the rectangles stay uncapped, the budget is
+        met by the background); probes is the number of real codings.  The file is decoded once; every level after that is one
+        torch.where over its symbols.  An estimate from the context model's bit costs (up to 16 capped volumes a launch, one
+        readback a round) starts budget_search(steps=C), whose contract holds on the real files: out fits, and the file of K + 1
+        does not (or K == C) -- at most 1 + 2 + 1 + ceil(log2 C) codings.  A ValueError if the file of level 0 is over the budget."""
+        import torch
+        from ._lib import lib, check, ptr, current_stream
+        max_bytes = int(max_bytes)
+        self._check_target()
+        c = parse_container(data)
+        self.check_container(c)
+        C = self.C
+        roi = np.isinf(cap_plane(c.H, c.W, self.factor, rois=rois, background=0.0)) if rois else None
+        sym = self._decode_device(c)
+        planes = lambda k: np.full((c.h, c.w), k, np.int64) if roi is None else np.where(roi, C, k).astype(np.int64)
+        files = {}
+
+        def coded(k):
+            if k not in files:
+                files[k] = self._container(self._capped(sym, planes(k)), c.H, c.W)
+            return files[k]
+
+        def estimate(ks):                                             # bytes of the whole-volume pass per level, one readback
+            vols = torch.stack([self._capped(sym, planes(k)) for k in ks])
+            q = self.ae.get_centers_variable()[vols].contiguous()
+            bits = self.pc.bitcost(q, vols, is_training=False, pad_value=self.pc.auto_pad_value(self.ae))
+            buf = torch.empty(1024 + len(ks), dtype=torch.float32, device=self.device)
+            check(lib.ic_mean_rows_f32(ptr(bits), len(ks), bits.numel() // len(ks), 8.0, ptr(buf), ptr(buf[1024:]),
+                                       current_stream(self.device)), 'ic_mean_rows_f32')
+            return [float(v) for v in buf[1024:].cpu().numpy()]
+
+        guess = C
+        if len(coded(C)) > max_bytes and C > 1:
+            # the container and the streams' ends cost the same at every level, to first order: take them from the one real file
+            step = (C + 15) // 16
+            ks = list(range(step, C + 1, step))
+            if ks[-1] != C:
+                ks[-1] = C
+            est = estimate(ks)
+            room = max_bytes - (len(files[C]) - est[-1])
+            below = [k for k, b in zip(ks, est) if b <= room]
+            ks = list(range(1, step)) if not below else list(range(below[-1] + 1, min(below[-1] + step, C)))
+            guess = below[-1] if below else 0
+            if ks:
+                fit = [k for k, b in zip(ks, estimate(ks)) if b <= room]
+                guess = fit[-1] if fit else guess
+        try:
+            k, probes = budget_search(lambda k: len(coded(k)) <= max_bytes, guess, steps=C)
+        except ValueError:
+            raise ValueError('budget of {} bytes: the smallest file, at level 0, has {} bytes'.format(max_bytes, len(coded(0))))
+        return files[k], int(k), probes
+
+    def repair(self, data, cap=None):
+        """what a damaged or cut file still holds, written as an intact file in the format this Codec writes -> (bytes, report).  A
+        format-4 / format-5 source is read as salvage reads it (the intact tiles decoded, the others filled from their neighbours by
+        ic_pc_conceal_tiles; report: salvage's SalvageReport), a format-6 / format-8 source as recover reads it (recover_symbols;
+        report: recover's RecoverReport); the symbols stay on the device and are coded again, under `cap` if one is given (as
+        transcode's).  decompress(out) is salvage's / recover's picture; an intact file gives transcode(data) and an empty list.
+        Formats 1 and 2 carry no checksums to read a damaged file by: refused in salvage's words."""
+        self._check_target()
+        raw = bytes(data)
+        if len(raw) >= 6 and raw[:4] == MAGIC and struct.unpack('<H', raw[4:6])[0] in _LAYERED_VERSIONS:
+            head = self._recover_head(raw)
+            c = head[0]
+            keep = self._keep_plane(c, cap)
+            syms, held = self._recover_decode([head], 'symbols')
+            report = self._recover_report(head, held[0])
+        else:
+            c, reasons, file_crc_ok = self._salvage_head(raw)
+            keep = self._keep_plane(c, cap)
+            syms, damage = self.pred.decode_tiles_batch([(c.streams, c.first_syms, (c.C, c.h, c.w))], c.th, c.tw, want='symbols', conceal=True,
+                                                        order='wavefront' if isinstance(c, WavefrontContainer) else 'raster')
+            report = self._report(c, reasons, damage[0], file_crc_ok)
+        return self._container(self._capped(syms[0], keep), c.H, c.W), report
 
     def open_stream(self, max_workspace_bytes=1 << 31, fronts=False):
         """a StreamDecoder: a format-6 file fed as it arrives, recover's picture of the bytes so far, every layer decoded once;
@@ -1741,19 +1971,33 @@ def _recover_line(path, report):
             d.pixels[1] + d.pixels[3]) for d in report.tiles), crc)
 
 
+TRANSCODE_COMMANDS = ('transcode', 'transcode-dir')
+
+
 def check_option_args(flags):
     """--checked / --wavefront / --salvage / --channels / --layers / --progressive / --front-layers / --front-progressive / --partial /
     --recover / --chunk / --fronts / --cap / --roi / --background / --max-bytes / --bpp against the command, --tile
     and each other: decided before any model is built"""
     cap, background, rois = getattr(flags, 'cap', None), getattr(flags, 'background', None), getattr(flags, 'roi', None) or []
     max_bytes, bpp = getattr(flags, 'max_bytes', None), getattr(flags, 'bpp', None)
+    transcoding = flags.command in TRANSCODE_COMMANDS
     for name, value in (('--cap', cap), ('--background', background), ('--max-bytes', max_bytes), ('--bpp', bpp)):
-        if value is not None and flags.command not in ('compress', 'compress-dir'):
+        if value is not None and flags.command not in ('compress', 'compress-dir') + TRANSCODE_COMMANDS:
             raise ValueError('{} belongs to compress / compress-dir: the cap on the importance map is the encoder\'s, a file is read '
                              'without it'.format(name))
-    if rois and flags.command != 'compress':
+    if rois and flags.command == 'transcode-dir':
+        raise ValueError('--roi belongs to compress / transcode: a rectangle is in the pixels of one image')
+    if rois and flags.command not in ('compress', 'transcode'):
         raise ValueError('--roi belongs to compress: a rectangle is in the pixels of one image' if flags.command == 'compress-dir' else
                          '--roi belongs to compress: the cap on the importance map is the encoder\'s, a file is read without it')
+    if transcoding:
+        for name, value in (('--cap', cap), ('--background', background)):
+            if value is not None and _check_level(value, name) != float('inf') and float(value) != int(float(value)):
+                raise ValueError('{} {:g} is not an integer: a fractional cap rescales z and needs the bottleneck, so it belongs to '
+                                 'compress from the image; a file takes the integer levels 0 .. C'.format(name, float(value)))
+        for name in ('salvage', 'recover'):
+            if getattr(flags, name, False) and (rois or max_bytes is not None or bpp is not None):
+                raise ValueError('--{} does not go with --roi, --max-bytes or --bpp: a repaired file takes --cap alone'.format(name))
     if max_bytes is not None and bpp is not None:
         raise ValueError('--max-bytes does not go with --bpp: the one names the budget in bytes, the other per pixel')
     if cap is not None and (max_bytes is not None or bpp is not None):
@@ -1799,21 +2043,21 @@ def check_option_args(flags):
         if flags.channels < 1:
             raise ValueError('--channels {} is not at least 1'.format(flags.channels))
     if getattr(flags, 'checked', False):
-        if flags.command not in ('compress', 'compress-dir'):
+        if flags.command not in ('compress', 'compress-dir') + TRANSCODE_COMMANDS:
             raise ValueError('--checked belongs to compress / compress-dir: a file says by itself what it is')
         if flags.tile is None:
             raise ValueError('--checked needs --tile: the checksums of format 4 are per tile')
     if getattr(flags, 'wavefront', False):
-        if flags.command not in ('compress', 'compress-dir'):
+        if flags.command not in ('compress', 'compress-dir') + TRANSCODE_COMMANDS:
             raise ValueError('--wavefront belongs to compress / compress-dir: a file says by itself what it is')
         if flags.tile is None:
             raise ValueError('--wavefront needs --tile: format 5 codes every tile front by front')
-    if getattr(flags, 'salvage', False) and flags.command not in ('decompress', 'decompress-dir'):
+    if getattr(flags, 'salvage', False) and flags.command not in ('decompress', 'decompress-dir') + TRANSCODE_COMMANDS:
         raise ValueError('--salvage belongs to decompress / decompress-dir')
     layers, progressive = getattr(flags, 'layers', None), getattr(flags, 'progressive', False)
     if layers is not None or progressive:
         name = '--layers' if layers is not None else '--progressive'
-        if flags.command not in ('compress', 'compress-dir'):
+        if flags.command not in ('compress', 'compress-dir') + TRANSCODE_COMMANDS:
             raise ValueError('{} belongs to compress / compress-dir: a file says by itself what it is'.format(name))
         if flags.tile is None:
             raise ValueError('{} needs --tile: format 6 cuts every tile into layers'.format(name))
@@ -1826,7 +2070,7 @@ def check_option_args(flags):
     front_layers, front_progressive = getattr(flags, 'front_layers', None), getattr(flags, 'front_progressive', False)
     if front_layers is not None or front_progressive:
         name = '--front-layers' if front_layers is not None else '--front-progressive'
-        if flags.command not in ('compress', 'compress-dir'):
+        if flags.command not in ('compress', 'compress-dir') + TRANSCODE_COMMANDS:
             raise ValueError('{} belongs to compress / compress-dir: a file says by itself what it is'.format(name))
         if flags.tile is None:
             raise ValueError('{} needs --tile: format 8 cuts every tile into layers'.format(name))
@@ -1849,7 +2093,7 @@ def check_option_args(flags):
         if getattr(flags, 'channels', None) is not None:
             raise ValueError('--partial does not go with --channels: the complete layers decide the channels')
     if getattr(flags, 'recover', False):
-        if flags.command not in ('decompress', 'decompress-dir'):
+        if flags.command not in ('decompress', 'decompress-dir') + TRANSCODE_COMMANDS:
             raise ValueError('--recover belongs to decompress / decompress-dir: it reads what a damaged or cut layered file still holds')
         if getattr(flags, 'salvage', False):
             raise ValueError('--recover does not go with --salvage: the one reads layered files (format 6), the other formats 4 and 5')
@@ -1917,7 +2161,7 @@ def check_dir_args(flags, factor):
         raise ValueError('--batch {} is not at least 1'.format(flags.batch))
     tile = None
     if flags.tile is not None:
-        if flags.command != 'compress-dir':
+        if flags.command not in ('compress-dir', 'transcode-dir'):
             raise ValueError('--tile belongs to compress / compress-dir: a file says by itself how it is tiled')
         if flags.tile <= 0 or flags.tile % factor != 0:
             raise ValueError('--tile {} is not a positive multiple of the subsampling factor {}'.format(flags.tile, factor))
@@ -1945,6 +2189,8 @@ def _main_dir(flags, ae_config, pc_config):
     channels = check_channels(getattr(flags, 'channels', None), codec.C)
     os.makedirs(flags.output, exist_ok=True)
     total_in = total_out = total_pixels = 0
+    if flags.command == 'transcode-dir':
+        return _transcode_dir(flags, codec, jobs)
     if flags.command == 'decompress-dir' and flags.salvage:
         return _salvage_dir(flags, codec, jobs)
     if flags.command == 'decompress-dir' and flags.partial:
@@ -1985,6 +2231,81 @@ def _main_dir(flags, ae_config, pc_config):
     else:
         print('total: {} files, {} pixels from {} bytes = {:.4f} bpp'.format(len(jobs), total_pixels, total_in, 8.0 * total_in / total_pixels))
     return 0
+
+
+def _source_version(data):
+    """the format version a file names, for a printed line (the readers decide what it is worth); None without one"""
+    return struct.unpack('<H', data[4:6])[0] if len(data) >= 6 and data[:4] == MAGIC else None
+
+
+def _transcode_line(path, data, out):
+    return '{}: format {} -> format {}, {} -> {} bytes'.format(path, _source_version(data), _source_version(out), len(data), len(out))
+
+
+def _cap_option(value):
+    """--cap / --background of a transcode (check_option_args has seen it: an integer or +inf) -> what Codec.transcode takes"""
+    return None if value is None else value if value == float('inf') else int(value)
+
+
+def _transcode_one(flags, codec, src, dst, data, rois=None):
+    """one file of transcode / transcode-dir by the flags' own path -- repair, budget or plain -- written and printed"""
+    report = None
+    note = ''
+    if getattr(flags, 'salvage', False) or getattr(flags, 'recover', False):
+        try:
+            out = codec.transcode(data, cap=_cap_option(flags.cap))
+        except ValueError:                                           # (as decompress --salvage: the strict reader first)
+            out, report = codec.repair(data, cap=_cap_option(flags.cap))
+    elif flags.max_bytes is not None or flags.bpp is not None:
+        c = parse_container(data)
+        out, level, probes = codec.transcode_to_budget(data, _budget_of(flags, c.H, c.W), rois=rois or None)
+        note = _budget_note(level, probes)
+    else:
+        out = codec.transcode(data, cap=_cap_option(flags.cap), rois=rois or None, background=_cap_option(flags.background))
+    with open(dst, 'wb') as f:
+        f.write(out)
+    print(_transcode_line(dst, data, out) + note)
+    if isinstance(report, SalvageReport) and (report.damaged or not report.file_crc_ok):
+        print(_damage_line(src, report))
+    if isinstance(report, RecoverReport):
+        print(_recover_line(src, report))
+    return out
+
+
+def _transcode_dir(flags, codec, jobs):
+    """transcode-dir: --batch files per transcode_many call; with a budget a search per file, with --salvage / --recover a repair per
+    file, and there a file of which nothing can be read is named on stderr and skipped.  Exit status 0 when every file was written."""
+    written = total_in = total_out = 0
+    one_by_one = flags.salvage or flags.recover or _budget_of(flags, 1, 1) is not None
+    for start in range(0, len(jobs), flags.batch):
+        part = jobs[start:start + flags.batch]
+        datas = []
+        for src, _ in part:
+            with open(src, 'rb') as f:
+                datas.append(f.read())
+        if one_by_one:
+            for (src, dst), data in zip(part, datas):
+                try:
+                    out = _transcode_one(flags, codec, src, dst, data)
+                except ValueError as e:
+                    if not (flags.salvage or flags.recover):
+                        raise ValueError('{}: {}'.format(src, e))
+                    print('error: {}: {}'.format(src, e), file=sys.stderr)
+                    continue
+                written, total_in, total_out = written + 1, total_in + len(data), total_out + len(out)
+            continue
+        try:
+            outs = codec.transcode_many(datas, caps=None if flags.cap is None else [_cap_option(flags.cap)] * len(datas))
+        except ValueError as e:
+            m = re.match(r'file (\d+): ', str(e))
+            raise ValueError('{}: {}'.format(part[int(m.group(1))][0], str(e)[m.end():]) if m else str(e))
+        for (src, dst), data, out in zip(part, datas, outs):
+            with open(dst, 'wb') as f:
+                f.write(out)
+            print(_transcode_line(dst, data, out))
+            written, total_in, total_out = written + 1, total_in + len(data), total_out + len(out)
+    print('total: {} of {} files, {} -> {} bytes'.format(written, len(jobs), total_in, total_out))
+    return 0 if written == len(jobs) else 2
 
 
 def _partial_line(path, report):
@@ -2188,9 +2509,10 @@ def main(argv=None):
     argv = sys.argv[1:] if argv is None else list(argv)
     if argv and argv[0] == 'verify':
         return _main_verify(argv[1:])
-    p = argparse.ArgumentParser(description='compress an image to a codec file, or a codec file back to an image; '
+    p = argparse.ArgumentParser(description='compress an image to a codec file, or a codec file back to an image; transcode a codec '
+                                            'file to another format or a lower rate without its image; '
                                             'the -dir commands do so for every file of a directory, --batch files per call')
-    p.add_argument('command', choices=['compress', 'decompress', 'compress-dir', 'decompress-dir', 'stream'])
+    p.add_argument('command', choices=['compress', 'decompress', 'compress-dir', 'decompress-dir', 'stream', 'transcode', 'transcode-dir'])
     p.add_argument('input')
     p.add_argument('output')
     p.add_argument('--ae_config', default='cvpr/low', help='a config file, or a name below $CONFIG_BASE_AE / the package\'s ae_configs')
@@ -2202,7 +2524,7 @@ def main(argv=None):
     p.add_argument('--tile', type=int, default=None, metavar='PIXELS',
                    help='compress: square tiles of this many image pixels (a positive multiple of the subsampling factor), one stream '
                         'per tile, decoded concurrently (format 2); default: one stream (format 1)')
-    p.add_argument('--batch', type=int, default=8, metavar='N', help='compress-dir / decompress-dir: files per call (default 8)')
+    p.add_argument('--batch', type=int, default=8, metavar='N', help='the -dir commands: files per call (default 8)')
     p.add_argument('--checked', action='store_true', help='compress / compress-dir with --tile: a CRC per tile stream and one over the '
                                                           'header (format 4), so that a damaged file can be salvaged')
     p.add_argument('--wavefront', action='store_true', help='compress / compress-dir with --tile: the layout of --checked, every tile coded '
@@ -2233,13 +2555,15 @@ def main(argv=None):
                                                          'swept once; without it such a file is refused')
     p.add_argument('--cap', type=float, default=None, metavar='T',
                    help='compress / compress-dir: an upper bound T in [0, C] on the importance map, the same in every latent cell: a rate '
-                        'below the model\'s own (0: every channel masked; C or more: no cap); the file format is unchanged')
+                        'below the model\'s own (0: every channel masked; C or more: no cap); the file format is unchanged; '
+                        'transcode / transcode-dir: the same on a file\'s symbols, an integer level K only')
     p.add_argument('--roi', action='append', default=None, metavar='X,Y,W,H',
                    help='compress: a rectangle in image pixels that keeps --cap (or no cap) while the rest gets --background; repeatable')
-    p.add_argument('--background', type=float, default=None, metavar='T', help='compress with --roi: the cap outside the rectangles')
+    p.add_argument('--background', type=float, default=None, metavar='T', help='compress / transcode with --roi: the cap outside the rectangles')
     p.add_argument('--max-bytes', dest='max_bytes', type=int, default=None, metavar='N',
                    help='compress / compress-dir: the largest cap level (of the grid k C / 256) whose file has at most N bytes; with --roi '
-                        'the rectangles stay uncapped and the level is the background\'s; prints the level and the number of codings')
+                        'the rectangles stay uncapped and the level is the background\'s; prints the level and the number of codings; '
+                        'transcode / transcode-dir: the largest integer level 0 .. C')
     p.add_argument('--bpp', type=float, default=None, metavar='B', help='compress / compress-dir: --max-bytes floor(B H W / 8), per image')
     flags = p.parse_args(argv)
     from . import config_parser, val, weights as _weights
@@ -2256,7 +2580,7 @@ def main(argv=None):
         else:
             wts = val.load_weights_for_job(None, flags.weights, ae_config, pc_config)
         codec = Codec(ae_config, pc_config, wts, flags.device)
-        if flags.command == 'compress':
+        if flags.command in ('compress', 'transcode'):
             if flags.tile is not None:
                 if flags.tile <= 0 or flags.tile % codec.factor != 0:
                     raise ValueError('--tile {} is not a positive multiple of the subsampling factor {}'.format(flags.tile, codec.factor))
@@ -2266,6 +2590,11 @@ def main(argv=None):
                 codec.layers = layers
                 codec.front_layers = front_layers
             rois = [parse_roi_arg(r) for r in flags.roi or []]
+        if flags.command == 'transcode':
+            with open(flags.input, 'rb') as f:
+                data = f.read()
+            _transcode_one(flags, codec, flags.input, flags.output, data, rois=rois)
+        elif flags.command == 'compress':
             if flags.max_bytes is not None or flags.bpp is not None:
                 from PIL import Image
                 img = np.asarray(Image.open(flags.input).convert('RGB'), dtype=np.uint8)     # as compress_file reads it

@@ -461,13 +461,14 @@ class PredictionNetwork(object):
             raise ValueError('a preview (channels={}) needs a context model of width k = 24, this one has k = {}'.format(channels, self.pc._k))
         return channels, self.conceal_fallback()
 
-    def decode_stream(self, stream_bytes, symbols_shape, first_sym, flags=0, channels=None):
+    def decode_stream(self, stream_bytes, symbols_shape, first_sym, flags=0, channels=None, on_device=False):
         """Row N3: the whole sequential decode on the device (ic_pc_decode_f32) -- per symbol the same context-model
         kernels as get_freqs, the table, the arithmetic-decoder step and the gather of the next context are enqueued
         back to back without a host round trip.  stream_bytes: what the encoder wrote; symbols_shape: un-padded
         (C,h,w); first_sym: the uncoded first symbol.  -> (C,h,w) int64 numpy.
         channels=K: a preview (ic_pc_decode_channels_f32) -- the decoder stops after channels 0 .. K - 1, the others hold the fill
-        symbol (conceal_fallback): codec.preview_symbols of the full decode.  None: all channels, the call as it always was."""
+        symbol (conceal_fallback): codec.preview_symbols of the full decode.  None: all channels, the call as it always was.
+        on_device=True: -> the (C,h,w) int64 DEVICE tensor instead (Codec.transcode codes it again: the symbols never visit the host)."""
         C, h, w = (int(v) for v in symbols_shape)
         preview = self._preview(channels, C)
         dev = self.centers.device
@@ -485,7 +486,7 @@ class PredictionNetwork(object):
             check(lib.ic_pc_decode_channels_f32(*(args + preview)), 'ic_pc_decode_channels_f32')
         if int(status.item()) != 0:
             raise ValueError('Cannot decode symbol because total is too large')
-        return out.cpu().numpy()
+        return out if on_device else out.cpu().numpy()
 
     def encode_tiles(self, symbols, th, tw, order='raster', layer_ends=None, front_ends=None):
         """symbols: un-padded (C,h,w) -> [(stream_bytes, first_sym)] for the tiles of codec.tile_grid(h, w, th, tw), in grid order.
