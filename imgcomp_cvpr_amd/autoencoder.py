@@ -366,6 +366,67 @@ class _CVPR(_Network):
                                               N, C, hh, ww, _lib.current_stream(bottleneck.device)), 'ic_heatmap_quantize_cap_f32')
         return EncoderOutput(qbar, qhard, symbols, z, heatmap)
 
+    # -- the kernel family of one shape, forced on another (host queries only: no device call) ---------------
+
+    PLAN_LIKE_MAX_PIXELS = 1 << 25      # from here on the edge kernels and the 3x3 forms meet their 31-bit offset limits and fall back
+
+    def _decode_family(self, H, W, flags):
+        """what decode(q of an (1, 3, H, W) picture) runs under the ABI flags `flags`: (3x3 form of ic_conv3x3_c128_pick_form, its
+        F(2x2) decomposition 'whole' | 'ksplit' | 'mixed' or None, h12 on the F(4x4)-over-phases kernel?) -- network.hip's rules"""
+        h4, w4 = H // 4, W // 4
+        form = int(lib.ic_conv3x3_c128_pick_form(1, h4, w4, flags))
+        split = None
+        if form == 1:
+            import ctypes
+            pl = (ctypes.c_longlong * 5)()
+            check(lib.ic_wino3x3_c128_plan(1, h4, w4, flags & ~(_lib.CONV3_WINO4_WG8 | _lib.CONV3_WINO4_WG4), pl), 'ic_wino3x3_c128_plan')
+            whole, seg, _, t16, ksplit = (int(v) for v in pl)
+            # whole-K, its per-wave form, the NB-segment and the 16 x 16 jobs do the same operations per output; K-split sums four
+            # partial chains (tests/test_gpu_ops.py: the decompositions bit for bit)
+            split = 'whole' if ksplit == 0 else 'ksplit' if whole + seg + t16 == 0 else 'mixed'
+        h12_w4 = bool(flags & _lib.CONV5_BOTH_PACKED) and not (flags & _lib.CONV5_NO_WINO4) and \
+            int(lib.ic_wino4_conv5s2_supported(1, h4, w4)) == 1 and \
+            (bool(flags & _lib.CONV5_WINO4) or form == 2 or int(lib.ic_wino4_conv5s2_workgroups(1, h4, w4, 0)) >= 160)
+        return form, split, h12_w4
+
+    def decode_family(self, H, W):
+        """_decode_family of an (1, 3, H, W) picture under this object's own plan_flags"""
+        return self._decode_family(int(H), int(W), self._abi_flags(self.plan_flags))
+
+    def plan_like(self, H, W):
+        """the IC_CONV3_* / IC_CONV5_* bits that force, on a picture of ANOTHER shape, the kernel family decode gives an (1, 3, H, W)
+        picture under this object's own plan_flags: the 3x3 form (direct, F(2x2), F(4x4)) with the F(2x2) decomposition that sums
+        alike, and h12's form (F(4x4) over phases or the direct kernel).  Pass them as decode(..., plan_flags=bits) of the other
+        picture; plan_holds says whether that picture can take them.  None where flags cannot say it: an F(2x2) plan that mixes
+        whole-K and K-split launches, own flags whose form bits the wanted form cannot be OR-ed onto, IC_CONV3_LEAVE_IDLE_CUS
+        (per-layer plans), a picture of PLAN_LIKE_MAX_PIXELS or more (the kernels' 31-bit fall-backs)."""
+        H, W = int(H), int(W)
+        f = self.get_subsampling_factor()
+        if H < f or W < f or H % f or W % f:
+            raise ValueError('H and W must be positive multiples of {}, got {}x{}'.format(f, H, W))
+        flags = self._abi_flags(self.plan_flags)
+        if H * W >= self.PLAN_LIKE_MAX_PIXELS or flags & _lib.CONV3_LEAVE_IDLE_CUS:
+            return None
+        form, split, h12_w4 = self._decode_family(H, W, flags)
+        if form == 1 and split == 'mixed':
+            return None
+        want = {0: _lib.CONV3_DIRECT, 2: _lib.CONV3_WINO4}.get(form, _lib.CONV3_WINO_KSPLIT if split == 'ksplit' else _lib.CONV3_WINO_WHOLEK)
+        if (flags & _lib.CONV3_FORM_MASK) | want != want:
+            return None
+        return want | (_lib.CONV5_WINO4 if h12_w4 else _lib.CONV5_NO_WINO4)
+
+    def plan_holds(self, bits, H, W, Hw, Ww, top=0, left=0):
+        """does decode of an (1, 3, Hw, Ww) window with plan_flags=bits (plan_like(H, W)) run the family of the (1, 3, H, W) picture,
+        with its F(4x4) tiles where the picture has them?  top, left: the window's origin in the picture, in pixels; an F(4x4) tile
+        is 4 x 4 positions at H/4, 16 x 16 pixels."""
+        if bits is None or Hw * Ww >= self.PLAN_LIKE_MAX_PIXELS:
+            return False
+        flags = self._abi_flags(self.plan_flags)
+        full, here = self._decode_family(int(H), int(W), flags), self._decode_family(int(Hw), int(Ww), flags | int(bits))
+        if full != here:
+            return False
+        return not (full[0] == 2 or full[2]) or (int(top) % 16 == 0 and int(left) % 16 == 0)
+
     def _decode(self, q, is_training, plan_flags=0):
         assert not is_training
         _lib.require_cuda(q, 'q')

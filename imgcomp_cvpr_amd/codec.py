@@ -5,6 +5,8 @@
                                                                                 --front-layers a,b,.. | --front-progressive]]
                                                                 [--cap T | --max-bytes N | --bpp B] [--roi X,Y,W,H ... [--background T]]
     python -m imgcomp_cvpr_amd.codec decompress IN.icf  OUT.png [same options] [--salvage | --channels K | --partial | --recover]
+    python -m imgcomp_cvpr_amd.codec decompress IN.icf  OUT.png [same options] --region X,Y,W,H [--channels K]    a rectangle, from the tiles it needs
+    python -m imgcomp_cvpr_amd.codec info PATH [PATH ...] [--region X,Y,W,H]    what the files hold and what a region would decode, without model or device
     python -m imgcomp_cvpr_amd.codec compress-dir   IN_DIR OUT_DIR [--tile PIXELS [same choices]] [--batch N] [--cap T | --max-bytes N | --bpp B]   every *.png / *.jpg -> OUT_DIR/<stem>.icf
     python -m imgcomp_cvpr_amd.codec decompress-dir IN_DIR OUT_DIR [--batch N] [--salvage | --channels K | --partial | --recover]    every *.icf -> OUT_DIR/<stem>.png
     python -m imgcomp_cvpr_amd.codec verify PATH [PATH ...]         files or directories of *.icf: the checksums, without model or device
@@ -148,6 +150,15 @@ quantiser's contract), so --cap / --roi / --background at integer levels and --m
 level.  A fractional level rescales z and needs the bottleneck: refused here, it is compress's.  --salvage / --recover (repair) write
 what a damaged format-4 / 5 (salvage's reader and concealment) or a damaged or cut format-6 / 8 file (recover's) still holds as an
 intact file, with the reader's report; formats 1 and 2 carry no checksums to read a damaged file by.
+decompress --region (Codec.decompress_region, decompress_regions_many, region_plan, decoder_reach): a pixel rectangle of a tiled file
+from the tiles it needs.  A pixel depends on a bounded block of latent cells (decoder_reach walks the decoder's layers: 4 n3 + 3
+pixels before a cell's 8 x 8 block and 4 n3 + 10 behind it, n3 = 6 B + 2; 18 and 17 cells for B = 5), so the rectangle names a
+range of tile rows and columns (region_plan); their streams are decoded as a volume of their own and the autoencoder's decoder runs
+over that window with the kernel forms of the whole picture forced on it (Autoencoder.plan_like), which keeps the pixels those of
+decompress bit for bit; where the picture runs F(4x4) kernels the window is wider (decoder_cells: the transforms carry rounding in
+from about twice as far), and where the forms cannot be had on the window the whole picture is decoded and cropped.  The whole file is
+parsed and checked whatever the rectangle.  No new format, entry point or kernel: the launches above over fewer tiles and a smaller
+map.  info prints region_plan for a file on the host.
 """
 import argparse
 import io
@@ -250,17 +261,132 @@ def cap_plane(H, W, factor, level=None, rois=(), background=None):
     plane = np.full((h, w), np.float32(_check_level(background, 'background')), dtype=np.float32)
     top, left = ((-H) % f) // 2, ((-W) % f) // 2
     for r in rois:
-        try:
-            x, y, rw, rh = (int(v) for v in r)
-        except (TypeError, ValueError):
-            raise ValueError('rectangle {!r} is not (x, y, w, h) in pixels'.format(r))
-        if rw < 1 or rh < 1:
-            raise ValueError('rectangle {}: the extent {} x {} is not positive'.format((x, y, rw, rh), rw, rh))
-        x0, y0, x1, y1 = max(x, 0), max(y, 0), min(x + rw, W), min(y + rh, H)
-        if x0 >= x1 or y0 >= y1:
-            raise ValueError('rectangle {} does not intersect the {} x {} image'.format((x, y, rw, rh), W, H))
+        x0, y0, x1, y1 = _clip_rect(r, H, W)
         plane[(y0 + top) // f:(y1 - 1 + top) // f + 1, (x0 + left) // f:(x1 - 1 + left) // f + 1] = inside
     return plane
+
+
+def _clip_rect(rect, H, W):
+    """(x, y, w, h) in pixels of an H x W image -> (x0, y0, x1, y1) clipped to it; the ValueErrors of cap_plane's rectangles"""
+    try:
+        x, y, rw, rh = (int(v) for v in rect)
+    except (TypeError, ValueError):
+        raise ValueError('rectangle {!r} is not (x, y, w, h) in pixels'.format(rect))
+    if rw < 1 or rh < 1:
+        raise ValueError('rectangle {}: the extent {} x {} is not positive'.format((x, y, rw, rh), rw, rh))
+    x0, y0, x1, y1 = max(x, 0), max(y, 0), min(x + rw, W), min(y + rh, H)
+    if x0 >= x1 or y0 >= y1:
+        raise ValueError('rectangle {} does not intersect the {} x {} image'.format((x, y, rw, rh), W, H))
+    return x0, y0, x1, y1
+
+
+def decoder_layers(B):
+    """the decoder network as a list of (kernel extent, upsampling): what weights.ae_conv_specs names below autoencoder/decoder --
+    from_bn (3 x 3 transposed, stride 2), 6 B + 2 convolutions of 3 x 3, h12 and h13 (5 x 5 transposed, stride 2)"""
+    from .weights import ae_conv_specs, DEC
+    B = int(B)
+    if B < 0:
+        raise ValueError('decoder layers: B = {} is negative'.format(B))
+    return [(int(shape[0]), 2 if kind == 'deconv' else 1) for scope, kind, shape in ae_conv_specs(1, B) if scope.startswith(DEC + '/')]
+
+
+def _f4_needs(a, b):
+    """the positions whose VALUES the F(4x4, 3x3) kernels read for the outputs a .. b of a 3 x 3 convolution, tiles of 4 from position
+    0: in exact arithmetic an output needs its 3 neighbours, but the transforms mix a tile's 6 inputs -- y0 = m0 + .. + m4 of
+    t0 .. t4 takes d0 .. d4 (positions 4 t - 1 .. 4 t + 3), y1 and y2 take d1 .. d4, y3 = .. + m5 takes d1 .. d5 (w4_bt / w4_at of
+    conv3x3_wino4.hip) -- and what cancels in exact arithmetic leaves its rounding.  F(2x2) has no such term: its y0 takes d0 .. d2."""
+    return 4 * (a // 4) - (1 if a % 4 == 0 else 0), 4 * (b // 4) + (4 if b % 4 == 3 else 3)
+
+
+def decoder_cells(p0, p1, B, f4_convs=False, f4_h12=False):
+    """the latent cells whose values the decoder's kernels read for the pixels p0 .. p1 (inclusive) of the padded picture, along
+    one axis -> (first, last), not clipped to the plane.  Walked backwards through decoder_layers.  With both flags False it is the
+    dependency in exact arithmetic, ceil((p0 - 7 - after) / 8) .. floor((p1 + before) / 8) of decoder_reach -- which is also what
+    the direct and the F(2x2) kernels read.  f4_convs: the 3 x 3 layers run F(4x4) (_f4_needs: about two positions a layer instead
+    of one).  f4_h12: h12 runs as F(4x4) 3 x 3 convolutions over the four phases of its output, position i of H/2 in tile i // 2 of H/4.
+    A window that holds these cells gives the picture's values bit for bit under the picture's kernels, not only close ones."""
+    a, b = int(p0), int(p1)
+    layers = decoder_layers(B)
+    for n in range(len(layers) - 1, -1, -1):
+        k, up = layers[n]
+        if up == 2 and f4_h12 and n == len(layers) - 2:
+            a, b = _f4_needs(a // 2, b // 2)
+        elif up == 2:
+            pad = (k - 2) // 2                                       # output o takes input i with o = 2 i + t - pad, t = 0 .. k - 1
+            a, b = -((k - 1 - pad - a) // 2), (b + pad) // 2
+        elif f4_convs and k == 3:
+            a, b = _f4_needs(a, b)
+        else:
+            a, b = a - k // 2, b + k // 2
+    return a, b
+
+
+def decoder_reach(B):
+    """how far a latent cell reaches in the decoded picture -> (before, after) in pixels: a change of cell c changes pixels of
+    [f c - before, f c + f - 1 + after] at most, f = 8 the subsampling factor; 4 n3 + 3 and 4 n3 + 10 with n3 = 6 B + 2.  Walked
+    through decoder_layers: a SAME convolution of extent k widens an interval [a, b] to [a - k // 2, b + k // 2]; a stride-2
+    transposed one -- the adjoint of the SAME convolution 2 n -> n, whose pad in front is (k - 2) // 2 -- maps it to
+    [2 a - (k - 2) // 2, 2 b + k - 1 - (k - 2) // 2].  Equivalently pixel p of the padded picture depends on the cells c with
+    ceil((p - (f - 1) - after) / f) <= c <= floor((p + before) / f)."""
+    a, b, f = 0, 0, 1
+    for k, up in decoder_layers(B):
+        if up == 1:
+            a, b = a - k // 2, b + k // 2
+        else:
+            pad = (k - 2) // 2
+            a, b, f = 2 * a - pad, 2 * b + k - 1 - pad, 2 * f
+    return -a, b - (f - 1)
+
+
+RegionPlan = namedtuple('RegionPlan', ['rect', 'rows', 'cols', 'tiles', 'window', 'offset'])
+
+
+def region_plan(H, W, factor, h, w, th, tw, rect, reach, align=1):
+    """which tiles a pixel rectangle of an H x W image needs, on the host.  rect = (x, y, w, h) in pixels of the image, clipped to
+    it (a ValueError for a rectangle of no extent or one that misses the image, as cap_plane's); the image sits in the padded
+    picture at val.add_padding's centred offsets (top ((-H) % factor) // 2, left likewise); reach = (before, after) of
+    decoder_reach -- or a function (p0, p1) -> (first cell, last cell) for the padded pixels p0 .. p1 of one axis, as decoder_cells
+    is, where the kernels read more than the arithmetic needs; (h, w) the latent plane, cut by tile_grid(h, w, th, tw).  -> RegionPlan:
+        rect    (x, y, w, h), clipped
+        rows    (r0, r1), cols (c0, c1): the tile rows r0 .. r1 - 1 and tile columns c0 .. c1 - 1 that hold a cell a pixel of the
+                rectangle depends on -- pixel p depends on the cells ceil((p - (factor - 1) - after) / factor) .. floor((p + before) /
+                factor), clipped to the plane
+        tiles   their indices in tile_grid(h, w, th, tw), raster order
+        window  (y0, x0, wh, ww) in cells, the block those tiles cover: y0 = r0 th, wh = min(h, r1 th) - y0 and likewise across --
+                cut at the tile grid, never inside a tile, so tile_grid(wh, ww, th, tw) is exactly those tiles, a ragged last row
+                or column included
+        offset  (oy, ox): the rectangle's corner inside the window's decoded picture, in pixels
+    align = A > 1: r0 and c0 go down to the next tile whose first cell is a multiple of A (the window may then hold a row or a
+    column of tiles the rule does not ask for): the decoder's F(4x4) kernels cut the plane at H/4 into 4 x 4 tiles from the corner,
+    2 x 2 cells, and a window's tiles must fall where the picture's do."""
+    H, W, f, h, w, th, tw, A = int(H), int(W), int(factor), int(h), int(w), int(th), int(tw), int(align)
+    if H < 1 or W < 1 or f < 1 or A < 1:
+        raise ValueError('region_plan: image {} x {}, factor {}, align {}'.format(H, W, f, A))
+    if (h, w) != ((H + f - 1) // f, (W + f - 1) // f):
+        raise ValueError('region_plan: a {} x {} plane does not belong to a {} x {} image at factor {}'.format(h, w, H, W, f))
+    tile_grid(h, w, th, tw)                                          # (its ValueError for an empty plane or tile)
+    if callable(reach):
+        cells = reach
+    else:
+        before, after = (int(v) for v in reach)
+        cells = lambda p0, p1: (-((after + f - 1 - p0) // f), (p1 + before) // f)      # ceil((p0 - (f - 1) - after) / f), floor((p1 + before) / f)
+    x0, y0, x1, y1 = _clip_rect(rect, H, W)
+    top, left = ((-H) % f) // 2, ((-W) % f) // 2
+
+    def tiles_of(p0, p1, n, t):                                      # padded pixels p0 .. p1 - 1 -> tile indices [t0, t1) of n cells cut by t
+        lo, hi = cells(p0, p1 - 1)
+        lo, hi = max(0, int(lo)), min(n - 1, int(hi))
+        t0 = lo // t
+        while (t0 * t) % A:
+            t0 -= 1
+        return t0, hi // t + 1
+
+    r0, r1 = tiles_of(y0 + top, y1 + top, h, th)
+    c0, c1 = tiles_of(x0 + left, x1 + left, w, tw)
+    ncols = (w + tw - 1) // tw
+    wy, wx = r0 * th, c0 * tw
+    return RegionPlan((x0, y0, x1 - x0, y1 - y0), (r0, r1), (c0, c1), [r * ncols + c for r in range(r0, r1) for c in range(c0, c1)],
+                      (wy, wx, min(h, r1 * th) - wy, min(w, c1 * tw) - wx), (y0 + top - wy * f, x0 + left - wx * f))
 
 
 def budget_search(fits, estimate_index, steps=CAP_STEPS):
@@ -1548,6 +1674,121 @@ class Codec(object):
                     raise ValueError('file {}: {}'.format(i, e))
         return out
 
+    # -- a pixel rectangle of a tiled file, from the tiles it needs --
+
+    def region_plan(self, c, rect):
+        """region_plan for a parsed tiled container with this model's reach under the kernels the whole picture runs
+        (Autoencoder.decode_family): decoder_reach where the 3 x 3 layers run the direct or the F(2x2) form, the wider decoder_cells
+        where they or h12 run F(4x4), whose transforms carry the rounding of a tile's other inputs into an output -- about 32 cells
+        a side instead of 17 for B = 5.  align = 2: the window begins at an even cell, a multiple of 4 positions at H/4, so the
+        4 x 4 tiles of the F(4x4) kernels fall where the whole picture has them."""
+        B = int(self.ae.config.arch_param_B)
+        form, _, h12_w4 = self.ae.decode_family(c.h * self.factor, c.w * self.factor)
+        reach = (lambda p0, p1: decoder_cells(p0, p1, B, form == 2, h12_w4)) if form == 2 or h12_w4 else decoder_reach(B)
+        return region_plan(c.H, c.W, self.factor, c.h, c.w, c.th, c.tw, rect, reach, align=2)
+
+    def _region_head(self, data, rect):
+        """one request, on the host: the whole file parsed and checked as decompress does -> (container, RegionPlan, window container
+        or None, plan bits).  The window container is the file cut to the plan's tiles -- (h, w), streams and first symbols -- which is
+        all a decoder reads of it; None: the whole picture is decoded and cropped, because the rectangle needs every tile or because
+        the window cannot have the kernel family of the whole picture (Autoencoder.plan_like / plan_holds)."""
+        c = parse_container(data)
+        self.check_container(c)
+        if not isinstance(c, _TILED):
+            raise ValueError('region decode needs tiles: a format-{} file is one stream over the whole volume and decodes only as a '
+                             'whole; write it with --tile'.format(c.version))
+        plan = self.region_plan(c, rect)
+        f = self.factor
+        y0, x0, wh, ww = plan.window
+        if (wh, ww) == (c.h, c.w):
+            return c, plan, None, 0
+        bits = self.ae.plan_like(c.h * f, c.w * f)
+        if not self.ae.plan_holds(bits, c.h * f, c.w * f, wh * f, ww * f, y0 * f, x0 * f):
+            return c, plan, None, 0
+        return c, plan, c._replace(h=wh, w=ww, streams=[c.streams[t] for t in plan.tiles],
+                                   first_syms=[c.first_syms[t] for t in plan.tiles]), bits
+
+    @staticmethod
+    def _region_crop(img_hwc, plan):
+        x, y, rw, rh = plan.rect
+        return np.ascontiguousarray(img_hwc[y:y + rh, x:x + rw, :])
+
+    def _window_pixels(self, ae, q, plan, bits):
+        """q (C, wh, ww) of a window on the device -> the rectangle's (3, rh, rw) uint8 pixels, still there"""
+        import torch
+        x_out = ae.decode(q[None], is_training=False, plan_flags=bits).to(torch.uint8)[0]      # tf.cast truncates (val.py)
+        (oy, ox), (_, _, rw, rh) = plan.offset, plan.rect
+        return x_out[:, oy:oy + rh, ox:ox + rw].contiguous()
+
+    def decompress_region(self, data, rect, channels=None):
+        """container bytes of a tiled file (formats 2, 4, 5, 6, 8), rect = (x, y, w, h) in pixels of the image (clipped to it, as
+        --roi's) -> the HWC uint8 pixels of the rectangle, bit for bit decompress(data)[y:y + h, x:x + w]; with channels=K those of
+        decompress(data, channels=K).
+        The whole file is parsed and checked as decompress does -- sizes, every CRC, the model -- so a damaged file is refused
+        wherever the damage lies.  Then only the tiles whose cells the rectangle's pixels depend on (region_plan, decoder_reach)
+        are entropy-decoded, as a volume of their own (decode_tiles_batch, q staying on the device), and the autoencoder's decoder
+        runs over that window alone.
+        The kernels of the whole picture are forced on the window (Autoencoder.plan_like): the 3 x 3 layers' form and h12's depend on
+        the shape and round differently.  Forcing alone does not suffice for an F(4x4) picture: its transforms carry the rounding of
+        a tile's other inputs into an output, so the window is that of decoder_cells there, about 34 cells a side instead of 18
+        (Codec.region_plan); with it the window's values are the picture's bit for bit before the cast.  Where the form cannot be
+        had the WHOLE picture is decoded and cropped -- never other pixels: a rectangle that needs every tile; an F(4x4) picture
+        whose window's width at H/4 is no multiple of 4 (an odd number of cells: odd tile extents only); a picture whose automatic
+        F(2x2) plan mixes whole-K and K-split launches (256 or more tile groups at H/4 with a remainder that runs K-split); plan
+        flags of this Codec that pin a decomposition or leave CUs idle; a picture of 2^25 pixels or more.
+        A ValueError for format 1 (it names --tile), for a rectangle of no extent or one that misses the image, and for everything
+        decompress refuses."""
+        channels = check_channels(channels, self.C)
+        c, plan, win, bits = self._region_head(data, rect)
+        if win is None:
+            return self._region_crop(self.decompress(data, channels=channels), plan)
+        try:
+            q = self.pred.decode_tiles_batch([(win.streams, win.first_syms, (win.C, win.h, win.w))], win.th, win.tw, want='q', channels=channels,
+                                             **(_ends_kw(win) if isinstance(win, LayeredContainer) else
+                                                {'order': 'wavefront' if isinstance(win, WavefrontContainer) else 'raster'}))[0]
+        except ValueError as e:
+            raise ValueError('decoder status is not 0: {}'.format(e))
+        return np.transpose(self._window_pixels(self.ae, q, plan, bits).cpu().numpy(), (1, 2, 0)).copy()
+
+    def decompress_regions_many(self, requests, max_workspace_bytes=1 << 31, channels=None):
+        """[(container bytes, rect)] -> [HWC uint8], element i equal to decompress_region(*requests[i]) (with channels=K: to
+        decompress_region(.., channels=K), one K for the call); the same file may be asked for more than once.
+        Every file is parsed and checked first; the first refusal raises its ValueError with the index of the request in front
+        and nothing has reached the device.  The windows are grouped as decompress_many groups files: per kind (raster,
+        wavefront, layered, front-layered) those of the most frequent tile extent (and layer ends) are the volumes of ONE
+        decode_tiles_batch call -- a request whose whole picture is needed is the volume of all its tiles -- and go through the
+        decoder up to IN_FLIGHT at a time, each with the forced plan of its own picture; the other requests take
+        decompress_region one by one."""
+        channels = check_channels(channels, self.C)
+        requests, heads = list(requests), []
+        for i, req in enumerate(requests):
+            try:
+                data, rect = req
+                heads.append(self._region_head(data, rect))
+            except ValueError as e:
+                raise ValueError('request {}: {}'.format(i, e))
+        out = [None] * len(heads)
+        try:
+            for together, qs in self._decode_together([c if win is None else win for c, _, win, _ in heads], 'q', max_workspace_bytes, channels):
+                jobs = []
+                for i, q in zip(together, qs):
+                    c, plan, win, bits = heads[i]
+                    if win is None:                                  # the whole picture: the rectangle sits at the padding's offsets in it
+                        f = self.factor
+                        plan = plan._replace(offset=(plan.rect[1] + ((-c.H) % f) // 2, plan.rect[0] + ((-c.W) % f) // 2))
+                    jobs.append((q, plan, bits))
+                for i, x in zip(together, self._in_flight(jobs, lambda ae, job: self._window_pixels(ae, *job))):
+                    out[i] = np.transpose(x.cpu().numpy(), (1, 2, 0)).copy()
+        except ValueError as e:
+            raise ValueError(re.sub(r'^file (\d+): ', r'request \1: ', str(e)))
+        for i, (data, rect) in enumerate(requests):
+            if out[i] is None:
+                try:
+                    out[i] = self.decompress_region(data, rect, channels=channels)
+                except ValueError as e:
+                    raise ValueError('request {}: {}'.format(i, e))
+        return out
+
     # -- what a damaged format-4 file still holds --
 
     def _salvage_head(self, data):
@@ -1976,7 +2217,7 @@ TRANSCODE_COMMANDS = ('transcode', 'transcode-dir')
 
 def check_option_args(flags):
     """--checked / --wavefront / --salvage / --channels / --layers / --progressive / --front-layers / --front-progressive / --partial /
-    --recover / --chunk / --fronts / --cap / --roi / --background / --max-bytes / --bpp against the command, --tile
+    --recover / --chunk / --fronts / --cap / --roi / --background / --max-bytes / --bpp / --region against the command, --tile
     and each other: decided before any model is built"""
     cap, background, rois = getattr(flags, 'cap', None), getattr(flags, 'background', None), getattr(flags, 'roi', None) or []
     max_bytes, bpp = getattr(flags, 'max_bytes', None), getattr(flags, 'bpp', None)
@@ -2042,6 +2283,15 @@ def check_option_args(flags):
             raise ValueError('--channels does not go with --salvage: a preview of a damaged file is not offered')
         if flags.channels < 1:
             raise ValueError('--channels {} is not at least 1'.format(flags.channels))
+    if getattr(flags, 'region', None) is not None:
+        if flags.command != 'decompress':
+            raise ValueError('--region belongs to decompress: a rectangle is in the pixels of one image')
+        for name, why in (('salvage', 'region decode of a damaged file is not offered'),
+                          ('partial', 'region decode of a cut file is not offered'),
+                          ('recover', 'region decode of a damaged or cut file is not offered')):
+            if getattr(flags, name, False):
+                raise ValueError('--region does not go with --{}: {}'.format(name, why))
+        parse_roi_arg(flags.region, '--region')
     if getattr(flags, 'checked', False):
         if flags.command not in ('compress', 'compress-dir') + TRANSCODE_COMMANDS:
             raise ValueError('--checked belongs to compress / compress-dir: a file says by itself what it is')
@@ -2104,14 +2354,14 @@ def check_option_args(flags):
             raise ValueError('--recover does not go with --channels: what every tile still holds decides its channels')
 
 
-def parse_roi_arg(text):
+def parse_roi_arg(text, option='--roi'):
     """'X,Y,W,H' -> (x, y, w, h); a ValueError for anything but four integers with a positive extent (the image is checked by cap_plane)"""
     try:
         x, y, w, h = (int(v) for v in str(text).split(','))
     except ValueError:
-        raise ValueError('--roi {!r} is not X,Y,W,H in pixels'.format(text))
+        raise ValueError('{} {!r} is not X,Y,W,H in pixels'.format(option, text))
     if w < 1 or h < 1:
-        raise ValueError('--roi {!r}: the extent {} x {} is not positive'.format(text, w, h))
+        raise ValueError('{} {!r}: the extent {} x {} is not positive'.format(option, text, w, h))
     return x, y, w, h
 
 
@@ -2476,6 +2726,98 @@ def _main_verify(argv):
     return 1 if bad else 0
 
 
+INFO_FACTOR = 8                                                      # the subsampling factor of the one architecture (info builds no network to ask)
+
+
+def _tile_bytes(c):
+    """coded bytes per tile of a parsed tiled container, all layers of a layered one"""
+    return [sum(len(s) for s in b) if isinstance(c, LayeredContainer) else len(b) for b in c.streams]
+
+
+def _region_line(path, img, plan, channels=None, C=None):
+    y0, x0, wh, ww = plan.window
+    line = '{}: {} x {} at ({}, {}), from {} tiles: rows {} .. {}, columns {} .. {}, a window of {} x {} cells'.format(
+        path, img.shape[0], img.shape[1], plan.rect[1], plan.rect[0], len(plan.tiles), plan.rows[0], plan.rows[1] - 1,
+        plan.cols[0], plan.cols[1] - 1, wh, ww)
+    return line if channels is None else '{}, preview from {} of {} channels'.format(line, channels, C)
+
+
+def info_file(data, region=None):
+    """container bytes -> the text of `info`: format, image size, latent and tile extents, the tile grid, layer ends, bytes per tile
+    and per layer; with region = (x, y, w, h) the tiles and the window decompress_region would decode for it and their share of
+    the payload (region_plan at the reach of the file's autoencoder config, an even first cell as Codec.region_plan asks; once for
+    the arithmetic's reach and once for the F(4x4) kernels', since which of them a picture's decoder runs is the library's decision).  The
+    strict reader parses the file; host only: no model, no device.  A ValueError for a file the reader refuses, a format-1 file with
+    a region, a config that is not found."""
+    c = parse_container(data)
+    lines = ['format {}, {} bytes, model {} / {} ({:08x})'.format(c.version, len(data), c.ae_name, c.pc_name, c.fingerprint),
+             'image {} x {} (H x W), latent {} x {} x {} (C x h x w)'.format(c.H, c.W, c.C, c.h, c.w)]
+    if not isinstance(c, _TILED):
+        lines.append('one stream over the whole volume, {} bytes: no tiles'.format(len(c.payload)))
+        if region is not None:
+            raise ValueError('region decode needs tiles: a format-{} file is one stream over the whole volume and decodes only as a '
+                             'whole; write it with --tile'.format(c.version))
+        return '\n'.join(lines)
+    per_tile = _tile_bytes(c)
+    rows, cols = (c.h + c.th - 1) // c.th, (c.w + c.tw - 1) // c.tw
+    lines.append('tiles of {} x {} cells, grid {} x {} = {} tiles, last row {} cells high, last column {} wide'.format(
+        c.th, c.tw, rows, cols, len(per_tile), c.h - (rows - 1) * c.th, c.w - (cols - 1) * c.tw))
+    lines.append('payload {} bytes; per tile min {}, mean {:.1f}, max {}'.format(sum(per_tile), min(per_tile), sum(per_tile) / float(len(per_tile)), max(per_tile)))
+    lines.append('bytes per tile: {}'.format(','.join(str(n) for n in per_tile)))
+    if isinstance(c, LayeredContainer):
+        lines.append('layer ends {}; bytes per layer {}'.format(','.join(str(e) for e in c.layer_ends),
+                                                                ','.join(str(sum(len(s) for s in layer)) for layer in c.segments)))
+    if region is not None:
+        from . import config_parser
+        ae_config, _ = config_parser.parse(_resolve_config(c.ae_name, 'ae_configs', 'CONFIG_BASE_AE'))
+        before, after = decoder_reach(ae_config.arch_param_B)
+        f = INFO_FACTOR
+        if (c.h, c.w) != ((c.H + f - 1) // f, (c.W + f - 1) // f):
+            raise ValueError('header mismatch: symbol volume {} x {} does not belong to a {} x {} image (expected {} x {})'.format(
+                c.h, c.w, c.H, c.W, (c.H + f - 1) // f, (c.W + f - 1) // f))
+        B = int(ae_config.arch_param_B)
+        # which kernels a picture's decoder runs is the library's decision (Codec.region_plan asks it); both plans are shown
+        for what, reach in (('reach {} before, {} after'.format(before, after), (before, after)),
+                            ('where the decoder runs its F(4x4) kernels', lambda p0, p1: decoder_cells(p0, p1, B, True, True))):
+            plan = region_plan(c.H, c.W, f, c.h, c.w, c.th, c.tw, region, reach, align=2)
+            y0, x0, wh, ww = plan.window
+            part = sum(per_tile[t] for t in plan.tiles)
+            lines.append('region {},{},{},{} ({}): tile rows {} .. {}, columns {} .. {}, {} of {} tiles'.format(
+                plan.rect[0], plan.rect[1], plan.rect[2], plan.rect[3], what, plan.rows[0], plan.rows[1] - 1, plan.cols[0],
+                plan.cols[1] - 1, len(plan.tiles), len(per_tile)))
+            lines.append('  window {} x {} cells at ({}, {}), a decoder pass of {} x {} pixels of {} x {}; {} of {} payload bytes = {:.1f} %'.format(
+                wh, ww, y0, x0, wh * f, ww * f, c.h * f, c.w * f, part, sum(per_tile), 100.0 * part / max(1, sum(per_tile))))
+            lines.append('  tiles {}'.format(','.join(str(t) for t in plan.tiles)))
+    return '\n'.join(lines)
+
+
+def _main_info(argv):
+    p = argparse.ArgumentParser(prog='codec info', description='what a codec file holds, and what a region of it would decode: no model, no device')
+    p.add_argument('paths', nargs='+', metavar='PATH', help='a codec file, or a directory whose *.icf files are described')
+    p.add_argument('--region', default=None, metavar='X,Y,W,H', help='the tiles and the window decompress --region would decode for this rectangle')
+    flags = p.parse_args(argv)
+    try:
+        region = None if flags.region is None else parse_roi_arg(flags.region, '--region')
+    except ValueError as e:
+        print('error: {}'.format(e), file=sys.stderr)
+        return 2
+    bad = 0
+    files = list_verify_files(flags.paths)
+    for path in files:
+        try:
+            with open(path, 'rb') as f:
+                text = info_file(f.read(), region)
+        except (IOError, OSError) as e:
+            bad, text = bad + 1, 'cannot read: {}'.format(e)
+        except ValueError as e:
+            bad, text = bad + 1, str(e)
+        print('{}: {}'.format(path, text.replace('\n', '\n  ')))
+    if not files:
+        print('info: no file to describe', file=sys.stderr)
+        return 1
+    return 1 if bad else 0
+
+
 STREAM_CHUNK = 16384
 
 
@@ -2509,6 +2851,8 @@ def main(argv=None):
     argv = sys.argv[1:] if argv is None else list(argv)
     if argv and argv[0] == 'verify':
         return _main_verify(argv[1:])
+    if argv and argv[0] == 'info':
+        return _main_info(argv[1:])
     p = argparse.ArgumentParser(description='compress an image to a codec file, or a codec file back to an image; transcode a codec '
                                             'file to another format or a lower rate without its image; '
                                             'the -dir commands do so for every file of a directory, --batch files per call')
@@ -2565,6 +2909,9 @@ def main(argv=None):
                         'the rectangles stay uncapped and the level is the background\'s; prints the level and the number of codings; '
                         'transcode / transcode-dir: the largest integer level 0 .. C')
     p.add_argument('--bpp', type=float, default=None, metavar='B', help='compress / compress-dir: --max-bytes floor(B H W / 8), per image')
+    p.add_argument('--region', default=None, metavar='X,Y,W,H',
+                   help='decompress: only this rectangle of the image, in image pixels (clipped to it), decoded from the tiles it needs '
+                        '(a file written with --tile); goes with --channels, not with --salvage, --partial or --recover')
     flags = p.parse_args(argv)
     from . import config_parser, val, weights as _weights
     try:
@@ -2638,6 +2985,14 @@ def main(argv=None):
             print(_decompress_line(flags.output, img, len(data)))
             if report is not None and (report.damaged or not report.file_crc_ok):
                 print(_damage_line(flags.input, report))
+        elif getattr(flags, 'region', None) is not None:
+            from PIL import Image
+            channels = check_channels(flags.channels, codec.C)
+            with open(flags.input, 'rb') as f:
+                data = f.read()
+            img = codec.decompress_region(data, parse_roi_arg(flags.region, '--region'), channels=channels)
+            Image.fromarray(img).save(flags.output)
+            print(_region_line(flags.output, img, codec.region_plan(parse_container(data), parse_roi_arg(flags.region, '--region')), channels, codec.C))
         else:
             channels = check_channels(flags.channels, codec.C)
             img = codec.decompress_file(flags.input, flags.output, channels=channels)
