@@ -237,7 +237,7 @@ class TrainGraph(object):
         # 32 x 32 31.8 against 40.3 us, 30 of 40 x 40 68 against 95) and where at least half of the segments' tiles exist
         wgs = int(lib.ic_wino4_3x3_c128_workgroups(N, H, W))
         tiles = N * (-(-H // 4)) * (-(-W // 4))
-        fits = wgs >= 160 and 2 * tiles >= 8 * wgs
+        fits = wgs >= self.WINO4_MIN_WORKGROUPS and 2 * tiles >= 8 * wgs
         mode = self.WINO4
         # per direction: (forward, data gradient) -- WINO4 True: both, 'fwd' / 'bwd': one of them (A/B runs and the parity report)
         self._w3_f4 = (fits and mode in (True, 'fwd'), fits and mode in (True, 'bwd'))
@@ -335,6 +335,7 @@ class TrainGraph(object):
         return dx
 
     WINOGRAD_WGRAD = True     # 3x3 128 -> 128 filter gradients in the Winograd domain (ic_conv3x3_c128_wgrad_f32)
+    WINO4_MIN_WORKGROUPS = 160  # 3x3 layers take F(4x4) from this many work-groups on (_pack_all_3x3); a test lowers it on its instance
     WGRAD_SIDE_STREAM = False  # filter gradients on a second stream beside the data-gradient chain: measured SLOWER (see _wgrad_beside)
 
     def _wgrad_beside(self, l, x_in, g):

@@ -103,25 +103,41 @@ def _deconv(x, w_tf, stride=2):
     return full[:, :, pt:pt + oh, pl:pl + ow]
 
 
-def _cba(x, p, scope, stride, relu, transpose=False):
+class _Trace(object):
+    """the ReLU decisions of one train_loss call: the masks to force (scope -> bool mask, may be empty), and what the call itself
+    decided -- its masks and its pre-activations, detached.  Passed down the call tree: no module-level state."""
+
+    def __init__(self, forced=None):
+        self.forced = forced or {}
+        self.relu, self.relu_pre = {}, {}
+
+
+def _cba(x, p, scope, stride, relu, transpose=False, trace=None):
     y = _deconv(x, p[scope + '/weights']) if transpose else _conv(x, p[scope + '/weights'], stride)
     y = _bn_train(y, p, scope)
-    return F.relu(y) if relu else y
+    if not relu:
+        return y
+    if trace is not None:
+        trace.relu[scope] = y.detach() > 0
+        trace.relu_pre[scope] = y.detach()
+        if scope in trace.forced:
+            return y * torch.as_tensor(trace.forced[scope]).to(y.dtype)
+    return F.relu(y)
 
 
-def _res_block(x, p, scope, relu_first=True):
-    y = _cba(x, p, scope + '/conv1', 1, relu_first)
+def _res_block(x, p, scope, relu_first=True, trace=None):
+    y = _cba(x, p, scope + '/conv1', 1, relu_first, trace=trace)
     y = _cba(y, p, scope + '/conv2', 1, False)
     return y + x
 
 
-def _res_stack(net, p, root, kind, B):
+def _res_stack(net, p, root, kind, B, trace=None):
     final = 'res_block_enc_final' if kind == 'enc' else 'dec_after_res'
     res0 = net
     for b in range(B):
         res_b = net
         for i in (1, 2, 3):
-            net = _res_block(net, p, '{}/res_block_{}_{}/{}_{}_{}'.format(root, kind, b, kind, b, i))
+            net = _res_block(net, p, '{}/res_block_{}_{}/{}_{}_{}'.format(root, kind, b, kind, b, i), trace=trace)
         net = net + res_b
     net = _res_block(net, p, '{}/{}'.format(root, final), relu_first=False)
     return net + res0
@@ -147,21 +163,47 @@ def _pc_bitcost(q, symbols, p, pad_value):
     return nll * float(np.log2(np.e))
 
 
-def train_loss(x_uint8, weights, ae_cfg, pc_cfg, dtype=torch.float64):
+def _force_clip(u, lo, hi, low, high):
+    """clip(u, lo, hi) with the two decisions given: `low` -> lo, `high` -> hi, elsewhere u passes through with its gradient"""
+    low, high = torch.as_tensor(low), torch.as_tensor(high)
+    return torch.where(high, torch.full_like(u, hi), torch.where(low, torch.full_like(u, lo), u))
+
+
+def train_loss(x_uint8, weights, ae_cfg, pc_cfg, dtype=torch.float64, decisions=None):
     """-> (total_loss tensor, dict of components, dict name -> parameter tensor with .grad after backward()).
-    ae_cfg / pc_cfg: dicts of the config values."""
+    ae_cfg / pc_cfg: dicts of the config values.
+
+    decisions: None, or a dict of the step's DISCRETE decisions to evaluate the step at instead of this evaluation's own (a key
+    that is absent leaves the own decision in place; None changes nothing at all):
+      'symbols'                         int64 (N, C, h, w): qhard = centers[symbols], and the context model's targets; qsoft is unchanged
+      'relu'                            {layer scope: bool mask}: that layer's relu(y) becomes y * mask (h1, h2, the residual blocks'
+                                        conv1 except the final blocks', from_bn, h12).  The context model's ReLUs stay its own
+      'heatmap_low' / 'heatmap_high'    bool (N, C, h, w): heatmap 0 / 1, elsewhere sigmoid(.) * C - c passes through
+      'x_out_low' / 'x_out_high'        bool (N, 3, H, W): x_out 0 / 255, elsewhere the de-normalised value passes through
+    The components carry this evaluation's own decisions in the same structure ('decisions') and the float values they were taken
+    on ('relu_pre' {scope: pre-activation}, 'heatmap_pre', 'x_out_pre'; detached): two evaluations in different precisions can be
+    compared at ONE set of decisions, and a decision that differs can be checked to sit inside the rounding band of its threshold."""
+    forced = decisions or {}
+    trace = _Trace(forced.get('relu'))
     p = {k: torch.tensor(np.asarray(v), dtype=dtype, requires_grad=('moving_' not in k)) for k, v in weights.items()}
     x = torch.as_tensor(np.asarray(x_uint8)).to(dtype)
     B = ae_cfg['arch_param_B']
     C = ae_cfg['num_chan_bn']
+    own = {}
     # encoder (autoencoder.py:218-244, is_training=True)
     net = O.normalize(x, ae_cfg.get('normalization', 'FIXED'))
-    net = _cba(net, p, O.ENC + '/h1', 2, True)
-    net = _cba(net, p, O.ENC + '/h2', 2, True)
-    net = _res_stack(net, p, O.ENC, 'enc', B)
+    net = _cba(net, p, O.ENC + '/h1', 2, True, trace=trace)
+    net = _cba(net, p, O.ENC + '/h2', 2, True, trace=trace)
+    net = _res_stack(net, p, O.ENC, 'enc', B, trace=trace)
     net = _cba(net, p, O.ENC + '/to_bn', 2, False)
+    hm_pre = None
     if ae_cfg.get('heatmap', True):
-        hm = torch.clamp(torch.clamp(torch.sigmoid(net[:, 0:1]) * C - torch.arange(C, dtype=dtype).view(1, C, 1, 1), max=1.0), min=0.0)
+        hm_pre = torch.sigmoid(net[:, 0:1]) * C - torch.arange(C, dtype=dtype).view(1, C, 1, 1)
+        own['heatmap_low'], own['heatmap_high'] = hm_pre.detach() <= 0.0, hm_pre.detach() >= 1.0
+        if 'heatmap_low' in forced or 'heatmap_high' in forced:
+            hm = _force_clip(hm_pre, 0.0, 1.0, forced.get('heatmap_low', own['heatmap_low']), forced.get('heatmap_high', own['heatmap_high']))
+        else:
+            hm = torch.clamp(torch.clamp(hm_pre, max=1.0), min=0.0)
         z = hm * net[:, 1:]
     else:
         # autoencoder.py:236-242: to_bn emits C channels, z is its output, no mask
@@ -169,15 +211,22 @@ def train_loss(x_uint8, weights, ae_cfg, pc_cfg, dtype=torch.float64):
     c = p[O.ENC + '/centers']
     dist = (z.unsqueeze(-1) - c) ** 2
     qsoft = (torch.softmax(-dist, -1) * c).sum(-1)
-    symbols = torch.argmin(dist.detach(), -1)
+    own['symbols'] = torch.argmin(dist.detach(), -1)
+    symbols = torch.as_tensor(forced['symbols']).long() if 'symbols' in forced else own['symbols']
     qhard = c.detach()[symbols]
     qbar = qsoft + (qhard - qsoft).detach()
     # decoder on qbar (train.py:102)
-    net = _cba(qbar, p, O.DEC + '/from_bn', 2, True, transpose=True)
-    net = _res_stack(net, p, O.DEC, 'dec', B)
-    net = _cba(net, p, O.DEC + '/h12', 2, True, transpose=True)
+    net = _cba(qbar, p, O.DEC + '/from_bn', 2, True, transpose=True, trace=trace)
+    net = _res_stack(net, p, O.DEC, 'dec', B, trace=trace)
+    net = _cba(net, p, O.DEC + '/h12', 2, True, transpose=True, trace=trace)
     net = _cba(net, p, O.DEC + '/h13', 2, False, transpose=True)
-    x_out = torch.clamp(O.denormalize(net, ae_cfg.get('normalization', 'FIXED')), 0, 255)
+    x_pre = O.denormalize(net, ae_cfg.get('normalization', 'FIXED'))
+    own['x_out_low'], own['x_out_high'] = x_pre.detach() <= 0.0, x_pre.detach() >= 255.0
+    own['relu'] = trace.relu
+    if 'x_out_low' in forced or 'x_out_high' in forced:
+        x_out = _force_clip(x_pre, 0.0, 255.0, forced.get('x_out_low', own['x_out_low']), forced.get('x_out_high', own['x_out_high']))
+    else:
+        x_out = torch.clamp(x_pre, 0, 255)
     # context model on stop_gradient(qbar) (train.py:104-105)
     bc = _pc_bitcost(qbar.detach(), symbols, p, float(c.detach()[0]))
     # loss (train.py:303-336)
@@ -204,7 +253,9 @@ def train_loss(x_uint8, weights, ae_cfg, pc_cfg, dtype=torch.float64):
                         for k, t in p.items() if k.startswith('probclass3d/') and k.endswith('/weights'))
     total = d_loss + pc_loss + reg
     comps = {'d_loss_scaled': d_loss, 'pc_loss': pc_loss, 'reg': reg, 'H_real': H_real, 'H_mask': H_mask,
-             'x_out': x_out, 'symbols': symbols, 'bc': bc, 'heatmap': hm, 'z': z, 'qbar': qbar}
+             'x_out': x_out, 'symbols': symbols, 'bc': bc, 'heatmap': hm, 'z': z, 'qbar': qbar,
+             'decisions': own, 'relu_pre': trace.relu_pre, 'x_out_pre': x_pre.detach(),
+             'heatmap_pre': hm_pre.detach() if hm_pre is not None else None}
     return total, comps, p
 
 

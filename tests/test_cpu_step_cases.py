@@ -1,0 +1,137 @@
+"""tests/step_cases.py and the decision forcing of oracle/train_oracle.py are what tests/test_gpu_step_decisions.py takes them for
+(no GPU: the oracle on the CPU in float32 and float64, and the host side of the library).  The conditions are conditions on the
+oracle, the helpers and the table: a case that misses one gets another seed (the next that passes), never a weaker condition."""
+import pytest
+import torch
+
+from tests import step_cases as S
+from tests.util import rel_err
+
+MSE_GTOL = 2e-5          # float32 against float64 evaluation of the oracle at ONE set of decisions, mse cases (measured <= 4.0e-6)
+
+
+@pytest.mark.parametrize('case', S.CASES, ids=lambda c: c.id)
+def test_forcing_the_oracles_own_decisions_changes_nothing(case):
+    """train_loss(decisions = its own decisions) reproduces the unforced total and every gradient to 1e-12 of the tensor scale (only
+    the operation order of y * mask against relu, and of the clips, differs); forcing a part of them does too."""
+    total, comps, grads = S.unforced(case)
+    assert set(comps['decisions']) == {'symbols', 'relu', 'heatmap_low', 'heatmap_high', 'x_out_low', 'x_out_high'}
+    assert len(comps['decisions']['relu']) == len(comps['relu_pre']) == 2 + 15 + 1 + 15 + 1
+    for dec in (comps['decisions'], {'relu': comps['decisions']['relu']}, {'symbols': comps['symbols'], 'x_out_high': comps['decisions']['x_out_high']}):
+        total_f, comps_f, grads_f = S.oracle(case, decisions=dec)
+        assert abs(float(total_f) - float(total)) <= 1e-12 * max(1.0, abs(float(total)))
+        assert len(grads_f) == len(grads) == 219
+        name, err = S.worst_gradient_error(grads_f, grads)
+        assert err <= 1e-12, (name, err)
+        assert torch.equal(comps_f['symbols'], comps['symbols']) and rel_err(comps_f['x_out'], comps['x_out']) <= 1e-12
+        counts = S.in_band(S.oracle_side(comps_f), comps)
+        assert counts['differing'] == 0 and counts['out_of_band'] == 0 and counts['total'] > 1000000
+
+
+def test_a_forced_decision_is_live():
+    """flip, in the oracle's own decisions, the h1 ReLU sign of the element with the smallest |pre|: the gradients differ from the
+    unforced ones by more than 1e-8 of the tensor scale; and one flipped symbol, heatmap clip and x_out clip each move them too."""
+    case = S.BY_ID['wide']
+    _, comps, grads = S.unforced(case)
+    h1 = 'autoencoder/encoder/h1'
+
+    def moved(dec):
+        _, comps_f, grads_f = S.oracle(case, decisions=dec)
+        return S.worst_gradient_error(grads_f, grads)[1], comps_f
+    relu = dict(comps['decisions']['relu'])
+    i = int(comps['relu_pre'][h1].abs().argmin())
+    relu[h1] = relu[h1].clone()
+    relu[h1].view(-1)[i] = ~relu[h1].view(-1)[i]
+    err, comps_f = moved({'relu': relu})
+    assert err > 1e-8, err
+    # what the forced evaluation reports are still ITS OWN decisions: the flipped element is one differing decision of the other side
+    assert torch.equal(comps_f['decisions']['relu'][h1], comps['decisions']['relu'][h1])
+    side = S.oracle_side(comps)
+    side = dict(side, decisions=dict(side['decisions'], relu=relu))
+    counts = S.in_band(side, comps)
+    assert counts['relu'] == counts['differing'] == 1 and counts['out_of_band'] == 1          # relu_out is the oracle's own: a band of 0
+    sym = comps['symbols'].clone()
+    sym.view(-1)[0] = (sym.view(-1)[0] + 1) % 6
+    assert moved({'symbols': sym})[0] > 1e-8
+    for key, other in (('heatmap_low', 'heatmap_high'), ('x_out_high', 'x_out_low')):
+        m = comps['decisions'][key].clone()
+        passing = (~m & ~comps['decisions'][other]).view(-1).nonzero()          # an element that passes through: clip it
+        assert len(passing) > 0
+        m.view(-1)[int(passing[len(passing) // 2])] = True
+        assert moved({key: m})[0] > 1e-8, key
+
+
+@pytest.mark.parametrize('case', S.CASES, ids=lambda c: c.id)
+def test_fp32_oracle_meets_float64_at_forced_decisions(case):
+    """the float32 evaluation of the oracle against the float64 one WITH THE FLOAT32 DECISIONS FORCED: the worst of all gradients
+    within 2e-5 of its scale for the mse cases (measured <= 4.0e-6), within GTOL = 2e-4 for msssim (measured <= 7.0e-5: float32 MS-SSIM
+    on the CPU is the loose part); the decisions that differ from the float64 oracle's own are at most 1e-5 of all (measured <= 2 of
+    3.6 M) and every one of them is inside the rounding band of its threshold.  This test admits a seed into the table.  Which seed
+    shows a flip is not asserted: that depends on the host's float32 convolution."""
+    _, comps64, _ = S.unforced(case)
+    _, comps32, grads32 = S.oracle(case, dtype=torch.float32)
+    side = S.oracle_side(comps32)
+    counts = S.in_band(side, comps64)
+    print('{}: decisions {}'.format(case.id, dict(counts)))
+    assert counts['out_of_band'] == 0, counts
+    assert counts['differing'] <= S.MAX_DIFFERING * counts['total'], counts
+    _, comps_f, grads_f = S.oracle(case, decisions=comps32['decisions'])
+    assert torch.equal(comps_f['symbols'], comps32['symbols'])          # the symbols the forced evaluation used
+    name, err = S.worst_gradient_error(grads32, grads_f)
+    print('{}: worst gradient, float32 against float64 at the float32 decisions: {} {:.3e}'.format(case.id, name, err))
+    assert err <= (S.GTOL if case.distortion == 'ms_ssim' else MSE_GTOL), (name, err)
+
+
+def test_table_reaches_what_it_claims():
+    """restated in Python: wide takes 1 x 16 segments, ragged and msssim 2 x 8, all three pass the half-full rule, and each is below
+    the 160 work-groups from which TrainGraph takes F(4x4) by itself -- which is why no other step test reaches this path."""
+    from imgcomp_cvpr_amd import training
+    assert training.TrainGraph.WINO4_MIN_WORKGROUPS == 160
+    assert [c.id for c in S.CASES] == ['wide', 'ragged', 'msssim']
+    for c in S.CASES:
+        N, _, H, W = c.shape
+        assert H % 8 == 0 and W % 8 == 0 and c.maps == (H // 4, W // 4)
+        kind, per_map = S.segments(*c.maps)
+        assert kind == c.segments, (c.id, kind)
+        wgs = S.workgroups(N, *c.maps)
+        assert wgs == 2 * N * per_map and 1 <= wgs < training.TrainGraph.WINO4_MIN_WORKGROUPS, (c.id, wgs)
+        assert S.half_full(N, *c.maps), c.id
+        assert False in c.modes and True in c.modes
+    assert S.BY_ID['wide'].modes == (False, 'fwd', 'bwd', True)
+    assert [S.workgroups(c.shape[0], *c.maps) for c in S.CASES] == [8, 8, 12]
+    # wide: a segment row holds 10 of its 16 tiles, as on the 40 x 40 maps of the default 160 x 160 crops; ragged: 3 tile rows in
+    # 2-row segments; msssim: 16 tiles of a map in 2 segments of 16 = exactly half full
+    assert S.segments(40, 40) == ('1x16', 10) and S.segments(8, 40) == ('1x16', 2) and -(-40 // 4) == 10
+    assert S.segments(12, 32) == ('2x8', 2) and -(-12 // 4) == 3
+    m = S.BY_ID['msssim']
+    assert 2 * m.shape[0] * 16 == 8 * S.workgroups(m.shape[0], *m.maps) and m.shape[3] <= m.shape[2]
+    assert not S.half_full(1, 4, 4) and S.segments(8, 128) == ('1x16', 4)
+    assert {c.seed for c in S.CASES} == {1}
+
+
+def test_table_geometry_by_the_library_queries():
+    """the same by the library's host arithmetic (ic_wino4_3x3_c128_workgroups / _stats_parts / _waves: no device call)"""
+    from imgcomp_cvpr_amd import _lib as L
+    for c in S.CASES:
+        N, (H, W) = c.shape[0], c.maps
+        assert L.lib.ic_wino4_3x3_c128_supported(N, H, W) == 1 and L.lib.ic_conv3x3_c128_pick_algo(N, H, W, 0) == 1
+        assert int(L.lib.ic_wino4_3x3_c128_workgroups(N, H, W)) == S.workgroups(N, H, W)
+        assert int(L.lib.ic_wino4_3x3_c128_stats_parts(N, H, W)) == S.workgroups(N, H, W) // 2 > 0
+    for H, W in [(8, 40), (12, 32), (16, 16), (40, 40), (8, 128), (4, 64), (32, 32), (7, 32), (6, 64)]:
+        assert int(L.lib.ic_wino4_3x3_c128_workgroups(1, H, W)) == S.workgroups(1, H, W), (H, W)
+
+
+def test_default_path_of_the_oracle_is_untouched():
+    """decisions=None is the evaluation of before: clamp and relu themselves, and the per-step history of train_steps goes through"""
+    from oracle import train_oracle as T
+    case = S.BY_ID['wide']
+    _, comps, _ = S.unforced(case)
+    ae, pc = S.configs(case)
+    assert torch.equal(comps['x_out'], torch.clamp(comps['x_out_pre'], 0, 255))
+    assert torch.equal(comps['heatmap'], torch.clamp(comps['heatmap_pre'], 0, 1))
+    from imgcomp_cvpr_amd import weights as W
+    ae.heatmap = False                                     # without the importance map there is no such decision
+    _, comps_n, _ = T.train_loss(S.image(case)[:1, :, :16, :16], W.synthetic_weights(ae, pc), ae.as_dict(), pc.as_dict(), torch.float64)
+    assert comps_n['heatmap'] is None and comps_n['heatmap_pre'] is None and 'heatmap_low' not in comps_n['decisions']
+    hist, _ = T.train_steps(S.image(case)[:1, :, :16, :16], W.synthetic_weights(ae, pc), ae.as_dict(), pc.as_dict(), 1)
+    assert len(hist) == 1 and hist[0]['H_real'] == float(comps_n['H_real'].detach())

@@ -5,7 +5,7 @@ import numpy as np
 import pytest
 import torch
 
-from tests.util import assert_close, dev, rel_err, record_flips, RTOL, NET_RTOL, HEATMAP_RTOL
+from tests.util import assert_close, dev, rel_err, record_flips, _boundary_margin, RTOL, NET_RTOL, HEATMAP_RTOL
 
 pytestmark = pytest.mark.gpu
 
@@ -32,13 +32,6 @@ def algo(request, nets):
                      'wino_seg2': _lib.CONV3_WINO_SEG2, 'wino4': _lib.CONV3_WINO4 | _lib.CONV5_WINO4}[request.param]
     yield request.param
     ae.plan_flags = 0
-
-
-def _boundary_margin(z64, centers):
-    """distance of every z to the nearest quantiser decision midpoint (float64)."""
-    c = np.sort(np.asarray(centers, np.float64))
-    mids = (c[1:] + c[:-1]) / 2
-    return np.min(np.abs(z64[..., None] - mids), axis=-1)
 
 
 @pytest.mark.parametrize('shape,kind', [((1, 3, 64, 64), 'natural'), ((2, 3, 40, 72), 'noise')])

@@ -46,6 +46,13 @@ def record_flips(what, flips):
     return float(flips.mean())
 
 
+def _boundary_margin(z64, centers):
+    """distance of every z to the nearest quantiser decision midpoint (float64)."""
+    c = np.sort(np.asarray(centers, np.float64))
+    mids = (c[1:] + c[:-1]) / 2
+    return np.min(np.abs(z64[..., None] - mids), axis=-1)
+
+
 def dev(a, device, dtype=torch.float32):
     return torch.as_tensor(np.ascontiguousarray(a)).to(dtype).to(device)
 
