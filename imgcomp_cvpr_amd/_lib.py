@@ -107,6 +107,13 @@ def packed_volume_table(shapes):
     return volume_table([(h, w, o, o) for (C, h, w), o in zip(shapes, offs)]), offs, total
 
 
+# what every ic_pc_decode_tiles_batch*_f32 entry takes first: bitstreams, total_bytes, tiles, ntiles, volumes, nvolumes, wtab, centers,
+# k, L, resolution, symbols, q, status, C, workspace, workspace_bytes, flags, stream -- and what the segmented ones take last:
+# layer_ends, nlayers, segs.  Between the two stands each entry's own tail.
+_PC_TILES_BATCH = [c_void_p, c_longlong, c_void_p, c_int, c_void_p, c_int, POINTER(c_void_p), c_void_p, c_int, c_int, c_float,
+                   c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_int, c_void_p]
+_PC_TILES_SEGS = [c_void_p, c_int, c_void_p]
+
 # name -> (restype, argtypes); mirrors include/imgcomp_hip.h one-to-one (tests/test_abi.py checks
 # that every ic_* prototype of the header is listed here and exported by the .so).
 PROTOTYPES = {
@@ -158,37 +165,22 @@ PROTOTYPES = {
     'ic_pc_decode_tiles_f32': (c_int, [c_void_p, c_longlong, c_void_p, c_int, POINTER(c_void_p), c_void_p, c_int, c_int, c_float,
                                        c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_int, c_void_p]),
     'ic_pc_decode_tiles_batch_workspace_bytes': (c_size_t, [c_int] * 6),
-    'ic_pc_decode_tiles_batch_f32': (c_int, [c_void_p, c_longlong, c_void_p, c_int, c_void_p, c_int, POINTER(c_void_p), c_void_p, c_int,
-                                             c_int, c_float, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_int, c_void_p]),
+    'ic_pc_decode_tiles_batch_f32': (c_int, _PC_TILES_BATCH),
     'ic_pc_decode_channels_f32': (c_int, [c_void_p, c_longlong, c_int, POINTER(c_void_p), c_void_p, c_int, c_int, c_float,
                                           c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_int, c_void_p, c_int, c_int]),
-    'ic_pc_decode_tiles_batch_channels_f32': (c_int, [c_void_p, c_longlong, c_void_p, c_int, c_void_p, c_int, POINTER(c_void_p), c_void_p,
-                                                      c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_size_t,
-                                                      c_int, c_void_p, c_int, c_int]),
+    'ic_pc_decode_tiles_batch_channels_f32': (c_int, _PC_TILES_BATCH + [c_int, c_int]),
     'ic_pc_decode_tiles_batch_layers_workspace_bytes': (c_size_t, [c_int] * 7),
-    'ic_pc_decode_tiles_batch_layers_f32': (c_int, [c_void_p, c_longlong, c_void_p, c_int, c_void_p, c_int, POINTER(c_void_p), c_void_p,
-                                                    c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_size_t,
-                                                    c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p]),
+    'ic_pc_decode_tiles_batch_layers_f32': (c_int, _PC_TILES_BATCH + [c_int, c_int] + _PC_TILES_SEGS),
     'ic_pc_decode_tiles_batch_layers_pertile_workspace_bytes': (c_size_t, [c_int] * 7),
-    'ic_pc_decode_tiles_batch_layers_pertile_f32': (c_int, [c_void_p, c_longlong, c_void_p, c_int, c_void_p, c_int, POINTER(c_void_p), c_void_p,
-                                                            c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_size_t,
-                                                            c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p]),
+    'ic_pc_decode_tiles_batch_layers_pertile_f32': (c_int, _PC_TILES_BATCH + [c_void_p, c_int] + _PC_TILES_SEGS),
     'ic_pc_decode_tiles_batch_fronts_workspace_bytes': (c_size_t, [c_int] * 7),
-    'ic_pc_decode_tiles_batch_fronts_f32': (c_int, [c_void_p, c_longlong, c_void_p, c_int, c_void_p, c_int, POINTER(c_void_p), c_void_p,
-                                                    c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_size_t,
-                                                    c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p]),
+    'ic_pc_decode_tiles_batch_fronts_f32': (c_int, _PC_TILES_BATCH + [c_int, c_int] + _PC_TILES_SEGS),
     'ic_pc_decode_tiles_batch_fronts_pertile_workspace_bytes': (c_size_t, [c_int] * 7),
-    'ic_pc_decode_tiles_batch_fronts_pertile_f32': (c_int, [c_void_p, c_longlong, c_void_p, c_int, c_void_p, c_int, POINTER(c_void_p), c_void_p,
-                                                            c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_size_t,
-                                                            c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p]),
+    'ic_pc_decode_tiles_batch_fronts_pertile_f32': (c_int, _PC_TILES_BATCH + [c_void_p, c_int] + _PC_TILES_SEGS),
     'ic_pc_decode_tiles_batch_layers_resume_workspace_bytes': (c_size_t, [c_int] * 7),
-    'ic_pc_decode_tiles_batch_layers_resume_f32': (c_int, [c_void_p, c_longlong, c_void_p, c_int, c_void_p, c_int, POINTER(c_void_p), c_void_p,
-                                                           c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_size_t,
-                                                           c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p]),
+    'ic_pc_decode_tiles_batch_layers_resume_f32': (c_int, _PC_TILES_BATCH + [c_void_p, c_void_p, c_int] + _PC_TILES_SEGS),
     'ic_pc_decode_tiles_batch_fronts_resume_workspace_bytes': (c_size_t, [c_int] * 7),
-    'ic_pc_decode_tiles_batch_fronts_resume_f32': (c_int, [c_void_p, c_longlong, c_void_p, c_int, c_void_p, c_int, POINTER(c_void_p), c_void_p,
-                                                           c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_size_t,
-                                                           c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p]),
+    'ic_pc_decode_tiles_batch_fronts_resume_f32': (c_int, _PC_TILES_BATCH + [c_void_p, c_void_p, c_int] + _PC_TILES_SEGS),
     'ic_pc_encode_segments_f32': (c_int, [c_void_p, c_void_p, c_int, c_longlong, c_int, c_float, c_void_p, c_int, c_void_p, c_longlong,
                                           c_void_p, c_void_p, c_void_p]),
     'ic_pc_conceal_tiles_workspace_bytes': (c_size_t, [c_int, c_int, c_longlong]),

@@ -1314,157 +1314,273 @@ extern "C" int ic_pc_decode_channels_f32(const uint8_t* bitstream, long long nby
                           flags, channels, fill_sym, stream);
 }
 
-// workspace of ic_pc_decode_tiles_f32: the table, then either one slot per tile (k = 24, flags 0) or what the single-volume
-// paths need for the largest tile plus that tile's symbols
+// ---- the tile entries: nine of them, behind them one request, one check, one workspace layout, one launch ------------------------
+
+// a slot (k = 24): a tile's padded volume and its three caches
 static size_t pc_dec_tile_slot_bytes(int C, int th, int tw, int k) {
     return pc_dec_align((size_t)(C + 4) * (th + 8) * (tw + 8) * sizeof(float)) + pc_dec_cache_bytes(C, th, tw, k);
 }
 
-extern "C" size_t ic_pc_decode_tiles_workspace_bytes(int C, int th_max, int tw_max, int ntiles, int k) {
-    if (C <= 0 || th_max <= 0 || tw_max <= 0 || ntiles <= 0 || k <= 0) return 0;
-    const size_t slots = k == 24 ? (size_t)ntiles * pc_dec_tile_slot_bytes(C, th_max, tw_max, k) : 0;
+// What an entry is given besides the tile table, which all have: it requires the host pointers of these, and its workspace holds
+// their device copies.
+enum : unsigned {
+    PC_TILES_VOLUMES = 1,             // the volume table: every entry but ic_pc_decode_tiles_f32, which has one (h, w)
+    PC_TILES_SEGS = 2,                // segment table and layer ends: the layers and fronts entries
+    PC_TILES_LIMITS = 4,              // a channel limit per tile: their pertile and resume forms
+    PC_TILES_RESUME = 8,              // the layer every tile continues with, and the done words that no copy touches: the resume forms
+    PC_TILES_PLANES = 16,             // the symbol planes: ic_pc_decode_tiles_batch_fronts_resume_f32
+    PC_TILES_LAYERS = PC_TILES_VOLUMES | PC_TILES_SEGS,
+    PC_TILES_PERTILE = PC_TILES_LAYERS | PC_TILES_LIMITS,
+    PC_TILES_LAYERS_RESUME = PC_TILES_PERTILE | PC_TILES_RESUME,
+    PC_TILES_FRONTS_RESUME = PC_TILES_LAYERS_RESUME | PC_TILES_PLANES,
+};
+
+// Where everything lies in a tile entry's workspace, as offsets.  The size functions return `total`, the entries take their pointers
+// from the rest, and nothing else in this file knows the order: tile table, volume table, segment table, layer ends, limits, from,
+// done -- each aligned, those the entry does not have empty.  Then either one slot per tile (k = 24) or what the single-volume paths
+// need for the largest tile plus that tile's symbols (the slow path), the larger of the two.  Last the symbol planes, a byte per
+// symbol of the largest tile, per tile: behind everything the layers resume entry lays out, so that the two resume entries may be
+// handed the same workspace and share everything up to the done words.
+struct PcTilesLayout { size_t tiles, volumes, segs, ends, limits, from, done, slots, planes, total, slot_bytes, plane_bytes; };
+
+static PcTilesLayout pc_tiles_layout(int C, int th_max, int tw_max, int ntiles, int nvolumes, int k, int nlayers, unsigned tables) {
+    PcTilesLayout l{};
+    size_t p = 0;
+    const auto table = [&p](unsigned present, size_t bytes) { const size_t at = p; p += present ? pc_dec_align(bytes) : 0; return at; };
+    l.tiles = table(1, (size_t)ntiles * sizeof(ic_pc_tile_t));
+    l.volumes = table(tables & PC_TILES_VOLUMES, (size_t)nvolumes * sizeof(ic_pc_volume_t));
+    l.segs = table(tables & PC_TILES_SEGS, (size_t)ntiles * nlayers * sizeof(ic_pc_seg_t));
+    l.ends = table(tables & PC_TILES_SEGS, (size_t)nlayers * sizeof(int));
+    l.limits = table(tables & PC_TILES_LIMITS, (size_t)ntiles * sizeof(int));
+    l.from = table(tables & PC_TILES_RESUME, (size_t)ntiles * sizeof(int));
+    l.done = table(tables & PC_TILES_RESUME, (size_t)ntiles * sizeof(int));
+    l.slot_bytes = pc_dec_tile_slot_bytes(C, th_max, tw_max, k);
+    const size_t slots = k == 24 ? (size_t)ntiles * l.slot_bytes : 0;
     const size_t loop = ic_pc_decode_workspace_bytes(C, th_max, tw_max, k) + pc_dec_align((size_t)C * th_max * tw_max * sizeof(int64_t));
-    return pc_dec_align((size_t)ntiles * sizeof(ic_pc_tile_t)) + (slots > loop ? slots : loop);
+    l.slots = p; p += slots > loop ? slots : loop;
+    l.plane_bytes = pc_dec_align((size_t)C * th_max * tw_max);
+    l.planes = p; p += (tables & PC_TILES_PLANES) ? (size_t)ntiles * l.plane_bytes : 0;
+    l.total = p;
+    return l;
 }
 
-// what both tile entries ask of a descriptor, for a tile of an (h, w) volume
+// what the eight size functions return: the layout's total, 0 for counts that no entry takes
+static size_t pc_tiles_workspace_bytes(int C, int th_max, int tw_max, int ntiles, int nvolumes, int k, int nlayers, unsigned tables) {
+    if (C <= 0 || th_max <= 0 || tw_max <= 0 || ntiles <= 0 || k <= 0) return 0;
+    if ((tables & PC_TILES_VOLUMES) && nvolumes <= 0) return 0;
+    if ((tables & PC_TILES_SEGS) && (nlayers < 1 || nlayers > 16)) return 0;
+    return pc_tiles_layout(C, th_max, tw_max, ntiles, nvolumes, k, nlayers, tables).total;
+}
+
+// Everything an entry is given (host only, not ABI).  `tables` says which entry it is: which of the pointers below it requires and
+// what its workspace holds.  What an entry does not have keeps the value pc_tiles_request gives it.
+struct PcTilesRequest {
+    unsigned tables;
+    const uint8_t* bitstreams; long long total_bytes; const ic_pc_tile_t* tiles; int ntiles;
+    const ic_pc_volume_t* volumes; int nvolumes;      // PC_TILES_VOLUMES; else nvolumes is 0 and
+    ic_pc_volume_t one;                               //   this is the volume: it travels in the kernel arguments, the tiles' `volume` is not read
+    const float* const* wtab; const float* centers; int k, L; float resolution;
+    int64_t* symbols; float* q;                       // symbols || q; the single-volume entry has no q, so symbols
+    int* status; int C; void* workspace; size_t workspace_bytes;
+    int flags;                                        // the caller's
+    ic_stream_t stream;
+    bool takes_channels;                              // the channels entry: like the segmented ones it has no slow path, whatever `channels`
+    int channels, fill_sym;                           // channels == C: the full decode, whatever fill_sym; channels < C (k = 24 kernels only): the
+                                                      //   first channels of every tile, the others fill_sym
+    const int* ends; int nlayers; const ic_pc_seg_t* segs;        // PC_TILES_SEGS; else nlayers is 0
+    const int* tile_channels;                         // PC_TILES_LIMITS: in place of `channels`, which is then C
+    const int* tile_from;                             // PC_TILES_RESUME
+    int order;                                        // what the decoder is told.  PC_TILES_SEGS: 0 (raster, plane cuts) or IC_PC_DECODE_WAVEFRONT
+                                                      //   (front cuts), the caller's own flags must be 0 for both; else the caller's flags
+    int th_max, tw_max;                               // the largest tile: pc_tiles_check fills them in
+};
+
+// the arguments that all entries but the single-volume one begin with, and the values of a full decode of unsegmented streams
+static PcTilesRequest pc_tiles_request(unsigned tables, const uint8_t* bitstreams, long long total_bytes, const ic_pc_tile_t* tiles_host,
+                                       int ntiles, const ic_pc_volume_t* volumes_host, int nvolumes, const float* const* wtab_host,
+                                       const float* centers, int k, int L, float resolution, int64_t* symbols, float* q, int* status, int C,
+                                       void* workspace, size_t workspace_bytes, int flags, ic_stream_t stream) {
+    PcTilesRequest r{};
+    r.tables = tables;
+    r.bitstreams = bitstreams; r.total_bytes = total_bytes; r.tiles = tiles_host; r.ntiles = ntiles;
+    r.volumes = volumes_host; r.nvolumes = nvolumes;
+    r.wtab = wtab_host; r.centers = centers; r.k = k; r.L = L; r.resolution = resolution;
+    r.symbols = symbols; r.q = q; r.status = status; r.C = C; r.workspace = workspace; r.workspace_bytes = workspace_bytes;
+    r.flags = flags; r.stream = stream;
+    r.channels = C; r.fill_sym = 0; r.order = flags;
+    return r;
+}
+
+// what every entry asks of a descriptor, for a tile of an (h, w) volume
 static bool pc_tile_ok(const ic_pc_tile_t& d, int h, int w, long long total_bytes, int L) {
     return d.th >= 1 && d.tw >= 1 && d.y0 >= 0 && d.x0 >= 0 && d.th <= h - d.y0 && d.tw <= w - d.x0 &&
            d.stream_off >= 0 && d.stream_bytes >= 0 && d.stream_off <= total_bytes && d.stream_bytes <= total_bytes - d.stream_off &&
            d.first_sym >= 0 && d.first_sym < L;
 }
 
-// The tiles of one call, behind the entries' checks of arguments, flags and workspace size.  nvolumes > 0: the volume table
-// gets its device copy behind the tile table.  nvolumes == 0: one volume, volumes_host[0], which travels in the kernel
-// arguments; the `volume` field of the tiles is not read.  channels == C: the full decode; channels < C (k = 24 kernels only, checked
-// by the caller): the first channels of every tile, the others fill_sym.
-static int pc_decode_tiles_impl(const uint8_t* bitstreams, const ic_pc_tile_t* tiles_host, int ntiles, int th_max, int tw_max,
-                                const ic_pc_volume_t* volumes_host, int nvolumes, const float* const* wtab_host, const float* centers,
-                                int k, int L, float resolution, int64_t* symbols, float* q, int* status, int C, void* workspace,
-                                int flags, int channels, int fill_sym, ic_stream_t stream,
-                                const int* layer_ends_host = nullptr, int nlayers = 0, const ic_pc_seg_t* segs_host = nullptr,
-                                const int* tile_channels_host = nullptr, const int* tile_from_host = nullptr,
-                                size_t planes_off = 0) {
-    const bool wavefront = (flags & IC_PC_DECODE_WAVEFRONT) != 0;
-    hipStream_t st = (hipStream_t)stream;
-    char* p = (char*)workspace;
-    const size_t table_bytes = pc_dec_align((size_t)ntiles * sizeof(ic_pc_tile_t));
-    const size_t vtable_bytes = nvolumes ? pc_dec_align((size_t)nvolumes * sizeof(ic_pc_volume_t)) : 0;
-    if (k == 24 && (flags == 0 || wavefront)) {
+// Everything about the request and its tables is decided here, on the host, before the first HIP call and without a read through a
+// device pointer: every fault of an argument first, then what is unsupported, then the workspace size.  -> th_max, tw_max, the layout.
+static int pc_tiles_check(PcTilesRequest& r, PcTilesLayout& l) {
+    const bool batch = r.tables & PC_TILES_VOLUMES, segmented = r.tables & PC_TILES_SEGS;
+    const bool pertile = r.tables & PC_TILES_LIMITS, resume = r.tables & PC_TILES_RESUME;
+    IC_CHECK_ARG(r.bitstreams && r.tiles && r.wtab && r.centers && (r.symbols || r.q) && r.status && r.workspace);
+    IC_CHECK_ARG((!batch || r.volumes) && (!segmented || (r.ends && r.segs)) && (!pertile || r.tile_channels) && (!resume || r.tile_from));
+    IC_CHECK_ARG(r.total_bytes >= 0 && r.ntiles > 0 && r.C > 0 && r.k > 0 && r.L > 0);
+    IC_CHECK_ARG(batch ? r.nvolumes > 0 : r.one.h > 0 && r.one.w > 0);
+    IC_CHECK_ARG(r.channels >= 1 && r.channels <= r.C && r.fill_sym >= 0 && r.fill_sym < r.L);
+    if (segmented) {
+        IC_CHECK_ARG(r.nlayers >= 1 && r.nlayers <= 16);
+        IC_CHECK_ARG(r.ends[0] >= 1 && r.ends[r.nlayers - 1] == r.C);
+        for (int g = 1; g < r.nlayers; ++g) IC_CHECK_ARG(r.ends[g] > r.ends[g - 1]);
+    }
+    for (int n = 0; n < r.nvolumes; ++n) {
+        const ic_pc_volume_t& v = r.volumes[n];
+        IC_CHECK_ARG(v.h >= 1 && v.w >= 1 && v.symbols_off >= 0 && v.q_off >= 0);
+    }
+    r.th_max = r.tw_max = 0;
+    for (int t = 0; t < r.ntiles; ++t) {
+        ic_pc_tile_t d = r.tiles[t];
+        const int from = resume ? r.tile_from[t] : 0, limit = pertile ? r.tile_channels[t] : r.channels;
+        IC_CHECK_ARG(from >= 0 && from <= r.nlayers);     // (from == nlayers: the tile is whole, its limit can only be C)
+        IC_CHECK_ARG(limit >= 1 && limit <= r.C && (from ? r.ends[from - 1] : 0) <= limit);
+        IC_CHECK_ARG(!batch || (d.volume >= 0 && d.volume < r.nvolumes));
+        if (segmented) { d.stream_off = 0; d.stream_bytes = 0; }             // not read: the segments stand for them
+        const ic_pc_volume_t& v = batch ? r.volumes[d.volume] : r.one;
+        IC_CHECK_ARG(pc_tile_ok(d, v.h, v.w, r.total_bytes, r.L));
+        // the segments THIS call reads: from `from` on (segment 0 only for a tile that starts afresh), of the layers that begin below
+        // the limit, the launch's or the tile's own
+        for (int g = from; g < r.nlayers && (g == 0 || r.ends[g - 1] < limit); ++g) {
+            const ic_pc_seg_t& sg = r.segs[(size_t)t * r.nlayers + g];
+            IC_CHECK_ARG(sg.off >= 0 && sg.nbytes >= 0 && sg.off <= r.total_bytes && sg.nbytes <= r.total_bytes - sg.off);
+        }
+        r.th_max = d.th > r.th_max ? d.th : r.th_max;
+        r.tw_max = d.tw > r.tw_max ? d.tw : r.tw_max;
+    }
+    if (r.L > 16) return IC_ERR_UNSUPPORTED;
+    // the wavefront order has one decoder, the k = 24 kernel: no slow path, no combination with the test flags -- and as a flag it
+    // is the unsegmented batch entries' alone (the fronts entries are told by their name, their flags are 0 like the layers entries')
+    if ((r.flags & IC_PC_DECODE_WAVEFRONT) && (!batch || segmented || r.k != 24 || r.flags != IC_PC_DECODE_WAVEFRONT)) return IC_ERR_UNSUPPORTED;
+    // only the k = 24 kernels have the channel limit and the segments: no slow path for the entries that take either
+    if ((r.takes_channels || segmented) && (r.k != 24 || (r.flags & ~IC_PC_DECODE_WAVEFRONT))) return IC_ERR_UNSUPPORTED;
+    l = pc_tiles_layout(r.C, r.th_max, r.tw_max, r.ntiles, r.nvolumes, r.k, r.nlayers, r.tables);
+    if (r.workspace_bytes < l.total) return IC_ERR_WORKSPACE;
+    return IC_OK;
+}
+
+// the form of pc_dec_tiles_batch_kernel for a launch, by its six template arguments (per implies lim and seg, from implies per): the
+// 24 forms named here are the ones the file instantiates
+typedef void (*PcTilesKernel)(const PcTilesBatchArgs);
+template <bool WAVE, bool LIM, bool SEG, bool PER, bool FROM>
+static PcTilesKernel pc_tiles_kernel_of(bool syms) {
+    return syms ? pc_dec_tiles_batch_kernel<WAVE, true, LIM, SEG, PER, FROM> : pc_dec_tiles_batch_kernel<WAVE, false, LIM, SEG, PER, FROM>;
+}
+static PcTilesKernel pc_tiles_kernel(bool wave, bool syms, bool lim, bool seg, bool per, bool from) {
+    if (!seg) return !lim ? (wave ? pc_tiles_kernel_of<true, false, false, false, false>(syms) : pc_tiles_kernel_of<false, false, false, false, false>(syms))
+                          : (wave ? pc_tiles_kernel_of<true, true, false, false, false>(syms) : pc_tiles_kernel_of<false, true, false, false, false>(syms));
+    if (!wave) return !lim ? pc_tiles_kernel_of<false, false, true, false, false>(syms) : !per ? pc_tiles_kernel_of<false, true, true, false, false>(syms)
+                    : !from ? pc_tiles_kernel_of<false, true, true, true, false>(syms) : pc_tiles_kernel_of<false, true, true, true, true>(syms);
+    return !lim ? pc_tiles_kernel_of<true, false, true, false, false>(syms) : !per ? pc_tiles_kernel_of<true, true, true, false, false>(syms)
+         : !from ? pc_tiles_kernel_of<true, true, true, true, false>(syms) : pc_tiles_kernel_of<true, true, true, true, true>(syms);
+}
+
+// The tiles of one call, behind pc_tiles_check.
+static int pc_decode_tiles_impl(const PcTilesRequest& r, const PcTilesLayout& l) {
+    const bool wavefront = (r.order & IC_PC_DECODE_WAVEFRONT) != 0;
+    hipStream_t st = (hipStream_t)r.stream;
+    char* const ws = (char*)r.workspace;
+    const int ntiles = r.ntiles, C = r.C;
+    if (r.k == 24 && (r.order == 0 || wavefront)) {
         PcTilesBatchArgs a{};
-        ic_pc_tile_t* tiles_dev = (ic_pc_tile_t*)p; p += table_bytes;
         // the tables are pageable host memory: the runtime has taken its copy of them when these return
-        if (hipMemcpyAsync(tiles_dev, tiles_host, (size_t)ntiles * sizeof(ic_pc_tile_t), hipMemcpyHostToDevice, st) != hipSuccess) return IC_ERR_ARG;
-        if (nvolumes) {
-            ic_pc_volume_t* volumes_dev = (ic_pc_volume_t*)p; p += vtable_bytes;
-            if (hipMemcpyAsync(volumes_dev, volumes_host, (size_t)nvolumes * sizeof(ic_pc_volume_t), hipMemcpyHostToDevice, st) != hipSuccess) return IC_ERR_ARG;
-            a.volumes = volumes_dev;
+        const auto upload = [&](size_t at, const void* host, size_t bytes) {
+            return hipMemcpyAsync(ws + at, host, bytes, hipMemcpyHostToDevice, st) == hipSuccess;
+        };
+        if (!upload(l.tiles, r.tiles, (size_t)ntiles * sizeof(ic_pc_tile_t))) return IC_ERR_ARG;
+        a.tiles = (const ic_pc_tile_t*)(ws + l.tiles);
+        if (r.nvolumes) {
+            if (!upload(l.volumes, r.volumes, (size_t)r.nvolumes * sizeof(ic_pc_volume_t))) return IC_ERR_ARG;
+            a.volumes = (const ic_pc_volume_t*)(ws + l.volumes);
         } else {
-            a.one = volumes_host[0];
+            a.one = r.one;
         }
-        if (nlayers) {                // the layers and fronts entries (k = 24): segment table and layer ends behind the two tables
-            ic_pc_seg_t* segs_dev = (ic_pc_seg_t*)p; p += pc_dec_align((size_t)ntiles * nlayers * sizeof(ic_pc_seg_t));
-            int* ends_dev = (int*)p; p += pc_dec_align((size_t)nlayers * sizeof(int));
-            if (hipMemcpyAsync(segs_dev, segs_host, (size_t)ntiles * nlayers * sizeof(ic_pc_seg_t), hipMemcpyHostToDevice, st) != hipSuccess) return IC_ERR_ARG;
-            if (hipMemcpyAsync(ends_dev, layer_ends_host, (size_t)nlayers * sizeof(int), hipMemcpyHostToDevice, st) != hipSuccess) return IC_ERR_ARG;
-            a.segs = segs_dev; a.ends = ends_dev; a.nlayers = nlayers;
+        if (r.nlayers) {              // the layers and fronts entries
+            if (!upload(l.segs, r.segs, (size_t)ntiles * r.nlayers * sizeof(ic_pc_seg_t))) return IC_ERR_ARG;
+            if (!upload(l.ends, r.ends, (size_t)r.nlayers * sizeof(int))) return IC_ERR_ARG;
+            a.segs = (const ic_pc_seg_t*)(ws + l.segs); a.ends = (const int*)(ws + l.ends); a.nlayers = r.nlayers;
         }
-        if (tile_channels_host) {     // the per-tile entry: the limits behind the segment table and the layer ends
-            int* limits_dev = (int*)p; p += pc_dec_align((size_t)ntiles * sizeof(int));
-            if (hipMemcpyAsync(limits_dev, tile_channels_host, (size_t)ntiles * sizeof(int), hipMemcpyHostToDevice, st) != hipSuccess) return IC_ERR_ARG;
-            a.tile_channels = limits_dev;
+        if (r.tile_channels) {        // their pertile and resume forms
+            if (!upload(l.limits, r.tile_channels, (size_t)ntiles * sizeof(int))) return IC_ERR_ARG;
+            a.tile_channels = (const int*)(ws + l.limits);
         }
-        if (tile_from_host) {         // the resume entry: the layers to continue with behind the limits, then `done`, which no copy touches
-            int* from_dev = (int*)p; p += pc_dec_align((size_t)ntiles * sizeof(int));
-            if (hipMemcpyAsync(from_dev, tile_from_host, (size_t)ntiles * sizeof(int), hipMemcpyHostToDevice, st) != hipSuccess) return IC_ERR_ARG;
-            a.tile_from = from_dev;
-            a.done = (int*)p; p += pc_dec_align((size_t)ntiles * sizeof(int));
-            if (wavefront) {          // the fronts resume entry: the symbol planes behind everything the layers resume entry lays out
-                a.planes = (unsigned char*)workspace + planes_off;
-                a.plane_bytes = pc_dec_align((size_t)C * th_max * tw_max);
-            }
+        if (r.tile_from) {            // the resume forms: `done` is the kernel's alone, no copy touches it
+            if (!upload(l.from, r.tile_from, (size_t)ntiles * sizeof(int))) return IC_ERR_ARG;
+            a.tile_from = (const int*)(ws + l.from);
+            a.done = (int*)(ws + l.done);
+            if (wavefront) { a.planes = (unsigned char*)ws + l.planes; a.plane_bytes = l.plane_bytes; }
         }
-        a.f.d.centers = centers; a.f.d.C = C; a.f.d.L = L; a.f.d.resolution = resolution;
-        a.f.w0 = wtab_host[0]; a.f.b0 = wtab_host[1]; a.f.w1 = wtab_host[2]; a.f.b1 = wtab_host[3];
-        a.f.w2 = wtab_host[4]; a.f.b2 = wtab_host[5]; a.f.w3 = wtab_host[6]; a.f.b3 = wtab_host[7];
-        a.bits = bitstreams; a.tiles = tiles_dev; a.slots = p;
-        a.slot_bytes = pc_dec_tile_slot_bytes(C, th_max, tw_max, k);
-        a.off_c0 = pc_dec_align((size_t)(C + 4) * (th_max + 8) * (tw_max + 8) * sizeof(float));
-        a.off_c1 = a.off_c0 + pc_dec_align(pc_dec_cache_floats(C, th_max, tw_max, k, 0) * sizeof(float));
-        a.off_c2 = a.off_c1 + pc_dec_align(pc_dec_cache_floats(C, th_max, tw_max, k, 1) * sizeof(float));
-        a.symbols = (long long*)symbols; a.q = q; a.status = status;
-        const long long nvol = (long long)(C + 4) * (th_max + 8) * (tw_max + 8);
-        if (tile_from_host)
+        a.f.d.centers = r.centers; a.f.d.C = C; a.f.d.L = r.L; a.f.d.resolution = r.resolution;
+        a.f.w0 = r.wtab[0]; a.f.b0 = r.wtab[1]; a.f.w1 = r.wtab[2]; a.f.b1 = r.wtab[3];
+        a.f.w2 = r.wtab[4]; a.f.b2 = r.wtab[5]; a.f.w3 = r.wtab[6]; a.f.b3 = r.wtab[7];
+        a.bits = r.bitstreams; a.slots = ws + l.slots; a.slot_bytes = l.slot_bytes;
+        a.off_c0 = pc_dec_align((size_t)(C + 4) * (r.th_max + 8) * (r.tw_max + 8) * sizeof(float));
+        a.off_c1 = a.off_c0 + pc_dec_align(pc_dec_cache_floats(C, r.th_max, r.tw_max, r.k, 0) * sizeof(float));
+        a.off_c2 = a.off_c1 + pc_dec_align(pc_dec_cache_floats(C, r.th_max, r.tw_max, r.k, 1) * sizeof(float));
+        a.symbols = (long long*)r.symbols; a.q = r.q; a.status = r.status;
+        const long long nvol = (long long)(C + 4) * (r.th_max + 8) * (r.tw_max + 8);
+        if (r.tile_from)
             hipLaunchKernelGGL(pc_dec_fill_fresh_slots_kernel, dim3((unsigned)((nvol + 255) / 256), (unsigned)ntiles), dim3(256), 0, st,
-                               a.slots, a.slot_bytes, nvol, centers, a.tile_from);
+                               a.slots, a.slot_bytes, nvol, r.centers, a.tile_from);
         else
             hipLaunchKernelGGL(pc_dec_fill_slots_kernel, dim3((unsigned)((nvol + 255) / 256), (unsigned)ntiles), dim3(256), 0, st,
-                               a.slots, a.slot_bytes, nvol, centers);
-        a.cdec = channels; a.fill = fill_sym;
-        const auto full = wavefront ? (symbols ? pc_dec_tiles_batch_kernel<true, true> : pc_dec_tiles_batch_kernel<true, false>)
-                                    : (symbols ? pc_dec_tiles_batch_kernel<false, true> : pc_dec_tiles_batch_kernel<false, false>);
-        const auto lim = wavefront ? (symbols ? pc_dec_tiles_batch_kernel<true, true, true> : pc_dec_tiles_batch_kernel<true, false, true>)
-                                   : (symbols ? pc_dec_tiles_batch_kernel<false, true, true> : pc_dec_tiles_batch_kernel<false, false, true>);
-        const auto seg_full = symbols ? pc_dec_tiles_batch_kernel<false, true, false, true> : pc_dec_tiles_batch_kernel<false, false, false, true>;
-        const auto seg_lim = symbols ? pc_dec_tiles_batch_kernel<false, true, true, true> : pc_dec_tiles_batch_kernel<false, false, true, true>;
-        const auto seg_per = symbols ? pc_dec_tiles_batch_kernel<false, true, true, true, true> : pc_dec_tiles_batch_kernel<false, false, true, true, true>;
-        const auto seg_resume = symbols ? pc_dec_tiles_batch_kernel<false, true, true, true, true, true> : pc_dec_tiles_batch_kernel<false, false, true, true, true, true>;
-        const auto front_full = symbols ? pc_dec_tiles_batch_kernel<true, true, false, true> : pc_dec_tiles_batch_kernel<true, false, false, true>;
-        const auto front_lim = symbols ? pc_dec_tiles_batch_kernel<true, true, true, true> : pc_dec_tiles_batch_kernel<true, false, true, true>;
-        const auto front_per = symbols ? pc_dec_tiles_batch_kernel<true, true, true, true, true> : pc_dec_tiles_batch_kernel<true, false, true, true, true>;
-        const auto front_resume = symbols ? pc_dec_tiles_batch_kernel<true, true, true, true, true, true> : pc_dec_tiles_batch_kernel<true, false, true, true, true, true>;
-        const auto kernel = tile_from_host ? (wavefront ? front_resume : seg_resume)
-                          : (wavefront && nlayers) ? (tile_channels_host ? front_per : channels < C ? front_lim : front_full)
-                          : tile_channels_host ? seg_per : nlayers ? (channels < C ? seg_lim : seg_full) : (channels < C ? lim : full);
+                               a.slots, a.slot_bytes, nvol, r.centers);
+        a.cdec = r.channels; a.fill = r.fill_sym;
+        const PcTilesKernel kernel = pc_tiles_kernel(wavefront, r.symbols != nullptr, r.tile_channels || r.channels < C, r.nlayers != 0,
+                                                     r.tile_channels != nullptr, r.tile_from != nullptr);
         hipLaunchKernelGGL(kernel, dim3((unsigned)ntiles), dim3(256), 0, st, a);
         IC_LAUNCH_CHECK();
         return IC_OK;
     }
     // the slow path (other k, or one of the test flags): tile after tile through the single-volume decoder, then into place
-    p += table_bytes + vtable_bytes;
-    const size_t loop_ws = ic_pc_decode_workspace_bytes(C, th_max, tw_max, k);
+    char* const p = ws + l.slots;
+    const size_t loop_ws = ic_pc_decode_workspace_bytes(C, r.th_max, r.tw_max, r.k);
     int64_t* tile_syms = (int64_t*)(p + loop_ws);
     for (int t = 0; t < ntiles; ++t) {
-        const ic_pc_tile_t& d = tiles_host[t];
-        const ic_pc_volume_t& v = volumes_host[nvolumes ? d.volume : 0];
-        const int rc = ic_pc_decode_f32(bitstreams + d.stream_off, d.stream_bytes, d.first_sym, wtab_host, centers, k, L, resolution,
-                                        tile_syms, status + t, C, d.th, d.tw, p, loop_ws, flags, stream);
+        const ic_pc_tile_t& d = r.tiles[t];
+        const ic_pc_volume_t& v = r.nvolumes ? r.volumes[d.volume] : r.one;
+        const int rc = ic_pc_decode_f32(r.bitstreams + d.stream_off, d.stream_bytes, d.first_sym, r.wtab, r.centers, r.k, r.L, r.resolution,
+                                        tile_syms, r.status + t, C, d.th, d.tw, p, loop_ws, r.flags, r.stream);
         if (rc) return rc;
         const long long n = (long long)C * d.th * d.tw;
         hipLaunchKernelGGL(pc_tile_place_batch_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const long long*)tile_syms,
-                           symbols ? (long long*)symbols + v.symbols_off : nullptr, q ? q + v.q_off : nullptr, centers,
+                           r.symbols ? (long long*)r.symbols + v.symbols_off : nullptr, r.q ? r.q + v.q_off : nullptr, r.centers,
                            C, d.th, d.tw, v.h, v.w, d.y0, d.x0);
     }
     IC_LAUNCH_CHECK();
     return IC_OK;
 }
 
+static int pc_decode_tiles(PcTilesRequest r) {
+    PcTilesLayout l;
+    const int rc = pc_tiles_check(r, l);
+    return rc ? rc : pc_decode_tiles_impl(r, l);
+}
+
+extern "C" size_t ic_pc_decode_tiles_workspace_bytes(int C, int th_max, int tw_max, int ntiles, int k) {
+    return pc_tiles_workspace_bytes(C, th_max, tw_max, ntiles, 0, k, 0, 0);
+}
+
 extern "C" int ic_pc_decode_tiles_f32(const uint8_t* bitstreams, long long total_bytes, const ic_pc_tile_t* tiles_host, int ntiles,
                                       const float* const* wtab_host, const float* centers, int k, int L, float resolution,
                                       int64_t* symbols, int* status, int C, int h, int w, void* workspace,
                                       size_t workspace_bytes, int flags, ic_stream_t stream) {
-    // everything about the descriptors is decided here, on the host, before the first HIP call
-    IC_CHECK_ARG(bitstreams && tiles_host && wtab_host && centers && symbols && status && workspace);
-    IC_CHECK_ARG(total_bytes >= 0 && ntiles > 0 && C > 0 && h > 0 && w > 0 && k > 0 && L > 0);
-    int th_max = 0, tw_max = 0;
-    for (int t = 0; t < ntiles; ++t) {
-        const ic_pc_tile_t& d = tiles_host[t];
-        IC_CHECK_ARG(pc_tile_ok(d, h, w, total_bytes, L));
-        th_max = d.th > th_max ? d.th : th_max;
-        tw_max = d.tw > tw_max ? d.tw : tw_max;
-    }
-    if (L > 16 || (flags & IC_PC_DECODE_WAVEFRONT)) return IC_ERR_UNSUPPORTED;      // (the wavefront order: the batch entry only)
-    if (workspace_bytes < ic_pc_decode_tiles_workspace_bytes(C, th_max, tw_max, ntiles, k)) return IC_ERR_WORKSPACE;
-    const ic_pc_volume_t one = {h, w, 0, 0};
-    return pc_decode_tiles_impl(bitstreams, tiles_host, ntiles, th_max, tw_max, &one, 0, wtab_host, centers, k, L, resolution,
-                                symbols, nullptr, status, C, workspace, flags, C, 0, stream);
+    PcTilesRequest r = pc_tiles_request(0, bitstreams, total_bytes, tiles_host, ntiles, nullptr, 0, wtab_host, centers, k, L, resolution,
+                                        symbols, nullptr, status, C, workspace, workspace_bytes, flags, stream);
+    r.one = {h, w, 0, 0};
+    return pc_decode_tiles(r);
 }
 
-// workspace of ic_pc_decode_tiles_batch_f32: the tile table, the volume table, then as ic_pc_decode_tiles_f32
 extern "C" size_t ic_pc_decode_tiles_batch_workspace_bytes(int C, int th_max, int tw_max, int ntiles, int nvolumes, int k) {
-    if (nvolumes <= 0) return 0;
-    const size_t base = ic_pc_decode_tiles_workspace_bytes(C, th_max, tw_max, ntiles, k);
-    return base ? base + pc_dec_align((size_t)nvolumes * sizeof(ic_pc_volume_t)) : 0;
+    return pc_tiles_workspace_bytes(C, th_max, tw_max, ntiles, nvolumes, k, 0, PC_TILES_VOLUMES);
 }
 
 extern "C" int ic_pc_decode_tiles_batch_f32(const uint8_t* bitstreams, long long total_bytes, const ic_pc_tile_t* tiles_host, int ntiles,
@@ -1472,27 +1588,8 @@ extern "C" int ic_pc_decode_tiles_batch_f32(const uint8_t* bitstreams, long long
                                             const float* centers, int k, int L, float resolution, int64_t* symbols, float* q,
                                             int* status, int C, void* workspace, size_t workspace_bytes, int flags,
                                             ic_stream_t stream) {
-    // everything about the two tables is decided here, on the host, before the first HIP call
-    IC_CHECK_ARG(bitstreams && tiles_host && volumes_host && wtab_host && centers && (symbols || q) && status && workspace);
-    IC_CHECK_ARG(total_bytes >= 0 && ntiles > 0 && nvolumes > 0 && C > 0 && k > 0 && L > 0);
-    for (int n = 0; n < nvolumes; ++n) {
-        const ic_pc_volume_t& v = volumes_host[n];
-        IC_CHECK_ARG(v.h >= 1 && v.w >= 1 && v.symbols_off >= 0 && v.q_off >= 0);
-    }
-    int th_max = 0, tw_max = 0;
-    for (int t = 0; t < ntiles; ++t) {
-        const ic_pc_tile_t& d = tiles_host[t];
-        IC_CHECK_ARG(d.volume >= 0 && d.volume < nvolumes);
-        IC_CHECK_ARG(pc_tile_ok(d, volumes_host[d.volume].h, volumes_host[d.volume].w, total_bytes, L));
-        th_max = d.th > th_max ? d.th : th_max;
-        tw_max = d.tw > tw_max ? d.tw : tw_max;
-    }
-    if (L > 16) return IC_ERR_UNSUPPORTED;
-    // the wavefront order has one decoder, the k = 24 kernel: no slow path, no combination with the test flags
-    if ((flags & IC_PC_DECODE_WAVEFRONT) && (k != 24 || flags != IC_PC_DECODE_WAVEFRONT)) return IC_ERR_UNSUPPORTED;
-    if (workspace_bytes < ic_pc_decode_tiles_batch_workspace_bytes(C, th_max, tw_max, ntiles, nvolumes, k)) return IC_ERR_WORKSPACE;
-    return pc_decode_tiles_impl(bitstreams, tiles_host, ntiles, th_max, tw_max, volumes_host, nvolumes, wtab_host, centers, k, L,
-                                resolution, symbols, q, status, C, workspace, flags, C, 0, stream);
+    return pc_decode_tiles(pc_tiles_request(PC_TILES_VOLUMES, bitstreams, total_bytes, tiles_host, ntiles, volumes_host, nvolumes, wtab_host,
+                                            centers, k, L, resolution, symbols, q, status, C, workspace, workspace_bytes, flags, stream));
 }
 
 // preview of the tiles of several volumes: as above with the channel limit; flags is 0 or IC_PC_DECODE_WAVEFRONT, k is 24
@@ -1501,76 +1598,25 @@ extern "C" int ic_pc_decode_tiles_batch_channels_f32(const uint8_t* bitstreams, 
                                                      const float* centers, int k, int L, float resolution, int64_t* symbols, float* q,
                                                      int* status, int C, void* workspace, size_t workspace_bytes, int flags,
                                                      ic_stream_t stream, int channels, int fill_sym) {
-    IC_CHECK_ARG(bitstreams && tiles_host && volumes_host && wtab_host && centers && (symbols || q) && status && workspace);
-    IC_CHECK_ARG(total_bytes >= 0 && ntiles > 0 && nvolumes > 0 && C > 0 && k > 0 && L > 0);
-    IC_CHECK_ARG(channels >= 1 && channels <= C && fill_sym >= 0 && fill_sym < L);
-    for (int n = 0; n < nvolumes; ++n) {
-        const ic_pc_volume_t& v = volumes_host[n];
-        IC_CHECK_ARG(v.h >= 1 && v.w >= 1 && v.symbols_off >= 0 && v.q_off >= 0);
-    }
-    int th_max = 0, tw_max = 0;
-    for (int t = 0; t < ntiles; ++t) {
-        const ic_pc_tile_t& d = tiles_host[t];
-        IC_CHECK_ARG(d.volume >= 0 && d.volume < nvolumes);
-        IC_CHECK_ARG(pc_tile_ok(d, volumes_host[d.volume].h, volumes_host[d.volume].w, total_bytes, L));
-        th_max = d.th > th_max ? d.th : th_max;
-        tw_max = d.tw > tw_max ? d.tw : tw_max;
-    }
-    if (L > 16 || k != 24 || (flags != 0 && flags != IC_PC_DECODE_WAVEFRONT)) return IC_ERR_UNSUPPORTED;
-    if (workspace_bytes < ic_pc_decode_tiles_batch_workspace_bytes(C, th_max, tw_max, ntiles, nvolumes, k)) return IC_ERR_WORKSPACE;
-    return pc_decode_tiles_impl(bitstreams, tiles_host, ntiles, th_max, tw_max, volumes_host, nvolumes, wtab_host, centers, k, L,
-                                resolution, symbols, q, status, C, workspace, flags, channels, fill_sym, stream);
+    PcTilesRequest r = pc_tiles_request(PC_TILES_VOLUMES, bitstreams, total_bytes, tiles_host, ntiles, volumes_host, nvolumes, wtab_host,
+                                        centers, k, L, resolution, symbols, q, status, C, workspace, workspace_bytes, flags, stream);
+    r.takes_channels = true; r.channels = channels; r.fill_sym = fill_sym;
+    return pc_decode_tiles(r);
+}
+
+// the segmented entries' own arguments: the limit is the launch's (`channels`) or the tiles' own (tile_channels_host, channels = C);
+// tile_from_layer_host: the resume entries; order: what the entry's name says
+static int pc_decode_tiles_segments(PcTilesRequest r, int channels, const int* tile_channels_host, const int* tile_from_layer_host,
+                                    int fill_sym, const int* layer_ends_host, int nlayers, const ic_pc_seg_t* segs_host, int order) {
+    r.channels = channels; r.fill_sym = fill_sym;
+    r.tile_channels = tile_channels_host; r.tile_from = tile_from_layer_host;
+    r.ends = layer_ends_host; r.nlayers = nlayers; r.segs = segs_host; r.order = order;
+    return pc_decode_tiles(r);
 }
 
 // ---- layered tiles (container format 6): every tile's raster stream as nlayers segments --------------------------------------
-static size_t pc_dec_layers_tables_bytes(int ntiles, int nlayers) {
-    return pc_dec_align((size_t)ntiles * nlayers * sizeof(ic_pc_seg_t)) + pc_dec_align((size_t)nlayers * sizeof(int));
-}
-
 extern "C" size_t ic_pc_decode_tiles_batch_layers_workspace_bytes(int C, int th_max, int tw_max, int ntiles, int nvolumes, int k, int nlayers) {
-    if (nlayers < 1 || nlayers > 16) return 0;
-    const size_t base = ic_pc_decode_tiles_batch_workspace_bytes(C, th_max, tw_max, ntiles, nvolumes, k);
-    return base ? base + pc_dec_layers_tables_bytes(ntiles, nlayers) : 0;
-}
-
-// the layers entry and the fronts entry: one set of checks; `order` is what the decoder is told, 0 (raster, plane cuts) or
-// IC_PC_DECODE_WAVEFRONT (front cuts) -- the caller's own flags must be 0 for both
-static int pc_decode_tiles_segments(const uint8_t* bitstreams, long long total_bytes, const ic_pc_tile_t* tiles_host, int ntiles,
-                                    const ic_pc_volume_t* volumes_host, int nvolumes, const float* const* wtab_host,
-                                    const float* centers, int k, int L, float resolution, int64_t* symbols, float* q,
-                                    int* status, int C, void* workspace, size_t workspace_bytes, int flags,
-                                    ic_stream_t stream, int channels, int fill_sym,
-                                    const int* layer_ends_host, int nlayers, const ic_pc_seg_t* segs_host, int order) {
-    // everything about the four tables is decided here, on the host, before the first HIP call
-    IC_CHECK_ARG(bitstreams && tiles_host && volumes_host && wtab_host && centers && (symbols || q) && status && workspace);
-    IC_CHECK_ARG(layer_ends_host && segs_host);
-    IC_CHECK_ARG(total_bytes >= 0 && ntiles > 0 && nvolumes > 0 && C > 0 && k > 0 && L > 0);
-    IC_CHECK_ARG(channels >= 1 && channels <= C && fill_sym >= 0 && fill_sym < L);
-    IC_CHECK_ARG(nlayers >= 1 && nlayers <= 16);
-    IC_CHECK_ARG(layer_ends_host[0] >= 1 && layer_ends_host[nlayers - 1] == C);
-    for (int g = 1; g < nlayers; ++g) IC_CHECK_ARG(layer_ends_host[g] > layer_ends_host[g - 1]);
-    for (int n = 0; n < nvolumes; ++n) {
-        const ic_pc_volume_t& v = volumes_host[n];
-        IC_CHECK_ARG(v.h >= 1 && v.w >= 1 && v.symbols_off >= 0 && v.q_off >= 0);
-    }
-    int th_max = 0, tw_max = 0;
-    for (int t = 0; t < ntiles; ++t) {
-        ic_pc_tile_t d = tiles_host[t];
-        IC_CHECK_ARG(d.volume >= 0 && d.volume < nvolumes);
-        d.stream_off = 0; d.stream_bytes = 0;             // not read: the segments stand for them
-        IC_CHECK_ARG(pc_tile_ok(d, volumes_host[d.volume].h, volumes_host[d.volume].w, total_bytes, L));
-        for (int g = 0; g < nlayers && (g == 0 || layer_ends_host[g - 1] < channels); ++g) {     // the layers that begin below `channels`
-            const ic_pc_seg_t& sg = segs_host[(size_t)t * nlayers + g];
-            IC_CHECK_ARG(sg.off >= 0 && sg.nbytes >= 0 && sg.off <= total_bytes && sg.nbytes <= total_bytes - sg.off);
-        }
-        th_max = d.th > th_max ? d.th : th_max;
-        tw_max = d.tw > tw_max ? d.tw : tw_max;
-    }
-    if (L > 16 || k != 24 || flags != 0) return IC_ERR_UNSUPPORTED;
-    if (workspace_bytes < ic_pc_decode_tiles_batch_layers_workspace_bytes(C, th_max, tw_max, ntiles, nvolumes, k, nlayers)) return IC_ERR_WORKSPACE;
-    return pc_decode_tiles_impl(bitstreams, tiles_host, ntiles, th_max, tw_max, volumes_host, nvolumes, wtab_host, centers, k, L,
-                                resolution, symbols, q, status, C, workspace, order, channels, fill_sym, stream,
-                                layer_ends_host, nlayers, segs_host);
+    return pc_tiles_workspace_bytes(C, th_max, tw_max, ntiles, nvolumes, k, nlayers, PC_TILES_LAYERS);
 }
 
 extern "C" int ic_pc_decode_tiles_batch_layers_f32(const uint8_t* bitstreams, long long total_bytes, const ic_pc_tile_t* tiles_host, int ntiles,
@@ -1579,55 +1625,14 @@ extern "C" int ic_pc_decode_tiles_batch_layers_f32(const uint8_t* bitstreams, lo
                                                    int* status, int C, void* workspace, size_t workspace_bytes, int flags,
                                                    ic_stream_t stream, int channels, int fill_sym,
                                                    const int* layer_ends_host, int nlayers, const ic_pc_seg_t* segs_host) {
-    return pc_decode_tiles_segments(bitstreams, total_bytes, tiles_host, ntiles, volumes_host, nvolumes, wtab_host, centers, k, L, resolution,
-                                    symbols, q, status, C, workspace, workspace_bytes, flags, stream, channels, fill_sym,
-                                    layer_ends_host, nlayers, segs_host, 0);
+    return pc_decode_tiles_segments(pc_tiles_request(PC_TILES_LAYERS, bitstreams, total_bytes, tiles_host, ntiles, volumes_host, nvolumes, wtab_host,
+                                                     centers, k, L, resolution, symbols, q, status, C, workspace, workspace_bytes, flags, stream),
+                                    channels, nullptr, nullptr, fill_sym, layer_ends_host, nlayers, segs_host, 0);
 }
 
 // ---- layered tiles with a channel limit per tile: what a damaged or cut format-6 file still holds of every tile ---------------
 extern "C" size_t ic_pc_decode_tiles_batch_layers_pertile_workspace_bytes(int C, int th_max, int tw_max, int ntiles, int nvolumes, int k, int nlayers) {
-    const size_t base = ic_pc_decode_tiles_batch_layers_workspace_bytes(C, th_max, tw_max, ntiles, nvolumes, k, nlayers);
-    return base ? base + pc_dec_align((size_t)ntiles * sizeof(int)) : 0;
-}
-
-static int pc_decode_tiles_segments_pertile(const uint8_t* bitstreams, long long total_bytes, const ic_pc_tile_t* tiles_host, int ntiles,
-                                            const ic_pc_volume_t* volumes_host, int nvolumes, const float* const* wtab_host,
-                                            const float* centers, int k, int L, float resolution, int64_t* symbols, float* q,
-                                            int* status, int C, void* workspace, size_t workspace_bytes, int flags,
-                                            ic_stream_t stream, const int* tile_channels_host, int fill_sym,
-                                            const int* layer_ends_host, int nlayers, const ic_pc_seg_t* segs_host, int order) {
-    // everything about the five tables is decided here, on the host, before the first HIP call
-    IC_CHECK_ARG(bitstreams && tiles_host && volumes_host && wtab_host && centers && (symbols || q) && status && workspace);
-    IC_CHECK_ARG(tile_channels_host && layer_ends_host && segs_host);
-    IC_CHECK_ARG(total_bytes >= 0 && ntiles > 0 && nvolumes > 0 && C > 0 && k > 0 && L > 0);
-    IC_CHECK_ARG(fill_sym >= 0 && fill_sym < L);
-    IC_CHECK_ARG(nlayers >= 1 && nlayers <= 16);
-    IC_CHECK_ARG(layer_ends_host[0] >= 1 && layer_ends_host[nlayers - 1] == C);
-    for (int g = 1; g < nlayers; ++g) IC_CHECK_ARG(layer_ends_host[g] > layer_ends_host[g - 1]);
-    for (int n = 0; n < nvolumes; ++n) {
-        const ic_pc_volume_t& v = volumes_host[n];
-        IC_CHECK_ARG(v.h >= 1 && v.w >= 1 && v.symbols_off >= 0 && v.q_off >= 0);
-    }
-    int th_max = 0, tw_max = 0;
-    for (int t = 0; t < ntiles; ++t) {
-        ic_pc_tile_t d = tiles_host[t];
-        const int channels = tile_channels_host[t];
-        IC_CHECK_ARG(channels >= 1 && channels <= C);
-        IC_CHECK_ARG(d.volume >= 0 && d.volume < nvolumes);
-        d.stream_off = 0; d.stream_bytes = 0;             // not read: the segments stand for them
-        IC_CHECK_ARG(pc_tile_ok(d, volumes_host[d.volume].h, volumes_host[d.volume].w, total_bytes, L));
-        for (int g = 0; g < nlayers && (g == 0 || layer_ends_host[g - 1] < channels); ++g) {     // the layers that begin below THIS tile's limit
-            const ic_pc_seg_t& sg = segs_host[(size_t)t * nlayers + g];
-            IC_CHECK_ARG(sg.off >= 0 && sg.nbytes >= 0 && sg.off <= total_bytes && sg.nbytes <= total_bytes - sg.off);
-        }
-        th_max = d.th > th_max ? d.th : th_max;
-        tw_max = d.tw > tw_max ? d.tw : tw_max;
-    }
-    if (L > 16 || k != 24 || flags != 0) return IC_ERR_UNSUPPORTED;
-    if (workspace_bytes < ic_pc_decode_tiles_batch_layers_pertile_workspace_bytes(C, th_max, tw_max, ntiles, nvolumes, k, nlayers)) return IC_ERR_WORKSPACE;
-    return pc_decode_tiles_impl(bitstreams, tiles_host, ntiles, th_max, tw_max, volumes_host, nvolumes, wtab_host, centers, k, L,
-                                resolution, symbols, q, status, C, workspace, order, C, fill_sym, stream,
-                                layer_ends_host, nlayers, segs_host, tile_channels_host);
+    return pc_tiles_workspace_bytes(C, th_max, tw_max, ntiles, nvolumes, k, nlayers, PC_TILES_PERTILE);
 }
 
 extern "C" int ic_pc_decode_tiles_batch_layers_pertile_f32(const uint8_t* bitstreams, long long total_bytes, const ic_pc_tile_t* tiles_host, int ntiles,
@@ -1636,15 +1641,15 @@ extern "C" int ic_pc_decode_tiles_batch_layers_pertile_f32(const uint8_t* bitstr
                                                            int* status, int C, void* workspace, size_t workspace_bytes, int flags,
                                                            ic_stream_t stream, const int* tile_channels_host, int fill_sym,
                                                            const int* layer_ends_host, int nlayers, const ic_pc_seg_t* segs_host) {
-    return pc_decode_tiles_segments_pertile(bitstreams, total_bytes, tiles_host, ntiles, volumes_host, nvolumes, wtab_host, centers, k, L,
-                                            resolution, symbols, q, status, C, workspace, workspace_bytes, flags, stream, tile_channels_host,
-                                            fill_sym, layer_ends_host, nlayers, segs_host, 0);
+    return pc_decode_tiles_segments(pc_tiles_request(PC_TILES_PERTILE, bitstreams, total_bytes, tiles_host, ntiles, volumes_host, nvolumes, wtab_host,
+                                                     centers, k, L, resolution, symbols, q, status, C, workspace, workspace_bytes, flags, stream),
+                                    C, tile_channels_host, nullptr, fill_sym, layer_ends_host, nlayers, segs_host, 0);
 }
 
 // ---- front-layered tiles (container format 8): every tile's wavefront-ordered stream as nlayers segments cut at fronts ------------
 // The arguments, the checks and the workspace of the two layered entries; only the meaning of a segment differs (pc_dec_wave_body, SEG).
 extern "C" size_t ic_pc_decode_tiles_batch_fronts_workspace_bytes(int C, int th_max, int tw_max, int ntiles, int nvolumes, int k, int nlayers) {
-    return ic_pc_decode_tiles_batch_layers_workspace_bytes(C, th_max, tw_max, ntiles, nvolumes, k, nlayers);
+    return pc_tiles_workspace_bytes(C, th_max, tw_max, ntiles, nvolumes, k, nlayers, PC_TILES_LAYERS);
 }
 
 extern "C" int ic_pc_decode_tiles_batch_fronts_f32(const uint8_t* bitstreams, long long total_bytes, const ic_pc_tile_t* tiles_host, int ntiles,
@@ -1653,13 +1658,13 @@ extern "C" int ic_pc_decode_tiles_batch_fronts_f32(const uint8_t* bitstreams, lo
                                                    int* status, int C, void* workspace, size_t workspace_bytes, int flags,
                                                    ic_stream_t stream, int channels, int fill_sym,
                                                    const int* layer_ends_host, int nlayers, const ic_pc_seg_t* segs_host) {
-    return pc_decode_tiles_segments(bitstreams, total_bytes, tiles_host, ntiles, volumes_host, nvolumes, wtab_host, centers, k, L, resolution,
-                                    symbols, q, status, C, workspace, workspace_bytes, flags, stream, channels, fill_sym,
-                                    layer_ends_host, nlayers, segs_host, IC_PC_DECODE_WAVEFRONT);
+    return pc_decode_tiles_segments(pc_tiles_request(PC_TILES_LAYERS, bitstreams, total_bytes, tiles_host, ntiles, volumes_host, nvolumes, wtab_host,
+                                                     centers, k, L, resolution, symbols, q, status, C, workspace, workspace_bytes, flags, stream),
+                                    channels, nullptr, nullptr, fill_sym, layer_ends_host, nlayers, segs_host, IC_PC_DECODE_WAVEFRONT);
 }
 
 extern "C" size_t ic_pc_decode_tiles_batch_fronts_pertile_workspace_bytes(int C, int th_max, int tw_max, int ntiles, int nvolumes, int k, int nlayers) {
-    return ic_pc_decode_tiles_batch_layers_pertile_workspace_bytes(C, th_max, tw_max, ntiles, nvolumes, k, nlayers);
+    return pc_tiles_workspace_bytes(C, th_max, tw_max, ntiles, nvolumes, k, nlayers, PC_TILES_PERTILE);
 }
 
 extern "C" int ic_pc_decode_tiles_batch_fronts_pertile_f32(const uint8_t* bitstreams, long long total_bytes, const ic_pc_tile_t* tiles_host, int ntiles,
@@ -1668,65 +1673,14 @@ extern "C" int ic_pc_decode_tiles_batch_fronts_pertile_f32(const uint8_t* bitstr
                                                            int* status, int C, void* workspace, size_t workspace_bytes, int flags,
                                                            ic_stream_t stream, const int* tile_channels_host, int fill_sym,
                                                            const int* layer_ends_host, int nlayers, const ic_pc_seg_t* segs_host) {
-    return pc_decode_tiles_segments_pertile(bitstreams, total_bytes, tiles_host, ntiles, volumes_host, nvolumes, wtab_host, centers, k, L,
-                                            resolution, symbols, q, status, C, workspace, workspace_bytes, flags, stream, tile_channels_host,
-                                            fill_sym, layer_ends_host, nlayers, segs_host, IC_PC_DECODE_WAVEFRONT);
+    return pc_decode_tiles_segments(pc_tiles_request(PC_TILES_PERTILE, bitstreams, total_bytes, tiles_host, ntiles, volumes_host, nvolumes, wtab_host,
+                                                     centers, k, L, resolution, symbols, q, status, C, workspace, workspace_bytes, flags, stream),
+                                    C, tile_channels_host, nullptr, fill_sym, layer_ends_host, nlayers, segs_host, IC_PC_DECODE_WAVEFRONT);
 }
 
 // ---- layered tiles, continued: every tile from the layer where an earlier call on the same workspace stopped --------------------
 extern "C" size_t ic_pc_decode_tiles_batch_layers_resume_workspace_bytes(int C, int th_max, int tw_max, int ntiles, int nvolumes, int k, int nlayers) {
-    const size_t base = ic_pc_decode_tiles_batch_layers_pertile_workspace_bytes(C, th_max, tw_max, ntiles, nvolumes, k, nlayers);
-    return base ? base + 2 * pc_dec_align((size_t)ntiles * sizeof(int)) : 0;       // from, done
-}
-
-// the symbol planes of the fronts resume entry: a byte per symbol of the largest tile, per tile
-static size_t pc_dec_planes_bytes(int C, int th_max, int tw_max, int ntiles) {
-    return (size_t)ntiles * pc_dec_align((size_t)C * th_max * tw_max);
-}
-
-// the two resume entries: one set of checks; `order` as in pc_decode_tiles_segments
-static int pc_decode_tiles_segments_resume(const uint8_t* bitstreams, long long total_bytes, const ic_pc_tile_t* tiles_host, int ntiles,
-                                           const ic_pc_volume_t* volumes_host, int nvolumes, const float* const* wtab_host,
-                                           const float* centers, int k, int L, float resolution, int64_t* symbols, float* q,
-                                           int* status, int C, void* workspace, size_t workspace_bytes, int flags,
-                                           ic_stream_t stream, const int* tile_from_layer_host, const int* tile_channels_host,
-                                           int fill_sym, const int* layer_ends_host, int nlayers, const ic_pc_seg_t* segs_host, int order) {
-    // everything about the six tables is decided here, on the host, before the first HIP call
-    IC_CHECK_ARG(bitstreams && tiles_host && volumes_host && wtab_host && centers && (symbols || q) && status && workspace);
-    IC_CHECK_ARG(tile_from_layer_host && tile_channels_host && layer_ends_host && segs_host);
-    IC_CHECK_ARG(total_bytes >= 0 && ntiles > 0 && nvolumes > 0 && C > 0 && k > 0 && L > 0);
-    IC_CHECK_ARG(fill_sym >= 0 && fill_sym < L);
-    IC_CHECK_ARG(nlayers >= 1 && nlayers <= 16);
-    IC_CHECK_ARG(layer_ends_host[0] >= 1 && layer_ends_host[nlayers - 1] == C);
-    for (int g = 1; g < nlayers; ++g) IC_CHECK_ARG(layer_ends_host[g] > layer_ends_host[g - 1]);
-    for (int n = 0; n < nvolumes; ++n) {
-        const ic_pc_volume_t& v = volumes_host[n];
-        IC_CHECK_ARG(v.h >= 1 && v.w >= 1 && v.symbols_off >= 0 && v.q_off >= 0);
-    }
-    int th_max = 0, tw_max = 0;
-    for (int t = 0; t < ntiles; ++t) {
-        ic_pc_tile_t d = tiles_host[t];
-        const int from = tile_from_layer_host[t], channels = tile_channels_host[t];
-        IC_CHECK_ARG(from >= 0 && from <= nlayers);       // (from == nlayers: the tile is whole, its limit can only be C)
-        const int cfrom = from ? layer_ends_host[from - 1] : 0;
-        IC_CHECK_ARG(channels >= 1 && channels <= C && cfrom <= channels);
-        IC_CHECK_ARG(d.volume >= 0 && d.volume < nvolumes);
-        d.stream_off = 0; d.stream_bytes = 0;             // not read: the segments stand for them
-        IC_CHECK_ARG(pc_tile_ok(d, volumes_host[d.volume].h, volumes_host[d.volume].w, total_bytes, L));
-        // the layers THIS call reads: from `from` on (segment 0 only for a tile that starts afresh), those that begin below the limit
-        for (int g = from; g < nlayers && (g == 0 || layer_ends_host[g - 1] < channels); ++g) {
-            const ic_pc_seg_t& sg = segs_host[(size_t)t * nlayers + g];
-            IC_CHECK_ARG(sg.off >= 0 && sg.nbytes >= 0 && sg.off <= total_bytes && sg.nbytes <= total_bytes - sg.off);
-        }
-        th_max = d.th > th_max ? d.th : th_max;
-        tw_max = d.tw > tw_max ? d.tw : tw_max;
-    }
-    if (L > 16 || k != 24 || flags != 0) return IC_ERR_UNSUPPORTED;
-    const size_t planes_off = ic_pc_decode_tiles_batch_layers_resume_workspace_bytes(C, th_max, tw_max, ntiles, nvolumes, k, nlayers);
-    if (workspace_bytes < planes_off + (order ? pc_dec_planes_bytes(C, th_max, tw_max, ntiles) : 0)) return IC_ERR_WORKSPACE;
-    return pc_decode_tiles_impl(bitstreams, tiles_host, ntiles, th_max, tw_max, volumes_host, nvolumes, wtab_host, centers, k, L,
-                                resolution, symbols, q, status, C, workspace, order, C, fill_sym, stream,
-                                layer_ends_host, nlayers, segs_host, tile_channels_host, tile_from_layer_host, planes_off);
+    return pc_tiles_workspace_bytes(C, th_max, tw_max, ntiles, nvolumes, k, nlayers, PC_TILES_LAYERS_RESUME);
 }
 
 extern "C" int ic_pc_decode_tiles_batch_layers_resume_f32(const uint8_t* bitstreams, long long total_bytes, const ic_pc_tile_t* tiles_host, int ntiles,
@@ -1735,15 +1689,14 @@ extern "C" int ic_pc_decode_tiles_batch_layers_resume_f32(const uint8_t* bitstre
                                                           int* status, int C, void* workspace, size_t workspace_bytes, int flags,
                                                           ic_stream_t stream, const int* tile_from_layer_host, const int* tile_channels_host,
                                                           int fill_sym, const int* layer_ends_host, int nlayers, const ic_pc_seg_t* segs_host) {
-    return pc_decode_tiles_segments_resume(bitstreams, total_bytes, tiles_host, ntiles, volumes_host, nvolumes, wtab_host, centers, k, L,
-                                           resolution, symbols, q, status, C, workspace, workspace_bytes, flags, stream, tile_from_layer_host,
-                                           tile_channels_host, fill_sym, layer_ends_host, nlayers, segs_host, 0);
+    return pc_decode_tiles_segments(pc_tiles_request(PC_TILES_LAYERS_RESUME, bitstreams, total_bytes, tiles_host, ntiles, volumes_host, nvolumes, wtab_host,
+                                                     centers, k, L, resolution, symbols, q, status, C, workspace, workspace_bytes, flags, stream),
+                                    C, tile_channels_host, tile_from_layer_host, fill_sym, layer_ends_host, nlayers, segs_host, 0);
 }
 
 // ---- front-layered tiles, continued: every tile's front sweep from the layer end where an earlier call on the same workspace stopped ---
 extern "C" size_t ic_pc_decode_tiles_batch_fronts_resume_workspace_bytes(int C, int th_max, int tw_max, int ntiles, int nvolumes, int k, int nlayers) {
-    const size_t base = ic_pc_decode_tiles_batch_layers_resume_workspace_bytes(C, th_max, tw_max, ntiles, nvolumes, k, nlayers);
-    return base ? base + pc_dec_planes_bytes(C, th_max, tw_max, ntiles) : 0;
+    return pc_tiles_workspace_bytes(C, th_max, tw_max, ntiles, nvolumes, k, nlayers, PC_TILES_FRONTS_RESUME);
 }
 
 extern "C" int ic_pc_decode_tiles_batch_fronts_resume_f32(const uint8_t* bitstreams, long long total_bytes, const ic_pc_tile_t* tiles_host, int ntiles,
@@ -1752,7 +1705,7 @@ extern "C" int ic_pc_decode_tiles_batch_fronts_resume_f32(const uint8_t* bitstre
                                                           int* status, int C, void* workspace, size_t workspace_bytes, int flags,
                                                           ic_stream_t stream, const int* tile_from_layer_host, const int* tile_channels_host,
                                                           int fill_sym, const int* layer_ends_host, int nlayers, const ic_pc_seg_t* segs_host) {
-    return pc_decode_tiles_segments_resume(bitstreams, total_bytes, tiles_host, ntiles, volumes_host, nvolumes, wtab_host, centers, k, L,
-                                           resolution, symbols, q, status, C, workspace, workspace_bytes, flags, stream, tile_from_layer_host,
-                                           tile_channels_host, fill_sym, layer_ends_host, nlayers, segs_host, IC_PC_DECODE_WAVEFRONT);
+    return pc_decode_tiles_segments(pc_tiles_request(PC_TILES_FRONTS_RESUME, bitstreams, total_bytes, tiles_host, ntiles, volumes_host, nvolumes, wtab_host,
+                                                     centers, k, L, resolution, symbols, q, status, C, workspace, workspace_bytes, flags, stream),
+                                    C, tile_channels_host, tile_from_layer_host, fill_sym, layer_ends_host, nlayers, segs_host, IC_PC_DECODE_WAVEFRONT);
 }

@@ -539,15 +539,14 @@ class PredictionNetwork(object):
         if len(streams) != len(grid) or len(first_syms) != len(grid):
             raise ValueError('{} streams and {} first symbols for a grid of {} tiles'.format(len(streams), len(first_syms), len(grid)))
         dev = self.centers.device
-        offs = np.concatenate([[0], np.cumsum([len(b) for b in streams])]).astype(np.int64)
-        table = _lib.tile_table([(y0, x0, a, b, offs[t], len(streams[t]), first_syms[t]) for t, (y0, x0, a, b) in enumerate(grid)])
-        data = torch.frombuffer(bytearray(b''.join(streams)) or bytearray(1), dtype=torch.uint8).to(dev)
+        table, _, blob, pos, _ = _tile_tables([(0, t, cell, first_syms[t], streams[t], None) for t, cell in enumerate(grid)])
+        data = torch.frombuffer(blob, dtype=torch.uint8).to(dev)
         out = torch.empty((C, h, w), dtype=torch.int64, device=dev)
         status = torch.zeros(len(grid), dtype=torch.int32, device=dev)
         need = lib.ic_pc_decode_tiles_workspace_bytes(C, min(th, h), min(tw, w), len(grid), self.pc._k)
         ws = torch.empty(need, dtype=torch.uint8, device=dev)
         centers = self.centers.contiguous().float()
-        check(lib.ic_pc_decode_tiles_f32(ptr(data), int(offs[-1]), table, len(grid), self.pc._tab, ptr(centers), self.pc._k, self.pc.L,
+        check(lib.ic_pc_decode_tiles_f32(ptr(data), pos, table, len(grid), self.pc._tab, ptr(centers), self.pc._k, self.pc.L,
                                          self.freqs_resolution, ptr(out), ptr(status), C, h, w, ptr(ws), need, int(flags),
                                          _lib.current_stream(dev)), 'ic_pc_decode_tiles_f32')
         for t, st in enumerate(status.tolist()):            # (the host waits here: the table and the streams are done with)
@@ -648,8 +647,8 @@ class PredictionNetwork(object):
         if layer_ends is not None:
             ends = check_layer_ends(layer_ends, C0)
             upto = C0 if channels is None else check_channels(channels, C0)
-            needed = [g for g in range(len(ends)) if g == 0 or ends[g - 1] < upto]     # the layers that begin below `channels`
-        shapes, grids, tiles, where, blobs, pos, missing, segs, limits = [], [], [], [], [], 0, [], [], []
+            needed = [g for g in range(len(ends)) if g == 0 or ends[g - 1] < upto]     # the layers that begin below `channels`: 0 .. len - 1
+        shapes, grids, listed, missing, limits = [], [], [], [], []
         if tile_layers is not None and len(tile_layers) != len(volumes):
             raise ValueError('tile_layers has {} entries for {} volumes'.format(len(tile_layers), len(volumes)))
         for n, (streams, first_syms, shape) in enumerate(volumes):
@@ -664,7 +663,7 @@ class PredictionNetwork(object):
             grids.append(grid)
             if tile_layers is not None and len(tile_layers[n]) != len(grid):
                 raise ValueError('volume {}: tile_layers has {} entries for a grid of {} tiles'.format(n, len(tile_layers[n]), len(grid)))
-            for t, (y0, x0, a, b) in enumerate(grid):
+            for t, cell in enumerate(grid):
                 if tile_layers is not None:
                     g_t = int(tile_layers[n][t])
                     if not 0 <= g_t <= len(ends):
@@ -674,37 +673,18 @@ class PredictionNetwork(object):
                         continue
                     if streams[t] is None or len(streams[t]) != len(ends) or any(streams[t][g] is None for g in range(g_t)):
                         raise ValueError('volume {}, tile {}: {} layers to read need the segments 0 .. {} of {}'.format(n, t, g_t, g_t - 1, len(ends)))
-                    tiles.append((y0, x0, a, b, 0, 0, first_syms[t], n))
-                    where.append((n, t, y0, x0))
+                    listed.append((n, t, cell, first_syms[t], streams[t], range(g_t)))
                     limits.append(ends[g_t - 1])
-                    for g in range(len(ends)):
-                        if g < g_t:
-                            segs.append((pos, len(streams[t][g])))
-                            blobs.append(bytes(streams[t][g]))
-                            pos += len(streams[t][g])
-                        else:
-                            segs.append((0, 0))
-                    continue
-                if streams[t] is None:
+                elif streams[t] is None:
                     missing.append((n, t))
-                    continue
-                if layer_ends is not None:
+                elif layer_ends is not None:
                     if len(streams[t]) != len(ends) or any(streams[t][g] is None for g in needed):
                         raise ValueError('volume {}, tile {}: {} layers need the segments {} of {}'.format(n, t, len(ends), needed, len(ends)))
-                    tiles.append((y0, x0, a, b, 0, 0, first_syms[t], n))
-                    where.append((n, t, y0, x0))
-                    for g in range(len(ends)):
-                        if g in needed:
-                            segs.append((pos, len(streams[t][g])))
-                            blobs.append(bytes(streams[t][g]))
-                            pos += len(streams[t][g])
-                        else:
-                            segs.append((0, 0))
-                    continue
-                tiles.append((y0, x0, a, b, pos, len(streams[t]), first_syms[t], n))
-                where.append((n, t, y0, x0))
-                blobs.append(bytes(streams[t]))
-                pos += len(streams[t])
+                    listed.append((n, t, cell, first_syms[t], streams[t], range(len(needed))))
+                else:
+                    listed.append((n, t, cell, first_syms[t], streams[t], None))
+        table, seg_table, blob, pos, where = _tile_tables(listed)
+        tiles = [cell for _, _, cell, _, _, _ in listed]
         C, k = shapes[0][0], self.pc._k
         preview = self._preview(channels, C)
         G = 0 if layer_ends is None else len(ends)
@@ -723,9 +703,8 @@ class PredictionNetwork(object):
                 return int(entry_ws(C, th_max, tw_max, ntiles, len(shapes), k, G))
             return int(lib.ic_pc_decode_tiles_batch_workspace_bytes(C, th_max, tw_max, ntiles, len(shapes), k))
 
-        chunks = chunk_tiles([(a, b) for _, _, a, b, _, _, _, _ in tiles], need, int(max_workspace_bytes))
-        table = _lib.tile_table(tiles)
-        data = torch.frombuffer(bytearray(b''.join(blobs)) or bytearray(1), dtype=torch.uint8).to(dev)
+        chunks = chunk_tiles([(a, b) for _, _, a, b in tiles], need, int(max_workspace_bytes))
+        data = torch.frombuffer(blob, dtype=torch.uint8).to(dev)
         alloc = torch.zeros if missing else torch.empty
         q = alloc(total, dtype=torch.float32, device=dev) if want in ('q', 'both') else None
         sym = alloc(total, dtype=torch.int64, device=dev) if want in ('symbols', 'both') or conceal or tile_layers is not None else None    # the rules read symbols
@@ -736,7 +715,7 @@ class PredictionNetwork(object):
             ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
         step = ctypes.sizeof(_lib.PcTile)
         if G:
-            seg_table, host_ends = _lib.seg_table(segs), (ctypes.c_int * G)(*ends)
+            host_ends = (ctypes.c_int * G)(*ends)
             layers = (C, self.conceal_fallback()) if preview is None else preview
             host_limits = (ctypes.c_int * max(len(limits), 1))(*limits)
         for a, b in chunks:
@@ -756,17 +735,8 @@ class PredictionNetwork(object):
                 check(lib.ic_pc_decode_tiles_batch_channels_f32(*(args + preview)), 'ic_pc_decode_tiles_batch_channels_f32')
         if tile_layers is not None:
             failed = set(where[i][:2] for i, st in enumerate(status.tolist()) if st != 0)      # (the host waits here, as below)
-            held, have = [], []
-            for n, grid in enumerate(grids):
-                row = [0 if (n, t) in failed or int(tile_layers[n][t]) == 0 else ends[int(tile_layers[n][t]) - 1] for t in range(len(grid))]
-                have.append(row)
-                held.append([(t, 0 if (n, t) in failed else int(tile_layers[n][t]), row[t], 'decoder' if (n, t) in failed else None)
-                             for t in range(len(grid)) if row[t] < C])
-            if any(held):
-                self._conceal_channels(sym, q, shapes, grids, vtable, have, th, tw, centers)
-            cut = lambda buf: [buf[o:o + c * h * w].view(c, h, w) for (c, h, w), o in zip(shapes, offs)]
-            res = cut(q) if want == 'q' else cut(sym) if want == 'symbols' else list(zip(cut(q), cut(sym)))
-            return res, held
+            held = self._conceal_held(sym, q, shapes, grids, vtable, tile_layers, failed, ends, th, tw, centers)
+            return _cut(q, sym, shapes, offs, want), held
         damage = [[] for _ in shapes]
         for n, t in missing:
             damage[n].append((t, 'missing'))
@@ -779,8 +749,7 @@ class PredictionNetwork(object):
         damage = [sorted(d) for d in damage]
         if conceal and any(damage):
             self._conceal(sym, q, shapes, grids, vtable, damage, th, tw, centers)
-        cut = lambda buf: [buf[o:o + c * h * w].view(c, h, w) for (c, h, w), o in zip(shapes, offs)]
-        res = cut(q) if want == 'q' else cut(sym) if want == 'symbols' else list(zip(cut(q), cut(sym)))
+        res = _cut(q, sym, shapes, offs, want)
         return (res, damage) if conceal else res
 
     def open_layers(self, volumes_geometry, th, tw, layer_ends=None, max_workspace_bytes=1 << 31, front_ends=None):
@@ -836,6 +805,21 @@ class PredictionNetwork(object):
                                                _lib.current_stream(dev)), 'ic_pc_conceal_tiles_channels')
         torch.cuda.current_stream(dev).synchronize()        # the three host tables and the workspace are done with
 
+    def _conceal_held(self, sym, q, shapes, grids, vtable, tile_layers, failed, ends, th, tw, centers):
+        """what decode_tiles_batch(tile_layers=...) and LayerSession.advance report: -> [per volume [(tile, layers_read, channels,
+        reason)] in tile order for the tiles that hold fewer than C channels]; a tile in `failed` = {(n, t)} holds nothing, reason
+        'decoder'.  If there is any such tile, _conceal_channels has filled what they do not hold."""
+        C = shapes[0][0]
+        held, have = [], []
+        for n, grid in enumerate(grids):
+            row = [0 if (n, t) in failed or int(tile_layers[n][t]) == 0 else ends[int(tile_layers[n][t]) - 1] for t in range(len(grid))]
+            have.append(row)
+            held.append([(t, 0 if (n, t) in failed else int(tile_layers[n][t]), row[t], 'decoder' if (n, t) in failed else None)
+                         for t in range(len(grid)) if row[t] < C])
+        if any(held):
+            self._conceal_channels(sym, q, shapes, grids, vtable, have, th, tw, centers)
+        return held
+
     def get_pr(self, input_ctx):
         """:param input_ctx: symbols of ONE context, CHW = input_ctx_shape -> (L,) float32."""
         assert tuple(input_ctx.shape) == tuple(self.input_ctx_shape), '{} != {}'.format(
@@ -849,6 +833,40 @@ class PredictionNetwork(object):
         f = self._tables(input_ctx)[1][0]
         assert np.all(f > 0), 'We do not want zero frequencies!: {}'.format(f)
         return f
+
+
+def _tile_tables(listed):
+    """The host tables of one decode over tiles.  listed: per tile (n, t, (y0, x0, a, b), first_sym, stream, None), or
+    (n, t, (y0, x0, a, b), first_sym, segments, layers) where `layers` is the range of the tile's segments to read.
+    -> (tile table, segment table, blob, its length, where): the blob is everything that is read, joined (one byte if that is nothing);
+    a stream's place in it stands in its tile's row; a tile of segments has zeros there and len(segments) rows of the segment table,
+    (0, 0) for those outside `layers`; where = [(n, t, y0, x0)] per row of the tile table."""
+    tiles, segs, blobs, pos, where = [], [], [], 0, []
+    for n, t, (y0, x0, a, b), first_sym, payload, layers in listed:
+        where.append((n, t, y0, x0))
+        if layers is None:
+            tiles.append((y0, x0, a, b, pos, len(payload), first_sym, n))
+            blobs.append(bytes(payload))
+            pos += len(payload)
+            continue
+        tiles.append((y0, x0, a, b, 0, 0, first_sym, n))
+        for g, seg in enumerate(payload):
+            if g in layers:
+                segs.append((pos, len(seg)))
+                blobs.append(bytes(seg))
+                pos += len(seg)
+            else:
+                segs.append((0, 0))
+    return _lib.tile_table(tiles), _lib.seg_table(segs), bytearray(b''.join(blobs)) or bytearray(1), pos, where
+
+
+def _cut(q, sym, shapes, offs, want, copy=False):
+    """the flat q / symbols of the volumes `shapes` at the element offsets `offs` -> per volume what `want` asks for, as (C,h,w)
+    views, or as copies"""
+    def cut(buf):
+        views = [buf[o:o + c * h * w].view(c, h, w) for (c, h, w), o in zip(shapes, offs)]
+        return [v.clone() for v in views] if copy else views
+    return cut(q) if want == 'q' else cut(sym) if want == 'symbols' else list(zip(cut(q), cut(sym)))
 
 
 # -- host-side helpers of the reference's NumPy branch (reference code/probclass.py:268-292,341-351,367-387) --
@@ -925,7 +943,7 @@ class LayerSession(object):
             if len(streams) != len(grid) or len(first_syms) != len(grid) or len(tile_layers[n]) != len(grid):
                 raise ValueError('volume {}: {} streams, {} first symbols and {} entries of tile_layers for a grid of {} tiles'.format(
                     n, len(streams), len(first_syms), len(tile_layers[n]), len(grid)))
-            for t, (y0, x0, a, b) in enumerate(grid):
+            for t, cell in enumerate(grid):
                 g_t = int(tile_layers[n][t])
                 if not 0 <= g_t <= G:
                     raise ValueError('volume {}, tile {}: {} layers to read of {}'.format(n, t, g_t, G))
@@ -933,7 +951,7 @@ class LayerSession(object):
                     continue
                 if streams[t] is None or len(streams[t]) != G or any(streams[t][g] is None for g in range(g_t)):
                     raise ValueError('volume {}, tile {}: {} layers to read need the segments 0 .. {} of {}'.format(n, t, g_t, g_t - 1, G))
-                listed.append((n, t, y0, x0, a, b, int(first_syms[t]), g_t, streams[t]))
+                listed.append((n, t, cell, int(first_syms[t]), streams[t], g_t))
         dev = pred.centers.device
         centers = pred.centers.contiguous().float()
         for n, grid in enumerate(self.grids):                                  # a tile that holds nothing now has no slot to continue in
@@ -942,49 +960,33 @@ class LayerSession(object):
                     self.done[n][t], self.place[n][t] = 0, None
         failed = set()
         if listed:
-            shape = (len(listed), max(v[4] for v in listed), max(v[5] for v in listed))
-            tiles, segs, blobs, pos, froms, limits = [], [], [], 0, [], []
-            for i, (n, t, y0, x0, a, b, first, g_t, streams) in enumerate(listed):
+            shape = (len(listed), max(cell[2] for _, _, cell, _, _, _ in listed), max(cell[3] for _, _, cell, _, _, _ in listed))
+            reads, froms, limits = [], [], []
+            for i, (n, t, cell, first, streams, g_t) in enumerate(listed):
                 have = self.done[n][t] if self.place[n][t] == (i, shape) else 0
                 g_from, channels = resume_plan(have, g_t, ends)
-                tiles.append((y0, x0, a, b, 0, 0, first, n))
+                reads.append((n, t, cell, first, streams, range(g_from, g_t)))
                 froms.append(g_from)
                 limits.append(channels)
-                for g in range(G):
-                    if g_from <= g < g_t:
-                        segs.append((pos, len(streams[g])))
-                        blobs.append(bytes(streams[g]))
-                        pos += len(streams[g])
-                    else:
-                        segs.append((0, 0))
             need = self._need(shape[1], shape[2], shape[0])
             assert need <= self.ws.numel()
-            table, seg_table = _lib.tile_table(tiles), _lib.seg_table(segs)
+            table, seg_table, blob, pos, _ = _tile_tables(reads)
             host_ends, host_from, host_limits = (ctypes.c_int * G)(*ends), (ctypes.c_int * len(froms))(*froms), (ctypes.c_int * len(limits))(*limits)
-            data = torch.frombuffer(bytearray(b''.join(blobs)) or bytearray(1), dtype=torch.uint8).to(dev)
-            status = torch.zeros(len(tiles), dtype=torch.int32, device=dev)
+            data = torch.frombuffer(blob, dtype=torch.uint8).to(dev)
+            status = torch.zeros(len(reads), dtype=torch.int32, device=dev)
             check(getattr(lib, self.entry)(
-                ptr(data), pos, table, len(tiles), self.vtable, len(self.shapes), pred.pc._tab, ptr(centers), pred.pc._k, pred.pc.L,
+                ptr(data), pos, table, len(reads), self.vtable, len(self.shapes), pred.pc._tab, ptr(centers), pred.pc._k, pred.pc.L,
                 pred.freqs_resolution, ptr(self.sym), ptr(self.q), ptr(status), C, ptr(self.ws), need, 0, _lib.current_stream(dev),
                 host_from, host_limits, pred.conceal_fallback(), host_ends, G, seg_table), self.entry)
             self.launches += 1
-            for (n, t, _, _, _, _, _, g_t, _), i, st in zip(listed, range(len(listed)), status.tolist()):      # (the host waits here)
+            for (n, t, _, _, _, g_t), i, st in zip(listed, range(len(listed)), status.tolist()):      # (the host waits here)
                 if st != 0:
                     failed.add((n, t))
                     self.done[n][t], self.place[n][t] = 0, None
                 else:
                     self.done[n][t], self.place[n][t] = g_t, (i, shape)
-        held, have = [], []
-        for n, grid in enumerate(self.grids):
-            row = [0 if (n, t) in failed or int(tile_layers[n][t]) == 0 else ends[int(tile_layers[n][t]) - 1] for t in range(len(grid))]
-            have.append(row)
-            held.append([(t, 0 if (n, t) in failed else int(tile_layers[n][t]), row[t], 'decoder' if (n, t) in failed else None)
-                         for t in range(len(grid)) if row[t] < C])
-        if any(held):
-            pred._conceal_channels(self.sym, self.q, self.shapes, self.grids, self.vtable, have, self.th, self.tw, centers)
-        cut = lambda buf: [buf[o:o + c * h * w].view(c, h, w).clone() for (c, h, w), o in zip(self.shapes, self.offs)]
-        res = cut(self.q) if want == 'q' else cut(self.sym) if want == 'symbols' else list(zip(cut(self.q), cut(self.sym)))
-        return res, held
+        held = pred._conceal_held(self.sym, self.q, self.shapes, self.grids, self.vtable, tile_layers, failed, ends, self.th, self.tw, centers)
+        return _cut(self.q, self.sym, self.shapes, self.offs, want, copy=True), held
 
 
 def pad_for_probclass3d(x, context_size, pad_value=0, learn_pad_var=False):

@@ -273,6 +273,21 @@ PINNED_WORKSPACE_BYTES = {
     (1, 1, 1, 1, 1, 64): (704768, 708864, 709376, 709632),
 }
 
+# (C, th, tw, ntiles, nvolumes, k, nlayers) -> ic_pc_decode_tiles_batch_<kind>_workspace_bytes of these kinds, in this order; recorded
+# from the library while every size function was a sum of its own, before one layout stood behind all of them
+SEGMENTED_KINDS = ('layers', 'layers_pertile', 'fronts', 'fronts_pertile', 'layers_resume', 'fronts_resume')
+PINNED_SEGMENTED_WORKSPACE_BYTES = {
+    (4, 3, 5, 2, 2, 24, 1): (306528, 306784, 306528, 306784, 307296, 307808),
+    (4, 3, 5, 2, 2, 24, 4): (306528, 306784, 306528, 306784, 307296, 307808),
+    (4, 3, 5, 2, 2, 24, 16): (306784, 307040, 306784, 307040, 307552, 308064),
+    (32, 16, 16, 24, 8, 24, 1): (96997376, 96997632, 96997376, 96997632, 96998144, 97194752),
+    (32, 16, 16, 24, 8, 24, 4): (96998400, 96998656, 96998400, 96998656, 96999168, 97195776),
+    (32, 16, 16, 24, 8, 24, 16): (97003008, 97003264, 97003008, 97003264, 97003776, 97200384),
+    (1, 1, 1, 1, 1, 24, 1): (211808, 212064, 211808, 212064, 212576, 212832),
+    (1, 1, 1, 1, 1, 24, 4): (211808, 212064, 211808, 212064, 212576, 212832),
+    (1, 1, 1, 1, 1, 24, 16): (211808, 212064, 211808, 212064, 212576, 212832),
+}
+
 
 def test_workspace_bytes_pinned():
     """the workspace sizes are ABI: callers allocate by them and the entries lay their workspace out by them, so they are what
@@ -284,3 +299,11 @@ def test_workspace_bytes_pinned():
                lib.ic_pc_decode_tiles_workspace_bytes(C, th, tw, ntiles, k),
                lib.ic_pc_decode_tiles_batch_workspace_bytes(C, th, tw, ntiles, nvolumes, k))
         assert got == want, ((C, th, tw, ntiles, nvolumes, k), got, want)
+    for (C, th, tw, ntiles, nvolumes, k, nlayers), want in PINNED_SEGMENTED_WORKSPACE_BYTES.items():
+        got = tuple(getattr(lib, 'ic_pc_decode_tiles_batch_{}_workspace_bytes'.format(kind))(C, th, tw, ntiles, nvolumes, k, nlayers)
+                    for kind in SEGMENTED_KINDS)
+        assert got == want, ((C, th, tw, ntiles, nvolumes, k, nlayers), got, want)
+        for none in (0, 17):                                 # no such number of layers: no size
+            got = tuple(getattr(lib, 'ic_pc_decode_tiles_batch_{}_workspace_bytes'.format(kind))(C, th, tw, ntiles, nvolumes, k, none)
+                        for kind in SEGMENTED_KINDS)
+            assert got == (0,) * len(SEGMENTED_KINDS), ((C, th, tw, ntiles, nvolumes, k, none), got)
