@@ -226,8 +226,17 @@ static int ae_encode(const float* x, const void* const* tab, int B, int C, int L
     // to_bn: 128 -> C(+1), 5x5 / 2, BN, linear
     const float* const* tb = t + 6 + 3 * nconv;
     const int Cb = C + (heatmap_on ? 1 : 0);
-    if ((rc = ic_conv2d_mfma_bn_act_f32(bufs[o], tb[0], tb[1], tb[2], bott, N, 128, H / 4, W / 4, Cb, 5, 5, 2, 0, 0, st)))
-        return rc;
+    if (ic_conv2d_mfma_packed_floats(5, 5, 128, Cb, 2, 0)) {
+        if ((rc = ic_conv2d_mfma_bn_act_f32(bufs[o], tb[0], tb[1], tb[2], bott, N, 128, H / 4, W / 4, Cb, 5, 5, 2, 0, 0, st)))
+            return rc;
+    } else {
+        // more channels than the matrix-core form packs (Cb > 128, e.g. ae_configs/base: 193): the table holds the filter as it
+        // is, [5][5][128][Cb], and the generic kernel runs it -- inference accepts what the training graph accepts
+        ConvArgs b{};
+        b.x = bufs[o]; b.w = tb[0]; b.scale = tb[1]; b.shift = tb[2]; b.y = bott;
+        b.N = N; b.Cin = 128; b.H = H / 4; b.W = W / 4; b.Cout = Cb; b.KH = 5; b.KW = 5; b.stride = 2; b.relu = 0;
+        if ((rc = icx_conv2d(b, false, st))) return rc;
+    }
     const float* centers = tb[3];
     if (bottleneck_out) {
         hipError_t e = hipMemcpyAsync(bottleneck_out, bott, (size_t)N * Cb * (H / 8) * (W / 8) * sizeof(float), hipMemcpyDeviceToDevice, st);

@@ -567,6 +567,9 @@ int ic_mean_rows_f32(const float* v, int rows, long long count, float denom, flo
  *   h1, h2, 32 residual convs (res_block_enc_0/enc_0_1/conv1 ... res_block_enc_final/conv2),
  *   to_bn; then centers.  Count = 3*35 + 1 = 106.  The 32 residual filters are PACKED with
  *   ic_pack_conv3x3_c128_f32, h2 and to_bn with ic_pack_conv2d_mfma_f32; h1 is TF layout.
+ *   to_bn has C + heatmap_on output channels: where ic_conv2d_mfma_packed_floats(5, 5, 128, that, 2, 0) is 0 (more than
+ *   128, e.g. ae_configs/base: 193) its filter stays in TF layout [5,5,128,C + heatmap_on] and the generic kernel runs it.
+ *   In general there are 6 B + 2 residual convs per side (the counts above are B = 5's).
  * dec_tab_host: from_bn, 32 residual convs, h12, h13 -> 3*35 = 105 pointers (from_bn and h13 filters in TF
  *   conv2d_transpose layout, residual filters packed, h12 packed with ic_pack_conv2d_mfma_f32).
  * B = arch_param_B (5).  C = num_chan_bn.  x: (N,3,H,W) float 0..255, H and W multiples of 8.

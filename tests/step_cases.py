@@ -20,6 +20,10 @@ All: cvpr/med + res_shallow, H_target = 0.5 (the rate term active), synthetic we
   ragged  2x3x48x128   mse          12 x 32    2 x 8, 3 tile rows in 2-row segments
   msssim  3x3x64x64    ms_ssim      16 x 16    2 x 8, half full (the HIP MS-SSIM distortion; W <= H as its plan asks at this size)
 One image seed per case: seed 1 for all three (admitted by test_cpu_step_cases.test_fp32_oracle_meets_float64_at_forced_decisions).
+
+A case may carry overrides of the autoencoder config (tests/config_cases.py: other B, C, L, no importance map, normalization = OFF);
+the helpers below take the case for everything that depends on them -- the variables, the centres, and the counts of gradients, ReLU
+layers and residual layers (219 / 34 / 64 for the table above).
 """
 import functools
 from collections import OrderedDict, namedtuple
@@ -33,7 +37,8 @@ GTOL = 2e-4                       # every gradient of a small step, relative to 
 MAX_DIFFERING = 1e-5              # share of all decisions that may differ from the float64 oracle's own (CPU runs: <= 2 of 3.6 M)
 WINO4_MODES = (False, 'fwd', 'bwd', True)
 
-Case = namedtuple('Case', 'id shape distortion seed maps segments modes')
+# overrides: ((key, value), ...) set on the autoencoder config after cvpr/med is parsed (tests/config_cases.py); empty for the table below
+Case = namedtuple('Case', 'id shape distortion seed maps segments modes overrides', defaults=((),))
 
 CASES = (
     Case('wide', (2, 3, 32, 160), 'mse', 1, (8, 40), '1x16', WINO4_MODES),
@@ -76,18 +81,69 @@ def configs(case):
     pc, _ = cp.parse(cp.builtin_config_path('pc_configs', 'cvpr', 'res_shallow'))
     ae.distortion_to_minimize = case.distortion
     ae.H_target = 0.5
+    for key, value in case.overrides:
+        setattr(ae, key, value)
     return ae, pc
 
 
+def fold_fixed_normalization(w):
+    """normalization = OFF: the plain synthetic variables are degenerate on 0 .. 255 input (nearly all symbols in one bin, x_out
+    far below the image), so the FIXED normalisation is folded into the edge layers IN PLACE -- with m, s the means of the three
+    channel means and standard deviations of oracle.norm_consts:  h1: weights /= s, moving_mean += (m / s) sum_{ky,kx,ci} w;
+    h13: gamma *= s, beta = beta s + m.  (Exact for an interior pixel of a grey image; it only shapes the synthetic statistics.)"""
+    from oracle import oracle as O
+    mean, std = O.norm_consts(torch.float64)
+    m, s = float(mean.mean()), float(std.mean())
+    h1, h13 = 'autoencoder/encoder/h1', 'autoencoder/decoder/h13'
+    k = np.asarray(w[h1 + '/weights'], np.float64)
+    w[h1 + '/weights'] = (k / s).astype(np.float32)
+    w[h1 + '/BatchNorm/moving_mean'] = (np.asarray(w[h1 + '/BatchNorm/moving_mean'], np.float64) + (m / s) * k.sum(axis=(0, 1, 2))).astype(np.float32)
+    w[h13 + '/BatchNorm/gamma'] = (np.asarray(w[h13 + '/BatchNorm/gamma'], np.float64) * s).astype(np.float32)
+    w[h13 + '/BatchNorm/beta'] = (np.asarray(w[h13 + '/BatchNorm/beta'], np.float64) * s + m).astype(np.float32)
+    return w
+
+
 @functools.lru_cache(maxsize=None)
-def weights():
-    """the synthetic variables (they do not depend on the distortion or H_target; shared, read-only)"""
+def _weights_for(overrides):
     from imgcomp_cvpr_amd import weights as W
-    return W.synthetic_weights(*configs(CASES[0]))
+    ae, pc = configs(CASES[0]._replace(overrides=overrides))
+    w = W.synthetic_weights(ae, pc)
+    return fold_fixed_normalization(w) if ae.normalization == 'OFF' else w
 
 
-def centers():
-    return np.asarray(weights()['autoencoder/encoder/centers'], np.float64)
+def weights(case=None):
+    """the synthetic variables of the case's configuration, the fixed normalisation folded in where the case switches it OFF (they
+    do not depend on the distortion or H_target: one set per set of overrides; shared, read-only).  None: the table's own."""
+    return _weights_for(case.overrides if case is not None else ())
+
+
+def centers(case=None):
+    return np.asarray(weights(case)['autoencoder/encoder/centers'], np.float64)
+
+
+# ---- what a step of a configuration holds, from B, the importance map and the parameter list ----------------------------------------
+
+def relu_layers(case):
+    """layers whose ReLU sign is a decision: h1, h2, from_bn, h12 and conv1 of the 3 B residual blocks per side (not the final blocks')"""
+    return 4 + 6 * int(configs(case)[0].arch_param_B)
+
+
+def residual_layers(case):
+    """3x3 128 -> 128 layers: (6 B + 2) per side"""
+    return 2 * (6 * int(configs(case)[0].arch_param_B) + 2)
+
+
+def gradients(case):
+    """trainable variables = the parameter list without BatchNorm's moving statistics; restated from the layer count: {filter,
+    gamma, beta} of the residual layers and the six edge layers, the centres, {filter, bias} of the context model's four layers"""
+    n = sum(1 for name in weights(case) if 'moving_' not in name)
+    assert n == 3 * (residual_layers(case) + 6) + 1 + 2 * 4, n
+    return n
+
+
+def decision_kinds(case):
+    hm = {'heatmap_low', 'heatmap_high'} if bool(configs(case)[0].heatmap) else set()
+    return {'symbols', 'relu', 'x_out_low', 'x_out_high'} | hm
 
 
 def image(case, seed=None):
@@ -102,7 +158,7 @@ def oracle(case, dtype=torch.float64, decisions=None, seed=None):
     from oracle import train_oracle as T
     torch.set_num_threads(16)
     ae, pc = configs(case)
-    total, comps, p = T.train_loss(image(case, seed), weights(), ae.as_dict(), pc.as_dict(), dtype, decisions=decisions)
+    total, comps, p = T.train_loss(image(case, seed), weights(case), ae.as_dict(), pc.as_dict(), dtype, decisions=decisions)
     total.backward()
     comps = {k: (v.detach() if torch.is_tensor(v) else v) for k, v in comps.items()}
     return total.detach(), comps, OrderedDict((n, t.grad) for n, t in p.items() if t.grad is not None)
@@ -167,9 +223,9 @@ def _max_abs(a, b):
     return float((a.double() - b.double()).abs().max())
 
 
-def in_band(side, ref):
-    """side: the decisions under test; ref: the comps of the UNFORCED float64 oracle.  Every decision of `side` that differs from the
-    oracle's own must sit inside the rounding band of its threshold:
+def in_band(side, ref, case=None):
+    """side: the decisions under test; ref: the comps of the UNFORCED float64 oracle; case: whose centres (None: the table's).
+    Every decision of `side` that differs from the oracle's own must sit inside the rounding band of its threshold:
       ReLU sign     |pre64| <= 2 max|y_side - relu(pre64)| over its layer
       symbol        the rule of tests/test_gpu_network.py: no flip where _boundary_margin(z64) > 2 max|z_side - z64| + 1e-12
       heatmap clip  |u64 - 0| resp. |u64 - 1| <= 2 max|heatmap_side - heatmap64|        (u64 = sigmoid(.) C - c before the clip)
@@ -187,7 +243,7 @@ def in_band(side, ref):
         counts['total'] += diff.numel()
         counts['out_of_band'] += int((diff & (pre.abs() > band)).sum())
     flips = (d['symbols'] != r['symbols']).numpy()
-    margin = _boundary_margin(ref['z'].double().numpy(), centers())
+    margin = _boundary_margin(ref['z'].double().numpy(), centers(case))
     counts['symbols'] = int(flips.sum())
     counts['total'] += flips.size
     counts['out_of_band'] += int(np.sum(flips & (margin > 2 * _max_abs(side['z'], ref['z']) + 1e-12)))

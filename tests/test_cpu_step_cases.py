@@ -15,12 +15,12 @@ def test_forcing_the_oracles_own_decisions_changes_nothing(case):
     """train_loss(decisions = its own decisions) reproduces the unforced total and every gradient to 1e-12 of the tensor scale (only
     the operation order of y * mask against relu, and of the clips, differs); forcing a part of them does too."""
     total, comps, grads = S.unforced(case)
-    assert set(comps['decisions']) == {'symbols', 'relu', 'heatmap_low', 'heatmap_high', 'x_out_low', 'x_out_high'}
-    assert len(comps['decisions']['relu']) == len(comps['relu_pre']) == 2 + 15 + 1 + 15 + 1
+    assert set(comps['decisions']) == S.decision_kinds(case) == {'symbols', 'relu', 'heatmap_low', 'heatmap_high', 'x_out_low', 'x_out_high'}
+    assert len(comps['decisions']['relu']) == len(comps['relu_pre']) == S.relu_layers(case) == 2 + 15 + 1 + 15 + 1
     for dec in (comps['decisions'], {'relu': comps['decisions']['relu']}, {'symbols': comps['symbols'], 'x_out_high': comps['decisions']['x_out_high']}):
         total_f, comps_f, grads_f = S.oracle(case, decisions=dec)
         assert abs(float(total_f) - float(total)) <= 1e-12 * max(1.0, abs(float(total)))
-        assert len(grads_f) == len(grads) == 219
+        assert len(grads_f) == len(grads) == S.gradients(case) == 219
         name, err = S.worst_gradient_error(grads_f, grads)
         assert err <= 1e-12, (name, err)
         assert torch.equal(comps_f['symbols'], comps['symbols']) and rel_err(comps_f['x_out'], comps['x_out']) <= 1e-12
@@ -107,6 +107,9 @@ def test_table_reaches_what_it_claims():
     assert 2 * m.shape[0] * 16 == 8 * S.workgroups(m.shape[0], *m.maps) and m.shape[3] <= m.shape[2]
     assert not S.half_full(1, 4, 4) and S.segments(8, 128) == ('1x16', 4)
     assert {c.seed for c in S.CASES} == {1}
+    # the existing cases carry no overrides, and the counts derived from B, the importance map and the parameter list are theirs
+    for c in S.CASES:
+        assert c.overrides == () and (S.gradients(c), S.relu_layers(c), S.residual_layers(c)) == (219, 34, 64)
 
 
 def test_table_geometry_by_the_library_queries():

@@ -1,5 +1,5 @@
 """-m gpu: one whole training step per case and F(4x4) mode of tests/step_cases.py against the float64 oracle WITH THE DEVICE'S
-DISCRETE DECISIONS FORCED (oracle.train_oracle.train_loss(decisions=...)): every one of the 219 gradients at GTOL = 2e-4 on maps
+DISCRETE DECISIONS FORCED (oracle.train_oracle.train_loss(decisions=...)): every one of the gradients (219 here) at GTOL = 2e-4 on maps
 larger than 8 x 8, on the shipped path of the 3x3 layers (F(4x4) forward with the BatchNorm sums in its epilogue, F(4x4) data
 gradient; TrainGraph.WINO4_MIN_WORKGROUPS lowered on the instance) and on the F(2x2) path, with every decision that differs from the
 oracle's own checked to sit inside the rounding band of its threshold.  tests/step_cases.py says why.
@@ -23,7 +23,7 @@ def _run(cuda, case, mode):
     if key not in _RUNS:
         from imgcomp_cvpr_amd import training
         ae, pc = S.configs(case)
-        g = training.TrainGraph(ae, pc, S.weights(), cuda, wino4=mode)
+        g = training.TrainGraph(ae, pc, S.weights(case), cuda, wino4=mode)
         if mode is not False:
             g.WINO4_MIN_WORKGROUPS = 1               # on the instance: the class default stays 160
         x = dev(S.image(case), cuda)
@@ -38,24 +38,27 @@ def _run(cuda, case, mode):
     return _RUNS[key]
 
 
-@pytest.mark.parametrize('case,mode', S.CASE_MODES, ids=[S.case_mode_id(cm) for cm in S.CASE_MODES])
-def test_step_matches_oracle_at_the_devices_decisions(cuda, case, mode):
+def check_step(cuda, case, mode):
+    """the whole comparison of one case and mode (tests/test_gpu_config_space.py runs its own cases through it, unchanged); the
+    counts of gradients, ReLU layers and residual layers come from the case's configuration (S.gradients / relu_layers /
+    residual_layers)"""
     label = 'step {} wino4={}'.format(case.id, mode)
     run = _run(cuda, case, mode)
     out, side = run['out'], run['side']
-    # 1. the path taken
+    n_grads, n_relu, n_res = S.gradients(case), S.relu_layers(case), S.residual_layers(case)
+    # 1. the path taken (every case's maps pass TrainGraph's half-full rule: tests/test_cpu_step_cases.py, test_cpu_config_cases.py)
     assert run['f4'] == (mode in (True, 'fwd'), mode in (True, 'bwd')) and run['class_default'] == 160
-    assert run['served'] == (64 if run['f4'][0] else 0), 'conv + BatchNorm sums served {} of the 64 residual 3x3 layers'.format(run['served'])
+    assert run['served'] == (n_res if run['f4'][0] else 0), 'conv + BatchNorm sums served {} of the {} residual 3x3 layers'.format(run['served'], n_res)
     # 2. forward, against the unforced float64 oracle
     _, ref, _ = S.unforced(case)
     assert_close(side['z'], ref['z'], label + ': z', 1e-4)
     assert_close(side['bc'], ref['bc'], label + ': bit cost', 1e-4)
     assert_close(side['x_out'], ref['x_out'], label + ': x_out', 1e-4)
-    assert list(side['relu_out']) == list(ref['relu_pre']) and len(side['relu_out']) == 34
+    assert list(side['relu_out']) == list(ref['relu_pre']) and len(side['relu_out']) == n_relu
     scope = max(side['relu_out'], key=lambda s: rel_err(side['relu_out'][s], torch.relu(ref['relu_pre'][s])))
     assert_close(side['relu_out'][scope], torch.relu(ref['relu_pre'][scope]), label + ': worst post-ReLU layer output', 1e-4)
     # 3. decisions: every difference inside the rounding band of its threshold, and few
-    counts = S.in_band(side, ref)
+    counts = S.in_band(side, ref, case)
     print('{}: decisions {}'.format(label, dict(counts)))
     util.REPORT.append(('{}: differing decisions relu {} hm {} x_out {}'.format(label, counts['relu'], counts['heatmap'], counts['x_out']),
                         counts['differing'], counts['differing'] / counts['total'], S.MAX_DIFFERING))
@@ -65,7 +68,7 @@ def test_step_matches_oracle_at_the_devices_decisions(cuda, case, mode):
     # 4. gradients and scalars, against the float64 oracle at the device's decisions
     _, forced, grads = S.oracle(case, decisions=side['decisions'])
     assert torch.equal(forced['symbols'], side['decisions']['symbols'])          # the symbols the forced evaluation used
-    assert set(grads) == set(run['grads']) and len(grads) == 219
+    assert set(grads) == set(run['grads']) and len(grads) == n_grads
     print('{}: worst gradient {}; against the UNFORCED oracle (not asserted: what the differing decisions alone move) {}'.format(
         label, S.worst_gradient_error(run['grads'], grads), S.worst_gradient_error(run['grads'], S.unforced(case)[2])))
     for name, ref_grad in grads.items():
@@ -78,6 +81,12 @@ def test_step_matches_oracle_at_the_devices_decisions(cuda, case, mode):
     if case.distortion == 'ms_ssim':
         K = float(S.configs(case)[0].K_ms_ssim)
         assert abs(out['ms_ssim'] - (1.0 - float(forced['d_loss_scaled']) / K)) <= 2e-4
+
+
+@pytest.mark.parametrize('case,mode', S.CASE_MODES, ids=[S.case_mode_id(cm) for cm in S.CASE_MODES])
+def test_step_matches_oracle_at_the_devices_decisions(cuda, case, mode):
+    assert (S.gradients(case), S.relu_layers(case), S.residual_layers(case)) == (219, 34, 64)          # cvpr/med: B = 5
+    check_step(cuda, case, mode)
 
 
 def test_wide_forward_does_not_depend_on_the_backward_mode(cuda):
