@@ -3,7 +3,8 @@
     python -m imgcomp_cvpr_amd.codec compress   IN.png  OUT.icf [--ae_config cvpr/low] [--pc_config cvpr/res_shallow] [--weights synthetic|FILE.npz|CKPT]
                                                                 [--tile PIXELS [--checked | --wavefront | --layers a,b,.. | --progressive |
                                                                                 --front-layers a,b,.. | --front-progressive]]
-                                                                [--cap T | --max-bytes N | --bpp B] [--roi X,Y,W,H ... [--background T]]
+                                                                [--cap T | --max-bytes N | --bpp B | --min-psnr D | --min-ms-ssim S]
+                                                                [--roi X,Y,W,H ... [--background T]]
     python -m imgcomp_cvpr_amd.codec decompress IN.icf  OUT.png [same options] [--salvage | --channels K | --partial | --recover]
     python -m imgcomp_cvpr_amd.codec decompress IN.icf  OUT.png [same options] --region X,Y,W,H [--channels K]    a rectangle, from the tiles it needs
     python -m imgcomp_cvpr_amd.codec info PATH [PATH ...] [--region X,Y,W,H]    what the files hold and what a region would decode, without model or device
@@ -14,7 +15,11 @@
     python -m imgcomp_cvpr_amd.codec stream IN.icf OUT_DIR --fronts [model options] [--chunk BYTES]    the same for a format-6 or a format-8 file
     python -m imgcomp_cvpr_amd.codec transcode IN.icf OUT.icf [model options] [--tile PIXELS [the choices of compress]]
                                                               [--cap K | --max-bytes N | --bpp B] [--roi X,Y,W,H ... [--background K]] [--salvage | --recover]
+                                                              [--min-psnr D | --min-ms-ssim S]    against the picture IN.icf decodes to
     python -m imgcomp_cvpr_amd.codec transcode-dir IN_DIR OUT_DIR [the same, without --roi] [--batch N]     every *.icf -> OUT_DIR/<stem>.icf
+    python -m imgcomp_cvpr_amd.codec measure IN.png IN.icf [model options] [--channels K] [--region X,Y,W,H]    bytes, bpp, PSNR, MS-SSIM of the file
+    python -m imgcomp_cvpr_amd.codec rd IN.png OUT.json [model options] [--tile PIXELS [the choices of compress]] [--levels N] [--roi X,Y,W,H ...]
+                                                              the rate-distortion table of the cap levels k C / N as JSON, a line per level
 
 compress:   pad to a multiple of the subsampling factor (val.add_padding) -> ae.encode -> PredictionNetwork.encode_stream (the
             range coder on the device, ic_pc_encode_f32) -> container.
@@ -159,9 +164,21 @@ decompress bit for bit; where the picture runs F(4x4) kernels the window is wide
 from about twice as far), and where the forms cannot be had on the window the whole picture is decoded and cropped.  The whole file is
 parsed and checked whatever the rectangle.  No new format, entry point or kernel: the launches above over fewer tiles and a smaller
 map.  info prints region_plan for a file on the host.
+measure / rd / --min-psnr / --min-ms-ssim (Codec.measure, rd_curve, compress_to_quality, transcode_to_quality; quality_search): the other
+axis of the rate knobs.  measure decodes a file, leaves the picture on the device and puts it and the uploaded original through
+metrics.val_metrics_device (float64, the operations of the NumPy code val.py reports) -> Measure(bytes, bpp, mse, psnr, ms_ssim), of the
+whole picture or of a rectangle.  rd_curve runs the encoder once, requantises its bottleneck 16 levels a launch, codes every level to a
+real file and decodes every level by a batch-1 pass of its own (the kernel form of a layer depends on the batch size; the pixels must be
+decompress's), so row i is measure(img, compress(img, cap=level_i)) in every field.  compress_to_quality searches cap_levels for the
+smallest level whose picture reaches a PSNR or an MS-SSIM; a probe is a requantisation, a decode and a metrics call, nothing is
+entropy-coded until the level is found.  Quality need not be monotone in the level (under untrained weights it is not), so
+quality_search -- budget_search on the mirrored index -- establishes both halves of its contract by calls: the level meets the target,
+the next one down does not.  transcode_to_quality does the same for a file over the integer levels 0 .. C against the picture the file
+decodes to now, without the encoder.  No new kernel, entry point or format.  With synthetic weights the numbers mean nothing.
 """
 import argparse
 import io
+import json
 import os
 import re
 import struct
@@ -432,6 +449,112 @@ def budget_search(fits, estimate_index, steps=CAP_STEPS):
         else:
             hi = mid
     return lo, probes[0]
+
+
+def quality_search(meets, steps=CAP_STEPS):
+    """the smallest-level search behind a quality target, over the indices 0 .. steps: budget_search run on the mirrored index.
+    meets(k) -> bool is one decoded and measured picture at level k.  -> (k, probes) with meets(k) true and k == 0 or meets(k - 1)
+    false, BOTH established by calls of meets: quality need not be monotone in the level (under untrained weights it is not), so the
+    bisection keeps not meets(lo) and meets(hi) and ends on an adjacent pair whatever lies between.  Order: 0 (returned if it
+    meets); steps and, if it meets, steps - 1; then bisection of what remains -- at most 1 + 2 + ceil(log2 steps) calls, none
+    repeated (budget_search's 1 + 2 + 1 + ceil(log2 steps) with the estimate at the top, which saves its fourth call).  A ValueError
+    if meets(steps) is false: the file without a cap misses the target."""
+    steps = int(steps)
+    if steps < 1:
+        raise ValueError('quality search: {} steps, at least 1 is needed'.format(steps))
+    seen = {}
+
+    def fits(j):
+        seen[steps - j] = bool(meets(steps - j))
+        return seen[steps - j]
+
+    try:
+        j, probes = budget_search(fits, 0, steps=steps)
+    except ValueError:
+        if seen.get(steps) is not False:                             # (the error is meets's own)
+            raise
+        raise ValueError('no level meets the target: the top level, {}, does not'.format(steps))
+    return steps - j, probes
+
+
+Measure = namedtuple('Measure', ['bytes', 'bpp', 'mse', 'psnr', 'ms_ssim'])
+MIN_MEASURE_SIDE = 16                                                # 2^4: one whole pixel at the last of MS-SSIM's five scales
+
+
+def measure_from_values(values, nbytes, pixels):
+    """the six float64 values of metrics.val_metrics_device (the five scale terms of MS-SSIM, then the mean squared error) and a
+    file of nbytes bytes for `pixels` pixels -> Measure.  psnr = metrics.psnr_from_mse(mse); ms_ssim = metrics.msssim_from_scale_values,
+    but nan where a scale term is negative (or nan), as the NumPy code's fractional power gives it -- the Python-float helper would
+    return a complex number there."""
+    from . import metrics
+    vals = [float(v) for v in values]
+    if len(vals) != 6:
+        raise ValueError('measure: expected the 5 scale values and the mean squared error, got {} values'.format(len(vals)))
+    scales, mse = vals[:5], vals[5]
+    ms_ssim = metrics.msssim_from_scale_values(scales) if all(v >= 0 for v in scales) else float('nan')     # (a NaN compares false)
+    return Measure(int(nbytes), 8.0 * int(nbytes) / int(pixels), mse, metrics.psnr_from_mse(mse), ms_ssim)
+
+
+def check_measured_image(img_hwc_uint8, H, W):
+    """the original handed to Codec.measure for a file of an H x W picture -> the (H, W, 3) uint8 array; a ValueError naming both
+    shapes if it is not that picture's"""
+    img = np.asarray(img_hwc_uint8)
+    if img.ndim != 3 or img.shape[2] not in (3, 4) or img.dtype != np.uint8:
+        raise ValueError('expected an HWC uint8 image with 3 channels, got {} {}'.format(img.shape, img.dtype))
+    if img.shape[:2] != (int(H), int(W)):
+        raise ValueError('the image is {} x {}, the file decodes to {} x {}: a measure compares a picture with its own original'.format(
+            img.shape[0], img.shape[1], int(H), int(W)))
+    return img[:, :, :3]
+
+
+def measure_rect(rect, H, W):
+    """the rect argument of Codec.measure -> (x0, y0, x1, y1) clipped to the H x W picture as a region of interest is (_clip_rect); a
+    ValueError if less than MIN_MEASURE_SIDE pixels a side remain"""
+    x0, y0, x1, y1 = _clip_rect(rect, H, W)
+    if x1 - x0 < MIN_MEASURE_SIDE or y1 - y0 < MIN_MEASURE_SIDE:
+        raise ValueError('rectangle {}: {} x {} pixels of it lie in the image, MS-SSIM needs at least {} a side'.format(
+            tuple(int(v) for v in rect), x1 - x0, y1 - y0, MIN_MEASURE_SIDE))
+    return x0, y0, x1, y1
+
+
+def quality_target(psnr=None, ms_ssim=None):
+    """exactly one of psnr (dB; +inf is a target, NaN is not) and ms_ssim (0 .. 1) -> (the Measure field, the value)"""
+    if (psnr is None) == (ms_ssim is None):
+        raise ValueError('a quality target is exactly one of psnr (dB) and ms_ssim (0 .. 1), got {}'.format(
+            'both' if psnr is not None else 'neither'))
+    name, value = ('psnr', psnr) if psnr is not None else ('ms_ssim', ms_ssim)
+    try:
+        v = float(value)
+    except (TypeError, ValueError):
+        raise ValueError('{} target {!r} is not a number'.format(name, value))
+    if v != v or (name == 'ms_ssim' and not 0.0 <= v <= 1.0):
+        raise ValueError('{} target {} is not {}'.format(name, value, 'a number of dB' if name == 'psnr' else 'in 0 .. 1'))
+    return name, v
+
+
+def meets_target(measure, name, value):
+    """does a Measure reach the target of quality_target?  A nan never does."""
+    return bool(getattr(measure, name) >= value)
+
+
+def rd_levels(C, n=16):
+    """the n + 1 levels k C / n, k = 0 .. n, of a rate-distortion table (--levels N), 1 <= n <= CAP_STEPS -> list of float"""
+    if isinstance(n, (bool, np.bool_)) or not isinstance(n, (int, np.integer)) or not 1 <= int(n) <= CAP_STEPS:
+        raise ValueError('--levels {!r}: the table has N + 1 levels k C / N with N an integer in 1 .. {}'.format(n, CAP_STEPS))
+    return [float(k) * int(C) / int(n) for k in range(int(n) + 1)]
+
+
+def check_rd_levels(levels, C):
+    """the levels argument of Codec.rd_curve: None (rd_levels(C)) or a non-empty increasing sequence of levels in [0, +inf]"""
+    if levels is None:
+        return rd_levels(C)
+    try:
+        out = [_check_level(v, 'level') for v in levels]
+    except TypeError:
+        raise ValueError('levels {!r} are not a sequence of numbers'.format(levels))
+    if not out or any(b <= a for a, b in zip(out, out[1:])):
+        raise ValueError('levels {} are not a non-empty increasing sequence'.format(out))
+    return out
 
 
 def wavefront_dependencies(masks, num_layers):
@@ -1508,14 +1631,18 @@ class Codec(object):
 
     def _image(self, sym, c):
         """symbols (C,h,w) numpy of container c -> the HWC uint8 image"""
+        return np.ascontiguousarray(np.transpose(self._picture(sym, c.H, c.W).cpu().numpy(), (1, 2, 0)))
+
+    def _picture(self, sym, H, W, ae=None):
+        """symbols (C,h,w), numpy or on the device, of an H x W image -> its (3, H, W) uint8 picture, left on the device: _image
+        before the copy to the host.  ae: the autoencoder object that runs the pass (a lane of _in_flight; None: this Codec's own)"""
         import torch
         s = torch.as_tensor(sym).to(self.device)
         q = self.ae.get_centers_variable()[s][None].contiguous()
-        x_out = self.ae.decode(q, is_training=False).to(torch.uint8)            # tf.cast truncates (val.py)
-        img = np.transpose(x_out[0].cpu().numpy(), (1, 2, 0))
+        x_out = (ae or self.ae).decode(q, is_training=False).to(torch.uint8)    # tf.cast truncates (val.py)
         f = self.factor
-        t, l = ((-c.H) % f) // 2, ((-c.W) % f) // 2                               # val.add_padding's offsets
-        return np.ascontiguousarray(img[t:t + c.H, l:l + c.W, :])
+        t, l = ((-H) % f) // 2, ((-W) % f) // 2                                   # val.add_padding's offsets
+        return x_out[0, :, t:t + H, l:l + W]
 
     # -- a list of images per call: the same bytes / pixels as the calls above, file by file --
 
@@ -2076,6 +2203,135 @@ class Codec(object):
             report = self._report(c, reasons, damage[0], file_crc_ok)
         return self._container(self._capped(syms[0], keep), c.H, c.W), report
 
+    # -- the other axis: what a file, a level, a target costs in picture quality --
+
+    def _original(self, img_hw3_uint8):
+        """(H, W, 3) uint8 numpy -> the (1, 3, H, W) uint8 device tensor the metrics take: the one upload of a measure"""
+        import torch
+        return torch.as_tensor(np.ascontiguousarray(np.transpose(img_hw3_uint8, (2, 0, 1)))[None]).to(self.device)
+
+    def _values(self, orig, pic, box=None):
+        """orig (1, 3, H, W) and pic (3, H, W), uint8 on the device; box None or (x0, y0, x1, y1) -> the six float64 values of
+        metrics.val_metrics_device as one device tensor (scale values, then the mean squared error), nothing waited for"""
+        import torch
+        from . import metrics
+        pic = pic[None]
+        if box is not None:
+            x0, y0, x1, y1 = box
+            orig, pic = orig[:, :, y0:y1, x0:x1], pic[:, :, y0:y1, x0:x1]
+        scales, mse = metrics.val_metrics_device(orig.contiguous(), pic.contiguous())
+        return torch.cat([scales, mse.reshape(1)])
+
+    def written_version(self):
+        """the format version of the files this Codec writes (its refusals are _check_target's)"""
+        self._check_target()
+        if self._front_ends() is not None:
+            return FORMAT_VERSION_FRONTS
+        if self._layer_ends() is not None:
+            return FORMAT_VERSION_LAYERED
+        if self.tile is None:
+            return FORMAT_VERSION
+        return FORMAT_VERSION_WAVEFRONT if self._order() == 'wavefront' else FORMAT_VERSION_CHECKED if self.checked else FORMAT_VERSION_TILED
+
+    def measure(self, img_hwc_uint8, data, channels=None, rect=None):
+        """how good is this file?  -> Measure(bytes, bpp, mse, psnr, ms_ssim) of decompress(data, channels=channels) against its
+        original img: the decoded picture stays on the device, the original is uploaded once, and both go through
+        metrics.val_metrics_device (float64, the operations of the NumPy code val.py reports) -- measure_from_values says how the
+        fields follow.  bytes and bpp are the whole file's, header included: bpp = 8 len(data) / (H W).  rect = (x, y, w, h): the
+        metrics of that pixel rectangle of both pictures, clipped to the image as a region of interest is; bytes and bpp stay the
+        file's.  data is read as decompress reads it and refused as decompress refuses it; a ValueError too for an img of another
+        shape than the file's picture and for a rectangle of which less than 16 pixels a side lie in the image."""
+        sym, c = self.decode_symbols(data, channels=channels)
+        img = check_measured_image(img_hwc_uint8, c.H, c.W)
+        box = None if rect is None else measure_rect(rect, c.H, c.W)
+        values = self._values(self._original(img), self._picture(sym, c.H, c.W), box)
+        return measure_from_values(values.tolist(), len(data), c.H * c.W)
+
+    def _cap_planes(self, H, W, levels, rois=None):
+        """(1, T, h, w) float32 on the device for requantize: per level the plane compress(cap=level) builds, or with rois the one
+        of compress(rois=rois, background=level)"""
+        import torch
+        planes = [self.cap_plane(H, W, None, rois, lv) if rois else self.cap_plane(H, W, lv) for lv in levels]
+        return torch.as_tensor(np.stack(planes)[None]).to(self.device)
+
+    def _quality_inputs(self, img_hwc_uint8):
+        """the part of rd_curve and compress_to_quality that runs once per image -> (bottleneck, original on the device, (H, W))"""
+        x, (H, W) = self._image_tensor(img_hwc_uint8)
+        self._check_target()
+        _, bott = self.ae.encode_capped(x, None, keep_bottleneck=True)
+        return bott, self._original(np.asarray(img_hwc_uint8)[:, :, :3]), (H, W)
+
+    def rd_curve(self, img_hwc_uint8, levels=None, rois=None):
+        """what does a cap level cost in quality on this picture?  -> [(level, Measure)], row i equal in every field to
+        measure(img, compress(img, cap=levels[i])) -- with rois to measure(img, compress(img, rois=rois, background=levels[i])), the
+        rectangles uncapped as in compress_to_budget.  levels: None (rd_levels(C): the 17 levels k C / 16) or a non-empty increasing
+        sequence of levels.  The encoder runs once; the levels are requantised from its bottleneck 16 a launch, each coded to a real
+        file in this Codec's format (the tiles of a launch's levels by one coder launch per tile shape), and each decoded by a
+        batch-1 pass of its own, up to IN_FLIGHT at a time: the kernel form of a layer depends on the batch size, and a batch of
+        levels might run one that rounds differently from decompress's."""
+        levels = check_rd_levels(levels, self.C)
+        bott, orig, (H, W) = self._quality_inputs(img_hwc_uint8)
+        sizes, values = [], []
+        for start in range(0, len(levels), 16):
+            part = levels[start:start + 16]
+            syms = list(self.ae.requantize(bott, self._cap_planes(H, W, part, rois), hard_only=True).symbols)
+            sizes += [len(d) for d in self._containers(syms, [(H, W)] * len(part))]
+            pics = self._in_flight(syms, lambda ae, s: self._picture(s, H, W, ae))
+            values += [self._values(orig, pic) for pic in pics]
+        import torch
+        return [(lv, measure_from_values(v, n, H * W)) for lv, n, v in zip(levels, sizes, torch.stack(values).tolist())]
+
+    def compress_to_quality(self, img_hwc_uint8, psnr=None, ms_ssim=None, rois=None):
+        """give me the smallest level that still reaches the target -> (data, level, Measure, probes).  Exactly one of psnr (dB) and
+        ms_ssim (0 .. 1) is the target.  The search runs over cap_levels(C), the grid of compress_to_budget; a probe is one
+        requantisation of the kept bottleneck, one batch-1 decode and one metrics call -- nothing is entropy-coded to probe.
+        quality_search's contract holds on the measured pictures: data -- byte for byte compress(img, cap=level), with rois
+        compress(img, rois=rois, background=level) -- meets the target, Measure == measure(img, data), and the next level down misses
+        it (or level == 0); a nan never meets a target; probes <= 1 + 2 + 8.  A ValueError, which says what the file without a cap
+        reaches, if that file misses the target."""
+        name, target = quality_target(psnr, ms_ssim)
+        bott, orig, (H, W) = self._quality_inputs(img_hwc_uint8)
+        levels = cap_levels(self.C)
+        probed = {}
+
+        def meets(k):
+            sym = self.ae.requantize(bott, self._cap_planes(H, W, [levels[k]], rois), hard_only=True).symbols[0]
+            probed[k] = (sym, measure_from_values(self._values(orig, self._picture(sym, H, W)).tolist(), 0, H * W))
+            return meets_target(probed[k][1], name, target)
+
+        try:
+            k, probes = quality_search(meets, CAP_STEPS)
+        except ValueError:
+            if CAP_STEPS not in probed or meets_target(probed[CAP_STEPS][1], name, target):
+                raise
+            raise ValueError('{} target {:g}: the file without a cap reaches {:g}'.format(name, target, getattr(probed[CAP_STEPS][1], name)))
+        data = self._container(probed[k][0], H, W)
+        return data, float(levels[k]), probed[k][1]._replace(bytes=len(data), bpp=8.0 * len(data) / (H * W)), probes
+
+    def transcode_to_quality(self, data, psnr=None, ms_ssim=None):
+        """a file to a file of lower rate, as far as its picture stays within the target OF THE PICTURE THE FILE DECODES TO NOW
+        -> (out, K, Measure, probes): the smallest integer level K in 0 .. C, in quality_search's sense, whose picture measured
+        against decompress(data) meets the target; out is byte for byte transcode(data, cap=K), Measure its measure against
+        decompress(data).  The symbols are decoded once and stay on the device; a probe is one torch.where over them (cap_symbols),
+        one batch-1 decode and one metrics call; the encoder is never run.  Level C is the file's own picture (psnr inf, ms_ssim 1)
+        and meets every target, so probes <= 1 + 2 + ceil(log2 C)."""
+        name, target = quality_target(psnr, ms_ssim)
+        self._check_target()
+        c = parse_container(data)
+        self.check_container(c)
+        sym = self._decode_device(c)
+        orig = self._picture(sym, c.H, c.W)[None].contiguous()
+        probed = {}
+
+        def meets(k):
+            capped = self._capped(sym, np.full((c.h, c.w), k, np.int64))
+            probed[k] = (capped, measure_from_values(self._values(orig, self._picture(capped, c.H, c.W)).tolist(), 0, c.H * c.W))
+            return meets_target(probed[k][1], name, target)
+
+        K, probes = quality_search(meets, self.C)
+        out = self._container(probed[K][0], c.H, c.W)
+        return out, int(K), probed[K][1]._replace(bytes=len(out), bpp=8.0 * len(out) / (c.H * c.W)), probes
+
     def open_stream(self, max_workspace_bytes=1 << 31, fronts=False):
         """a StreamDecoder: a format-6 file fed as it arrives, recover's picture of the bytes so far, every layer decoded once;
         fronts=True: a format-8 file is taken as well, every front swept once"""
@@ -2213,12 +2469,13 @@ def _recover_line(path, report):
 
 
 TRANSCODE_COMMANDS = ('transcode', 'transcode-dir')
+WRITING_COMMANDS = ('compress', 'compress-dir', 'rd') + TRANSCODE_COMMANDS          # the commands that take --tile and its choices
 
 
 def check_option_args(flags):
     """--checked / --wavefront / --salvage / --channels / --layers / --progressive / --front-layers / --front-progressive / --partial /
-    --recover / --chunk / --fronts / --cap / --roi / --background / --max-bytes / --bpp / --region against the command, --tile
-    and each other: decided before any model is built"""
+    --recover / --chunk / --fronts / --cap / --roi / --background / --max-bytes / --bpp / --region / --min-psnr / --min-ms-ssim /
+    --levels against the command, --tile and each other: decided before any model is built"""
     cap, background, rois = getattr(flags, 'cap', None), getattr(flags, 'background', None), getattr(flags, 'roi', None) or []
     max_bytes, bpp = getattr(flags, 'max_bytes', None), getattr(flags, 'bpp', None)
     transcoding = flags.command in TRANSCODE_COMMANDS
@@ -2226,9 +2483,32 @@ def check_option_args(flags):
         if value is not None and flags.command not in ('compress', 'compress-dir') + TRANSCODE_COMMANDS:
             raise ValueError('{} belongs to compress / compress-dir: the cap on the importance map is the encoder\'s, a file is read '
                              'without it'.format(name))
+    min_psnr, min_ms_ssim = getattr(flags, 'min_psnr', None), getattr(flags, 'min_ms_ssim', None)
+    quality = '--min-psnr' if min_psnr is not None else '--min-ms-ssim' if min_ms_ssim is not None else None
+    if quality is not None:
+        if flags.command not in ('compress', 'compress-dir') + TRANSCODE_COMMANDS:
+            raise ValueError('{} belongs to compress / compress-dir / transcode / transcode-dir: it searches for the level a file is '
+                             'written at'.format(quality))
+        if min_psnr is not None and min_ms_ssim is not None:
+            raise ValueError('--min-psnr does not go with --min-ms-ssim: a search has one target')
+        for name, value in (('--cap', cap), ('--max-bytes', max_bytes), ('--bpp', bpp), ('--background', background)):
+            if value is not None:
+                raise ValueError('{} does not go with {}: the quality target searches for the level'.format(quality, name))
+        if transcoding and rois:
+            raise ValueError('{} does not go with --roi here: a file is lowered to a quality at one level for every cell'.format(quality))
+        for name in ('salvage', 'recover'):
+            if getattr(flags, name, False):
+                raise ValueError('{} does not go with --{}: a repaired file takes --cap alone'.format(quality, name))
+        quality_target(min_psnr, min_ms_ssim)
+    if getattr(flags, 'levels', None) is not None:
+        if flags.command != 'rd':
+            raise ValueError('--levels belongs to rd: the number of steps of the rate-distortion table')
+        rd_levels(1, flags.levels)
+    if flags.command == 'measure' and getattr(flags, 'tile', None) is not None:
+        raise ValueError('--tile belongs to compress / compress-dir: a file says by itself how it is tiled')
     if rois and flags.command == 'transcode-dir':
         raise ValueError('--roi belongs to compress / transcode: a rectangle is in the pixels of one image')
-    if rois and flags.command not in ('compress', 'transcode'):
+    if rois and flags.command not in ('compress', 'transcode', 'rd'):
         raise ValueError('--roi belongs to compress: a rectangle is in the pixels of one image' if flags.command == 'compress-dir' else
                          '--roi belongs to compress: the cap on the importance map is the encoder\'s, a file is read without it')
     if transcoding:
@@ -2244,7 +2524,7 @@ def check_option_args(flags):
     if cap is not None and (max_bytes is not None or bpp is not None):
         raise ValueError('--cap does not go with {}: the one names the level, the other searches for it'.format(
             '--max-bytes' if max_bytes is not None else '--bpp'))
-    if rois and background is None and max_bytes is None and bpp is None:
+    if rois and background is None and max_bytes is None and bpp is None and quality is None and flags.command != 'rd':
         raise ValueError('--roi needs --background or a budget (--max-bytes / --bpp): the level of the cells outside the rectangles')
     if background is not None and not rois:
         raise ValueError('--background needs --roi: without a rectangle --cap is the level of every cell')
@@ -2277,28 +2557,30 @@ def check_option_args(flags):
         if getattr(flags, 'tile', None) is not None:
             raise ValueError('--tile belongs to compress / compress-dir: a file says by itself how it is tiled')
     if getattr(flags, 'channels', None) is not None:
-        if flags.command not in ('decompress', 'decompress-dir'):
+        if flags.command not in ('decompress', 'decompress-dir', 'measure'):
             raise ValueError('--channels belongs to decompress / decompress-dir: a preview is a way of reading a file')
         if getattr(flags, 'salvage', False):
             raise ValueError('--channels does not go with --salvage: a preview of a damaged file is not offered')
         if flags.channels < 1:
             raise ValueError('--channels {} is not at least 1'.format(flags.channels))
     if getattr(flags, 'region', None) is not None:
-        if flags.command != 'decompress':
+        if flags.command not in ('decompress', 'measure'):
             raise ValueError('--region belongs to decompress: a rectangle is in the pixels of one image')
         for name, why in (('salvage', 'region decode of a damaged file is not offered'),
                           ('partial', 'region decode of a cut file is not offered'),
                           ('recover', 'region decode of a damaged or cut file is not offered')):
             if getattr(flags, name, False):
                 raise ValueError('--region does not go with --{}: {}'.format(name, why))
-        parse_roi_arg(flags.region, '--region')
+        region = parse_roi_arg(flags.region, '--region')
+        if flags.command == 'measure' and min(region[2:]) < MIN_MEASURE_SIDE:
+            raise ValueError('--region {!r}: MS-SSIM needs at least {} pixels a side'.format(flags.region, MIN_MEASURE_SIDE))
     if getattr(flags, 'checked', False):
-        if flags.command not in ('compress', 'compress-dir') + TRANSCODE_COMMANDS:
+        if flags.command not in WRITING_COMMANDS:
             raise ValueError('--checked belongs to compress / compress-dir: a file says by itself what it is')
         if flags.tile is None:
             raise ValueError('--checked needs --tile: the checksums of format 4 are per tile')
     if getattr(flags, 'wavefront', False):
-        if flags.command not in ('compress', 'compress-dir') + TRANSCODE_COMMANDS:
+        if flags.command not in WRITING_COMMANDS:
             raise ValueError('--wavefront belongs to compress / compress-dir: a file says by itself what it is')
         if flags.tile is None:
             raise ValueError('--wavefront needs --tile: format 5 codes every tile front by front')
@@ -2307,7 +2589,7 @@ def check_option_args(flags):
     layers, progressive = getattr(flags, 'layers', None), getattr(flags, 'progressive', False)
     if layers is not None or progressive:
         name = '--layers' if layers is not None else '--progressive'
-        if flags.command not in ('compress', 'compress-dir') + TRANSCODE_COMMANDS:
+        if flags.command not in WRITING_COMMANDS:
             raise ValueError('{} belongs to compress / compress-dir: a file says by itself what it is'.format(name))
         if flags.tile is None:
             raise ValueError('{} needs --tile: format 6 cuts every tile into layers'.format(name))
@@ -2320,7 +2602,7 @@ def check_option_args(flags):
     front_layers, front_progressive = getattr(flags, 'front_layers', None), getattr(flags, 'front_progressive', False)
     if front_layers is not None or front_progressive:
         name = '--front-layers' if front_layers is not None else '--front-progressive'
-        if flags.command not in ('compress', 'compress-dir') + TRANSCODE_COMMANDS:
+        if flags.command not in WRITING_COMMANDS:
             raise ValueError('{} belongs to compress / compress-dir: a file says by itself what it is'.format(name))
         if flags.tile is None:
             raise ValueError('{} needs --tile: format 8 cuts every tile into layers'.format(name))
@@ -2376,6 +2658,42 @@ def _budget_of(flags, H, W):
 
 def _budget_note(level, probes):
     return ', cap level {:g} after {} codings'.format(level, probes)
+
+
+def _quality_of(flags):
+    """--min-psnr / --min-ms-ssim as the keyword arguments of compress_to_quality / transcode_to_quality, or None"""
+    if getattr(flags, 'min_psnr', None) is not None:
+        return {'psnr': flags.min_psnr}
+    if getattr(flags, 'min_ms_ssim', None) is not None:
+        return {'ms_ssim': flags.min_ms_ssim}
+    return None
+
+
+def _measure_text(m):
+    return 'PSNR {:.4f} dB, MS-SSIM {:.6f}, MSE {:.4f}'.format(m.psnr, m.ms_ssim, m.mse)
+
+
+def _quality_note(level, measure, probes):
+    return ', cap level {:g} after {} probes: {}'.format(level, probes, _measure_text(measure))
+
+
+def _measure_line(path, m, channels=None, C=None, rect=None):
+    line = '{}: {} bytes = {:.4f} bpp, {}'.format(path, m.bytes, m.bpp, _measure_text(m))
+    if rect is not None:
+        line += ', of the region x {}..{} y {}..{}'.format(rect[0], rect[2], rect[1], rect[3])
+    return line if channels is None else '{}, preview from {} of {} channels'.format(line, channels, C)
+
+
+def _rd_line(level, m):
+    return 'level {:g}: {} bytes = {:.4f} bpp, {}'.format(level, m.bytes, m.bpp, _measure_text(m))
+
+
+def rd_table(codec, rows, image, H, W, rois=None):
+    """what the rd command writes as JSON: the rows of Codec.rd_curve with the format and the configs they were measured under"""
+    return {'image': image, 'H': int(H), 'W': int(W), 'ae_config': codec.ae_name, 'pc_config': codec.pc_name,
+            'format': codec.written_version(), 'tile': None if codec.tile is None else [v * codec.factor for v in codec.tile],
+            'rois': [list(r) for r in rois or []],
+            'rows': [dict(m._asdict(), level=level) for level, m in rows]}
 
 
 def parse_layers_arg(text, option='--layers'):
@@ -2455,6 +2773,9 @@ def _main_dir(flags, ae_config, pc_config):
             if _budget_of(flags, 1, 1) is not None:              # a budget per file: a search per file, one after the other
                 found = [codec.compress_to_budget(img, _budget_of(flags, img.shape[0], img.shape[1])) for img in imgs]
                 datas, notes = [d for d, _, _ in found], [_budget_note(level, probes) for _, level, probes in found]
+            elif _quality_of(flags) is not None:                 # a target per file, likewise
+                found = [codec.compress_to_quality(img, **_quality_of(flags)) for img in imgs]
+                datas, notes = [d for d, _, _, _ in found], [_quality_note(level, m, probes) for _, level, m, probes in found]
             else:
                 datas = codec.compress_many(imgs, caps=None if getattr(flags, 'cap', None) is None else [flags.cap] * len(imgs))
             for (src, dst), img, data, note in zip(part, imgs, datas, notes):
@@ -2510,6 +2831,9 @@ def _transcode_one(flags, codec, src, dst, data, rois=None):
         c = parse_container(data)
         out, level, probes = codec.transcode_to_budget(data, _budget_of(flags, c.H, c.W), rois=rois or None)
         note = _budget_note(level, probes)
+    elif _quality_of(flags) is not None:
+        out, level, m, probes = codec.transcode_to_quality(data, **_quality_of(flags))
+        note = _quality_note(level, m, probes)
     else:
         out = codec.transcode(data, cap=_cap_option(flags.cap), rois=rois or None, background=_cap_option(flags.background))
     with open(dst, 'wb') as f:
@@ -2523,10 +2847,10 @@ def _transcode_one(flags, codec, src, dst, data, rois=None):
 
 
 def _transcode_dir(flags, codec, jobs):
-    """transcode-dir: --batch files per transcode_many call; with a budget a search per file, with --salvage / --recover a repair per
+    """transcode-dir: --batch files per transcode_many call; with a budget or a quality target a search per file, with --salvage / --recover a repair per
     file, and there a file of which nothing can be read is named on stderr and skipped.  Exit status 0 when every file was written."""
     written = total_in = total_out = 0
-    one_by_one = flags.salvage or flags.recover or _budget_of(flags, 1, 1) is not None
+    one_by_one = flags.salvage or flags.recover or _budget_of(flags, 1, 1) is not None or _quality_of(flags) is not None
     for start in range(0, len(jobs), flags.batch):
         part = jobs[start:start + flags.batch]
         datas = []
@@ -2856,7 +3180,8 @@ def main(argv=None):
     p = argparse.ArgumentParser(description='compress an image to a codec file, or a codec file back to an image; transcode a codec '
                                             'file to another format or a lower rate without its image; '
                                             'the -dir commands do so for every file of a directory, --batch files per call')
-    p.add_argument('command', choices=['compress', 'decompress', 'compress-dir', 'decompress-dir', 'stream', 'transcode', 'transcode-dir'])
+    p.add_argument('command', choices=['compress', 'decompress', 'compress-dir', 'decompress-dir', 'stream', 'transcode', 'transcode-dir',
+                                       'measure', 'rd'])
     p.add_argument('input')
     p.add_argument('output')
     p.add_argument('--ae_config', default='cvpr/low', help='a config file, or a name below $CONFIG_BASE_AE / the package\'s ae_configs')
@@ -2911,7 +3236,15 @@ def main(argv=None):
     p.add_argument('--bpp', type=float, default=None, metavar='B', help='compress / compress-dir: --max-bytes floor(B H W / 8), per image')
     p.add_argument('--region', default=None, metavar='X,Y,W,H',
                    help='decompress: only this rectangle of the image, in image pixels (clipped to it), decoded from the tiles it needs '
-                        '(a file written with --tile); goes with --channels, not with --salvage, --partial or --recover')
+                        '(a file written with --tile); goes with --channels, not with --salvage, --partial or --recover; '
+                        'measure: the metrics of this rectangle of both pictures, at least 16 pixels a side')
+    p.add_argument('--min-psnr', dest='min_psnr', type=float, default=None, metavar='D',
+                   help='compress / compress-dir: the smallest cap level (of the grid k C / 256) whose picture still reaches D dB against '
+                        'the image; with --roi the rectangles stay uncapped and the level is the background\'s; prints the level, the '
+                        'measure and the number of probes; transcode / transcode-dir: the smallest integer level 0 .. C whose picture '
+                        'stays within D dB of the picture the file decodes to now; not with --cap, --max-bytes, --bpp or --background')
+    p.add_argument('--min-ms-ssim', dest='min_ms_ssim', type=float, default=None, metavar='S', help='the same with an MS-SSIM of S in 0 .. 1')
+    p.add_argument('--levels', type=int, default=None, metavar='N', help='rd: the N + 1 levels k C / N of the table, 1 <= N <= 256 (default 16)')
     flags = p.parse_args(argv)
     from . import config_parser, val, weights as _weights
     try:
@@ -2927,7 +3260,7 @@ def main(argv=None):
         else:
             wts = val.load_weights_for_job(None, flags.weights, ae_config, pc_config)
         codec = Codec(ae_config, pc_config, wts, flags.device)
-        if flags.command in ('compress', 'transcode'):
+        if flags.command in ('compress', 'transcode', 'rd'):
             if flags.tile is not None:
                 if flags.tile <= 0 or flags.tile % codec.factor != 0:
                     raise ValueError('--tile {} is not a positive multiple of the subsampling factor {}'.format(flags.tile, codec.factor))
@@ -2949,6 +3282,13 @@ def main(argv=None):
                 with open(flags.output, 'wb') as f:
                     f.write(data)
                 print(_compress_line(flags.output, data, img.shape[0] * img.shape[1]) + _budget_note(level, probes))
+            elif _quality_of(flags) is not None:
+                from PIL import Image
+                img = np.asarray(Image.open(flags.input).convert('RGB'), dtype=np.uint8)     # as compress_file reads it
+                data, level, m, probes = codec.compress_to_quality(img, rois=rois or None, **_quality_of(flags))
+                with open(flags.output, 'wb') as f:
+                    f.write(data)
+                print(_compress_line(flags.output, data, img.shape[0] * img.shape[1]) + _quality_note(level, m, probes))
             elif flags.cap is not None or rois:
                 data, pixels = codec.compress_file(flags.input, flags.output, cap=flags.cap, rois=rois or None, background=flags.background)
                 print(_compress_line(flags.output, data, pixels))
@@ -2957,6 +3297,24 @@ def main(argv=None):
                 print(_compress_line(flags.output, data, pixels))
         elif flags.command == 'stream':
             _main_stream(flags, codec)
+        elif flags.command == 'measure':
+            from PIL import Image
+            img = np.asarray(Image.open(flags.input).convert('RGB'), dtype=np.uint8)         # as compress_file reads it
+            channels = check_channels(flags.channels, codec.C)
+            rect = None if flags.region is None else parse_roi_arg(flags.region, '--region')
+            with open(flags.output, 'rb') as f:
+                data = f.read()
+            m = codec.measure(img, data, channels=channels, rect=rect)
+            print(_measure_line(flags.output, m, channels, codec.C, None if rect is None else _clip_rect(rect, img.shape[0], img.shape[1])))
+        elif flags.command == 'rd':
+            from PIL import Image
+            img = np.asarray(Image.open(flags.input).convert('RGB'), dtype=np.uint8)         # as compress_file reads it
+            rows = codec.rd_curve(img, levels=rd_levels(codec.C, 16 if flags.levels is None else flags.levels), rois=rois or None)
+            with open(flags.output, 'w') as f:
+                json.dump(rd_table(codec, rows, flags.input, img.shape[0], img.shape[1], rois), f, indent=1)
+                f.write('\n')
+            for level, m in rows:
+                print(_rd_line(level, m))
         elif flags.partial:
             from PIL import Image
             with open(flags.input, 'rb') as f:
