@@ -41,6 +41,13 @@ def CONV3_IN_FLIGHT(n):
 PC_DECODE_PER_LAYER = 0x01
 PC_DECODE_RECOMPUTE = 0x02
 PC_DECODE_WAVEFRONT = 0x04           # ic_pc_decode_tiles_batch_f32: streams in wavefront order (format 5)
+PC_ENCODE_SKIP = -1                  # ic_pc_encode_f32 / _segments_f32: a symbol that is stepped over (IC_PC_ENCODE_SKIP)
+
+
+def PC_DECODE_DEPTH(b):
+    """IC_PC_DECODE_DEPTH(b): ic_pc_decode_tiles_batch_channels_f32 with PC_DECODE_WAVEFRONT, every stream begins with a depth plane of
+    b x b blocks (format 10)"""
+    return (int(b) & 0xff) << 8
 
 
 def conv3_leave_idle_layers(n):

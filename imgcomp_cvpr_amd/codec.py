@@ -2,7 +2,8 @@
 
     python -m imgcomp_cvpr_amd.codec compress   IN.png  OUT.icf [--ae_config cvpr/low] [--pc_config cvpr/res_shallow] [--weights synthetic|FILE.npz|CKPT]
                                                                 [--tile PIXELS [--checked | --wavefront | --layers a,b,.. | --progressive |
-                                                                                --front-layers a,b,.. | --front-progressive]]
+                                                                                --front-layers a,b,.. | --front-progressive |
+                                                                                --depth [--depth-block B]]]
                                                                 [--cap T | --max-bytes N | --bpp B | --min-psnr D | --min-ms-ssim S]
                                                                 [--roi X,Y,W,H ... [--background T]]
     python -m imgcomp_cvpr_amd.codec decompress IN.icf  OUT.png [same options] [--salvage | --channels K | --partial | --recover]
@@ -126,6 +127,22 @@ format-5 file steps through, so the bytes [0, layer_prefix_bytes(g)) decode as t
 (ic_pc_decode_tiles_batch_fronts_f32 restarts the coder at each cut).  The price: a layer's prefix also carries the symbols of later
 channels that share its fronts, so the early prefixes are longer than format 6's; nothing is coded twice.  decompress, --channels,
 --partial, --recover and verify read it as they read format 6, and so does stream --fronts; --salvage and stream without it do not.
+--tile --depth [--depth-block B] (Codec(tile=(th, tw), depth_block=B)): format 10, "depth-mapped tiles" -- the layout of formats 4 / 5
+(a CRC per tile and one over the header, always) with the depth block B (default 4, 1 .. 255) as one '<H' behind the tile extent; 9
+is not used and is refused.  Every tile's stream is a DEPTH PLANE followed by the range coder's bytes, and the tile's CRC covers both.
+The plane (depth_plane) has one byte per block of B x B latent cells, counted from the tile's corner, ragged at the far edges: 0 if
+every symbol of the block's cells is the fill symbol (fill_symbol: the centre nearest zero, what the importance map and a --cap leave
+in the channels they mask), else 1 + the largest channel that holds another symbol in any of them.  Position (c, y, x) of a tile is
+LIVE iff c < depth[y // B][x // B]; the coder's bytes are those of format 5 over the live positions alone (depth_live_mask: the
+wavefront order with the dead positions left out; index 0 is still the uncoded first symbol), and a dead position decodes to the fill
+symbol without a coder step -- the depth wins over the first symbol.  So neither side pays for a symbol that carries nothing, a capped
+or region-of-interest file decodes as fast as its content allows without --channels, and a tile whose upper channels are dead
+everywhere ends its front sweep early.  The plane is stored raw: 16 bytes per 16 x 16 tile at B = 4, 64 at B = 2, 256 at B = 1.
+parse_container refuses, naming the tile, a stream shorter than its plane and a depth above C; C > 255 is refused for this format.
+decompress, --channels K, --region, the -dir commands, transcode to and from it, measure, rd and the searches read and write it like
+format 5; verify and info are host only (info prints B, the live share and the front steps per tile the depths imply).  --salvage,
+--partial, --recover, stream and repair refuse a format-10 file in one sentence.  Not with --wavefront or the layered formats; a
+context model the wavefront order refuses, or of another width than k = 24, is refused.
 stream (Codec.open_stream -> StreamDecoder): a format-6 file that is still arriving.  feed(chunk) takes the bytes as they come, image()
 gives recover's picture and report of the bytes so far -- but the decoder goes on where the last image() stopped: the session
 (PredictionNetwork.open_layers) keeps every tile's decoder workspace on the device and ic_pc_decode_tiles_batch_layers_resume_f32
@@ -214,7 +231,12 @@ MAX_LAYERS = 16
 # 6 (segments cut at channel planes of the raster order) or 8 (cut at fronts of the wavefront order, front_layer_cuts)
 LayeredContainer = namedtuple('LayeredContainer', TiledContainer._fields + ('layer_ends', 'segments', 'segment_crcs'))
 PartialReport = namedtuple('PartialReport', ['layers_total', 'layers_decoded', 'channels', 'file_crc_ok'])
-_TILED = (TiledContainer, CheckedContainer, WavefrontContainer, LayeredContainer)
+FORMAT_VERSION_DEPTH = 10                                            # format 5 plus a depth plane per tile; 9 is not used
+DEFAULT_DEPTH_BLOCK = 4
+# streams[t] is tile t's depth plane (ceil(th' / B) * ceil(tw' / B) bytes, row-major, blocks counted from the tile's corner) followed
+# by the range coder's bytes over the tile's live positions; depth_block is B
+DepthContainer = namedtuple('DepthContainer', CheckedContainer._fields + ('depth_block',))
+_TILED = (TiledContainer, CheckedContainer, WavefrontContainer, LayeredContainer, DepthContainer)
 _WITH_CRCS = (FORMAT_VERSION_CHECKED, FORMAT_VERSION_WAVEFRONT)
 WAVEFRONT_COEFFS = (2, 4)                                            # T = x + 2 y + 4 c: fixed by format 5
 
@@ -699,6 +721,74 @@ def wavefront_prefix_count(C, h, w, channels):
     return sum(_below(T - 4 * c, h, w) for c in range(C))
 
 
+def check_depth_block(depth_block, C):
+    """the block side B of format 10: an integer in 1 .. 255, for a volume of at most 255 channels (a depth is one byte); else a
+    ValueError naming the cause -> int"""
+    if isinstance(depth_block, (bool, np.bool_)) or not isinstance(depth_block, (int, np.integer)) or not 1 <= int(depth_block) <= 255:
+        raise ValueError('depth block = {!r}: the blocks of a depth plane are B x B cells with an integer B in 1 .. 255'.format(depth_block))
+    if int(C) > 255:
+        raise ValueError('depth-mapped tiles store a depth in one byte: C = {} is above 255'.format(int(C)))
+    return int(depth_block)
+
+
+def depth_plane(symbols_chw, fill, B):
+    """the depth plane of a (C, h, w) tile: uint8 (ceil(h / B), ceil(w / B)); a block's entry is 0 if every symbol of its cells is
+    `fill`, else 1 + the largest channel that holds another symbol in any of its cells.  Blocks are B x B cells counted from the
+    tile's corner, ragged at the far edges."""
+    sym = np.asarray(symbols_chw)
+    if sym.ndim != 3:
+        raise ValueError('depth_plane: a (C, h, w) symbol volume is expected, got shape {}'.format(sym.shape))
+    C, h, w = sym.shape
+    B = check_depth_block(B, C)
+    cell = ((sym != fill) * (np.arange(C, dtype=np.int64) + 1)[:, None, None]).max(axis=0)     # per cell: 1 + deepest channel, 0: none
+    nby, nbx = -(-h // B), -(-w // B)
+    padded = np.zeros((nby * B, nbx * B), dtype=np.int64)
+    padded[:h, :w] = cell
+    return padded.reshape(nby, B, nbx, B).max(axis=(1, 3)).astype(np.uint8)
+
+
+def _depth_per_cell(C, th, tw, depth, B):
+    """the depth plane spread over the cells of a (th, tw) tile, clamped to C -> int64 (th, tw)"""
+    C, th, tw = int(C), int(th), int(tw)
+    B = check_depth_block(B, C)
+    d = np.asarray(depth)
+    if d.shape != (-(-th // B), -(-tw // B)):
+        raise ValueError('depth plane of shape {} for a {} x {} tile in blocks of {}: expected {} x {}'.format(
+            d.shape, th, tw, B, -(-th // B), -(-tw // B)))
+    return np.minimum(np.repeat(np.repeat(d.astype(np.int64), B, axis=0), B, axis=1)[:th, :tw], C)
+
+
+def depth_live(C, th, tw, depth, B):
+    """the live positions of a (C, th, tw) tile under a depth plane: bool (C, th, tw), [c, y, x] = c < depth[y // B][x // B]"""
+    return np.arange(int(C))[:, None, None] < _depth_per_cell(C, th, tw, depth, B)[None]
+
+
+def depth_live_mask(C, th, tw, depth, B):
+    """the keep-mask of format 10 in coding order: bool of C * th * tw elements, element i says whether position
+    wavefront_order(C, th, tw)[i] is live.  The coded sequence of a tile is its wavefront order with the dead positions left out --
+    and element 0, the first position, uncoded as ever; a dead position holds the fill symbol, the first one included."""
+    return depth_live(C, th, tw, depth, B).reshape(-1)[wavefront_order(C, th, tw)]
+
+
+def depth_front_steps(th, tw, dmax):
+    """the steps of the front sweep that decodes a (., th, tw) tile whose deepest block is dmax: the fronts T = 7 .. (tw + 3) +
+    2 (th + 3) + 4 (dmax + 3) of the padded volume, none for a tile that holds nothing.  dmax = C is the sweep of format 5."""
+    return 0 if int(dmax) < 1 else (int(tw) + 3) + 2 * (int(th) + 3) + 4 * (int(dmax) + 3) - 6
+
+
+def split_depth_stream(stream, C, th, tw, B, tile=None):
+    """a tile's stream of format 10 -> (depth plane uint8 (nby, nbx), the coder's bytes); a ValueError naming the tile for a stream
+    shorter than its plane and for a depth above C"""
+    nby, nbx = -(-int(th) // B), -(-int(tw) // B)
+    where = '' if tile is None else ' of tile {}'.format(tile)
+    if len(stream) < nby * nbx:
+        raise ValueError('stream{} holds {} bytes, its depth plane of {} x {} blocks alone has {}'.format(where, len(stream), nby, nbx, nby * nbx))
+    depth = np.frombuffer(bytes(stream[:nby * nbx]), dtype=np.uint8).reshape(nby, nbx)
+    if depth.size and int(depth.max()) > int(C):
+        raise ValueError('depth plane{} holds {}, above C = {}'.format(where, int(depth.max()), int(C)))
+    return depth, bytes(stream[nby * nbx:])
+
+
 def chunk_tiles(tile_shapes, need, budget):
     """cut a list of tiles [(th, tw)] into consecutive chunks [(start, stop)] for a decoder whose workspace grows with the number of
     tiles of a call: need(th_max, tw_max, ntiles) -> bytes for a chunk of ntiles tiles, the largest th x tw.  Greedy, order kept:
@@ -780,6 +870,26 @@ def build_wavefront_container(ae_name, pc_name, H, W, C, h, w, L, resolution, fi
     head = _tiled_head(FORMAT_VERSION_WAVEFRONT, ae_name, pc_name, H, W, C, h, w, L, resolution, fingerprint, th, tw,
                        [struct.pack('<HII', f, len(b), zlib.crc32(b) & 0xffffffff) for f, b in zip(first_syms, streams)],
                        sum(len(b) for b in streams))
+    body = head + struct.pack('<I', zlib.crc32(head) & 0xffffffff) + b''.join(streams)
+    return body + struct.pack('<I', zlib.crc32(body) & 0xffffffff)
+
+
+def build_depth_container(ae_name, pc_name, H, W, C, h, w, L, resolution, fingerprint, th, tw, depth_block, first_syms, streams):
+    """format 10: the layout of formats 4 / 5 with the depth block B as one '<H' behind the tile extent; streams[t] is tile t's depth
+    plane (depth_plane of its symbols, row-major bytes) followed by the range coder's bytes over its live positions
+    (depth_live_mask), and the tile's CRC covers both."""
+    streams = [bytes(b) for b in streams]
+    assert len(first_syms) == len(streams)
+    B = check_depth_block(depth_block, C)
+    a, p = ae_name.encode('utf-8'), pc_name.encode('utf-8')
+    head = b''.join([
+        MAGIC, struct.pack('<H', FORMAT_VERSION_DEPTH),
+        struct.pack('<H', len(a)), a, struct.pack('<H', len(p)), p,
+        struct.pack('<II', H, W), struct.pack('<HII', C, h, w), struct.pack('<H', L),
+        struct.pack('<d', float(resolution)), struct.pack('<I', fingerprint & 0xffffffff),
+        struct.pack('<HH', th, tw), struct.pack('<H', B), struct.pack('<I', len(streams))] +
+        [struct.pack('<HII', f, len(b), zlib.crc32(b) & 0xffffffff) for f, b in zip(first_syms, streams)] +
+        [struct.pack('<Q', sum(len(b) for b in streams))])
     body = head + struct.pack('<I', zlib.crc32(head) & 0xffffffff) + b''.join(streams)
     return body + struct.pack('<I', zlib.crc32(body) & 0xffffffff)
 
@@ -884,7 +994,7 @@ def parse_container(data):
     if data[:4] != MAGIC:
         raise ValueError('wrong magic {!r}: not a codec file (expected {!r})'.format(data[:4], MAGIC))
     version, = struct.unpack('<H', data[4:6])
-    if version not in (FORMAT_VERSION, FORMAT_VERSION_TILED, FORMAT_VERSION_CHECKED, FORMAT_VERSION_WAVEFRONT) + _LAYERED_VERSIONS:
+    if version not in (FORMAT_VERSION, FORMAT_VERSION_TILED, FORMAT_VERSION_CHECKED, FORMAT_VERSION_WAVEFRONT, FORMAT_VERSION_DEPTH) + _LAYERED_VERSIONS:
         raise ValueError(_unsupported(version))
     stored, = struct.unpack('<I', data[-4:])
     actual = zlib.crc32(data[:-4]) & 0xffffffff
@@ -926,12 +1036,15 @@ def _parse_front(r):
     return ae_name, pc_name, H, W, C, h, w
 
 
-def _parse_tile_extent(r, h, w):
-    """L .. tile count, which every tiled format has -> (L, resolution, fingerprint, th, tw, ntiles)"""
+def _parse_tile_extent(r, h, w, depth=None):
+    """L .. tile count, which every tiled format has -> (L, resolution, fingerprint, th, tw, ntiles); depth: a list that receives the
+    depth block of a format-10 header, which stands behind the tile extent"""
     L, = r.unpack('<H', 'L')
     resolution, = r.unpack('<d', 'frequency resolution')
     fingerprint, = r.unpack('<I', 'model fingerprint')
     th, tw = r.unpack('<HH', 'tile extent')
+    if depth is not None:
+        depth.append(r.unpack('<H', 'depth block')[0])
     ntiles, = r.unpack('<I', 'tile count')
     if th == 0 or tw == 0:
         raise ValueError('tile extent {} x {}: a tile has at least one row and one column'.format(th, tw))
@@ -944,11 +1057,11 @@ def _parse_tile_extent(r, h, w):
     return L, resolution, fingerprint, th, tw, ntiles
 
 
-def _parse_tile_table(r, version, h, w):
+def _parse_tile_table(r, version, h, w, depth=None):
     """L .. payload length of a format-2 / format-4 / format-5 header, every length against the bytes that remain -> (L, resolution,
-    fingerprint, th, tw, first_syms, lengths, crcs or None, n)"""
-    L, resolution, fingerprint, th, tw, ntiles = _parse_tile_extent(r, h, w)
-    checked = version in _WITH_CRCS
+    fingerprint, th, tw, first_syms, lengths, crcs or None, n); depth as _parse_tile_extent takes it (format 10: the table of format 4)"""
+    L, resolution, fingerprint, th, tw, ntiles = _parse_tile_extent(r, h, w, depth)
+    checked = version in _WITH_CRCS or version == FORMAT_VERSION_DEPTH
     row = 10 if checked else 6
     table = r.take(row * ntiles, 'tile table')            # against the bytes that remain, before anything of its size is built
     first_syms, lengths, crcs = [], [], [] if checked else None
@@ -970,7 +1083,8 @@ def _parse_tile_table(r, version, h, w):
 
 def _parse_tiled(r, version, ae_name, pc_name, H, W, C, h, w):
     """the rest of a format-2 / format-4 / format-5 file after the symbol volume shape (the CRC over the file has been checked)."""
-    L, resolution, fingerprint, th, tw, first_syms, lengths, crcs, n = _parse_tile_table(r, version, h, w)
+    depth = [] if version == FORMAT_VERSION_DEPTH else None
+    L, resolution, fingerprint, th, tw, first_syms, lengths, crcs, n = _parse_tile_table(r, version, h, w, depth)
     if crcs is not None:
         end = r.pos
         stored, = r.unpack('<I', 'header CRC')
@@ -991,6 +1105,14 @@ def _parse_tiled(r, version, ae_name, pc_name, H, W, C, h, w):
         actual = zlib.crc32(b) & 0xffffffff
         if actual != crc:
             raise ValueError('stream CRC mismatch in tile {}: the table says {:08x}, the stream gives {:08x}'.format(t, crc, actual))
+    if version == FORMAT_VERSION_DEPTH:
+        B = depth[0]
+        if not 1 <= B <= 255 or C > 255:
+            raise ValueError('depth block {} with C = {}: format 10 has blocks of 1 .. 255 cells and at most 255 channels'.format(B, C))
+        for t, ((_, _, a, b), s) in enumerate(zip(tile_grid(h, w, th, tw), streams)):
+            split_depth_stream(s, C, a, b, B, tile=t)     # a stream shorter than its plane, a depth above C: refused, naming the tile
+        return DepthContainer(version, ae_name, pc_name, H, W, C, h, w, L, resolution, fingerprint, th, tw, first_syms, streams, payload,
+                              crcs, B)
     cls = WavefrontContainer if version == FORMAT_VERSION_WAVEFRONT else CheckedContainer
     return cls(version, ae_name, pc_name, H, W, C, h, w, L, resolution, fingerprint, th, tw, first_syms, streams, payload, crcs)
 
@@ -1089,11 +1211,22 @@ def _prefix_from_bytes(data, g):
     return r.pos + sum(rows[2 * i] for i in range(_check_layer_index(g, G) * ntiles))
 
 
+def _refuse_depth(data, what):
+    """--salvage, --partial, --recover, stream and repair do not read format 10: one sentence, before anything else of the file is looked at"""
+    if len(data) >= 6 and data[:4] == MAGIC and struct.unpack('<H', data[4:6])[0] == FORMAT_VERSION_DEPTH:
+        raise ValueError('format version {} (depth-mapped tiles) is not read by {}: a file to be salvaged is written with --tile --checked '
+                         'or --tile --wavefront (versions {} and {}), a file to be read from a prefix, recovered or streamed with the '
+                         'layered formats --layers / --front-layers (versions {} and {}); an intact file decodes with '
+                         'decompress'.format(FORMAT_VERSION_DEPTH, what, FORMAT_VERSION_CHECKED, FORMAT_VERSION_WAVEFRONT,
+                                             FORMAT_VERSION_LAYERED, FORMAT_VERSION_FRONTS))
+
+
 def _partial_open(data):
     if len(data) < _MIN_SIZE:
         raise ValueError('header damaged: truncated file: {} bytes, the smallest container has {}'.format(len(data), _MIN_SIZE))
     if data[:4] != MAGIC:
         raise ValueError('header damaged: wrong magic {!r}: not a codec file (expected {!r})'.format(data[:4], MAGIC))
+    _refuse_depth(data, '--partial / --recover / stream')
     version, = struct.unpack('<H', data[4:6])
     if version not in _LAYERED_VERSIONS:
         raise ValueError('header damaged: format version {} is not the layered version {}: only a layered file (--tile --layers / '
@@ -1219,6 +1352,7 @@ def parse_salvage(data):
     if data[:4] != MAGIC:
         raise ValueError('wrong magic {!r}: not a codec file (expected {!r})'.format(data[:4], MAGIC))
     version, = struct.unpack('<H', data[4:6])
+    _refuse_depth(data, '--salvage')
     if version in (FORMAT_VERSION, FORMAT_VERSION_TILED):
         raise ValueError('format version {} has nothing to salvage with: one CRC over the whole file, none per tile (only version {}, '
                          'written with --tile --checked, can be salvaged)'.format(version, FORMAT_VERSION_CHECKED))
@@ -1298,7 +1432,9 @@ class Codec(object):
     Reading needs no option: the file's version decides."""
 
     def __init__(self, ae_config, pc_config, weights, device='cuda', plan_flags=0, device_encode=True, tile=None, checked=False,
-                 order='raster', layers=None, front_layers=None):
+                 order='raster', layers=None, front_layers=None, depth_block=None):
+        if depth_block is not None:
+            self._check_depth(depth_block, tile, order, layers, front_layers, ae_config.num_chan_bn)
         if tile is not None:
             tile = (int(tile[0]), int(tile[1]))
             if not (1 <= tile[0] <= 0xffff and 1 <= tile[1] <= 0xffff):
@@ -1322,6 +1458,7 @@ class Codec(object):
         if front_layers is not None:
             front_layers = front_layers if isinstance(front_layers, str) else check_layer_ends(front_layers, ae_config.num_chan_bn)
         self.tile, self.checked, self.order, self.layers, self.front_layers = tile, bool(checked), order, layers, front_layers
+        self.depth_block = None if depth_block is None else int(depth_block)
         import torch
         from . import autoencoder, probclass
         self.device = torch.device(device)
@@ -1342,7 +1479,12 @@ class Codec(object):
             raise ValueError(self.layered_refusal)
         if front_layers is not None and (self.wavefront_refusal or self.layered_refusal):
             raise ValueError(self.wavefront_refusal or self.layered_refusal)
-        self.pred = probclass.PredictionNetwork(self.pc, pc_config, self.ae.get_centers_variable())
+        self.depth_refusal = self.wavefront_refusal or (None if k == 24 else (
+            'depth-mapped tiles: the front decoder that reads a depth plane covers context models of width k = 24, this one has '
+            'k = {}'.format(k)))
+        if depth_block is not None and self.depth_refusal:
+            raise ValueError(self.depth_refusal)
+        self.pred =probclass.PredictionNetwork(self.pc, pc_config, self.ae.get_centers_variable())
         self.ae_name, self.pc_name = config_name(ae_config), config_name(pc_config)
         self.factor = int(self.ae.get_subsampling_factor())
         self.C, self.L = int(ae_config.num_chan_bn), int(ae_config.num_centers)
@@ -1384,6 +1526,27 @@ class Codec(object):
                              "unlayered format 5")
         if isinstance(front_layers, str) and front_layers != 'default':
             raise ValueError("front_layers is None, 'default' or a sequence of layer ends, got {!r}".format(front_layers))
+
+    @staticmethod
+    def _check_depth(depth_block, tile, order, layers, front_layers, C):
+        if tile is None:
+            raise ValueError('depth_block needs a tile extent: format 10 is a tiled format')
+        if order == 'wavefront':
+            raise ValueError("depth_block does not go with order='wavefront': format 10 implies the order, order='wavefront' writes "
+                             "format 5, which codes every position")
+        if layers is not None or front_layers is not None:
+            raise ValueError('depth_block does not go with layers or front_layers: format 10 is one coder run per tile, the layered '
+                             'formats 6 and 8 cut a tile into several')
+        check_depth_block(depth_block, C)
+
+    def _depth(self):
+        """the depth block of the format-10 file compress writes, or None (the attributes may have been set after construction, as main does)"""
+        if getattr(self, 'depth_block', None) is None:
+            return None
+        self._check_depth(self.depth_block, self.tile, self.order, self.layers, getattr(self, 'front_layers', None), self.C)
+        if self.depth_refusal:
+            raise ValueError(self.depth_refusal)
+        return int(self.depth_block)
 
     def _front_ends(self):
         """the layer ends of the format-8 file compress writes, or None (the attributes may have been set after construction, as main does)"""
@@ -1496,6 +1659,12 @@ class Codec(object):
     def _container(self, sym, H, W):
         """the symbols (C, h, w) of an H x W image, on the device -> container bytes in this Codec's format"""
         C, h, w = (int(v) for v in sym.shape)
+        B = self._depth()
+        if B is not None:
+            th, tw = self.tile
+            coded = self.pred.encode_tiles(sym, th, tw, order='wavefront', depth_block=B)
+            return build_depth_container(self.ae_name, self.pc_name, H, W, C, h, w, self.L, self.pred.freqs_resolution,
+                                         self.fingerprint, th, tw, B, [f for _, f in coded], [b for b, _ in coded])
         fronts = self._front_ends()
         if fronts is not None:
             th, tw = self.tile
@@ -1576,6 +1745,8 @@ class Codec(object):
                 c.h, c.w, c.H, c.W, eh, ew))
         if isinstance(c, WavefrontContainer) and self.wavefront_refusal:
             raise ValueError('format 5 cannot be read with this model: {}'.format(self.wavefront_refusal))
+        if isinstance(c, DepthContainer) and self.depth_refusal:
+            raise ValueError('format {} cannot be read with this model: {}'.format(c.version, self.depth_refusal))
         if isinstance(c, LayeredContainer) and self.layered_refusal:
             raise ValueError('format {} cannot be read with this model: {}'.format(c.version, self.layered_refusal))
         if isinstance(c, LayeredContainer) and c.version == FORMAT_VERSION_FRONTS and self.wavefront_refusal:
@@ -1597,9 +1768,9 @@ class Codec(object):
             if isinstance(c, LayeredContainer):          # a batch of one: the layers are arguments of the batch entry
                 sym = self.pred.decode_tiles_batch([(c.streams, c.first_syms, (c.C, c.h, c.w))], c.th, c.tw, want='symbols',
                                                    channels=channels, **_ends_kw(c))[0].cpu().numpy()
-            elif isinstance(c, WavefrontContainer):      # a batch of one: the order is a flag of the batch entry
+            elif isinstance(c, (WavefrontContainer, DepthContainer)):      # a batch of one: the order and the depth block are flags of the batch entry
                 sym = self.pred.decode_tiles_batch([(c.streams, c.first_syms, (c.C, c.h, c.w))], c.th, c.tw, want='symbols',
-                                                   order='wavefront', channels=channels)[0].cpu().numpy()
+                                                   channels=channels, **_order_kw(c))[0].cpu().numpy()
             elif isinstance(c, _TILED):
                 sym = self.pred.decode_tiles(c.streams, c.first_syms, (c.C, c.h, c.w), c.th, c.tw, channels=channels)
             else:
@@ -1708,6 +1879,15 @@ class Codec(object):
         if not self.device_encode:
             return [self._container(sym, H, W) for sym, (H, W) in zip(syms, sizes)]
         out = [None] * len(syms)
+        B = self._depth()
+        if B is not None:
+            th, tw = self.tile
+            for i, coded in enumerate(self.pred.encode_tiles_batch(syms, th, tw, order='wavefront', depth_block=B)):
+                C, h, w = (int(v) for v in syms[i].shape)
+                out[i] = build_depth_container(self.ae_name, self.pc_name, sizes[i][0], sizes[i][1], C, h, w, self.L,
+                                               self.pred.freqs_resolution, self.fingerprint, th, tw, B,
+                                               [f for _, f in coded], [b for b, _ in coded])
+            return out
         fronts = self._front_ends()
         ends = fronts if fronts is not None else self._layer_ends()
         if ends is not None:
@@ -1748,10 +1928,11 @@ class Codec(object):
         layered, front-layered) the tiled files of the most frequent tile extent (and layer ends) in one decode_tiles_batch call ->
         yields (their indices, per file q or symbols on the device); the other files are the caller's, one by one"""
         kind = lambda c: (('fronts' if c.version == FORMAT_VERSION_FRONTS else 'layered') if isinstance(c, LayeredContainer)
-                          else 'wavefront' if isinstance(c, WavefrontContainer) else 'raster')
-        for order in ('raster', 'wavefront', 'layered', 'fronts'):
+                          else 'depth' if isinstance(c, DepthContainer) else 'wavefront' if isinstance(c, WavefrontContainer) else 'raster')
+        for order in ('raster', 'wavefront', 'layered', 'fronts', 'depth'):
             mine = [i for i, c in enumerate(heads) if isinstance(c, _TILED) and kind(c) == order]
-            extents = [(heads[i].th, heads[i].tw) + (tuple(heads[i].layer_ends) if order in ('layered', 'fronts') else ()) for i in mine]
+            extents = [(heads[i].th, heads[i].tw) + (tuple(heads[i].layer_ends) if order in ('layered', 'fronts') else
+                                                     (heads[i].depth_block,) if order == 'depth' else ()) for i in mine]
             major = max(sorted(set(extents)), key=extents.count) if extents else None
             together = [i for i, e in zip(mine, extents) if e == major]
             if not together:
@@ -1761,7 +1942,8 @@ class Codec(object):
                                                     for i in together], major[0], major[1], want=want,
                                                    max_workspace_bytes=max_workspace_bytes, channels=channels,
                                                    **({'layer_ends': list(major[2:])} if order == 'layered' else
-                                                      {'front_ends': list(major[2:])} if order == 'fronts' else {'order': order}))
+                                                      {'front_ends': list(major[2:])} if order == 'fronts' else
+                                                      {'order': 'wavefront', 'depth_block': major[2]} if order == 'depth' else {'order': order}))
             except ValueError as e:
                 m = re.search(r'volume (\d+)', str(e))
                 where = 'file {}: '.format(together[int(m.group(1))]) if m else ''
@@ -1848,7 +2030,7 @@ class Codec(object):
         return x_out[:, oy:oy + rh, ox:ox + rw].contiguous()
 
     def decompress_region(self, data, rect, channels=None):
-        """container bytes of a tiled file (formats 2, 4, 5, 6, 8), rect = (x, y, w, h) in pixels of the image (clipped to it, as
+        """container bytes of a tiled file (formats 2, 4, 5, 6, 8, 10), rect = (x, y, w, h) in pixels of the image (clipped to it, as
         --roi's) -> the HWC uint8 pixels of the rectangle, bit for bit decompress(data)[y:y + h, x:x + w]; with channels=K those of
         decompress(data, channels=K).
         The whole file is parsed and checked as decompress does -- sizes, every CRC, the model -- so a damaged file is refused
@@ -1871,8 +2053,7 @@ class Codec(object):
             return self._region_crop(self.decompress(data, channels=channels), plan)
         try:
             q = self.pred.decode_tiles_batch([(win.streams, win.first_syms, (win.C, win.h, win.w))], win.th, win.tw, want='q', channels=channels,
-                                             **(_ends_kw(win) if isinstance(win, LayeredContainer) else
-                                                {'order': 'wavefront' if isinstance(win, WavefrontContainer) else 'raster'}))[0]
+                                             **(_ends_kw(win) if isinstance(win, LayeredContainer) else _order_kw(win)))[0]
         except ValueError as e:
             raise ValueError('decoder status is not 0: {}'.format(e))
         return np.transpose(self._window_pixels(self.ae, q, plan, bits).cpu().numpy(), (1, 2, 0)).copy()
@@ -2045,6 +2226,7 @@ class Codec(object):
 
     def _check_target(self):
         """the refusals of the format this Codec writes, before anything is decoded"""
+        self._depth()
         self._front_ends()
         self._layer_ends()
         self._order()
@@ -2074,8 +2256,7 @@ class Codec(object):
             if isinstance(c, LayeredContainer):
                 return self.pred.decode_tiles_batch([(c.streams, c.first_syms, shape)], c.th, c.tw, want='symbols', **_ends_kw(c))[0]
             if isinstance(c, _TILED):
-                return self.pred.decode_tiles_batch([(c.streams, c.first_syms, shape)], c.th, c.tw, want='symbols',
-                                                    order='wavefront' if isinstance(c, WavefrontContainer) else 'raster')[0]
+                return self.pred.decode_tiles_batch([(c.streams, c.first_syms, shape)], c.th, c.tw, want='symbols', **_order_kw(c))[0]
             return self.pred.decode_stream(c.payload, shape, c.first_sym, on_device=True)
         except ValueError as e:
             raise ValueError('decoder status is not 0: {}'.format(str(e).replace('(volume 0, tile ', '(tile ')))
@@ -2189,6 +2370,7 @@ class Codec(object):
         Formats 1 and 2 carry no checksums to read a damaged file by: refused in salvage's words."""
         self._check_target()
         raw = bytes(data)
+        _refuse_depth(raw, 'repair')
         if len(raw) >= 6 and raw[:4] == MAGIC and struct.unpack('<H', raw[4:6])[0] in _LAYERED_VERSIONS:
             head = self._recover_head(raw)
             c = head[0]
@@ -2225,6 +2407,8 @@ class Codec(object):
     def written_version(self):
         """the format version of the files this Codec writes (its refusals are _check_target's)"""
         self._check_target()
+        if self._depth() is not None:
+            return FORMAT_VERSION_DEPTH
         if self._front_ends() is not None:
             return FORMAT_VERSION_FRONTS
         if self._layer_ends() is not None:
@@ -2353,6 +2537,13 @@ class Codec(object):
         img = self.decompress(data, channels=channels)
         Image.fromarray(img).save(image_path)
         return img
+
+
+def _order_kw(c):
+    """what decode_tiles_batch is told about the streams of an unlayered tiled container"""
+    if isinstance(c, DepthContainer):
+        return {'order': 'wavefront', 'depth_block': c.depth_block}
+    return {'order': 'wavefront' if isinstance(c, WavefrontContainer) else 'raster'}
 
 
 def _ends_kw(c):
@@ -2617,6 +2808,24 @@ def check_option_args(flags):
                              'default ones')
         if front_layers is not None:
             parse_layers_arg(front_layers, '--front-layers')
+    depth, depth_block = getattr(flags, 'depth', False), getattr(flags, 'depth_block', None)
+    if depth_block is not None and not depth:
+        raise ValueError('--depth-block needs --depth: it is the block side of the depth planes of format 10')
+    if depth:
+        if flags.command not in WRITING_COMMANDS:
+            raise ValueError('--depth belongs to compress / compress-dir: a file says by itself what it is')
+        if flags.tile is None:
+            raise ValueError('--depth needs --tile: format 10 stores a depth plane per tile')
+        if getattr(flags, 'wavefront', False):
+            raise ValueError('--depth does not go with --wavefront: format 10 implies the wavefront order, --wavefront writes format 5, '
+                             'which codes every position')
+        for name, on in (('--layers', layers is not None), ('--progressive', progressive), ('--front-layers', front_layers is not None),
+                         ('--front-progressive', front_progressive)):
+            if on:
+                raise ValueError('--depth does not go with {}: format 10 is one coder run per tile, the layered formats 6 and 8 cut a '
+                                 'tile into several'.format(name))
+        if depth_block is not None and not 1 <= depth_block <= 255:
+            raise ValueError('--depth-block {} is not in 1 .. 255'.format(depth_block))
     if getattr(flags, 'partial', False):
         if flags.command not in ('decompress', 'decompress-dir'):
             raise ValueError('--partial belongs to decompress / decompress-dir: it reads a prefix of a layered file')
@@ -2715,6 +2924,13 @@ def _layers_option(flags, C):
     return 'default' if getattr(flags, 'progressive', False) else None
 
 
+def _depth_option(flags):
+    """the `depth_block` argument of Codec for a command line: None without --depth, else --depth-block or its default"""
+    if not getattr(flags, 'depth', False):
+        return None
+    return DEFAULT_DEPTH_BLOCK if getattr(flags, 'depth_block', None) is None else int(flags.depth_block)
+
+
 def _front_layers_option(flags, C):
     """the `front_layers` argument of Codec for a command line, as _layers_option"""
     if getattr(flags, 'front_layers', None) is not None:
@@ -2753,7 +2969,7 @@ def _main_dir(flags, ae_config, pc_config):
         wts = val.load_weights_for_job(None, flags.weights, ae_config, pc_config)
     codec = Codec(ae_config, pc_config, wts, flags.device, tile=tile, checked=flags.checked,
                   order='wavefront' if flags.wavefront and tile is not None else 'raster',
-                  layers=layers, front_layers=front_layers)
+                  layers=layers, front_layers=front_layers, depth_block=_depth_option(flags) if tile is not None else None)
     channels = check_channels(getattr(flags, 'channels', None), codec.C)
     os.makedirs(flags.output, exist_ok=True)
     total_in = total_out = total_pixels = 0
@@ -3010,6 +3226,8 @@ def verify_file(data):
             G = len(c.layer_ends)
             return True, 'ok (format {}, {} bytes, G = {} layers, ends {}, prefix lengths {})'.format(
                 c.version, len(data), G, ','.join(str(e) for e in c.layer_ends), ','.join(str(layer_prefix_bytes(c, g)) for g in range(G + 1)))
+        if isinstance(c, DepthContainer):
+            return True, 'ok (format {}, {} bytes, depth blocks of {} cells)'.format(c.version, len(data), c.depth_block)
         return True, 'ok (format {}, {} bytes)'.format(c.version, len(data))
     except ValueError as strict:
         if len(data) >= 6 and data[:4] == MAGIC and struct.unpack('<H', data[4:6])[0] in _LAYERED_VERSIONS:
@@ -3091,6 +3309,17 @@ def info_file(data, region=None):
     if isinstance(c, LayeredContainer):
         lines.append('layer ends {}; bytes per layer {}'.format(','.join(str(e) for e in c.layer_ends),
                                                                 ','.join(str(sum(len(s) for s in layer)) for layer in c.segments)))
+    if isinstance(c, DepthContainer):
+        live, steps, plane_bytes = 0, [], 0
+        for (_, _, a, b), s in zip(tile_grid(c.h, c.w, c.th, c.tw), c.streams):
+            depth, _ = split_depth_stream(s, c.C, a, b, c.depth_block)
+            live += int(depth_live(c.C, a, b, depth, c.depth_block).sum())
+            steps.append(depth_front_steps(a, b, int(depth.max())))
+            plane_bytes += depth.size
+        lines.append('depth blocks of {} x {} cells, {} bytes of depth planes; live share {:.4f} ({} of {} positions are coded)'.format(
+            c.depth_block, c.depth_block, plane_bytes, live / float(c.C * c.h * c.w), live, c.C * c.h * c.w))
+        lines.append('front steps per tile: {} (all {} channels: {})'.format(
+            ','.join(str(n) for n in steps), c.C, ','.join(str(depth_front_steps(a, b, c.C)) for _, _, a, b in tile_grid(c.h, c.w, c.th, c.tw))))
     if region is not None:
         from . import config_parser
         ae_config, _ = config_parser.parse(_resolve_config(c.ae_name, 'ae_configs', 'CONFIG_BASE_AE'))
@@ -3208,6 +3437,12 @@ def main(argv=None):
                         'not with --wavefront, --layers or --progressive')
     p.add_argument('--front-progressive', dest='front_progressive', action='store_true',
                    help='compress / compress-dir with --tile: --front-layers with the default ends C/8, C/4, C/2, C')
+    p.add_argument('--depth', action='store_true',
+                   help='compress / compress-dir with --tile: depth-mapped tiles (format 10): the layout of --wavefront plus a depth plane per '
+                        'tile, and the positions above a block\'s depth -- which hold the fill symbol -- are neither coded nor decoded; '
+                        'not with --wavefront or the layered formats')
+    p.add_argument('--depth-block', dest='depth_block', type=int, default=None, metavar='B',
+                   help='--depth: blocks of B x B latent cells, 1 .. 255 (default {})'.format(DEFAULT_DEPTH_BLOCK))
     p.add_argument('--partial', action='store_true', help='decompress / decompress-dir: decode the complete layers of a (cut) format-6 / format-8 file and '
                                                           'print how many of them; not with --salvage or --channels')
     p.add_argument('--recover', action='store_true', help='decompress / decompress-dir: read what a damaged or cut format-6 file still holds, every '
@@ -3269,6 +3504,7 @@ def main(argv=None):
                 codec.order = 'wavefront' if flags.wavefront else 'raster'
                 codec.layers = layers
                 codec.front_layers = front_layers
+                codec.depth_block = _depth_option(flags)
             rois = [parse_roi_arg(r) for r in flags.roi or []]
         if flags.command == 'transcode':
             with open(flags.input, 'rb') as f:

@@ -811,20 +811,33 @@ __device__ __forceinline__ void pc_wave_chain(const float* __restrict__ in, int 
 // FROM sweeps keep every symbol they decode in `plane`, a byte per symbol in the slot's part of the workspace, (c, y, x) order of
 // the tile, and store nothing through out: the caller copies [cfrom, cdec) out of the plane behind the body.  A byte of the plane is
 // only ever copied out, never used as an index.  FROM = false reads none of this and is the decoder as before.
-template <bool SYMS, bool LIM = false, bool SEG = false, bool FROM = false>
+// DEPTH = true (IC_PC_DECODE_DEPTH, container format 10; only with LIM, without SEG): the stream holds the LIVE positions only,
+// c < depth[(y / dblock) * dnbx + x / dblock] (a byte above C counts as C); `depth` is the tile's plane, which the caller has taken off
+// the front of the stream (bits / nbytes are the coder's part), dmax its largest entry after the clamp, >= 1, and cdec =
+// min(channels, dmax).  No channel at or above dmax has a live position and none of them is in the context of a lower one (the masks
+// are causal in c), so the whole sweep -- cache phases and candidates -- runs over dmax channels in place of C.  Liveness is decided in
+// the parallel part of a chunk: the lanes of a dead slot compute no logits, the lane that owns the slot (co == 0) stores `fill`
+// through out and its centre into V there and then, and leaves a byte in s_live for wave 0, whose serial loop only steps over the
+// slot -- the plane is never read between two coder steps.  The first position is uncoded as ever; dead, it is `fill` like any other.
+template <bool SYMS, bool LIM = false, bool SEG = false, bool FROM = false, bool DEPTH = false>
 __device__ __forceinline__ void pc_dec_wave_body(const PcCachedArgs& f, const unsigned char* bits, long long nbytes, int h, int w, int first_sym,
                                                  float* vol, float* c0, float* c1, float* c2, int* status,
                                                  long long* __restrict__ out, long long out_cs, int out_rs, int cdec = 0,
                                                  const unsigned char* seg_base = nullptr, const ic_pc_seg_t* __restrict__ segs = nullptr,
                                                  const int* __restrict__ ends = nullptr, int nlayers = 0, int gfrom = 0,
-                                                 unsigned char* __restrict__ plane = nullptr) {
+                                                 unsigned char* __restrict__ plane = nullptr,
+                                                 const unsigned char* __restrict__ depth = nullptr, int dblock = 1, int dnbx = 0, int dmax = 0,
+                                                 int fill = 0) {
     static_assert(!FROM || (LIM && SEG), "a sweep continues at a layer cut of a limited sweep");
+    static_assert(!DEPTH || (LIM && !SEG), "the depth plane belongs to the unsegmented limited sweep");
     constexpr int K = 24, G = K / 4, CH = 64;             // CH: candidates of a front whose logits are in LDS at once
-    __shared__ float s_logits[CH][16];
+    __shared__ float s_logits[CH + (DEPTH ? 1 : 0)][16];  // DEPTH: one more row, CH bytes: s_live
     __shared__ float s_centers[16];
+    static_assert(sizeof(float) * 16 == CH, "s_live is one row of s_logits");
+    unsigned char* const s_live = reinterpret_cast<unsigned char*>(s_logits[DEPTH ? CH : 0]);       // (read and written with DEPTH only)
     const PcDecArgs& a = f.d;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int L = a.L, C = a.C;
+    const int L = a.L, C = DEPTH ? dmax : a.C;            // DEPTH: the channels that hold anything
     if (tid < L) s_centers[tid] = a.centers[tid];
     bool resumed = false;
     int cfrom = 0;
@@ -933,15 +946,30 @@ __device__ __forceinline__ void pc_dec_wave_body(const PcCachedArgs& f, const un
                 const int slot = n / L, co = n - slot * L;
                 int c, y, x;
                 if (!pc_front_voxel(fr, cb + slot, c, y, x)) continue;
+                if constexpr (DEPTH) {
+                    // (a load of the plane, behind the check of the stream's length that the caller has made: off the serial path)
+                    const bool live = c < min((int)depth[(y / dblock) * dnbx + x / dblock], C);
+                    if (co == 0) {
+                        s_live[slot] = live ? 1 : 0;
+                        if (!live) {
+                            if (SYMS && c < cdec) out[(long long)c * out_cs + (long long)y * out_rs + x] = fill;
+                            vol[((size_t)(c + 4) * PH + y + 4) * PW + x + 4] = s_centers[fill];
+                        }
+                    }
+                    if (!live) continue;
+                }
                 float v[1];
                 pc_wave_chain<1>(c2 + (((size_t)c * N2i + y) * N2j + x) * K, N2i, N2j, f.w3 + co, L, v);
                 s_logits[slot][co] = fmaxf(v[0] + f.b3[co], 0.f);
             }
             __syncthreads();
             if (wave == 0) {
+                unsigned long long livemask = ~0ull;                              // DEPTH: the chunk's live bytes as one scalar word
+                if constexpr (DEPTH) livemask = __ballot(lane < nc && s_live[lane] != 0);
                 for (int k = 0; k < nc; ++k) {
                     int c, y, x;
                     if (!pc_front_voxel(fr, cb + k, c, y, x)) continue;          // wave-uniform
+                    if constexpr (DEPTH) if (!((livemask >> k) & 1)) continue;   // dead: stored by the slot's lane above
                     int sym = first_sym;                                          // the first symbol is not coded
                     if ((c | y | x) != 0) {
                         const float logit = (lane >= 48 && lane < 48 + L) ? s_logits[k][lane - 48] : 0.f;
@@ -994,6 +1022,7 @@ struct PcTilesBatchArgs {
     int* done;                        //   and the channels the workspace holds of every tile (ntiles; written by the kernel alone)
     unsigned char* planes;            // WAVE FROM kernels only: a byte per symbol of every tile, plane_bytes per tile, (c, y, x) order
     size_t plane_bytes;               //   of the tile's own extent (written and read by the kernel alone)
+    int depth_block;                  // DEPTH kernels only: the side b of a block of the depth plane, 1 .. 255
 };
 
 // SEG: the tile's stream is its nlayers segments, segs[blockIdx.x * nlayers + g]; the descriptor's stream_off / stream_bytes are not
@@ -1018,10 +1047,16 @@ struct PcTilesBatchArgs {
 // `symbols`; it keeps every symbol it steps through in the tile's byte plane (see the body), and the copy loop writes the symbols of
 // [cfrom, cdec) from the plane next to q from V.  The plane of a tile holds every symbol of the channels below cdec after a sweep to
 // cdec, whichever launches decoded them: each lies on a front <= T_last(cdec), and every front is swept once.
-template <bool WAVE, bool SYMS, bool LIM = false, bool SEG = false, bool PER = false, bool FROM = false>
+// DEPTH (ic_pc_decode_tiles_batch_channels_f32 with IC_PC_DECODE_DEPTH(b); WAVE && LIM only, channels == C included): the first
+// nby * nbx bytes of the tile's stream, nby = ceil(th / b), nbx = ceil(tw / b), are its depth plane and the coder starts behind them.
+// A stream shorter than that: status 2, nothing decoded, nothing written.  All 256 lanes reduce the plane's largest entry (clamped to
+// C) to dmax; the sweep is the LIM sweep to cdec = min(channels, dmax) over dmax channels, and the copy loop's fill covers the
+// channels from cdec up -- dead everywhere, or beyond the preview.  dmax == 0: no body at all, status 0, everything is fill.
+template <bool WAVE, bool SYMS, bool LIM = false, bool SEG = false, bool PER = false, bool FROM = false, bool DEPTH = false>
 __global__ __launch_bounds__(256) void pc_dec_tiles_batch_kernel(const PcTilesBatchArgs t) {
     static_assert(!PER || (LIM && SEG), "the limit per tile belongs to the segmented decoders: a limited sweep over a tile's segments");
     static_assert(!FROM || PER, "a sweep continues where a sweep with a limit per tile stopped");
+    static_assert(!DEPTH || (WAVE && LIM && !SEG), "the depth plane belongs to the unsegmented wavefront sweep with a limit");
     constexpr int DONE_SIGN = (WAVE && FROM) ? -1 : 1, DONE_BASE = (WAVE && FROM) ? -2 : 0;     // done word of a status-0 sweep to c: DONE_BASE + DONE_SIGN * c
     const ic_pc_tile_t tl = t.tiles[blockIdx.x];
     // v = volumes ? volumes[tl.volume] : one, as a uniform branch around a scalar load.  (Written as a select, it becomes a select
@@ -1071,6 +1106,28 @@ __global__ __launch_bounds__(256) void pc_dec_tiles_batch_kernel(const PcTilesBa
                                           (float*)(slot + t.off_c0), (float*)(slot + t.off_c1), (float*)(slot + t.off_c2), t.status + blockIdx.x,
                                           SYMS ? t.symbols + v.symbols_off + corner : nullptr, plane, v.w, cdec,
                                           t.bits, segs, t.ends, t.nlayers);
+    } else if constexpr (DEPTH) {
+        __shared__ int s_dmax;
+        const int b = t.depth_block, nbx = (tl.tw + b - 1) / b, nd = ((tl.th + b - 1) / b) * nbx;        // nd <= th * tw
+        if (tl.stream_bytes < nd) {                       // (uniform) no room for the plane: not a stream of this format
+            if (threadIdx.x == 0) t.status[blockIdx.x] = 2;
+            return;
+        }
+        const unsigned char* depth = t.bits + tl.stream_off;
+        if (threadIdx.x == 0) s_dmax = 0;
+        __syncthreads();
+        int m = 0;
+        for (int i = threadIdx.x; i < nd; i += 256) m = max(m, min((int)depth[i], t.f.d.C));
+        if (m) atomicMax(&s_dmax, m);                     // LDS; once per tile
+        __syncthreads();
+        const int dmax = s_dmax;
+        cdec = min(cdec, dmax);
+        if (dmax > 0)
+            pc_dec_wave_body<SYMS, true, false, false, true>(t.f, depth + nd, tl.stream_bytes - nd, tl.th, tl.tw, tl.first_sym, (float*)slot,
+                                                             (float*)(slot + t.off_c0), (float*)(slot + t.off_c1), (float*)(slot + t.off_c2), t.status + blockIdx.x,
+                                                             SYMS ? t.symbols + v.symbols_off + corner : nullptr, plane, v.w, cdec,
+                                                             nullptr, nullptr, nullptr, 0, 0, nullptr, depth, b, nbx, dmax, t.fill);
+        else if (threadIdx.x == 0) t.status[blockIdx.x] = 0;
     } else if constexpr (WAVE)
         pc_dec_wave_body<SYMS, LIM>(t.f, t.bits + tl.stream_off, tl.stream_bytes, tl.th, tl.tw, tl.first_sym, (float*)slot,
                                     (float*)(slot + t.off_c0), (float*)(slot + t.off_c1), (float*)(slot + t.off_c2), t.status + blockIdx.x,
@@ -1294,7 +1351,7 @@ extern "C" int ic_pc_decode_f32(const uint8_t* bitstream, long long nbytes, int 
                                 int C, int h, int w, void* workspace, size_t workspace_bytes, int flags, ic_stream_t stream) {
     IC_CHECK_ARG(bitstream && wtab_host && centers && symbols && status && workspace);
     IC_CHECK_ARG(nbytes >= 0 && C > 0 && h > 0 && w > 0 && k > 0 && L > 0 && first_sym >= 0 && first_sym < L);
-    if (L > 16 || (flags & IC_PC_DECODE_WAVEFRONT)) return IC_ERR_UNSUPPORTED;      // (the wavefront order: the batch entry only)
+    if (L > 16 || (flags & (IC_PC_DECODE_WAVEFRONT | IC_PC_DECODE_DEPTH(0xff)))) return IC_ERR_UNSUPPORTED;      // (the wavefront order: the batch entry only; the depth plane: its channels form only)
     if (workspace_bytes < ic_pc_decode_workspace_bytes(C, h, w, k)) return IC_ERR_WORKSPACE;
     return pc_decode_impl(bitstream, nbytes, first_sym, wtab_host, centers, k, L, resolution, symbols, status, C, h, w, workspace,
                           flags, C, 0, stream);
@@ -1393,6 +1450,7 @@ struct PcTilesRequest {
     int order;                                        // what the decoder is told.  PC_TILES_SEGS: 0 (raster, plane cuts) or IC_PC_DECODE_WAVEFRONT
                                                       //   (front cuts), the caller's own flags must be 0 for both; else the caller's flags
     int th_max, tw_max;                               // the largest tile: pc_tiles_check fills them in
+    int depth_block;                                  // IC_PC_DECODE_DEPTH(b) of the caller's flags, 0 without: pc_tiles_check fills it in
 };
 
 // the arguments that all entries but the single-volume one begin with, and the values of a full decode of unsegmented streams
@@ -1457,6 +1515,15 @@ static int pc_tiles_check(PcTilesRequest& r, PcTilesLayout& l) {
         r.tw_max = d.tw > r.tw_max ? d.tw : r.tw_max;
     }
     if (r.L > 16) return IC_ERR_UNSUPPORTED;
+    // the depth plane (bits 8 - 15 of the flags) has one decoder too: the wavefront sweep with a limit of the k = 24 kernel, so the flag
+    // is the channels entry's alone, there only beside IC_PC_DECODE_WAVEFRONT, and unsupported everywhere else.  Behind this the flags
+    // are what they are without it.
+    r.depth_block = (r.flags >> 8) & 0xff;
+    if (r.depth_block) {
+        if (!r.takes_channels || !batch || segmented || r.k != 24 || r.flags != (IC_PC_DECODE_WAVEFRONT | IC_PC_DECODE_DEPTH(r.depth_block)))
+            return IC_ERR_UNSUPPORTED;
+        r.flags = r.order = IC_PC_DECODE_WAVEFRONT;
+    }
     // the wavefront order has one decoder, the k = 24 kernel: no slow path, no combination with the test flags -- and as a flag it
     // is the unsegmented batch entries' alone (the fronts entries are told by their name, their flags are 0 like the layers entries')
     if ((r.flags & IC_PC_DECODE_WAVEFRONT) && (!batch || segmented || r.k != 24 || r.flags != IC_PC_DECODE_WAVEFRONT)) return IC_ERR_UNSUPPORTED;
@@ -1467,14 +1534,16 @@ static int pc_tiles_check(PcTilesRequest& r, PcTilesLayout& l) {
     return IC_OK;
 }
 
-// the form of pc_dec_tiles_batch_kernel for a launch, by its six template arguments (per implies lim and seg, from implies per): the
-// 24 forms named here are the ones the file instantiates
+// the form of pc_dec_tiles_batch_kernel for a launch, by its template arguments (per implies lim and seg, from implies per; depth is
+// the wavefront sweep with a limit and without segments): the 26 forms named here are the ones the file instantiates
 typedef void (*PcTilesKernel)(const PcTilesBatchArgs);
 template <bool WAVE, bool LIM, bool SEG, bool PER, bool FROM>
 static PcTilesKernel pc_tiles_kernel_of(bool syms) {
     return syms ? pc_dec_tiles_batch_kernel<WAVE, true, LIM, SEG, PER, FROM> : pc_dec_tiles_batch_kernel<WAVE, false, LIM, SEG, PER, FROM>;
 }
-static PcTilesKernel pc_tiles_kernel(bool wave, bool syms, bool lim, bool seg, bool per, bool from) {
+static PcTilesKernel pc_tiles_kernel(bool wave, bool syms, bool lim, bool seg, bool per, bool from, bool depth) {
+    if (depth) return syms ? pc_dec_tiles_batch_kernel<true, true, true, false, false, false, true>
+                           : pc_dec_tiles_batch_kernel<true, false, true, false, false, false, true>;     // (pc_tiles_check: wave, not seg)
     if (!seg) return !lim ? (wave ? pc_tiles_kernel_of<true, false, false, false, false>(syms) : pc_tiles_kernel_of<false, false, false, false, false>(syms))
                           : (wave ? pc_tiles_kernel_of<true, true, false, false, false>(syms) : pc_tiles_kernel_of<false, true, false, false, false>(syms));
     if (!wave) return !lim ? pc_tiles_kernel_of<false, false, true, false, false>(syms) : !per ? pc_tiles_kernel_of<false, true, true, false, false>(syms)
@@ -1533,9 +1602,9 @@ static int pc_decode_tiles_impl(const PcTilesRequest& r, const PcTilesLayout& l)
         else
             hipLaunchKernelGGL(pc_dec_fill_slots_kernel, dim3((unsigned)((nvol + 255) / 256), (unsigned)ntiles), dim3(256), 0, st,
                                a.slots, a.slot_bytes, nvol, r.centers);
-        a.cdec = r.channels; a.fill = r.fill_sym;
+        a.cdec = r.channels; a.fill = r.fill_sym; a.depth_block = r.depth_block;
         const PcTilesKernel kernel = pc_tiles_kernel(wavefront, r.symbols != nullptr, r.tile_channels || r.channels < C, r.nlayers != 0,
-                                                     r.tile_channels != nullptr, r.tile_from != nullptr);
+                                                     r.tile_channels != nullptr, r.tile_from != nullptr, r.depth_block != 0);
         hipLaunchKernelGGL(kernel, dim3((unsigned)ntiles), dim3(256), 0, st, a);
         IC_LAUNCH_CHECK();
         return IC_OK;

@@ -117,13 +117,22 @@ __device__ __forceinline__ void pce_code_range(const float* __restrict__ logits,
             // ---- producer: the table of symbol i, reduced to what the coder needs of it ----
             const long long i = first + c * PCE_CHUNK + lane;
             const int b = (int)(c & 1);
-            if (i < end) {
+            const long long sym = i < end ? symbols[i] : 0;
+            if (i < end && sym == IC_PC_ENCODE_SKIP) {
+                // a position the stream does not code: the whole interval, (cum_lo, cum_hi, total) = (0, 1, 1).  With r = high - low + 1
+                // the coder's step gives high = low + r - 1 and low += 0, both unchanged, and the state it starts from is renormalised
+                // (top bits differ, no underflow position), so nothing is shifted out either: the serial loop steps over it as it is.
+                // The logits of the position are not read.
+                s_lo[b][lane] = 0u;
+                s_hi[b][lane] = 1u;
+                s_tot[b][lane] = 1u;
+                s_inv[b][lane] = 1.0;
+            } else if (i < end) {
                 float l[LC];
 #pragma unroll
                 for (int j = 0; j < LC; ++j) l[j] = logits[i * LC + j];
                 long long fr[LC];
                 pc_table_row(l, LC, resolution, fr, nullptr);
-                const long long sym = symbols[i];
                 unsigned long long lo = 0, f = 0, total = 0;
                 bool big = false;
 #pragma unroll

@@ -346,7 +346,7 @@ class PredictionNetwork(object):
         """(pr, freqs), each (num_contexts, L), contexts in the order of iter_over_blocks."""
         return self._tables(symbols_padded)
 
-    def encode_stream(self, symbols, capacity=None, order='raster', seg_ends=None):
+    def encode_stream(self, symbols, capacity=None, order='raster', seg_ends=None, depth_block=None):
         """The mirror of decode_stream: the whole coding side on the device (ic_pc_encode_f32).  symbols: un-padded (C,h,w) numpy /
         tensor -> (stream_bytes, first_sym); a batch (N,C,h,w) -> a list of N such pairs, coded concurrently by ONE launch.
         The tables are bit for bit those of get_all(pad_symbols_volume(symbols)) -- the symbol volume padded with symbol 0, the
@@ -357,7 +357,11 @@ class PredictionNetwork(object):
         are gathered through the permutation on the device, the kernel codes what it is given; the first symbol is the same.
         seg_ends=[n_0 < n_1 < ... = C h w] (raster only; ic_pc_encode_segments_f32): the volume's symbols cut at these cumulative counts
         into independent coder runs, one work-group each -- run s is arithmetic_coding.encode_sequence(flat[a:b], freqs[a:b]) with
-        a = max(1, n_{s-1}), b = n_s, over the same tables.  -> ([segment bytes ...], first_sym) per volume; capacity is per segment."""
+        a = max(1, n_{s-1}), b = n_s, over the same tables.  -> ([segment bytes ...], first_sym) per volume; capacity is per segment.
+        depth_block=B (order='wavefront' only, container format 10): the stream is codec.depth_plane(symbols, fill, B) as bytes, then
+        the coder's bytes over the LIVE positions of the wavefront order alone (codec.depth_live_mask): the plane and the mask are a
+        few tensor operations on the device, the dead positions go to the same launch as IC_PC_ENCODE_SKIP and are stepped over.  The
+        tables are those of the whole volume, as ever.  fill is conceal_fallback(), the centre nearest zero."""
         dev = self.centers.device
         sym = symbols if torch.is_tensor(symbols) else torch.as_tensor(np.ascontiguousarray(symbols))
         batched = sym.dim() == 4
@@ -378,6 +382,16 @@ class PredictionNetwork(object):
             coded = sym.view(N, count).index_select(1, perm).contiguous()
         elif order != 'raster':
             raise ValueError("order is 'raster' or 'wavefront', got {!r}".format(order))
+        planes = None
+        if depth_block is not None:
+            from .codec import check_depth_block
+            B = check_depth_block(depth_block, C)
+            if order != 'wavefront' or seg_ends is not None:
+                raise ValueError("depth_block leaves positions out of the wavefront order: order is {!r}{}".format(
+                    order, '' if seg_ends is None else ', with seg_ends'))
+            planes, keep = self._depth_plane(sym, B)
+            coded = torch.where(keep, sym, torch.full_like(sym, _lib.PC_ENCODE_SKIP)).view(N, count).index_select(1, perm).contiguous()
+            planes = planes.to(torch.uint8).cpu().numpy()
         if seg_ends is not None:
             if order != 'raster':
                 raise ValueError("seg_ends cuts a raster stream: order is {!r}".format(order))
@@ -398,8 +412,22 @@ class PredictionNetwork(object):
             if status[n] != 0:
                 raise ValueError('device range encoder: {} (status {})'.format(
                     {2: 'stream capacity too small', 3: 'symbol outside [0, L)'}.get(status[n], 'error'), status[n]))
-            res.append((bytes(out[n, :nbytes[n]].cpu().numpy()), int(sym[n, 0, 0, 0])))
+            head = b'' if planes is None else planes[n].tobytes()
+            res.append((head + bytes(out[n, :nbytes[n]].cpu().numpy()), int(sym[n, 0, 0, 0])))
         return res if batched else res[0]
+
+    def _depth_plane(self, sym, B):
+        """codec.depth_plane and the live positions of a batch (N,C,h,w) of symbol volumes on their device -> ((N, ceil(h/B), ceil(w/B))
+        int64 depths, (N,C,h,w) bool keep)"""
+        N, C, h, w = (int(v) for v in sym.shape)
+        fill = self.conceal_fallback()
+        chan = torch.arange(C, device=sym.device).view(1, C, 1, 1)
+        cell = ((sym != fill) * (chan + 1)).amax(1)                      # per cell: 1 + the deepest channel that holds something, 0: none
+        nby, nbx = -(-h // B), -(-w // B)
+        cell = torch.nn.functional.pad(cell, (0, nbx * B - w, 0, nby * B - h))
+        depth = cell.view(N, nby, B, nbx, B).amax((2, 4))
+        per_cell = depth.repeat_interleave(B, 1).repeat_interleave(B, 2)[:, :h, :w]
+        return depth, chan < per_cell[:, None]
 
     @staticmethod
     def _encode_status(st):
@@ -488,7 +516,7 @@ class PredictionNetwork(object):
             raise ValueError('Cannot decode symbol because total is too large')
         return out if on_device else out.cpu().numpy()
 
-    def encode_tiles(self, symbols, th, tw, order='raster', layer_ends=None, front_ends=None):
+    def encode_tiles(self, symbols, th, tw, order='raster', layer_ends=None, front_ends=None, depth_block=None):
         """symbols: un-padded (C,h,w) -> [(stream_bytes, first_sym)] for the tiles of codec.tile_grid(h, w, th, tw), in grid order.
         Every tile is coded as a volume of its own: its stream is encode_stream(symbols[:, y0:y0+th', x0:x0+tw']) byte for byte.
         Tiles of one shape (at most four: interior, right column, bottom row, corner) are one encode_stream batch, one launch.
@@ -497,9 +525,12 @@ class PredictionNetwork(object):
         (encode_stream(seg_ends=[e th' tw' ...])) -> [([segment bytes per layer], first_sym)].
         front_ends=[e_0 < ... = C] (container format 8; not with layer_ends or order='wavefront', the order is implied): every tile's
         stream in the wavefront order of its own extent, cut at that extent's fronts codec.front_layer_cuts(C, th', tw', front_ends)
-        (_encode_fronts) -> [([segment bytes per layer], first_sym)]."""
+        (_encode_fronts) -> [([segment bytes per layer], first_sym)].
+        depth_block=B (order='wavefront' only, container format 10): every tile's stream is its own depth plane, blocks counted from the
+        tile's corner, then the coder's bytes of its live positions (encode_stream)."""
         from .codec import tile_grid
         self._check_front_ends(front_ends, order, layer_ends)
+        self._check_depth_block(depth_block, order, layer_ends, front_ends)
         sym = symbols if torch.is_tensor(symbols) else torch.as_tensor(np.ascontiguousarray(symbols))
         assert sym.dim() == 3, 'Expected CHW symbols'
         sym = sym.to(self.centers.device).long()
@@ -511,7 +542,8 @@ class PredictionNetwork(object):
         for (a, b), members in by_shape.items():
             batch = torch.stack([sym[:, grid[t][0]:grid[t][0] + a, grid[t][1]:grid[t][1] + b] for t in members])
             seg_ends = None if layer_ends is None else [int(e) * a * b for e in layer_ends]
-            coded = self._encode_fronts(batch, front_ends) if front_ends is not None else self.encode_stream(batch, order=order, seg_ends=seg_ends)
+            coded = (self._encode_fronts(batch, front_ends) if front_ends is not None else
+                     self.encode_stream(batch, order=order, seg_ends=seg_ends, depth_block=depth_block))
             for t, r in zip(members, coded):
                 res[t] = r
         return res
@@ -521,6 +553,12 @@ class PredictionNetwork(object):
         if front_ends is not None and (layer_ends is not None or order != 'raster'):
             raise ValueError("front_ends cuts the wavefront order at fronts by itself: not with layer_ends (plane cuts of the raster "
                              "order) or order={!r}".format(order))
+
+    @staticmethod
+    def _check_depth_block(depth_block, order, layer_ends, front_ends):
+        if depth_block is not None and (order != 'wavefront' or layer_ends is not None or front_ends is not None):
+            raise ValueError("depth_block leaves positions out of the wavefront order: it needs order='wavefront' (got {!r}) and goes "
+                             "with neither layer_ends nor front_ends".format(order))
 
     def decode_tiles(self, streams, first_syms, symbols_shape, th, tw, flags=0, channels=None):
         """The mirror of encode_tiles: all tiles of a volume decoded by ONE launch, one work-group per tile
@@ -554,14 +592,16 @@ class PredictionNetwork(object):
                 raise ValueError('Cannot decode symbol because total is too large (tile {} at ({}, {}))'.format(t, grid[t][0], grid[t][1]))
         return out.cpu().numpy()
 
-    def encode_tiles_batch(self, volumes, th, tw, order='raster', layer_ends=None, front_ends=None):
+    def encode_tiles_batch(self, volumes, th, tw, order='raster', layer_ends=None, front_ends=None, depth_block=None):
         """encode_tiles for a list of un-padded (C,h,w) symbol volumes of any mix of (h, w): -> per volume the list encode_tiles
         gives for it, byte for byte.  The tiles of ALL volumes are grouped by tile shape -- for a folder of equal-sized images the
         same four shapes as for one -- and each group is one encode_stream batch, one ic_pc_encode_f32 launch.
         layer_ends: as encode_tiles, the ends converted to symbol counts per tile shape (raster only).
-        front_ends: as encode_tiles, every tile shape by its own cuts."""
+        front_ends: as encode_tiles, every tile shape by its own cuts.
+        depth_block: as encode_tiles."""
         from .codec import tile_grid
         self._check_front_ends(front_ends, order, layer_ends)
+        self._check_depth_block(depth_block, order, layer_ends, front_ends)
         dev = self.centers.device
         syms, grids = [], []
         for v in volumes:
@@ -577,13 +617,14 @@ class PredictionNetwork(object):
         for (_, a, b), members in by_shape.items():
             batch = torch.stack([syms[n][:, grids[n][t][0]:grids[n][t][0] + a, grids[n][t][1]:grids[n][t][1] + b] for n, t in members])
             seg_ends = None if layer_ends is None else [int(e) * a * b for e in layer_ends]
-            coded = self._encode_fronts(batch, front_ends) if front_ends is not None else self.encode_stream(batch, order=order, seg_ends=seg_ends)
+            coded = (self._encode_fronts(batch, front_ends) if front_ends is not None else
+                     self.encode_stream(batch, order=order, seg_ends=seg_ends, depth_block=depth_block))
             for (n, t), r in zip(members, coded):
                 res[n][t] = r
         return res
 
     def decode_tiles_batch(self, volumes, th, tw, want='q', max_workspace_bytes=1 << 31, flags=0, conceal=False, order='raster',
-                           channels=None, layer_ends=None, tile_layers=None, front_ends=None):
+                           channels=None, layer_ends=None, tile_layers=None, front_ends=None, depth_block=None):
         """The mirror of encode_tiles_batch: the tiles of ALL volumes decoded by one launch per chunk (ic_pc_decode_tiles_batch_f32,
         one work-group per tile).  volumes: [(streams, first_syms, (C,h,w))], each as decode_tiles takes them, one C throughout.
         want: 'q' -> per volume the (C,h,w) float32 DEVICE tensor centers[symbols] (what ae.decode consumes: the symbols never
@@ -613,8 +654,19 @@ class PredictionNetwork(object):
         front_ends=[e_0 < ... = C] (container format 8, ic_pc_decode_tiles_batch_fronts_f32 / _fronts_pertile_f32): everything said of
         layer_ends -- channels, tile_layers, what may be None, what is returned -- for streams[t] = the tile's G segments of its
         wavefront order cut at fronts, as encode_tiles(front_ends=...) gives them.  Not with layer_ends or order='wavefront' (the
-        order is implied)."""
-        from .codec import tile_grid, chunk_tiles, check_channels, check_layer_ends
+        order is implied).
+        depth_block=B (container format 10; order='wavefront', k = 24, flags 0; not with conceal=True, layer_ends, tile_layers or
+        front_ends): streams[t] is the tile's depth plane, then the coder's bytes of its live positions, as
+        encode_tiles(order='wavefront', depth_block=B) gives them; sets PC_DECODE_DEPTH(B) on ic_pc_decode_tiles_batch_channels_f32,
+        whose `channels` is C unless channels=K asks for a preview.  A dead position holds the fill symbol / its centre.  A stream
+        shorter than its plane is a ValueError that names the tile."""
+        from .codec import tile_grid, chunk_tiles, check_channels, check_layer_ends, check_depth_block
+        if depth_block is not None:
+            self._check_depth_block(depth_block, order, layer_ends, front_ends)
+            if conceal or tile_layers is not None or int(flags) != 0:
+                raise ValueError('depth_block does not go with conceal=True, tile_layers or flags ({})'.format(flags))
+            if self.pc._k != 24:
+                raise ValueError('depth-mapped tiles need a context model of width k = 24, this one has k = {}'.format(self.pc._k))
         fronts = front_ends is not None
         if fronts:
             self._check_front_ends(front_ends, order, layer_ends)
@@ -687,6 +739,10 @@ class PredictionNetwork(object):
         tiles = [cell for _, _, cell, _, _, _ in listed]
         C, k = shapes[0][0], self.pc._k
         preview = self._preview(channels, C)
+        if depth_block is not None:
+            flags = int(flags) | _lib.PC_DECODE_DEPTH(check_depth_block(depth_block, C))
+            if preview is None:
+                preview = (C, self.conceal_fallback())            # the entry that takes the flag: channels == C is the full decode
         G = 0 if layer_ends is None else len(ends)
         vtable, offs, total = _lib.packed_volume_table(shapes)
 
@@ -743,6 +799,8 @@ class PredictionNetwork(object):
         for i, st in enumerate(status.tolist()):            # (the host waits here: the tables and the streams are done with)
             if st != 0:
                 n, t, y0, x0 = where[i]
+                if depth_block is not None and st == 2:
+                    raise ValueError('stream shorter than its depth plane (volume {}, tile {} at ({}, {}))'.format(n, t, y0, x0))
                 if not conceal:
                     raise ValueError('Cannot decode symbol because total is too large (volume {}, tile {} at ({}, {}))'.format(n, t, y0, x0))
                 damage[n].append((t, 'decoder'))

@@ -105,6 +105,18 @@ int ic_build_has_tuning_forms(void);
 /* ic_pc_decode_tiles_batch_f32: every tile's stream codes its symbols front by front -- sorted by (T, c, y, x) with
  * T = x + 2 y + 4 c in tile coordinates, the first one uncoded (container format 5) -- and is decoded a front at a time */
 #define IC_PC_DECODE_WAVEFRONT    0x04
+/* ic_pc_decode_tiles_batch_channels_f32 with IC_PC_DECODE_WAVEFRONT and k = 24 only (container format 10): every tile's stream begins
+ * with a DEPTH PLANE, one byte per b x b block of latent cells counted from the tile's corner (ceil(th / b) x ceil(tw / b) bytes,
+ * row-major, ragged at the far edges; b in 1 .. 255), then the range coder's bytes.  Position (c, y, x) of a tile is LIVE iff
+ * c < depth[y / b][x / b] (a byte above C counts as C).  The coder's bytes hold the live positions of the wavefront order only, the
+ * first position uncoded as ever; a dead position decodes to fill_sym without a coder step, whatever first_sym says.  The sweep
+ * ends with the last front of channel min(channels, largest depth byte of the tile) - 1.  A tile whose stream is shorter than its
+ * depth plane gets status 2 and nothing of it is written.  Every other entry, every other flag beside it and every other k:
+ * IC_ERR_UNSUPPORTED, decided on the host. */
+#define IC_PC_DECODE_DEPTH(b)     (((b) & 0xff) << 8)
+/* ic_pc_encode_f32 / ic_pc_encode_segments_f32: a symbol equal to this is stepped over -- nothing is coded for it and its logits
+ * are not read (the positions a format-10 stream leaves out).  Every other value outside [0, L) stays status 3. */
+#define IC_PC_ENCODE_SKIP         (-1)
 
 int ic_abi_version(void);
 /* static string for a return code of this library (hipGetErrorString for codes > 0) */
@@ -536,7 +548,9 @@ int ic_pc_conceal_tiles_channels(int64_t* symbols, float* q, const ic_pc_tile_t*
  *   bitstream: out, device (N, capacity);  nothing is ever stored at or beyond `capacity` of a volume
  *   nbytes: out, device (N): bytes written, the zero-padded last byte included
  *   status: out, device (N): 0 ok, 1 = a table's total exceeded 2^30 + 2, 2 = capacity too small (the stream is cut off),
- *           3 = a symbol outside [0, L)
+ *           3 = a symbol outside [0, L) other than IC_PC_ENCODE_SKIP
+ *   A symbol equal to IC_PC_ENCODE_SKIP (-1) is stepped over: the bytes are those of encode_sequence over the other symbols and
+ *   their rows.  All of symbols[1:] skipped gives the one byte 0x80.
  * ic_pc_encode_capacity_bytes(count) = 4 count + 16 always suffices (a coder step commits at most 32 bits; measured worst case
  * 30.5 bits per symbol: frequency 1 of a total of 2^30 + 2, repeated). */
 size_t ic_pc_encode_capacity_bytes(long long count);
