@@ -50,6 +50,17 @@ def PC_DECODE_DEPTH(b):
     return (int(b) & 0xff) << 8
 
 
+def PC_DECODE_RANS(w):
+    """IC_PC_DECODE_RANS(W): ic_pc_decode_tiles_batch_channels_f32, alone in the flags: every stream is that of W interleaved rANS
+    coders (format 12)"""
+    return (int(w) & 0xff) << 16
+
+
+def PC_ENCODE_RANS(w):
+    """IC_PC_ENCODE_RANS(W): the `nsegs` of ic_pc_encode_segments_f32 that selects the interleaved rANS coder with W coders"""
+    return -int(w)
+
+
 def conv3_leave_idle_layers(n):
     return (n & 0x7f) << 12
 

@@ -3,7 +3,7 @@
     python -m imgcomp_cvpr_amd.codec compress   IN.png  OUT.icf [--ae_config cvpr/low] [--pc_config cvpr/res_shallow] [--weights synthetic|FILE.npz|CKPT]
                                                                 [--tile PIXELS [--checked | --wavefront | --layers a,b,.. | --progressive |
                                                                                 --front-layers a,b,.. | --front-progressive |
-                                                                                --depth [--depth-block B]]]
+                                                                                --depth [--depth-block B] | --rans [--lanes W]]]
                                                                 [--cap T | --max-bytes N | --bpp B | --min-psnr D | --min-ms-ssim S]
                                                                 [--roi X,Y,W,H ... [--background T]]
     python -m imgcomp_cvpr_amd.codec decompress IN.icf  OUT.png [same options] [--salvage | --channels K | --partial | --recover]
@@ -143,6 +143,18 @@ decompress, --channels K, --region, the -dir commands, transcode to and from it,
 format 5; verify and info are host only (info prints B, the live share and the front steps per tile the depths imply).  --salvage,
 --partial, --recover, stream and repair refuse a format-10 file in one sentence.  Not with --wavefront or the layered formats; a
 context model the wavefront order refuses, or of another width than k = 24, is refused.
+--tile --rans [--lanes W] (Codec(tile=(th, tw), rans=W | 'default')): format 12, "lane-parallel rANS tiles" -- the layout of format 10
+with the number of coders W (8, 16, 32 or 64, default 16) as the '<H' where format 10 keeps its block size; 11 is not used and is
+refused.  Every tile's stream is that of W interleaved rANS coders: position (c, y, x) lies on front t = x + 2 y + 4 c, where it has
+the candidate index e of the front decoder's enumeration (rans_slot); coder e mod W codes it in round (t, e div W) (rans_rounds), so
+the decoder steps W coders at once where format 5 steps one.  The coder's table is an integer function of the arithmetic coder's
+(rans_table: M = 2^16, g_j = max(1, f_j (M - L) // sum f), the deficit to the first largest f_j); the stream is the W final states,
+then the 16-bit words in the order the decoder takes them (rans_encode / rans_decode are the host statement, tests/rans_rule.py the
+slow one).  A full decode checks that every coder rests at 2^16 and that the words end the stream.  decompress, --channels K,
+--region, the -dir commands, transcode to and from it, measure, rd and the searches read and write it like format 5; verify and info
+are host only (info prints W and the states' share of the payload).  --salvage, --partial, --recover, stream and repair refuse a
+format-12 file in one sentence.  Not with --checked, --wavefront, --depth or the layered formats; a context model the wavefront order
+refuses, or of another width than k = 24, is refused.
 stream (Codec.open_stream -> StreamDecoder): a format-6 file that is still arriving.  feed(chunk) takes the bytes as they come, image()
 gives recover's picture and report of the bytes so far -- but the decoder goes on where the last image() stopped: the session
 (PredictionNetwork.open_layers) keeps every tile's decoder workspace on the device and ic_pc_decode_tiles_batch_layers_resume_f32
@@ -236,7 +248,14 @@ DEFAULT_DEPTH_BLOCK = 4
 # streams[t] is tile t's depth plane (ceil(th' / B) * ceil(tw' / B) bytes, row-major, blocks counted from the tile's corner) followed
 # by the range coder's bytes over the tile's live positions; depth_block is B
 DepthContainer = namedtuple('DepthContainer', CheckedContainer._fields + ('depth_block',))
-_TILED = (TiledContainer, CheckedContainer, WavefrontContainer, LayeredContainer, DepthContainer)
+FORMAT_VERSION_RANS = 12                                             # wavefront tiles coded by W interleaved rANS coders; 11 is not used
+RANS_LANES = (8, 16, 32, 64)
+DEFAULT_RANS_LANES = 16
+RANS_M = 1 << 16                                                     # the coder's table total and word size: fixed by format 12
+# streams[t] is tile t's W final coder states ('<I' each, lane l at byte 4 l) followed by the 16-bit words in the order the decoder
+# takes them; lanes is W
+RansContainer = namedtuple('RansContainer', CheckedContainer._fields + ('lanes',))
+_TILED = (TiledContainer, CheckedContainer, WavefrontContainer, LayeredContainer, DepthContainer, RansContainer)
 _WITH_CRCS = (FORMAT_VERSION_CHECKED, FORMAT_VERSION_WAVEFRONT)
 WAVEFRONT_COEFFS = (2, 4)                                            # T = x + 2 y + 4 c: fixed by format 5
 
@@ -789,6 +808,159 @@ def split_depth_stream(stream, C, th, tw, B, tile=None):
     return depth, bytes(stream[nby * nbx:])
 
 
+def check_rans_lanes(lanes):
+    """the number W of interleaved coders of format 12: one of RANS_LANES; else a ValueError -> int"""
+    if isinstance(lanes, (bool, np.bool_)) or not isinstance(lanes, (int, np.integer)) or int(lanes) not in RANS_LANES:
+        raise ValueError('lanes = {!r}: a tile of format 12 is coded by W interleaved coders, W one of {}'.format(
+            lanes, ', '.join(str(w) for w in RANS_LANES)))
+    return int(lanes)
+
+
+RANS_MAX_TOTAL = (1 << 30) + 2                                       # arithmetic_coding.MAX_TOTAL: the limit of every coder here
+
+
+def rans_table(freqs_row):
+    """the rANS coder's table of one context, an integer function of the arithmetic coder's integer table f (pc_table_row): with
+    T = sum f, M = 2^16, g_j = max(1, f_j (M - L) // T), and the deficit M - sum g, which is >= 1, added to the first entry with the
+    largest f_j -> int64 (L,), sum exactly M, every entry >= 1.  1 <= L <= 16.  The total is not looked at: T > RANS_MAX_TOTAL is
+    status 1 of the coders, as for every coder here."""
+    f = [int(v) for v in np.asarray(freqs_row).reshape(-1)]
+    L = len(f)
+    if not 1 <= L <= 16 or min(f) < 1:
+        raise ValueError('rans_table: a table row has 1 .. 16 frequencies, each >= 1, got {!r}'.format(f))
+    T = sum(f)
+    g = [max(1, fj * (RANS_M - L) // T) for fj in f]
+    g[f.index(max(f))] += RANS_M - sum(g)
+    return np.asarray(g, dtype=np.int64)
+
+
+def _rans_slots(C, th, tw):
+    """(t, e) of every position of a (C, th, tw) tile: int64 (C, th, tw) each"""
+    c, y, x = np.meshgrid(np.arange(C, dtype=np.int64), np.arange(th, dtype=np.int64), np.arange(tw, dtype=np.int64), indexing='ij')
+    t = x + 2 * y + 4 * c
+    iw = min(th, (tw + 1) // 2)
+    c_lo = np.maximum(0, -((-(t - (tw - 1) - 2 * (th - 1))) // 4))
+    y_lo = np.maximum(0, -((-(t - 4 * c - (tw - 1))) // 2))
+    return t, (c - c_lo) * iw + (y - y_lo)
+
+
+def rans_slot(C, th, tw, c, y, x):
+    """the candidate index e of position (c, y, x) on its front t = x + 2 y + 4 c -- the enumeration of the front decoder: channels
+    from the first that has a position on the front, iw = min(th, (tw + 1) // 2) slots each, rows from the first that has one.  The
+    positions of a front have distinct e, ascending in (c, y, x) order; an e that is no position is a hole.  Coder = e mod W, round =
+    (t, e div W)."""
+    C, th, tw, c, y, x = (int(v) for v in (C, th, tw, c, y, x))
+    if not (0 <= c < C and 0 <= y < th and 0 <= x < tw):
+        raise ValueError('rans_slot: ({}, {}, {}) is no position of a {} x {} x {} tile'.format(c, y, x, C, th, tw))
+    t = x + 2 * y + 4 * c
+    iw = min(th, (tw + 1) // 2)
+    c_lo = max(0, -((-(t - (tw - 1) - 2 * (th - 1))) // 4))
+    y_lo = max(0, -((-(t - 4 * c - (tw - 1))) // 2))
+    return (c - c_lo) * iw + (y - y_lo)
+
+
+_RANS_CACHE = {}
+
+
+def rans_rounds(C, th, tw, W):
+    """the rounds of format 12 for a (C, th, tw) tile coded by W coders: int64 (R, W), [r, l] = the flat raster index of the position
+    coder l codes in round r, -1 for a hole and for the uncoded first position.  Rounds are ordered by (t, e div W); rounds that
+    hold only -1 are dropped (they cost no bytes on either side)."""
+    C, th, tw, W = int(C), int(th), int(tw), check_rans_lanes(W)
+    if C < 1 or th < 1 or tw < 1:
+        raise ValueError('rans rounds: tile {} x {} x {} must be at least 1 in every extent'.format(C, th, tw))
+    key = (C, th, tw, W)
+    if key not in _RANS_CACHE:
+        t, e = _rans_slots(C, th, tw)
+        t, e = t.reshape(-1)[1:], e.reshape(-1)[1:]                  # without the first position
+        span = int(e.max()) // W + 1 if e.size else 1
+        keys, inverse = np.unique(t * span + e // W, return_inverse=True)
+        rounds = np.full((len(keys), W), -1, dtype=np.int64)
+        rounds[inverse.reshape(-1), e % W] = np.arange(1, C * th * tw, dtype=np.int64)
+        rounds.setflags(write=False)
+        if len(_RANS_CACHE) > 64:
+            _RANS_CACHE.clear()
+        _RANS_CACHE[key] = rounds
+    return _RANS_CACHE[key]
+
+
+def rans_encode(freqs, symbols, W):
+    """the tile stream of format 12.  freqs: (R W, L) rows of the arithmetic coder's table, symbols: (R W,) in round order (element
+    r W + l is coder l's of round r; -1: a hole, its row is not looked at) -> bytes: the W final states ('<I', coder l at byte 4 l),
+    then the 16-bit words ('<H') in the order the decoder takes them -- rounds ascending, within a round the coders that need one
+    in ascending order.  State x in [2^16, 2^32), initially 2^16; a step with (g, cg) of rans_table: if x >= g << 16, emit x & 0xffff
+    and x >>= 16; then x = ((x // g) << 16) + x % g + cg.  The rounds are coded backwards.  A ValueError for a total above
+    RANS_MAX_TOTAL (status 1 of the device) and for a symbol outside [0, L) (status 3)."""
+    W = check_rans_lanes(W)
+    sym = np.asarray(symbols, dtype=np.int64).reshape(-1)
+    fr = np.asarray(freqs, dtype=np.int64)
+    fr = fr.reshape(sym.size, -1) if sym.size else np.zeros((0, 1), np.int64)
+    if sym.size % W:
+        raise ValueError('rans_encode: {} symbols are no whole rounds of {} coders'.format(sym.size, W))
+    L = fr.shape[1]
+    state = [RANS_M] * W
+    words = []                                                       # backwards
+    for i in range(sym.size - 1, -1, -1):
+        s = int(sym[i])
+        if s == -1:
+            continue
+        if not 0 <= s < L:
+            raise ValueError('rans_encode: symbol {} outside [0, {})'.format(s, L))
+        if int(fr[i].sum()) > RANS_MAX_TOTAL:
+            raise ValueError('Cannot code symbol because total is too large')
+        row = rans_table(fr[i])
+        g, cg = int(row[s]), int(row[:s].sum())
+        x = state[i % W]
+        if x >= g << 16:
+            words.append(x & 0xffff)
+            x >>= 16
+        state[i % W] = ((x // g) << 16) + x % g + cg
+    return struct.pack('<{}I'.format(W), *state) + struct.pack('<{}H'.format(len(words)), *reversed(words))
+
+
+def rans_decode(data, rounds, W, freqs_of, out, full=True, stop=None):
+    """the mirror of rans_encode.  rounds: (R, W) indices into `out` as rans_rounds gives them; freqs_of(out, index) -> the table
+    row of that position, asked for when every earlier round is in `out` (a flat int64 array, written in place).  A step: s = x &
+    0xffff, the symbol with cg <= s < cg + g, x = g (x >> 16) + s - cg, and if x < 2^16, x = (x << 16) | the next word.  Past its
+    end the stream reads as zeros.  stop: the number of rounds to decode (a preview).  -> status: 0; 1 = a total above
+    RANS_MAX_TOTAL (decoding goes on); 4 = (full decodes only) some coder's state is not 2^16 at the end or the stream does not end
+    where the coders' run ends, 4 W + 2 words != len(data)."""
+    W = check_rans_lanes(W)
+    data = bytes(data)
+
+    def byte(i):
+        return data[i] if i < len(data) else 0
+
+    state = [byte(4 * l) | byte(4 * l + 1) << 8 | byte(4 * l + 2) << 16 | byte(4 * l + 3) << 24 for l in range(W)]
+    taken, status = 0, 0
+    rounds = np.asarray(rounds)
+    R = len(rounds) if stop is None else int(stop)
+    for r in range(R):
+        syms = []
+        for l in range(W):
+            i = int(rounds[r, l])
+            if i < 0:
+                continue
+            f = np.asarray(freqs_of(out, i), dtype=np.int64)
+            if int(f.sum()) > RANS_MAX_TOTAL:
+                status |= 1
+            cum = np.concatenate([[0], np.cumsum(rans_table(f))])
+            x = state[l]
+            s = x & 0xffff
+            k = int(np.searchsorted(cum, s, side='right')) - 1
+            x = int(cum[k + 1] - cum[k]) * (x >> 16) + s - int(cum[k])
+            if x < RANS_M:
+                x = x << 16 | byte(4 * W + 2 * taken) | byte(4 * W + 2 * taken + 1) << 8
+                taken += 1
+            state[l] = x
+            syms.append((i, k))
+        for i, k in syms:                                            # a round's positions do not see each other
+            out[i] = k
+    if full and stop is None and (any(x != RANS_M for x in state) or 4 * W + 2 * taken != len(data)):
+        status |= 4
+    return status
+
+
 def chunk_tiles(tile_shapes, need, budget):
     """cut a list of tiles [(th, tw)] into consecutive chunks [(start, stop)] for a decoder whose workspace grows with the number of
     tiles of a call: need(th_max, tw_max, ntiles) -> bytes for a chunk of ntiles tiles, the largest th x tw.  Greedy, order kept:
@@ -888,6 +1060,25 @@ def build_depth_container(ae_name, pc_name, H, W, C, h, w, L, resolution, finger
         struct.pack('<II', H, W), struct.pack('<HII', C, h, w), struct.pack('<H', L),
         struct.pack('<d', float(resolution)), struct.pack('<I', fingerprint & 0xffffffff),
         struct.pack('<HH', th, tw), struct.pack('<H', B), struct.pack('<I', len(streams))] +
+        [struct.pack('<HII', f, len(b), zlib.crc32(b) & 0xffffffff) for f, b in zip(first_syms, streams)] +
+        [struct.pack('<Q', sum(len(b) for b in streams))])
+    body = head + struct.pack('<I', zlib.crc32(head) & 0xffffffff) + b''.join(streams)
+    return body + struct.pack('<I', zlib.crc32(body) & 0xffffffff)
+
+
+def build_rans_container(ae_name, pc_name, H, W, C, h, w, L, resolution, fingerprint, th, tw, lanes, first_syms, streams):
+    """format 12: the layout of format 10 with the number of coders W as the '<H' behind the tile extent; streams[t] is tile t's
+    rANS stream (rans_encode over the rounds rans_rounds of its own extent), and the tile's CRC covers it."""
+    streams = [bytes(b) for b in streams]
+    assert len(first_syms) == len(streams)
+    lanes = check_rans_lanes(lanes)
+    a, p = ae_name.encode('utf-8'), pc_name.encode('utf-8')
+    head = b''.join([
+        MAGIC, struct.pack('<H', FORMAT_VERSION_RANS),
+        struct.pack('<H', len(a)), a, struct.pack('<H', len(p)), p,
+        struct.pack('<II', H, W), struct.pack('<HII', C, h, w), struct.pack('<H', L),
+        struct.pack('<d', float(resolution)), struct.pack('<I', fingerprint & 0xffffffff),
+        struct.pack('<HH', th, tw), struct.pack('<H', lanes), struct.pack('<I', len(streams))] +
         [struct.pack('<HII', f, len(b), zlib.crc32(b) & 0xffffffff) for f, b in zip(first_syms, streams)] +
         [struct.pack('<Q', sum(len(b) for b in streams))])
     body = head + struct.pack('<I', zlib.crc32(head) & 0xffffffff) + b''.join(streams)
@@ -994,7 +1185,8 @@ def parse_container(data):
     if data[:4] != MAGIC:
         raise ValueError('wrong magic {!r}: not a codec file (expected {!r})'.format(data[:4], MAGIC))
     version, = struct.unpack('<H', data[4:6])
-    if version not in (FORMAT_VERSION, FORMAT_VERSION_TILED, FORMAT_VERSION_CHECKED, FORMAT_VERSION_WAVEFRONT, FORMAT_VERSION_DEPTH) + _LAYERED_VERSIONS:
+    if version not in (FORMAT_VERSION, FORMAT_VERSION_TILED, FORMAT_VERSION_CHECKED, FORMAT_VERSION_WAVEFRONT, FORMAT_VERSION_DEPTH,
+                       FORMAT_VERSION_RANS) + _LAYERED_VERSIONS:
         raise ValueError(_unsupported(version))
     stored, = struct.unpack('<I', data[-4:])
     actual = zlib.crc32(data[:-4]) & 0xffffffff
@@ -1061,7 +1253,7 @@ def _parse_tile_table(r, version, h, w, depth=None):
     """L .. payload length of a format-2 / format-4 / format-5 header, every length against the bytes that remain -> (L, resolution,
     fingerprint, th, tw, first_syms, lengths, crcs or None, n); depth as _parse_tile_extent takes it (format 10: the table of format 4)"""
     L, resolution, fingerprint, th, tw, ntiles = _parse_tile_extent(r, h, w, depth)
-    checked = version in _WITH_CRCS or version == FORMAT_VERSION_DEPTH
+    checked = version in _WITH_CRCS or version in (FORMAT_VERSION_DEPTH, FORMAT_VERSION_RANS)
     row = 10 if checked else 6
     table = r.take(row * ntiles, 'tile table')            # against the bytes that remain, before anything of its size is built
     first_syms, lengths, crcs = [], [], [] if checked else None
@@ -1083,7 +1275,7 @@ def _parse_tile_table(r, version, h, w, depth=None):
 
 def _parse_tiled(r, version, ae_name, pc_name, H, W, C, h, w):
     """the rest of a format-2 / format-4 / format-5 file after the symbol volume shape (the CRC over the file has been checked)."""
-    depth = [] if version == FORMAT_VERSION_DEPTH else None
+    depth = [] if version in (FORMAT_VERSION_DEPTH, FORMAT_VERSION_RANS) else None       # (format 12 keeps W where format 10 keeps B)
     L, resolution, fingerprint, th, tw, first_syms, lengths, crcs, n = _parse_tile_table(r, version, h, w, depth)
     if crcs is not None:
         end = r.pos
@@ -1113,6 +1305,16 @@ def _parse_tiled(r, version, ae_name, pc_name, H, W, C, h, w):
             split_depth_stream(s, C, a, b, B, tile=t)     # a stream shorter than its plane, a depth above C: refused, naming the tile
         return DepthContainer(version, ae_name, pc_name, H, W, C, h, w, L, resolution, fingerprint, th, tw, first_syms, streams, payload,
                               crcs, B)
+    if version == FORMAT_VERSION_RANS:
+        lanes = depth[0]
+        if lanes not in RANS_LANES:
+            raise ValueError('{} coders per tile: format 12 has W in {}'.format(lanes, ', '.join(str(v) for v in RANS_LANES)))
+        for t, s in enumerate(streams):
+            if len(s) < 4 * lanes or (len(s) - 4 * lanes) % 2:
+                raise ValueError('stream of tile {} holds {} bytes: the states of its {} coders have {}, and 16-bit words follow'.format(
+                    t, len(s), lanes, 4 * lanes))
+        return RansContainer(version, ae_name, pc_name, H, W, C, h, w, L, resolution, fingerprint, th, tw, first_syms, streams, payload,
+                             crcs, lanes)
     cls = WavefrontContainer if version == FORMAT_VERSION_WAVEFRONT else CheckedContainer
     return cls(version, ae_name, pc_name, H, W, C, h, w, L, resolution, fingerprint, th, tw, first_syms, streams, payload, crcs)
 
@@ -1221,12 +1423,23 @@ def _refuse_depth(data, what):
                                              FORMAT_VERSION_LAYERED, FORMAT_VERSION_FRONTS))
 
 
+def _refuse_rans(data, what):
+    """--salvage, --partial, --recover, stream and repair do not read format 12: one sentence, before anything else of the file is looked at"""
+    if len(data) >= 6 and data[:4] == MAGIC and struct.unpack('<H', data[4:6])[0] == FORMAT_VERSION_RANS:
+        raise ValueError('format version {} (lane-parallel rANS tiles) is not read by {}: a file to be salvaged is written with --tile '
+                         '--checked or --tile --wavefront (versions {} and {}), a file to be read from a prefix, recovered or streamed '
+                         'with the layered formats --layers / --front-layers (versions {} and {}); an intact file decodes with '
+                         'decompress'.format(FORMAT_VERSION_RANS, what, FORMAT_VERSION_CHECKED, FORMAT_VERSION_WAVEFRONT,
+                                             FORMAT_VERSION_LAYERED, FORMAT_VERSION_FRONTS))
+
+
 def _partial_open(data):
     if len(data) < _MIN_SIZE:
         raise ValueError('header damaged: truncated file: {} bytes, the smallest container has {}'.format(len(data), _MIN_SIZE))
     if data[:4] != MAGIC:
         raise ValueError('header damaged: wrong magic {!r}: not a codec file (expected {!r})'.format(data[:4], MAGIC))
     _refuse_depth(data, '--partial / --recover / stream')
+    _refuse_rans(data, '--partial / --recover / stream')
     version, = struct.unpack('<H', data[4:6])
     if version not in _LAYERED_VERSIONS:
         raise ValueError('header damaged: format version {} is not the layered version {}: only a layered file (--tile --layers / '
@@ -1353,6 +1566,7 @@ def parse_salvage(data):
         raise ValueError('wrong magic {!r}: not a codec file (expected {!r})'.format(data[:4], MAGIC))
     version, = struct.unpack('<H', data[4:6])
     _refuse_depth(data, '--salvage')
+    _refuse_rans(data, '--salvage')
     if version in (FORMAT_VERSION, FORMAT_VERSION_TILED):
         raise ValueError('format version {} has nothing to salvage with: one CRC over the whole file, none per tile (only version {}, '
                          'written with --tile --checked, can be salvaged)'.format(version, FORMAT_VERSION_CHECKED))
@@ -1432,7 +1646,9 @@ class Codec(object):
     Reading needs no option: the file's version decides."""
 
     def __init__(self, ae_config, pc_config, weights, device='cuda', plan_flags=0, device_encode=True, tile=None, checked=False,
-                 order='raster', layers=None, front_layers=None, depth_block=None):
+                 order='raster', layers=None, front_layers=None, depth_block=None, rans=None):
+        if rans is not None:
+            self._check_rans(rans, tile, checked, order, layers, front_layers, depth_block)
         if depth_block is not None:
             self._check_depth(depth_block, tile, order, layers, front_layers, ae_config.num_chan_bn)
         if tile is not None:
@@ -1459,6 +1675,7 @@ class Codec(object):
             front_layers = front_layers if isinstance(front_layers, str) else check_layer_ends(front_layers, ae_config.num_chan_bn)
         self.tile, self.checked, self.order, self.layers, self.front_layers = tile, bool(checked), order, layers, front_layers
         self.depth_block = None if depth_block is None else int(depth_block)
+        self.rans = rans
         import torch
         from . import autoencoder, probclass
         self.device = torch.device(device)
@@ -1484,6 +1701,11 @@ class Codec(object):
             'k = {}'.format(k)))
         if depth_block is not None and self.depth_refusal:
             raise ValueError(self.depth_refusal)
+        self.rans_refusal = self.wavefront_refusal or (None if k == 24 else (
+            'lane-parallel rANS tiles: the front decoder that steps W coders at once covers context models of width k = 24, this one '
+            'has k = {}'.format(k)))
+        if rans is not None and self.rans_refusal:
+            raise ValueError(self.rans_refusal)
         self.pred =probclass.PredictionNetwork(self.pc, pc_config, self.ae.get_centers_variable())
         self.ae_name, self.pc_name = config_name(ae_config), config_name(pc_config)
         self.factor = int(self.ae.get_subsampling_factor())
@@ -1547,6 +1769,34 @@ class Codec(object):
         if self.depth_refusal:
             raise ValueError(self.depth_refusal)
         return int(self.depth_block)
+
+    @staticmethod
+    def _check_rans(rans, tile, checked, order, layers, front_layers, depth_block):
+        if tile is None:
+            raise ValueError('rans needs a tile extent: format 12 is a tiled format')
+        if checked:
+            raise ValueError('rans does not go with checked=True: format 12 has its own CRC per tile, checked=True writes format 4')
+        if order == 'wavefront':
+            raise ValueError("rans does not go with order='wavefront': format 12 implies the order, order='wavefront' writes format 5, "
+                             "one arithmetic coder per tile")
+        if depth_block is not None:
+            raise ValueError('rans does not go with depth_block: format 10 leaves positions out of an arithmetic coder\'s stream, '
+                             'format 12 codes every position with W rANS coders')
+        if layers is not None or front_layers is not None:
+            raise ValueError('rans does not go with layers or front_layers: format 12 is one interleaved stream per tile, the layered '
+                             'formats 6 and 8 cut a tile into several')
+        if not (isinstance(rans, str) and rans == 'default'):
+            check_rans_lanes(rans)
+
+    def _rans(self):
+        """the number of coders W of the format-12 file compress writes, or None (the attributes may have been set after construction, as main does)"""
+        if getattr(self, 'rans', None) is None:
+            return None
+        self._check_rans(self.rans, self.tile, self.checked, self.order, self.layers, getattr(self, 'front_layers', None),
+                         getattr(self, 'depth_block', None))
+        if self.rans_refusal:
+            raise ValueError(self.rans_refusal)
+        return DEFAULT_RANS_LANES if isinstance(self.rans, str) else int(self.rans)
 
     def _front_ends(self):
         """the layer ends of the format-8 file compress writes, or None (the attributes may have been set after construction, as main does)"""
@@ -1659,6 +1909,12 @@ class Codec(object):
     def _container(self, sym, H, W):
         """the symbols (C, h, w) of an H x W image, on the device -> container bytes in this Codec's format"""
         C, h, w = (int(v) for v in sym.shape)
+        lanes = self._rans()
+        if lanes is not None:
+            th, tw = self.tile
+            coded = self.pred.encode_tiles(sym, th, tw, order='rans', lanes=lanes)
+            return build_rans_container(self.ae_name, self.pc_name, H, W, C, h, w, self.L, self.pred.freqs_resolution,
+                                        self.fingerprint, th, tw, lanes, [f for _, f in coded], [b for b, _ in coded])
         B = self._depth()
         if B is not None:
             th, tw = self.tile
@@ -1747,6 +2003,8 @@ class Codec(object):
             raise ValueError('format 5 cannot be read with this model: {}'.format(self.wavefront_refusal))
         if isinstance(c, DepthContainer) and self.depth_refusal:
             raise ValueError('format {} cannot be read with this model: {}'.format(c.version, self.depth_refusal))
+        if isinstance(c, RansContainer) and self.rans_refusal:
+            raise ValueError('format {} cannot be read with this model: {}'.format(c.version, self.rans_refusal))
         if isinstance(c, LayeredContainer) and self.layered_refusal:
             raise ValueError('format {} cannot be read with this model: {}'.format(c.version, self.layered_refusal))
         if isinstance(c, LayeredContainer) and c.version == FORMAT_VERSION_FRONTS and self.wavefront_refusal:
@@ -1768,7 +2026,7 @@ class Codec(object):
             if isinstance(c, LayeredContainer):          # a batch of one: the layers are arguments of the batch entry
                 sym = self.pred.decode_tiles_batch([(c.streams, c.first_syms, (c.C, c.h, c.w))], c.th, c.tw, want='symbols',
                                                    channels=channels, **_ends_kw(c))[0].cpu().numpy()
-            elif isinstance(c, (WavefrontContainer, DepthContainer)):      # a batch of one: the order and the depth block are flags of the batch entry
+            elif isinstance(c, (WavefrontContainer, DepthContainer, RansContainer)):    # a batch of one: the order and the depth block are flags of the batch entry
                 sym = self.pred.decode_tiles_batch([(c.streams, c.first_syms, (c.C, c.h, c.w))], c.th, c.tw, want='symbols',
                                                    channels=channels, **_order_kw(c))[0].cpu().numpy()
             elif isinstance(c, _TILED):
@@ -1879,6 +2137,15 @@ class Codec(object):
         if not self.device_encode:
             return [self._container(sym, H, W) for sym, (H, W) in zip(syms, sizes)]
         out = [None] * len(syms)
+        lanes = self._rans()
+        if lanes is not None:
+            th, tw = self.tile
+            for i, coded in enumerate(self.pred.encode_tiles_batch(syms, th, tw, order='rans', lanes=lanes)):
+                C, h, w = (int(v) for v in syms[i].shape)
+                out[i] = build_rans_container(self.ae_name, self.pc_name, sizes[i][0], sizes[i][1], C, h, w, self.L,
+                                              self.pred.freqs_resolution, self.fingerprint, th, tw, lanes,
+                                              [f for _, f in coded], [b for b, _ in coded])
+            return out
         B = self._depth()
         if B is not None:
             th, tw = self.tile
@@ -1928,11 +2195,13 @@ class Codec(object):
         layered, front-layered) the tiled files of the most frequent tile extent (and layer ends) in one decode_tiles_batch call ->
         yields (their indices, per file q or symbols on the device); the other files are the caller's, one by one"""
         kind = lambda c: (('fronts' if c.version == FORMAT_VERSION_FRONTS else 'layered') if isinstance(c, LayeredContainer)
-                          else 'depth' if isinstance(c, DepthContainer) else 'wavefront' if isinstance(c, WavefrontContainer) else 'raster')
-        for order in ('raster', 'wavefront', 'layered', 'fronts', 'depth'):
+                          else 'depth' if isinstance(c, DepthContainer) else 'rans' if isinstance(c, RansContainer)
+                          else 'wavefront' if isinstance(c, WavefrontContainer) else 'raster')
+        for order in ('raster', 'wavefront', 'layered', 'fronts', 'depth', 'rans'):
             mine = [i for i, c in enumerate(heads) if isinstance(c, _TILED) and kind(c) == order]
             extents = [(heads[i].th, heads[i].tw) + (tuple(heads[i].layer_ends) if order in ('layered', 'fronts') else
-                                                     (heads[i].depth_block,) if order == 'depth' else ()) for i in mine]
+                                                     (heads[i].depth_block,) if order == 'depth' else
+                                                     (heads[i].lanes,) if order == 'rans' else ()) for i in mine]
             major = max(sorted(set(extents)), key=extents.count) if extents else None
             together = [i for i, e in zip(mine, extents) if e == major]
             if not together:
@@ -1943,7 +2212,8 @@ class Codec(object):
                                                    max_workspace_bytes=max_workspace_bytes, channels=channels,
                                                    **({'layer_ends': list(major[2:])} if order == 'layered' else
                                                       {'front_ends': list(major[2:])} if order == 'fronts' else
-                                                      {'order': 'wavefront', 'depth_block': major[2]} if order == 'depth' else {'order': order}))
+                                                      {'order': 'wavefront', 'depth_block': major[2]} if order == 'depth' else
+                                                      {'order': 'rans', 'lanes': major[2]} if order == 'rans' else {'order': order}))
             except ValueError as e:
                 m = re.search(r'volume (\d+)', str(e))
                 where = 'file {}: '.format(together[int(m.group(1))]) if m else ''
@@ -2226,6 +2496,7 @@ class Codec(object):
 
     def _check_target(self):
         """the refusals of the format this Codec writes, before anything is decoded"""
+        self._rans()
         self._depth()
         self._front_ends()
         self._layer_ends()
@@ -2371,6 +2642,7 @@ class Codec(object):
         self._check_target()
         raw = bytes(data)
         _refuse_depth(raw, 'repair')
+        _refuse_rans(raw, 'repair')
         if len(raw) >= 6 and raw[:4] == MAGIC and struct.unpack('<H', raw[4:6])[0] in _LAYERED_VERSIONS:
             head = self._recover_head(raw)
             c = head[0]
@@ -2407,6 +2679,8 @@ class Codec(object):
     def written_version(self):
         """the format version of the files this Codec writes (its refusals are _check_target's)"""
         self._check_target()
+        if self._rans() is not None:
+            return FORMAT_VERSION_RANS
         if self._depth() is not None:
             return FORMAT_VERSION_DEPTH
         if self._front_ends() is not None:
@@ -2543,6 +2817,8 @@ def _order_kw(c):
     """what decode_tiles_batch is told about the streams of an unlayered tiled container"""
     if isinstance(c, DepthContainer):
         return {'order': 'wavefront', 'depth_block': c.depth_block}
+    if isinstance(c, RansContainer):
+        return {'order': 'rans', 'lanes': c.lanes}
     return {'order': 'wavefront' if isinstance(c, WavefrontContainer) else 'raster'}
 
 
@@ -2826,6 +3102,29 @@ def check_option_args(flags):
                                  'tile into several'.format(name))
         if depth_block is not None and not 1 <= depth_block <= 255:
             raise ValueError('--depth-block {} is not in 1 .. 255'.format(depth_block))
+    rans, lanes = getattr(flags, 'rans', False), getattr(flags, 'lanes', None)
+    if lanes is not None and not rans:
+        raise ValueError('--lanes needs --rans: it is the number of interleaved coders of format 12')
+    if rans:
+        if flags.command not in WRITING_COMMANDS:
+            raise ValueError('--rans belongs to compress / compress-dir: a file says by itself what it is')
+        if flags.tile is None:
+            raise ValueError('--rans needs --tile: format 12 codes every tile with W interleaved coders')
+        if getattr(flags, 'checked', False):
+            raise ValueError('--rans does not go with --checked: format 12 has its own CRC per tile, --checked writes format 4')
+        if getattr(flags, 'wavefront', False):
+            raise ValueError('--rans does not go with --wavefront: format 12 implies the wavefront order, --wavefront writes format 5, '
+                             'one arithmetic coder per tile')
+        if depth:
+            raise ValueError('--rans does not go with --depth: format 10 leaves positions out of an arithmetic coder\'s stream, format '
+                             '12 codes every position with W rANS coders')
+        for name, on in (('--layers', layers is not None), ('--progressive', progressive), ('--front-layers', front_layers is not None),
+                         ('--front-progressive', front_progressive)):
+            if on:
+                raise ValueError('--rans does not go with {}: format 12 is one interleaved stream per tile, the layered formats 6 and 8 '
+                                 'cut a tile into several'.format(name))
+        if lanes is not None and lanes not in RANS_LANES:
+            raise ValueError('--lanes {} is not one of {}'.format(lanes, ', '.join(str(w) for w in RANS_LANES)))
     if getattr(flags, 'partial', False):
         if flags.command not in ('decompress', 'decompress-dir'):
             raise ValueError('--partial belongs to decompress / decompress-dir: it reads a prefix of a layered file')
@@ -2931,6 +3230,13 @@ def _depth_option(flags):
     return DEFAULT_DEPTH_BLOCK if getattr(flags, 'depth_block', None) is None else int(flags.depth_block)
 
 
+def _rans_option(flags):
+    """the `rans` argument of Codec for a command line: None without --rans, else --lanes or 'default'"""
+    if not getattr(flags, 'rans', False):
+        return None
+    return 'default' if getattr(flags, 'lanes', None) is None else int(flags.lanes)
+
+
 def _front_layers_option(flags, C):
     """the `front_layers` argument of Codec for a command line, as _layers_option"""
     if getattr(flags, 'front_layers', None) is not None:
@@ -2969,7 +3275,8 @@ def _main_dir(flags, ae_config, pc_config):
         wts = val.load_weights_for_job(None, flags.weights, ae_config, pc_config)
     codec = Codec(ae_config, pc_config, wts, flags.device, tile=tile, checked=flags.checked,
                   order='wavefront' if flags.wavefront and tile is not None else 'raster',
-                  layers=layers, front_layers=front_layers, depth_block=_depth_option(flags) if tile is not None else None)
+                  layers=layers, front_layers=front_layers, depth_block=_depth_option(flags) if tile is not None else None,
+                  rans=_rans_option(flags) if tile is not None else None)
     channels = check_channels(getattr(flags, 'channels', None), codec.C)
     os.makedirs(flags.output, exist_ok=True)
     total_in = total_out = total_pixels = 0
@@ -3228,6 +3535,8 @@ def verify_file(data):
                 c.version, len(data), G, ','.join(str(e) for e in c.layer_ends), ','.join(str(layer_prefix_bytes(c, g)) for g in range(G + 1)))
         if isinstance(c, DepthContainer):
             return True, 'ok (format {}, {} bytes, depth blocks of {} cells)'.format(c.version, len(data), c.depth_block)
+        if isinstance(c, RansContainer):
+            return True, 'ok (format {}, {} bytes, W = {} coders per tile)'.format(c.version, len(data), c.lanes)
         return True, 'ok (format {}, {} bytes)'.format(c.version, len(data))
     except ValueError as strict:
         if len(data) >= 6 and data[:4] == MAGIC and struct.unpack('<H', data[4:6])[0] in _LAYERED_VERSIONS:
@@ -3320,6 +3629,10 @@ def info_file(data, region=None):
             c.depth_block, c.depth_block, plane_bytes, live / float(c.C * c.h * c.w), live, c.C * c.h * c.w))
         lines.append('front steps per tile: {} (all {} channels: {})'.format(
             ','.join(str(n) for n in steps), c.C, ','.join(str(depth_front_steps(a, b, c.C)) for _, _, a, b in tile_grid(c.h, c.w, c.th, c.tw))))
+    if isinstance(c, RansContainer):
+        state_bytes = 4 * c.lanes * len(per_tile)
+        lines.append('W = {} interleaved coders per tile, {} bytes of coder states: {:.4f} of the payload'.format(
+            c.lanes, state_bytes, state_bytes / float(max(1, sum(per_tile)))))
     if region is not None:
         from . import config_parser
         ae_config, _ = config_parser.parse(_resolve_config(c.ae_name, 'ae_configs', 'CONFIG_BASE_AE'))
@@ -3443,6 +3756,13 @@ def main(argv=None):
                         'not with --wavefront or the layered formats')
     p.add_argument('--depth-block', dest='depth_block', type=int, default=None, metavar='B',
                    help='--depth: blocks of B x B latent cells, 1 .. 255 (default {})'.format(DEFAULT_DEPTH_BLOCK))
+    p.add_argument('--rans', action='store_true',
+                   help='compress / compress-dir with --tile: lane-parallel rANS tiles (format 12): the order of --wavefront, every tile coded '
+                        'by W interleaved rANS coders that the decoder steps a round at a time; not with --checked, --wavefront, --depth '
+                        'or the layered formats')
+    p.add_argument('--lanes', type=int, default=None, metavar='W',
+                   help='--rans: the number of coders per tile, one of {} (default {})'.format(', '.join(str(w) for w in RANS_LANES),
+                                                                                               DEFAULT_RANS_LANES))
     p.add_argument('--partial', action='store_true', help='decompress / decompress-dir: decode the complete layers of a (cut) format-6 / format-8 file and '
                                                           'print how many of them; not with --salvage or --channels')
     p.add_argument('--recover', action='store_true', help='decompress / decompress-dir: read what a damaged or cut format-6 file still holds, every '
@@ -3505,6 +3825,7 @@ def main(argv=None):
                 codec.layers = layers
                 codec.front_layers = front_layers
                 codec.depth_block = _depth_option(flags)
+                codec.rans = _rans_option(flags)
             rois = [parse_roi_arg(r) for r in flags.roi or []]
         if flags.command == 'transcode':
             with open(flags.input, 'rb') as f:

@@ -819,7 +819,33 @@ __device__ __forceinline__ void pc_wave_chain(const float* __restrict__ in, int 
 // the parallel part of a chunk: the lanes of a dead slot compute no logits, the lane that owns the slot (co == 0) stores `fill`
 // through out and its centre into V there and then, and leaves a byte in s_live for wave 0, whose serial loop only steps over the
 // slot -- the plane is never read between two coder steps.  The first position is uncoded as ever; dead, it is `fill` like any other.
-template <bool SYMS, bool LIM = false, bool SEG = false, bool FROM = false, bool DEPTH = false>
+// RANS = true (IC_PC_DECODE_RANS(W), container format 12; only with LIM, without SEG, FROM and DEPTH): the stream is that of W
+// interleaved rANS coders (imgcomp_hip.h), coder = candidate index mod W.  Phases 1 - 3 and the logits of a chunk of CH candidates
+// are the decoder's as before; behind the chunk's barrier wave 0 does not step a coder through the chunk symbol by symbol
+// (pc_dec_symbol_wave is not on this path) but
+//   - lane k builds the table of slot k from s_logits[k] -- pc_table_row, then pc_rans_row -- and stores its prefix sums back in
+//     place as integers (a chunk starts at a multiple of CH, so slot k belongs to coder k mod W);
+//   - in CH / W sub-rounds lanes l < W each decode the symbol of slot s W + l from their own state, take one 16-bit word if the
+//     state fell below 2^16 -- the lanes that need one take consecutive words in lane order, addressed with a ballot and a prefix
+//     count from the wave-uniform number of words taken, every byte read only below nbytes -- and store their own symbol through
+//     out and its centre into V.  A slot that is no position costs an idle lane and no word.
+// Every trip count is fixed by the tile's geometry and W; nothing waits on anything; a symbol is < L whatever the bytes are, because
+// the table's sums end at M.  At the end of a full decode (cdec == C) the states must all be 2^16 and the words taken must end the
+// stream: else status 4, OR-ed with status 1 of a table whose total was too large.
+template <int LC>
+__device__ __forceinline__ bool pc_dec_rans_build(float (*row)[16], int slot, float resolution) {
+    float l[LC];
+#pragma unroll
+    for (int j = 0; j < LC; ++j) l[j] = row[slot][j];
+    unsigned cum[LC];
+    const bool ok = pc_rans_row<LC>(l, resolution, cum);
+    unsigned* o = reinterpret_cast<unsigned*>(row[slot]);
+#pragma unroll
+    for (int j = 0; j < 16; ++j) o[j] = j < LC ? cum[j < LC ? j : 0] : PC_RANS_M;
+    return ok;
+}
+
+template <bool SYMS, bool LIM = false, bool SEG = false, bool FROM = false, bool DEPTH = false, bool RANS = false>
 __device__ __forceinline__ void pc_dec_wave_body(const PcCachedArgs& f, const unsigned char* bits, long long nbytes, int h, int w, int first_sym,
                                                  float* vol, float* c0, float* c1, float* c2, int* status,
                                                  long long* __restrict__ out, long long out_cs, int out_rs, int cdec = 0,
@@ -827,9 +853,10 @@ __device__ __forceinline__ void pc_dec_wave_body(const PcCachedArgs& f, const un
                                                  const int* __restrict__ ends = nullptr, int nlayers = 0, int gfrom = 0,
                                                  unsigned char* __restrict__ plane = nullptr,
                                                  const unsigned char* __restrict__ depth = nullptr, int dblock = 1, int dnbx = 0, int dmax = 0,
-                                                 int fill = 0) {
+                                                 int fill = 0, int rlanes = 0) {
     static_assert(!FROM || (LIM && SEG), "a sweep continues at a layer cut of a limited sweep");
     static_assert(!DEPTH || (LIM && !SEG), "the depth plane belongs to the unsegmented limited sweep");
+    static_assert(!RANS || (LIM && !SEG && !FROM && !DEPTH), "the interleaved coders belong to the unsegmented limited sweep");
     constexpr int K = 24, G = K / 4, CH = 64;             // CH: candidates of a front whose logits are in LDS at once
     __shared__ float s_logits[CH + (DEPTH ? 1 : 0)][16];  // DEPTH: one more row, CH bytes: s_live
     __shared__ float s_centers[16];
@@ -846,7 +873,20 @@ __device__ __forceinline__ void pc_dec_wave_body(const PcCachedArgs& f, const un
         if (resumed) cfrom = ((const __attribute__((address_space(4))) int*)ends)[gfrom - 1];
     }
     PcDecState s;                                         // wave 0 keeps the coder state, identical in all its lanes
-    if (!resumed) {
+    // RANS: wave 0, lane l < W keeps coder l's state; the words taken so far and the status are wave-uniform / per lane
+    unsigned rx = 0;
+    long long rtaken = 0;
+    int rerr = 0;
+    if constexpr (RANS) {
+        s.error = 0;
+        if (wave == 0 && lane < rlanes) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const long long o = 4ll * lane + i;
+                rx |= (o < nbytes ? (unsigned)bits[o] : 0u) << (8 * i);
+            }
+        }
+    } else if (!resumed) {
         pc_dec_state_init(s, bits, nbytes);
         if (wave == 0)
             for (int i = 0; i < PC_AC_BITS; ++i) s.code = (s.code << 1) | (unsigned)pc_dec_bit(bits, nbytes, s);
@@ -963,6 +1003,62 @@ __device__ __forceinline__ void pc_dec_wave_body(const PcCachedArgs& f, const un
                 s_logits[slot][co] = fmaxf(v[0] + f.b3[co], 0.f);
             }
             __syncthreads();
+            if constexpr (RANS) {
+                if (wave == 0) {
+                    {   // the tables of the chunk's slots, one per lane
+                        int c, y, x;
+                        if (lane < nc && pc_front_voxel(fr, cb + lane, c, y, x) && (c | y | x) != 0) {
+                            bool ok = true;
+                            switch (L) {
+#define PC_RANS_CASE(l) case l: ok = pc_dec_rans_build<l>(s_logits, lane, a.resolution); break;
+                                PC_RANS_CASE(1) PC_RANS_CASE(2) PC_RANS_CASE(3) PC_RANS_CASE(4) PC_RANS_CASE(5) PC_RANS_CASE(6)
+                                PC_RANS_CASE(7) PC_RANS_CASE(8) PC_RANS_CASE(9) PC_RANS_CASE(10) PC_RANS_CASE(11) PC_RANS_CASE(12)
+                                PC_RANS_CASE(13) PC_RANS_CASE(14) PC_RANS_CASE(15) PC_RANS_CASE(16)
+#undef PC_RANS_CASE
+                            }
+                            if (!ok) rerr |= 1;
+                        }
+                    }
+                    // the rows are read by other lanes of this wave: its LDS stores are done and visible before the first read
+                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+                    __builtin_amdgcn_wave_barrier();
+                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+                    for (int sb = 0; sb < nc; sb += rlanes) {                     // CH / W sub-rounds at the most; uniform
+                        const int k = sb + lane;
+                        int c = 0, y = 0, x = 0;
+                        const bool valid = lane < rlanes && k < nc && pc_front_voxel(fr, cb + k, c, y, x);
+                        int sym = first_sym;                                      // the first symbol is not coded
+                        bool need = false;
+                        if (valid && (c | y | x) != 0) {
+                            const unsigned* row = reinterpret_cast<const unsigned*>(s_logits[k]);
+                            unsigned cum[16];
+#pragma unroll
+                            for (int j = 0; j < 16; ++j) cum[j] = row[j];
+                            const unsigned sv = rx & 0xffffu;
+                            unsigned cg = 0, nx = PC_RANS_M;
+                            sym = 0;
+#pragma unroll
+                            for (int j = 1; j < 16; ++j) {                        // entries from L on are M: never <= sv
+                                if (cum[j] <= sv) { sym = j; cg = cum[j]; }
+                                else nx = min(nx, cum[j]);
+                            }
+                            rx = (nx - cg) * (rx >> 16) + (sv - cg);              // < 2^32: (nx - cg) ((x >> 16) + 1) <= 2^16 2^16
+                            need = rx < PC_RANS_M;
+                        }
+                        const unsigned long long needing = __ballot(need);
+                        if (need) {
+                            const long long o = 4ll * rlanes + 2 * (rtaken + __popcll(needing & ((1ull << lane) - 1)));
+                            const unsigned lo = o < nbytes ? bits[o] : 0u, hi = o + 1 < nbytes ? bits[o + 1] : 0u;
+                            rx = (rx << 16) | lo | (hi << 8);
+                        }
+                        rtaken += __popcll(needing);
+                        if (valid) {
+                            if (SYMS && c < cdec) out[(long long)c * out_cs + (long long)y * out_rs + x] = sym;
+                            vol[((size_t)(c + 4) * PH + y + 4) * PW + x + 4] = s_centers[sym];
+                        }
+                    }
+                }
+            } else
             if (wave == 0) {
                 unsigned long long livemask = ~0ull;                              // DEPTH: the chunk's live bytes as one scalar word
                 if constexpr (DEPTH) livemask = __ballot(lane < nc && s_live[lane] != 0);
@@ -986,6 +1082,13 @@ __device__ __forceinline__ void pc_dec_wave_body(const PcCachedArgs& f, const un
             __syncthreads();                              // V of this front before the next step's conv0; s_logits free again
         }
     }
+    if constexpr (RANS) {
+        if (wave == 0) {                                  // the end check of a full decode; status 1 and 4 OR-ed over the lanes
+            const bool bad4 = cdec == a.C && ((lane < rlanes && rx != PC_RANS_M) || 4ll * rlanes + 2 * rtaken != nbytes);
+            const int st = (__ballot(rerr != 0) ? 1 : 0) | (__ballot(bad4) ? 4 : 0);
+            if (lane == 0) *status = st;
+        }
+    } else
     if (tid == 0) *status = SEG ? (sticky | s.error) : s.error;
 }
 
@@ -1023,6 +1126,7 @@ struct PcTilesBatchArgs {
     unsigned char* planes;            // WAVE FROM kernels only: a byte per symbol of every tile, plane_bytes per tile, (c, y, x) order
     size_t plane_bytes;               //   of the tile's own extent (written and read by the kernel alone)
     int depth_block;                  // DEPTH kernels only: the side b of a block of the depth plane, 1 .. 255
+    int rans_lanes;                   // RANS kernels only: the number W of interleaved coders, 8 / 16 / 32 / 64
 };
 
 // SEG: the tile's stream is its nlayers segments, segs[blockIdx.x * nlayers + g]; the descriptor's stream_off / stream_bytes are not
@@ -1052,8 +1156,11 @@ struct PcTilesBatchArgs {
 // A stream shorter than that: status 2, nothing decoded, nothing written.  All 256 lanes reduce the plane's largest entry (clamped to
 // C) to dmax; the sweep is the LIM sweep to cdec = min(channels, dmax) over dmax channels, and the copy loop's fill covers the
 // channels from cdec up -- dead everywhere, or beyond the preview.  dmax == 0: no body at all, status 0, everything is fill.
-template <bool WAVE, bool SYMS, bool LIM = false, bool SEG = false, bool PER = false, bool FROM = false, bool DEPTH = false>
+// RANS (ic_pc_decode_tiles_batch_channels_f32 with IC_PC_DECODE_RANS(W); WAVE && LIM only, channels == C included): the tile's stream
+// is that of W interleaved rANS coders; the sweep is the LIM sweep to cdec, its serial part replaced (pc_dec_wave_body, RANS).
+template <bool WAVE, bool SYMS, bool LIM = false, bool SEG = false, bool PER = false, bool FROM = false, bool DEPTH = false, bool RANS = false>
 __global__ __launch_bounds__(256) void pc_dec_tiles_batch_kernel(const PcTilesBatchArgs t) {
+    static_assert(!RANS || (WAVE && LIM && !SEG && !DEPTH), "the interleaved coders belong to the unsegmented wavefront sweep with a limit");
     static_assert(!PER || (LIM && SEG), "the limit per tile belongs to the segmented decoders: a limited sweep over a tile's segments");
     static_assert(!FROM || PER, "a sweep continues where a sweep with a limit per tile stopped");
     static_assert(!DEPTH || (WAVE && LIM && !SEG), "the depth plane belongs to the unsegmented wavefront sweep with a limit");
@@ -1128,6 +1235,11 @@ __global__ __launch_bounds__(256) void pc_dec_tiles_batch_kernel(const PcTilesBa
                                                              SYMS ? t.symbols + v.symbols_off + corner : nullptr, plane, v.w, cdec,
                                                              nullptr, nullptr, nullptr, 0, 0, nullptr, depth, b, nbx, dmax, t.fill);
         else if (threadIdx.x == 0) t.status[blockIdx.x] = 0;
+    } else if constexpr (RANS) {
+        pc_dec_wave_body<SYMS, true, false, false, false, true>(t.f, t.bits + tl.stream_off, tl.stream_bytes, tl.th, tl.tw, tl.first_sym, (float*)slot,
+                                                                (float*)(slot + t.off_c0), (float*)(slot + t.off_c1), (float*)(slot + t.off_c2), t.status + blockIdx.x,
+                                                                SYMS ? t.symbols + v.symbols_off + corner : nullptr, plane, v.w, cdec,
+                                                                nullptr, nullptr, nullptr, 0, 0, nullptr, nullptr, 1, 0, 0, 0, t.rans_lanes);
     } else if constexpr (WAVE)
         pc_dec_wave_body<SYMS, LIM>(t.f, t.bits + tl.stream_off, tl.stream_bytes, tl.th, tl.tw, tl.first_sym, (float*)slot,
                                     (float*)(slot + t.off_c0), (float*)(slot + t.off_c1), (float*)(slot + t.off_c2), t.status + blockIdx.x,
@@ -1351,7 +1463,7 @@ extern "C" int ic_pc_decode_f32(const uint8_t* bitstream, long long nbytes, int 
                                 int C, int h, int w, void* workspace, size_t workspace_bytes, int flags, ic_stream_t stream) {
     IC_CHECK_ARG(bitstream && wtab_host && centers && symbols && status && workspace);
     IC_CHECK_ARG(nbytes >= 0 && C > 0 && h > 0 && w > 0 && k > 0 && L > 0 && first_sym >= 0 && first_sym < L);
-    if (L > 16 || (flags & (IC_PC_DECODE_WAVEFRONT | IC_PC_DECODE_DEPTH(0xff)))) return IC_ERR_UNSUPPORTED;      // (the wavefront order: the batch entry only; the depth plane: its channels form only)
+    if (L > 16 || (flags & (IC_PC_DECODE_WAVEFRONT | IC_PC_DECODE_DEPTH(0xff) | IC_PC_DECODE_RANS(0xff)))) return IC_ERR_UNSUPPORTED;      // (the wavefront order: the batch entry only; the depth plane and the rANS coders: its channels form only)
     if (workspace_bytes < ic_pc_decode_workspace_bytes(C, h, w, k)) return IC_ERR_WORKSPACE;
     return pc_decode_impl(bitstream, nbytes, first_sym, wtab_host, centers, k, L, resolution, symbols, status, C, h, w, workspace,
                           flags, C, 0, stream);
@@ -1451,6 +1563,7 @@ struct PcTilesRequest {
                                                       //   (front cuts), the caller's own flags must be 0 for both; else the caller's flags
     int th_max, tw_max;                               // the largest tile: pc_tiles_check fills them in
     int depth_block;                                  // IC_PC_DECODE_DEPTH(b) of the caller's flags, 0 without: pc_tiles_check fills it in
+    int rans_lanes;                                   // IC_PC_DECODE_RANS(W) of the caller's flags, 0 without: pc_tiles_check fills it in
 };
 
 // the arguments that all entries but the single-volume one begin with, and the values of a full decode of unsegmented streams
@@ -1518,6 +1631,15 @@ static int pc_tiles_check(PcTilesRequest& r, PcTilesLayout& l) {
     // the depth plane (bits 8 - 15 of the flags) has one decoder too: the wavefront sweep with a limit of the k = 24 kernel, so the flag
     // is the channels entry's alone, there only beside IC_PC_DECODE_WAVEFRONT, and unsupported everywhere else.  Behind this the flags
     // are what they are without it.
+    // the interleaved rANS coders (bits 16 - 23 of the flags) likewise: the channels entry's alone, k = 24, and there ALONE in the flags --
+    // the order is implied; beside IC_PC_DECODE_WAVEFRONT, a depth block or a slow-path flag, with another W, in any other entry: unsupported
+    r.rans_lanes = (r.flags >> 16) & 0xff;
+    if (r.rans_lanes) {
+        const int W = r.rans_lanes;
+        if (!r.takes_channels || !batch || segmented || r.k != 24 || r.flags != IC_PC_DECODE_RANS(W) || !(W == 8 || W == 16 || W == 32 || W == 64))
+            return IC_ERR_UNSUPPORTED;
+        r.flags = r.order = IC_PC_DECODE_WAVEFRONT;
+    }
     r.depth_block = (r.flags >> 8) & 0xff;
     if (r.depth_block) {
         if (!r.takes_channels || !batch || segmented || r.k != 24 || r.flags != (IC_PC_DECODE_WAVEFRONT | IC_PC_DECODE_DEPTH(r.depth_block)))
@@ -1535,13 +1657,15 @@ static int pc_tiles_check(PcTilesRequest& r, PcTilesLayout& l) {
 }
 
 // the form of pc_dec_tiles_batch_kernel for a launch, by its template arguments (per implies lim and seg, from implies per; depth is
-// the wavefront sweep with a limit and without segments): the 26 forms named here are the ones the file instantiates
+// the wavefront sweep with a limit and without segments): the 28 forms named here are the ones the file instantiates
 typedef void (*PcTilesKernel)(const PcTilesBatchArgs);
 template <bool WAVE, bool LIM, bool SEG, bool PER, bool FROM>
 static PcTilesKernel pc_tiles_kernel_of(bool syms) {
     return syms ? pc_dec_tiles_batch_kernel<WAVE, true, LIM, SEG, PER, FROM> : pc_dec_tiles_batch_kernel<WAVE, false, LIM, SEG, PER, FROM>;
 }
-static PcTilesKernel pc_tiles_kernel(bool wave, bool syms, bool lim, bool seg, bool per, bool from, bool depth) {
+static PcTilesKernel pc_tiles_kernel(bool wave, bool syms, bool lim, bool seg, bool per, bool from, bool depth, bool rans) {
+    if (rans) return syms ? pc_dec_tiles_batch_kernel<true, true, true, false, false, false, false, true>
+                          : pc_dec_tiles_batch_kernel<true, false, true, false, false, false, false, true>;     // (pc_tiles_check: wave, not seg, no depth)
     if (depth) return syms ? pc_dec_tiles_batch_kernel<true, true, true, false, false, false, true>
                            : pc_dec_tiles_batch_kernel<true, false, true, false, false, false, true>;     // (pc_tiles_check: wave, not seg)
     if (!seg) return !lim ? (wave ? pc_tiles_kernel_of<true, false, false, false, false>(syms) : pc_tiles_kernel_of<false, false, false, false, false>(syms))
@@ -1602,9 +1726,9 @@ static int pc_decode_tiles_impl(const PcTilesRequest& r, const PcTilesLayout& l)
         else
             hipLaunchKernelGGL(pc_dec_fill_slots_kernel, dim3((unsigned)((nvol + 255) / 256), (unsigned)ntiles), dim3(256), 0, st,
                                a.slots, a.slot_bytes, nvol, r.centers);
-        a.cdec = r.channels; a.fill = r.fill_sym; a.depth_block = r.depth_block;
-        const PcTilesKernel kernel = pc_tiles_kernel(wavefront, r.symbols != nullptr, r.tile_channels || r.channels < C, r.nlayers != 0,
-                                                     r.tile_channels != nullptr, r.tile_from != nullptr, r.depth_block != 0);
+        a.cdec = r.channels; a.fill = r.fill_sym; a.depth_block = r.depth_block; a.rans_lanes = r.rans_lanes;
+        const PcTilesKernel kernel = pc_tiles_kernel(wavefront, r.symbols != nullptr, r.tile_channels || r.channels < C || r.rans_lanes, r.nlayers != 0,
+                                                     r.tile_channels != nullptr, r.tile_from != nullptr, r.depth_block != 0, r.rans_lanes != 0);
         hipLaunchKernelGGL(kernel, dim3((unsigned)ntiles), dim3(256), 0, st, a);
         IC_LAUNCH_CHECK();
         return IC_OK;

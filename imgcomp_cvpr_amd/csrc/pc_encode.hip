@@ -243,6 +243,88 @@ __global__ __launch_bounds__(128) void pc_encode_segments_kernel(const PcEncSegA
                        a.e.out + slot * a.e.capacity, a.e.capacity, a.e.nbytes + slot, a.e.status + slot);
 }
 
+// ---- lane-parallel rANS tiles (container format 12): W interleaved coders, one stream, one wave per volume ---------------------
+// ic_pc_encode_segments_f32 with nsegs = IC_PC_ENCODE_RANS(W).  The inputs are in round order (element r W + l is coder l's of round
+// r); the wave runs the rounds from the last to the first and writes the stream from the end of the volume's capacity towards its
+// start, so the decoder, which runs them forwards, finds the words in the order it takes them.  Lane l < W is coder l: pc_table_row
+// (the ONE expression), pc_rans_row, then the step
+//     if x >= g << 16 (64-bit: g may be 2^16): emit x & 0xffff, x >>= 16 -- at most once;   x = ((x / g) << 16) + x % g + cg.
+// The words of a round go in front of what is written, the emitting lanes in ascending order: lane l stores at
+// end - 2 popcount(emitting lanes >= l), found with one ballot; then the W states in front of all words.  `end` is wave-uniform and a
+// round is stored only if it fits behind byte 0 of the volume's capacity -- as the states are -- so nothing is ever stored outside
+// [0, capacity).  Every trip count is fixed by (count, W); only which lanes store one word depends on the data.
+// A round with a bad symbol (status 3), else with a table whose total is too large (status 1), ends the run, as a round that does not
+// fit does (status 2): a uniform break.  nbytes is 0 then.
+struct PcEncRansArgs {
+    PcEncArgs e;                  // logits (N, count, L), symbols (N, count) in round order; out (N, capacity), nbytes / status (N)
+    int lanes;                    // W
+};
+
+template <int LC>
+__global__ __launch_bounds__(64) void pc_encode_rans_kernel(const PcEncRansArgs a) {
+    const int vol = blockIdx.x, lane = threadIdx.x, W = a.lanes;
+    const long long count = a.e.count, cap = a.e.capacity, R = count / W;
+    const float* __restrict__ logits = a.e.logits + (size_t)vol * count * LC;
+    const long long* __restrict__ symbols = a.e.symbols + (size_t)vol * count;
+    unsigned char* out = a.e.out + (size_t)vol * cap;
+    unsigned x = PC_RANS_M;
+    long long end = cap;                                                  // the stream so far is out[end .. cap); uniform
+    int status = 0;
+    for (long long r = R - 1; r >= 0; --r) {
+        int bad = 0;
+        bool emit = false;
+        unsigned word = 0;
+        if (lane < W) {
+            const long long i = r * W + lane;
+            const long long sym = symbols[i];
+            if (sym != IC_PC_ENCODE_SKIP) {
+                if (sym < 0 || sym >= LC) {
+                    bad = 3;
+                } else {
+                    float l[LC];
+#pragma unroll
+                    for (int j = 0; j < LC; ++j) l[j] = logits[i * LC + j];
+                    unsigned cum[LC];
+                    if (!pc_rans_row<LC>(l, a.e.resolution, cum)) bad = 1;
+                    unsigned cg = 0, nx = PC_RANS_M;
+#pragma unroll
+                    for (int j = 0; j < LC; ++j)
+                        if (j == (int)sym) { cg = cum[j]; nx = j + 1 < LC ? cum[j + 1] : PC_RANS_M; }
+                    const unsigned g = nx - cg;                           // 1 .. 2^16
+                    if (!bad) {
+                        if ((unsigned long long)x >= ((unsigned long long)g << 16)) { emit = true; word = x & 0xffffu; x >>= 16; }
+                        x = ((x / g) << 16) + x % g + cg;
+                    }
+                }
+            }
+        }
+        const unsigned long long bad3 = __ballot(bad == 3), bad1 = __ballot(bad == 1), emitting = __ballot(emit);
+        if (bad3 | bad1) { status = bad3 ? 3 : 1; break; }
+        const long long nb = 2ll * __popcll(emitting);
+        if (nb > end) { status = 2; break; }                              // never a store in front of the volume's capacity
+        if (emit) {
+            unsigned char* p = out + end - 2ll * __popcll(emitting >> lane);
+            p[0] = (unsigned char)word;
+            p[1] = (unsigned char)(word >> 8);
+        }
+        end -= nb;
+    }
+    if (!status) {
+        if (4ll * W > end) status = 2;
+        else {
+            end -= 4ll * W;
+            if (lane < W) {
+                unsigned char* p = out + end + 4 * lane;
+                p[0] = (unsigned char)x; p[1] = (unsigned char)(x >> 8); p[2] = (unsigned char)(x >> 16); p[3] = (unsigned char)(x >> 24);
+            }
+        }
+    }
+    if (lane == 0) {
+        a.e.nbytes[vol] = status ? 0 : cap - end;
+        a.e.status[vol] = status;
+    }
+}
+
 extern "C" size_t ic_pc_encode_capacity_bytes(long long count) {
     return count > 0 ? (size_t)(4 * count + 16) : 0;
 }
@@ -271,6 +353,26 @@ extern "C" int ic_pc_encode_segments_f32(const float* logits, const int64_t* sym
                                          long long* nbytes, int* status, ic_stream_t stream) {
     // everything is decided here, on the host, before the launch: a refused call writes nothing
     IC_CHECK_ARG(logits && symbols && bitstream && nbytes && status && seg_ends_host);
+    if (nsegs < 0) {                                                      // IC_PC_ENCODE_RANS(W): the interleaved coder, one wave per volume
+        const int W = -nsegs;
+        IC_CHECK_ARG(W == 8 || W == 16 || W == 32 || W == 64);
+        IC_CHECK_ARG(N > 0 && count > 0 && L > 0 && capacity >= 0 && resolution > 0.f);
+        IC_CHECK_ARG(seg_ends_host[0] == count && count % W == 0);
+        if (L > 16) return IC_ERR_UNSUPPORTED;
+        PcEncRansArgs ra{};
+        ra.e.logits = logits; ra.e.symbols = (const long long*)symbols; ra.e.out = bitstream; ra.e.nbytes = nbytes; ra.e.status = status;
+        ra.e.count = count; ra.e.capacity = capacity; ra.e.resolution = resolution;
+        ra.lanes = W;
+        hipStream_t rst = (hipStream_t)stream;
+#define PCE_CASE(l) case l: hipLaunchKernelGGL(pc_encode_rans_kernel<l>, dim3((unsigned)N), dim3(64), 0, rst, ra); break;
+        switch (L) {
+            PCE_CASE(1) PCE_CASE(2) PCE_CASE(3) PCE_CASE(4) PCE_CASE(5) PCE_CASE(6) PCE_CASE(7) PCE_CASE(8)
+            PCE_CASE(9) PCE_CASE(10) PCE_CASE(11) PCE_CASE(12) PCE_CASE(13) PCE_CASE(14) PCE_CASE(15) PCE_CASE(16)
+        }
+#undef PCE_CASE
+        IC_LAUNCH_CHECK();
+        return IC_OK;
+    }
     IC_CHECK_ARG(N > 0 && count > 0 && L > 0 && capacity >= 0 && resolution > 0.f && nsegs >= 1);
     if (L > 16 || nsegs > PCE_MAX_SEGS) return IC_ERR_UNSUPPORTED;
     IC_CHECK_ARG(seg_ends_host[0] >= 1 && seg_ends_host[nsegs - 1] == count);

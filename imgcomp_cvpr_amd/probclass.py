@@ -346,7 +346,7 @@ class PredictionNetwork(object):
         """(pr, freqs), each (num_contexts, L), contexts in the order of iter_over_blocks."""
         return self._tables(symbols_padded)
 
-    def encode_stream(self, symbols, capacity=None, order='raster', seg_ends=None, depth_block=None):
+    def encode_stream(self, symbols, capacity=None, order='raster', seg_ends=None, depth_block=None, lanes=None):
         """The mirror of decode_stream: the whole coding side on the device (ic_pc_encode_f32).  symbols: un-padded (C,h,w) numpy /
         tensor -> (stream_bytes, first_sym); a batch (N,C,h,w) -> a list of N such pairs, coded concurrently by ONE launch.
         The tables are bit for bit those of get_all(pad_symbols_volume(symbols)) -- the symbol volume padded with symbol 0, the
@@ -361,7 +361,11 @@ class PredictionNetwork(object):
         depth_block=B (order='wavefront' only, container format 10): the stream is codec.depth_plane(symbols, fill, B) as bytes, then
         the coder's bytes over the LIVE positions of the wavefront order alone (codec.depth_live_mask): the plane and the mask are a
         few tensor operations on the device, the dead positions go to the same launch as IC_PC_ENCODE_SKIP and are stepped over.  The
-        tables are those of the whole volume, as ever.  fill is conceal_fallback(), the centre nearest zero."""
+        tables are those of the whole volume, as ever.  fill is conceal_fallback(), the centre nearest zero.
+        order='rans', lanes=W (container format 12; W in codec.RANS_LANES, default codec.DEFAULT_RANS_LANES): the stream of W
+        interleaved rANS coders, codec.rans_encode over the same tables: logits and symbols are gathered through
+        codec.rans_rounds(C, h, w, W) on the device, a hole as IC_PC_ENCODE_SKIP, and one wave per volume codes the rounds backwards
+        (ic_pc_encode_segments_f32 with nsegs = -W).  Not with seg_ends or depth_block."""
         dev = self.centers.device
         sym = symbols if torch.is_tensor(symbols) else torch.as_tensor(np.ascontiguousarray(symbols))
         batched = sym.dim() == 4
@@ -375,13 +379,20 @@ class PredictionNetwork(object):
         logits = self.pc.logits(q, is_training=False)                  # (N,C,h,w,L)
         count = C * h * w
         coded = sym
+        if order == 'rans':
+            if seg_ends is not None or depth_block is not None:
+                raise ValueError("order='rans' is one interleaved stream per volume: not with seg_ends or depth_block")
+            res = self._encode_rans(logits, sym, lanes, capacity)
+            return res if batched else res[0]
+        if lanes is not None:
+            raise ValueError("lanes is the number of coders of order='rans', order is {!r}".format(order))
         if order == 'wavefront':
             from .codec import wavefront_order
             perm = torch.as_tensor(np.array(wavefront_order(C, h, w))).to(dev)       # (a copy: the cached order is read-only)
             logits = logits.view(N, count, self.pc.L).index_select(1, perm).contiguous()
             coded = sym.view(N, count).index_select(1, perm).contiguous()
         elif order != 'raster':
-            raise ValueError("order is 'raster' or 'wavefront', got {!r}".format(order))
+            raise ValueError("order is 'raster' or 'wavefront' -- or 'rans' --, got {!r}".format(order))
         planes = None
         if depth_block is not None:
             from .codec import check_depth_block
@@ -415,6 +426,35 @@ class PredictionNetwork(object):
             head = b'' if planes is None else planes[n].tobytes()
             res.append((head + bytes(out[n, :nbytes[n]].cpu().numpy()), int(sym[n, 0, 0, 0])))
         return res if batched else res[0]
+
+    def _encode_rans(self, logits, sym, lanes, capacity):
+        """encode_stream(order='rans') behind the logits: (N,C,h,w,L) logits and (N,C,h,w) symbols -> [(stream, first_sym)]"""
+        from .codec import rans_rounds, check_rans_lanes, DEFAULT_RANS_LANES, RANS_M
+        dev = self.centers.device
+        W = check_rans_lanes(DEFAULT_RANS_LANES if lanes is None else lanes)
+        N, C, h, w = (int(v) for v in sym.shape)
+        rounds = torch.as_tensor(np.array(rans_rounds(C, h, w, W))).to(dev).view(-1)          # (a copy: the cached rounds are read-only)
+        count = int(rounds.numel())
+        firsts = [int(v) for v in sym[:, 0, 0, 0].tolist()]
+        if count == 0:                                       # a 1 x 1 x 1 volume: nothing is coded, the coders rest at their initial state
+            return [(np.full(W, RANS_M, dtype='<u4').tobytes(), f) for f in firsts]
+        at = rounds.clamp(min=0)
+        glog = logits.view(N, C * h * w, self.pc.L).index_select(1, at).contiguous()
+        coded = torch.where(rounds >= 0, sym.view(N, C * h * w).index_select(1, at),
+                            torch.full((), _lib.PC_ENCODE_SKIP, dtype=torch.int64, device=dev)).contiguous()
+        cap = int(lib.ic_pc_encode_capacity_bytes(count)) if capacity is None else int(capacity)
+        out = torch.empty((N, max(cap, 1)), dtype=torch.uint8, device=dev)
+        info = torch.zeros((2, N), dtype=torch.int64, device=dev)       # row 0: nbytes; row 1: status (int32 in the low words)
+        status = info[1].view(torch.int32)[:N]
+        host_ends = (ctypes.c_longlong * 1)(count)
+        check(lib.ic_pc_encode_segments_f32(ptr(glog), ptr(coded), N, count, self.pc.L, self.freqs_resolution, host_ends, _lib.PC_ENCODE_RANS(W),
+                                            ptr(out), cap, ptr(info[0]), ptr(status), _lib.current_stream(dev)), 'ic_pc_encode_segments_f32')
+        nbytes, status, host = info[0].tolist(), status.tolist(), out.cpu().numpy()
+        res = []
+        for n in range(N):
+            self._encode_status(status[n])
+            res.append((bytes(host[n, cap - nbytes[n]:cap]), firsts[n]))       # the stream is the LAST nbytes of the volume's capacity
+        return res
 
     def _depth_plane(self, sym, B):
         """codec.depth_plane and the live positions of a batch (N,C,h,w) of symbol volumes on their device -> ((N, ceil(h/B), ceil(w/B))
@@ -516,7 +556,7 @@ class PredictionNetwork(object):
             raise ValueError('Cannot decode symbol because total is too large')
         return out if on_device else out.cpu().numpy()
 
-    def encode_tiles(self, symbols, th, tw, order='raster', layer_ends=None, front_ends=None, depth_block=None):
+    def encode_tiles(self, symbols, th, tw, order='raster', layer_ends=None, front_ends=None, depth_block=None, lanes=None):
         """symbols: un-padded (C,h,w) -> [(stream_bytes, first_sym)] for the tiles of codec.tile_grid(h, w, th, tw), in grid order.
         Every tile is coded as a volume of its own: its stream is encode_stream(symbols[:, y0:y0+th', x0:x0+tw']) byte for byte.
         Tiles of one shape (at most four: interior, right column, bottom row, corner) are one encode_stream batch, one launch.
@@ -527,7 +567,9 @@ class PredictionNetwork(object):
         stream in the wavefront order of its own extent, cut at that extent's fronts codec.front_layer_cuts(C, th', tw', front_ends)
         (_encode_fronts) -> [([segment bytes per layer], first_sym)].
         depth_block=B (order='wavefront' only, container format 10): every tile's stream is its own depth plane, blocks counted from the
-        tile's corner, then the coder's bytes of its live positions (encode_stream)."""
+        tile's corner, then the coder's bytes of its live positions (encode_stream).
+        order='rans', lanes=W (container format 12; not with layer_ends, front_ends or depth_block): every tile's stream is that of W
+        interleaved rANS coders over the rounds of its own extent (encode_stream)."""
         from .codec import tile_grid
         self._check_front_ends(front_ends, order, layer_ends)
         self._check_depth_block(depth_block, order, layer_ends, front_ends)
@@ -543,7 +585,7 @@ class PredictionNetwork(object):
             batch = torch.stack([sym[:, grid[t][0]:grid[t][0] + a, grid[t][1]:grid[t][1] + b] for t in members])
             seg_ends = None if layer_ends is None else [int(e) * a * b for e in layer_ends]
             coded = (self._encode_fronts(batch, front_ends) if front_ends is not None else
-                     self.encode_stream(batch, order=order, seg_ends=seg_ends, depth_block=depth_block))
+                     self.encode_stream(batch, order=order, seg_ends=seg_ends, depth_block=depth_block, lanes=lanes))
             for t, r in zip(members, coded):
                 res[t] = r
         return res
@@ -560,17 +602,20 @@ class PredictionNetwork(object):
             raise ValueError("depth_block leaves positions out of the wavefront order: it needs order='wavefront' (got {!r}) and goes "
                              "with neither layer_ends nor front_ends".format(order))
 
-    def decode_tiles(self, streams, first_syms, symbols_shape, th, tw, flags=0, channels=None):
+    def decode_tiles(self, streams, first_syms, symbols_shape, th, tw, flags=0, channels=None, order='raster', lanes=None):
         """The mirror of encode_tiles: all tiles of a volume decoded by ONE launch, one work-group per tile
         (ic_pc_decode_tiles_f32; other k than 24 or non-zero flags: tile after tile, the slow path).  streams / first_syms in the
         order of codec.tile_grid(h, w, th, tw); symbols_shape: un-padded (C,h,w).  -> (C,h,w) int64 numpy.
-        channels=K: a preview, through the batch entry as a batch of one (decode_tiles_batch)."""
+        channels=K: a preview, through the batch entry as a batch of one (decode_tiles_batch).
+        order='rans', lanes=W (container format 12): likewise through the batch entry, whose flag it is."""
         from .codec import tile_grid
         C, h, w = (int(v) for v in symbols_shape)
-        if channels is not None:
+        if order not in ('raster', 'rans'):
+            raise ValueError("decode_tiles reads raster streams or, with order='rans', rANS streams; order {!r} is decode_tiles_batch's".format(order))
+        if channels is not None or order == 'rans':
             try:
                 return self.decode_tiles_batch([(streams, first_syms, (C, h, w))], th, tw, want='symbols', flags=flags,
-                                               channels=channels)[0].cpu().numpy()
+                                               channels=channels, order=order, lanes=lanes)[0].cpu().numpy()
             except ValueError as e:
                 raise ValueError(str(e).replace('(volume 0, tile ', '(tile '))
         grid = tile_grid(h, w, th, tw)
@@ -592,13 +637,14 @@ class PredictionNetwork(object):
                 raise ValueError('Cannot decode symbol because total is too large (tile {} at ({}, {}))'.format(t, grid[t][0], grid[t][1]))
         return out.cpu().numpy()
 
-    def encode_tiles_batch(self, volumes, th, tw, order='raster', layer_ends=None, front_ends=None, depth_block=None):
+    def encode_tiles_batch(self, volumes, th, tw, order='raster', layer_ends=None, front_ends=None, depth_block=None, lanes=None):
         """encode_tiles for a list of un-padded (C,h,w) symbol volumes of any mix of (h, w): -> per volume the list encode_tiles
         gives for it, byte for byte.  The tiles of ALL volumes are grouped by tile shape -- for a folder of equal-sized images the
         same four shapes as for one -- and each group is one encode_stream batch, one ic_pc_encode_f32 launch.
         layer_ends: as encode_tiles, the ends converted to symbol counts per tile shape (raster only).
         front_ends: as encode_tiles, every tile shape by its own cuts.
-        depth_block: as encode_tiles."""
+        depth_block: as encode_tiles.
+        order='rans', lanes=W: as encode_tiles."""
         from .codec import tile_grid
         self._check_front_ends(front_ends, order, layer_ends)
         self._check_depth_block(depth_block, order, layer_ends, front_ends)
@@ -618,13 +664,13 @@ class PredictionNetwork(object):
             batch = torch.stack([syms[n][:, grids[n][t][0]:grids[n][t][0] + a, grids[n][t][1]:grids[n][t][1] + b] for n, t in members])
             seg_ends = None if layer_ends is None else [int(e) * a * b for e in layer_ends]
             coded = (self._encode_fronts(batch, front_ends) if front_ends is not None else
-                     self.encode_stream(batch, order=order, seg_ends=seg_ends, depth_block=depth_block))
+                     self.encode_stream(batch, order=order, seg_ends=seg_ends, depth_block=depth_block, lanes=lanes))
             for (n, t), r in zip(members, coded):
                 res[n][t] = r
         return res
 
     def decode_tiles_batch(self, volumes, th, tw, want='q', max_workspace_bytes=1 << 31, flags=0, conceal=False, order='raster',
-                           channels=None, layer_ends=None, tile_layers=None, front_ends=None, depth_block=None):
+                           channels=None, layer_ends=None, tile_layers=None, front_ends=None, depth_block=None, lanes=None):
         """The mirror of encode_tiles_batch: the tiles of ALL volumes decoded by one launch per chunk (ic_pc_decode_tiles_batch_f32,
         one work-group per tile).  volumes: [(streams, first_syms, (C,h,w))], each as decode_tiles takes them, one C throughout.
         want: 'q' -> per volume the (C,h,w) float32 DEVICE tensor centers[symbols] (what ae.decode consumes: the symbols never
@@ -659,8 +705,23 @@ class PredictionNetwork(object):
         front_ends): streams[t] is the tile's depth plane, then the coder's bytes of its live positions, as
         encode_tiles(order='wavefront', depth_block=B) gives them; sets PC_DECODE_DEPTH(B) on ic_pc_decode_tiles_batch_channels_f32,
         whose `channels` is C unless channels=K asks for a preview.  A dead position holds the fill symbol / its centre.  A stream
-        shorter than its plane is a ValueError that names the tile."""
-        from .codec import tile_grid, chunk_tiles, check_channels, check_layer_ends, check_depth_block
+        shorter than its plane is a ValueError that names the tile.
+        order='rans', lanes=W (container format 12; k = 24, flags 0; not with conceal=True, layer_ends, tile_layers, front_ends or
+        depth_block): streams[t] is the tile's stream of W interleaved rANS coders, as encode_tiles(order='rans', lanes=W) gives it;
+        sets PC_DECODE_RANS(W) on ic_pc_decode_tiles_batch_channels_f32, whose `channels` is C unless channels=K asks for a preview.
+        A full decode checks the stream's end: a ValueError that names the tile tells a stream that does not end where the coders'
+        run ends (status 4) from a table whose total is too large (status 1)."""
+        from .codec import tile_grid, chunk_tiles, check_channels, check_layer_ends, check_depth_block, check_rans_lanes, DEFAULT_RANS_LANES
+        rans = None
+        if order == 'rans':
+            if conceal or layer_ends is not None or tile_layers is not None or front_ends is not None or depth_block is not None or int(flags) != 0:
+                raise ValueError("order='rans' does not go with conceal=True, layer_ends, tile_layers, front_ends, depth_block or flags "
+                                 "({})".format(flags))
+            if self.pc._k != 24:
+                raise ValueError('lane-parallel rANS tiles need a context model of width k = 24, this one has k = {}'.format(self.pc._k))
+            rans = check_rans_lanes(DEFAULT_RANS_LANES if lanes is None else lanes)
+        elif lanes is not None:
+            raise ValueError("lanes is the number of coders of order='rans', order is {!r}".format(order))
         if depth_block is not None:
             self._check_depth_block(depth_block, order, layer_ends, front_ends)
             if conceal or tile_layers is not None or int(flags) != 0:
@@ -688,8 +749,8 @@ class PredictionNetwork(object):
             raise ValueError('channels={} with conceal=True: a preview of a damaged file is not offered'.format(channels))
         if want not in ('q', 'symbols', 'both'):
             raise ValueError("want is 'q', 'symbols' or 'both', got {!r}".format(want))
-        if order not in ('raster', 'wavefront'):
-            raise ValueError("order is 'raster' or 'wavefront', got {!r}".format(order))
+        if order not in ('raster', 'wavefront', 'rans'):
+            raise ValueError("order is 'raster' or 'wavefront' -- or 'rans' --, got {!r}".format(order))
         if order == 'wavefront':
             flags = int(flags) | _lib.PC_DECODE_WAVEFRONT
         if not volumes:
@@ -743,6 +804,10 @@ class PredictionNetwork(object):
             flags = int(flags) | _lib.PC_DECODE_DEPTH(check_depth_block(depth_block, C))
             if preview is None:
                 preview = (C, self.conceal_fallback())            # the entry that takes the flag: channels == C is the full decode
+        if rans is not None:
+            flags = _lib.PC_DECODE_RANS(rans)                     # alone in the flags: the order is implied
+            if preview is None:
+                preview = (C, self.conceal_fallback())
         G = 0 if layer_ends is None else len(ends)
         vtable, offs, total = _lib.packed_volume_table(shapes)
 
@@ -801,6 +866,9 @@ class PredictionNetwork(object):
                 n, t, y0, x0 = where[i]
                 if depth_block is not None and st == 2:
                     raise ValueError('stream shorter than its depth plane (volume {}, tile {} at ({}, {}))'.format(n, t, y0, x0))
+                if rans is not None and st & 4 and not st & 1:            # (status 1 beside it: the total is the cause, said below)
+                    raise ValueError('the stream does not end where the coders\' run ends: a coder state is not 2^16 or bytes are missing '
+                                     'or left over (status {}; volume {}, tile {} at ({}, {}))'.format(st, n, t, y0, x0))
                 if not conceal:
                     raise ValueError('Cannot decode symbol because total is too large (volume {}, tile {} at ({}, {}))'.format(n, t, y0, x0))
                 damage[n].append((t, 'decoder'))

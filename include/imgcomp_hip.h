@@ -117,6 +117,21 @@ int ic_build_has_tuning_forms(void);
 /* ic_pc_encode_f32 / ic_pc_encode_segments_f32: a symbol equal to this is stepped over -- nothing is coded for it and its logits
  * are not read (the positions a format-10 stream leaves out).  Every other value outside [0, L) stays status 3. */
 #define IC_PC_ENCODE_SKIP         (-1)
+/* Lane-parallel rANS tiles (container format 12): a tile is coded by W interleaved rANS coders, W in {8, 16, 32, 64}, that share
+ * one stream.  A position (c, y, x) lies on front t = x + 2 y + 4 c, where it has the candidate index e of the front decoder's
+ * enumeration; coder e mod W codes it in round (t, e div W), rounds ordered by t, then e div W.  The coder's table of a position is
+ * an integer function of the arithmetic coder's table f: M = 2^16, g_j = max(1, f_j (M - L) / sum f), the deficit M - sum g added
+ * to the first largest f_j.  State x in [2^16, 2^32), 16-bit words; decoding s = x & 0xffff, the symbol with cg <= s < cg + g,
+ * x = g (x >> 16) + s - cg, and if x < 2^16, x = (x << 16) | the next word.  Stream: W little-endian u32 final states (coder l at
+ * byte 4 l), then the little-endian words in the order the decoder takes them: rounds ascending, within a round the coders that
+ * need one in ascending order.  Past its end a stream reads as zeros.
+ * IC_PC_DECODE_RANS(W): ic_pc_decode_tiles_batch_channels_f32 with k = 24 only, alone in `flags` (the order is implied): every
+ * tile's stream is such a stream.  status 1 = a table's total exceeded 2^30 + 2, 4 = (channels == C only) a coder's state is not
+ * 2^16 at the end or the stream does not end where the coders' run ends (4 W + 2 words taken != stream_bytes); both OR-ed.
+ * Another W, another flag beside it, every other entry and every other k: IC_ERR_UNSUPPORTED, decided on the host.
+ * IC_PC_ENCODE_RANS(W) as `nsegs` of ic_pc_encode_segments_f32: see there. */
+#define IC_PC_DECODE_RANS(w)      (((w) & 0xff) << 16)
+#define IC_PC_ENCODE_RANS(w)      (-(w))
 
 int ic_abi_version(void);
 /* static string for a return code of this library (hipGetErrorString for codes > 0) */
@@ -561,7 +576,17 @@ int ic_pc_encode_f32(const float* logits, const int64_t* symbols, int N, long lo
  *   seg_ends_host: HOST array of nsegs cumulative symbol counts, strictly increasing, ends[0] >= 1, ends[nsegs-1] == count (else
  *     IC_ERR_ARG); they travel in the kernel arguments.  nsegs > 16 or L > 16: IC_ERR_UNSUPPORTED.  A refused call writes nothing.
  *   bitstream: out, device (N, nsegs, capacity);  nbytes, status: out, device (N, nsegs), values as ic_pc_encode_f32 per segment.
- *   An empty segment (ends[0] == 1) is the one byte 0x80; nsegs == 1 is ic_pc_encode_f32 byte for byte. */
+ *   An empty segment (ends[0] == 1) is the one byte 0x80; nsegs == 1 is ic_pc_encode_f32 byte for byte.
+ * nsegs = IC_PC_ENCODE_RANS(W), W in {8, 16, 32, 64} (container format 12, see IC_PC_DECODE_RANS): the interleaved rANS coder in
+ * place of the range coder, one wave per volume.  The inputs come in ROUND order: element r W + l of a volume's `symbols` and row
+ * r W + l of its `logits` are coder l's of round r, count = R W; a symbol equal to IC_PC_ENCODE_SKIP is a hole (its row is not
+ * read), symbol 0 of a volume is coded like any other.  seg_ends_host[0] == count and count % W == 0, else IC_ERR_ARG; every
+ * other negative nsegs: IC_ERR_ARG.
+ *   bitstream: out, device (N, capacity).  The stream is written backwards: volume n's stream is the LAST nbytes[n] bytes of its
+ *     capacity, bitstream[n * capacity + capacity - nbytes[n] ...]; nothing is ever stored outside [0, capacity) of the volume.
+ *   nbytes, status: out, device (N).  status 1 = a table's total exceeded 2^30 + 2, 2 = capacity too small, 3 = a symbol outside
+ *     [0, L) other than IC_PC_ENCODE_SKIP; nbytes is 0 unless the status is 0.
+ *   ic_pc_encode_capacity_bytes(count) suffices: at most 2 bytes per symbol, and 4 W for the states. */
 int ic_pc_encode_segments_f32(const float* logits, const int64_t* symbols, int N, long long count, int L, float resolution,
                               const long long* seg_ends_host, int nsegs, uint8_t* bitstream, long long capacity,
                               long long* nbytes, int* status, ic_stream_t stream);
