@@ -255,8 +255,34 @@ RANS_M = 1 << 16                                                     # the coder
 # streams[t] is tile t's W final coder states ('<I' each, lane l at byte 4 l) followed by the 16-bit words in the order the decoder
 # takes them; lanes is W
 RansContainer = namedtuple('RansContainer', CheckedContainer._fields + ('lanes',))
-_TILED = (TiledContainer, CheckedContainer, WavefrontContainer, LayeredContainer, DepthContainer, RansContainer)
-_WITH_CRCS = (FORMAT_VERSION_CHECKED, FORMAT_VERSION_WAVEFRONT)
+# One row per format version: what the builders, the readers and Codec look up where they would branch on the version.
+#   container    the namedtuple parse_container gives; name: what messages call the format
+#   checked      a CRC per stream or segment in the tile table and one over the header
+#   extra        the one '<H' behind the tile extent, by the name of its container field; check_extra(value, C) validates it
+#   layered      segments per tile, stored layer first (the layout of format 6)
+#   order        what encode_tiles* and decode_tiles_batch are told as order= (None: not told)
+#   param_kw     the keyword that carries the format's parameter to them: the layer ends or the extra field
+#   refusals     the Codec attributes that hold the model's refusal of the format, in the order a reader asks them
+#   readers      which readers of damaged or cut files take it: 'salvage' (--salvage) or 'partial' (--partial, --recover, stream); repair
+#                takes what either takes
+Format = namedtuple('Format', ['version', 'container', 'name', 'checked', 'extra', 'check_extra', 'layered', 'order', 'param_kw',
+                               'refusals', 'readers'])
+FORMATS = {row.version: row for row in (
+    Format(FORMAT_VERSION, Container, 'one stream', False, None, None, False, None, None, (), ()),
+    Format(FORMAT_VERSION_TILED, TiledContainer, 'tiles', False, None, None, False, 'raster', None, (), ()),
+    Format(FORMAT_VERSION_CHECKED, CheckedContainer, 'checked tiles', True, None, None, False, 'raster', None, (), ('salvage',)),
+    Format(FORMAT_VERSION_WAVEFRONT, WavefrontContainer, 'wavefront tiles', True, None, None, False, 'wavefront', None,
+           ('wavefront_refusal',), ('salvage',)),
+    Format(FORMAT_VERSION_LAYERED, LayeredContainer, 'layered tiles', True, None, None, True, None, 'layer_ends',
+           ('layered_refusal',), ('partial',)),
+    Format(FORMAT_VERSION_FRONTS, LayeredContainer, 'front-layered tiles', True, None, None, True, None, 'front_ends',
+           ('layered_refusal', 'wavefront_refusal'), ('partial',)),
+    Format(FORMAT_VERSION_DEPTH, DepthContainer, 'depth-mapped tiles', True, 'depth_block', lambda B, C: check_depth_block(B, C), False,
+           'wavefront', 'depth_block', ('depth_refusal',), ()),
+    Format(FORMAT_VERSION_RANS, RansContainer, 'lane-parallel rANS tiles', True, 'lanes', lambda W, C: check_rans_lanes(W), False,
+           'rans', 'lanes', ('rans_refusal',), ()))}
+_TILED = tuple(dict.fromkeys(row.container for row in FORMATS.values() if row.container is not Container))
+_WITH_CRCS = tuple(v for v, row in FORMATS.items() if 'salvage' in row.readers)      # the formats salvage reads
 WAVEFRONT_COEFFS = (2, 4)                                            # T = x + 2 y + 4 c: fixed by format 5
 
 # what salvage tells about a file: damaged is [DamagedTile] in tile order; latent = (y0, x0, th, tw) in the symbol volume, pixels =
@@ -1004,85 +1030,58 @@ def list_dir_jobs(in_dir, out_dir, command):
     return jobs
 
 
-def _tiled_head(version, ae_name, pc_name, H, W, C, h, w, L, resolution, fingerprint, th, tw, rows, n):
+def _tiled_head(version, ae_name, pc_name, H, W, C, h, w, L, resolution, fingerprint, th, tw, rows, n, extra=None):
     a, p = ae_name.encode('utf-8'), pc_name.encode('utf-8')
     return b''.join([
         MAGIC, struct.pack('<H', version),
         struct.pack('<H', len(a)), a, struct.pack('<H', len(p)), p,
         struct.pack('<II', H, W), struct.pack('<HII', C, h, w), struct.pack('<H', L),
         struct.pack('<d', float(resolution)), struct.pack('<I', fingerprint & 0xffffffff),
-        struct.pack('<HH', th, tw), struct.pack('<I', len(rows))] + rows + [struct.pack('<Q', n)])
+        struct.pack('<HH', th, tw), b'' if extra is None else struct.pack('<H', extra), struct.pack('<I', len(rows))] +
+        rows + [struct.pack('<Q', n)])
+
+
+def _build_tiled(version, ae_name, pc_name, H, W, C, h, w, L, resolution, fingerprint, th, tw, first_syms, streams, extra=None):
+    """formats 2, 4, 5, 10 and 12: the head, its CRC if the format has one, the streams, the CRC over the file"""
+    row = FORMATS[version]
+    streams = [bytes(b) for b in streams]
+    assert len(first_syms) == len(streams)
+    if row.extra is not None:
+        extra = row.check_extra(extra, C)
+    head = _tiled_head(version, ae_name, pc_name, H, W, C, h, w, L, resolution, fingerprint, th, tw,
+                       [struct.pack('<HII', f, len(b), zlib.crc32(b) & 0xffffffff) if row.checked else struct.pack('<HI', f, len(b))
+                        for f, b in zip(first_syms, streams)], sum(len(b) for b in streams), extra)
+    body = head + (struct.pack('<I', zlib.crc32(head) & 0xffffffff) if row.checked else b'') + b''.join(streams)
+    return body + struct.pack('<I', zlib.crc32(body) & 0xffffffff)
 
 
 def build_tiled_container(ae_name, pc_name, H, W, C, h, w, L, resolution, fingerprint, th, tw, first_syms, streams):
     """format 2: first_syms / streams per tile in the order of tile_grid(h, w, th, tw)."""
-    streams = [bytes(b) for b in streams]
-    assert len(first_syms) == len(streams)
-    head = _tiled_head(FORMAT_VERSION_TILED, ae_name, pc_name, H, W, C, h, w, L, resolution, fingerprint, th, tw,
-                       [struct.pack('<HI', f, len(b)) for f, b in zip(first_syms, streams)], sum(len(b) for b in streams))
-    body = head + b''.join(streams)
-    return body + struct.pack('<I', zlib.crc32(body) & 0xffffffff)
+    return _build_tiled(FORMAT_VERSION_TILED, ae_name, pc_name, H, W, C, h, w, L, resolution, fingerprint, th, tw, first_syms, streams)
 
 
 def build_checked_container(ae_name, pc_name, H, W, C, h, w, L, resolution, fingerprint, th, tw, first_syms, streams):
     """format 4: format 2 with a CRC-32 per stream in the tile table and a CRC-32 over the header behind the payload length."""
-    streams = [bytes(b) for b in streams]
-    assert len(first_syms) == len(streams)
-    head = _tiled_head(FORMAT_VERSION_CHECKED, ae_name, pc_name, H, W, C, h, w, L, resolution, fingerprint, th, tw,
-                       [struct.pack('<HII', f, len(b), zlib.crc32(b) & 0xffffffff) for f, b in zip(first_syms, streams)],
-                       sum(len(b) for b in streams))
-    body = head + struct.pack('<I', zlib.crc32(head) & 0xffffffff) + b''.join(streams)
-    return body + struct.pack('<I', zlib.crc32(body) & 0xffffffff)
+    return _build_tiled(FORMAT_VERSION_CHECKED, ae_name, pc_name, H, W, C, h, w, L, resolution, fingerprint, th, tw, first_syms, streams)
 
 
 def build_wavefront_container(ae_name, pc_name, H, W, C, h, w, L, resolution, fingerprint, th, tw, first_syms, streams):
     """format 5: the bytes of format 4 with version 5; streams[t] codes tile t's symbols in wavefront_order(C, th', tw')."""
-    streams = [bytes(b) for b in streams]
-    assert len(first_syms) == len(streams)
-    head = _tiled_head(FORMAT_VERSION_WAVEFRONT, ae_name, pc_name, H, W, C, h, w, L, resolution, fingerprint, th, tw,
-                       [struct.pack('<HII', f, len(b), zlib.crc32(b) & 0xffffffff) for f, b in zip(first_syms, streams)],
-                       sum(len(b) for b in streams))
-    body = head + struct.pack('<I', zlib.crc32(head) & 0xffffffff) + b''.join(streams)
-    return body + struct.pack('<I', zlib.crc32(body) & 0xffffffff)
+    return _build_tiled(FORMAT_VERSION_WAVEFRONT, ae_name, pc_name, H, W, C, h, w, L, resolution, fingerprint, th, tw, first_syms, streams)
 
 
 def build_depth_container(ae_name, pc_name, H, W, C, h, w, L, resolution, fingerprint, th, tw, depth_block, first_syms, streams):
     """format 10: the layout of formats 4 / 5 with the depth block B as one '<H' behind the tile extent; streams[t] is tile t's depth
     plane (depth_plane of its symbols, row-major bytes) followed by the range coder's bytes over its live positions
     (depth_live_mask), and the tile's CRC covers both."""
-    streams = [bytes(b) for b in streams]
-    assert len(first_syms) == len(streams)
-    B = check_depth_block(depth_block, C)
-    a, p = ae_name.encode('utf-8'), pc_name.encode('utf-8')
-    head = b''.join([
-        MAGIC, struct.pack('<H', FORMAT_VERSION_DEPTH),
-        struct.pack('<H', len(a)), a, struct.pack('<H', len(p)), p,
-        struct.pack('<II', H, W), struct.pack('<HII', C, h, w), struct.pack('<H', L),
-        struct.pack('<d', float(resolution)), struct.pack('<I', fingerprint & 0xffffffff),
-        struct.pack('<HH', th, tw), struct.pack('<H', B), struct.pack('<I', len(streams))] +
-        [struct.pack('<HII', f, len(b), zlib.crc32(b) & 0xffffffff) for f, b in zip(first_syms, streams)] +
-        [struct.pack('<Q', sum(len(b) for b in streams))])
-    body = head + struct.pack('<I', zlib.crc32(head) & 0xffffffff) + b''.join(streams)
-    return body + struct.pack('<I', zlib.crc32(body) & 0xffffffff)
+    return _build_tiled(FORMAT_VERSION_DEPTH, ae_name, pc_name, H, W, C, h, w, L, resolution, fingerprint, th, tw, first_syms, streams,
+                        depth_block)
 
 
 def build_rans_container(ae_name, pc_name, H, W, C, h, w, L, resolution, fingerprint, th, tw, lanes, first_syms, streams):
     """format 12: the layout of format 10 with the number of coders W as the '<H' behind the tile extent; streams[t] is tile t's
     rANS stream (rans_encode over the rounds rans_rounds of its own extent), and the tile's CRC covers it."""
-    streams = [bytes(b) for b in streams]
-    assert len(first_syms) == len(streams)
-    lanes = check_rans_lanes(lanes)
-    a, p = ae_name.encode('utf-8'), pc_name.encode('utf-8')
-    head = b''.join([
-        MAGIC, struct.pack('<H', FORMAT_VERSION_RANS),
-        struct.pack('<H', len(a)), a, struct.pack('<H', len(p)), p,
-        struct.pack('<II', H, W), struct.pack('<HII', C, h, w), struct.pack('<H', L),
-        struct.pack('<d', float(resolution)), struct.pack('<I', fingerprint & 0xffffffff),
-        struct.pack('<HH', th, tw), struct.pack('<H', lanes), struct.pack('<I', len(streams))] +
-        [struct.pack('<HII', f, len(b), zlib.crc32(b) & 0xffffffff) for f, b in zip(first_syms, streams)] +
-        [struct.pack('<Q', sum(len(b) for b in streams))])
-    body = head + struct.pack('<I', zlib.crc32(head) & 0xffffffff) + b''.join(streams)
-    return body + struct.pack('<I', zlib.crc32(body) & 0xffffffff)
+    return _build_tiled(FORMAT_VERSION_RANS, ae_name, pc_name, H, W, C, h, w, L, resolution, fingerprint, th, tw, first_syms, streams, lanes)
 
 
 def default_layer_ends(C):
@@ -1175,18 +1174,18 @@ class _Reader(object):
 
 
 def parse_container(data):
-    """bytes -> Container (version 1), TiledContainer (version 2), CheckedContainer (version 4) or WavefrontContainer (version 5).
+    """bytes -> the container type of the file's version (FORMATS): Container (1), TiledContainer (2), CheckedContainer (4),
+    WavefrontContainer (5), LayeredContainer (6 and 8), DepthContainer (10) or RansContainer (12).
     Order: size, magic, version, CRC over the whole file -- only then are the header's lengths read, each against the bytes that
-    remain; the payload length must equal exactly what is left before the CRC.  Versions 4 and 5 in addition: the header CRC and
-    every tile's stream CRC."""
+    remain; the payload length must equal exactly what is left before the CRC.  The formats with checksums in addition: the header
+    CRC and every stream's or segment's CRC; formats 10 and 12: the extra header field and every stream's own layout."""
     data = bytes(data)
     if len(data) < _MIN_SIZE:
         raise ValueError('truncated file: {} bytes, the smallest container has {}'.format(len(data), _MIN_SIZE))
     if data[:4] != MAGIC:
         raise ValueError('wrong magic {!r}: not a codec file (expected {!r})'.format(data[:4], MAGIC))
     version, = struct.unpack('<H', data[4:6])
-    if version not in (FORMAT_VERSION, FORMAT_VERSION_TILED, FORMAT_VERSION_CHECKED, FORMAT_VERSION_WAVEFRONT, FORMAT_VERSION_DEPTH,
-                       FORMAT_VERSION_RANS) + _LAYERED_VERSIONS:
+    if version not in FORMATS:
         raise ValueError(_unsupported(version))
     stored, = struct.unpack('<I', data[-4:])
     actual = zlib.crc32(data[:-4]) & 0xffffffff
@@ -1194,7 +1193,7 @@ def parse_container(data):
         raise ValueError('CRC mismatch: file says {:08x}, content gives {:08x} (corrupt or truncated file)'.format(stored, actual))
     r = _Reader(data[:-4])
     ae_name, pc_name, H, W, C, h, w = _parse_front(r)
-    if version in _LAYERED_VERSIONS:
+    if FORMATS[version].layered:
         return _parse_layered(r, ae_name, pc_name, H, W, C, h, w, strict=True, version=version)[0]
     if version != FORMAT_VERSION:
         return _parse_tiled(r, version, ae_name, pc_name, H, W, C, h, w)
@@ -1228,15 +1227,14 @@ def _parse_front(r):
     return ae_name, pc_name, H, W, C, h, w
 
 
-def _parse_tile_extent(r, h, w, depth=None):
-    """L .. tile count, which every tiled format has -> (L, resolution, fingerprint, th, tw, ntiles); depth: a list that receives the
-    depth block of a format-10 header, which stands behind the tile extent"""
+def _parse_tile_extent(r, h, w, has_extra=False):
+    """L .. tile count, which every tiled format has -> (L, resolution, fingerprint, th, tw, ntiles, extra); extra: the field that
+    stands behind the tile extent in a format-10 / format-12 header, else None"""
     L, = r.unpack('<H', 'L')
     resolution, = r.unpack('<d', 'frequency resolution')
     fingerprint, = r.unpack('<I', 'model fingerprint')
     th, tw = r.unpack('<HH', 'tile extent')
-    if depth is not None:
-        depth.append(r.unpack('<H', 'depth block')[0])
+    extra = r.unpack('<H', 'depth block')[0] if has_extra else None
     ntiles, = r.unpack('<I', 'tile count')
     if th == 0 or tw == 0:
         raise ValueError('tile extent {} x {}: a tile has at least one row and one column'.format(th, tw))
@@ -1246,14 +1244,14 @@ def _parse_tile_extent(r, h, w, depth=None):
     if ntiles != expected:
         raise ValueError('tile count {} does not equal the {} tiles of a {} x {} volume cut into {} x {}'.format(
             ntiles, expected, h, w, th, tw))
-    return L, resolution, fingerprint, th, tw, ntiles
+    return L, resolution, fingerprint, th, tw, ntiles, extra
 
 
-def _parse_tile_table(r, version, h, w, depth=None):
-    """L .. payload length of a format-2 / format-4 / format-5 header, every length against the bytes that remain -> (L, resolution,
-    fingerprint, th, tw, first_syms, lengths, crcs or None, n); depth as _parse_tile_extent takes it (format 10: the table of format 4)"""
-    L, resolution, fingerprint, th, tw, ntiles = _parse_tile_extent(r, h, w, depth)
-    checked = version in _WITH_CRCS or version in (FORMAT_VERSION_DEPTH, FORMAT_VERSION_RANS)
+def _parse_tile_table(r, version, h, w):
+    """L .. payload length of an unlayered tiled header, every length against the bytes that remain -> (L, resolution, fingerprint,
+    th, tw, first_syms, lengths, crcs or None, n, extra as _parse_tile_extent gives it)"""
+    checked = FORMATS[version].checked
+    L, resolution, fingerprint, th, tw, ntiles, extra = _parse_tile_extent(r, h, w, FORMATS[version].extra is not None)
     row = 10 if checked else 6
     table = r.take(row * ntiles, 'tile table')            # against the bytes that remain, before anything of its size is built
     first_syms, lengths, crcs = [], [], [] if checked else None
@@ -1270,13 +1268,12 @@ def _parse_tile_table(r, version, h, w, depth=None):
     n, = r.unpack('<Q', 'payload length')
     if sum(lengths) != n:
         raise ValueError('stream lengths of the {} tiles sum to {}, the payload length is {}'.format(ntiles, sum(lengths), n))
-    return L, resolution, fingerprint, th, tw, first_syms, lengths, crcs, n
+    return L, resolution, fingerprint, th, tw, first_syms, lengths, crcs, n, extra
 
 
 def _parse_tiled(r, version, ae_name, pc_name, H, W, C, h, w):
-    """the rest of a format-2 / format-4 / format-5 file after the symbol volume shape (the CRC over the file has been checked)."""
-    depth = [] if version in (FORMAT_VERSION_DEPTH, FORMAT_VERSION_RANS) else None       # (format 12 keeps W where format 10 keeps B)
-    L, resolution, fingerprint, th, tw, first_syms, lengths, crcs, n = _parse_tile_table(r, version, h, w, depth)
+    """the rest of an unlayered tiled file after the symbol volume shape (the CRC over the file has been checked)."""
+    L, resolution, fingerprint, th, tw, first_syms, lengths, crcs, n, extra = _parse_tile_table(r, version, h, w)
     if crcs is not None:
         end = r.pos
         stored, = r.unpack('<I', 'header CRC')
@@ -1291,32 +1288,29 @@ def _parse_tiled(r, version, ae_name, pc_name, H, W, C, h, w):
     for n_t in lengths:
         streams.append(payload[pos:pos + n_t])
         pos += n_t
+    c = FORMATS[version].container
     if crcs is None:
-        return TiledContainer(version, ae_name, pc_name, H, W, C, h, w, L, resolution, fingerprint, th, tw, first_syms, streams, payload)
+        return c(version, ae_name, pc_name, H, W, C, h, w, L, resolution, fingerprint, th, tw, first_syms, streams, payload)
     for t, (b, crc) in enumerate(zip(streams, crcs)):
         actual = zlib.crc32(b) & 0xffffffff
         if actual != crc:
             raise ValueError('stream CRC mismatch in tile {}: the table says {:08x}, the stream gives {:08x}'.format(t, crc, actual))
     if version == FORMAT_VERSION_DEPTH:
-        B = depth[0]
+        B = extra
         if not 1 <= B <= 255 or C > 255:
             raise ValueError('depth block {} with C = {}: format 10 has blocks of 1 .. 255 cells and at most 255 channels'.format(B, C))
         for t, ((_, _, a, b), s) in enumerate(zip(tile_grid(h, w, th, tw), streams)):
             split_depth_stream(s, C, a, b, B, tile=t)     # a stream shorter than its plane, a depth above C: refused, naming the tile
-        return DepthContainer(version, ae_name, pc_name, H, W, C, h, w, L, resolution, fingerprint, th, tw, first_syms, streams, payload,
-                              crcs, B)
     if version == FORMAT_VERSION_RANS:
-        lanes = depth[0]
+        lanes = extra
         if lanes not in RANS_LANES:
             raise ValueError('{} coders per tile: format 12 has W in {}'.format(lanes, ', '.join(str(v) for v in RANS_LANES)))
         for t, s in enumerate(streams):
             if len(s) < 4 * lanes or (len(s) - 4 * lanes) % 2:
                 raise ValueError('stream of tile {} holds {} bytes: the states of its {} coders have {}, and 16-bit words follow'.format(
                     t, len(s), lanes, 4 * lanes))
-        return RansContainer(version, ae_name, pc_name, H, W, C, h, w, L, resolution, fingerprint, th, tw, first_syms, streams, payload,
-                             crcs, lanes)
-    cls = WavefrontContainer if version == FORMAT_VERSION_WAVEFRONT else CheckedContainer
-    return cls(version, ae_name, pc_name, H, W, C, h, w, L, resolution, fingerprint, th, tw, first_syms, streams, payload, crcs)
+    return c(*((version, ae_name, pc_name, H, W, C, h, w, L, resolution, fingerprint, th, tw, first_syms, streams, payload, crcs) +
+               (() if extra is None else (extra,))))
 
 
 def _parse_layered(r, ae_name, pc_name, H, W, C, h, w, strict, version=FORMAT_VERSION_LAYERED):
@@ -1324,7 +1318,7 @@ def _parse_layered(r, ae_name, pc_name, H, W, C, h, w, strict, version=FORMAT_VE
     The header: every length against the bytes that remain, then its own CRC.  strict (parse_container; the CRC over the file has
     been checked): the payload length must equal what is left and every segment must match its CRC.  Not strict (parse_partial): the
     payload is what arrived of it; a segment that is not whole or fails its CRC is None."""
-    L, resolution, fingerprint, th, tw, ntiles = _parse_tile_extent(r, h, w)
+    L, resolution, fingerprint, th, tw, ntiles, _ = _parse_tile_extent(r, h, w)
     G, = r.unpack('<H', 'layer count')
     if not 1 <= G <= MAX_LAYERS:
         raise ValueError('layer count G = {} is outside 1 .. {}'.format(G, MAX_LAYERS))
@@ -1397,7 +1391,7 @@ def _prefix_from_bytes(data, g):
     r, version = _partial_open(data)
     try:
         ae_name, pc_name, H, W, C, h, w = _parse_front(r)
-        L, resolution, fingerprint, th, tw, ntiles = _parse_tile_extent(r, h, w)
+        L, resolution, fingerprint, th, tw, ntiles, _ = _parse_tile_extent(r, h, w)
         G, = r.unpack('<H', 'layer count')
         if not 1 <= G <= MAX_LAYERS:
             raise ValueError('layer count G = {} is outside 1 .. {}'.format(G, MAX_LAYERS))
@@ -1413,24 +1407,17 @@ def _prefix_from_bytes(data, g):
     return r.pos + sum(rows[2 * i] for i in range(_check_layer_index(g, G) * ntiles))
 
 
-def _refuse_depth(data, what):
-    """--salvage, --partial, --recover, stream and repair do not read format 10: one sentence, before anything else of the file is looked at"""
-    if len(data) >= 6 and data[:4] == MAGIC and struct.unpack('<H', data[4:6])[0] == FORMAT_VERSION_DEPTH:
-        raise ValueError('format version {} (depth-mapped tiles) is not read by {}: a file to be salvaged is written with --tile --checked '
-                         'or --tile --wavefront (versions {} and {}), a file to be read from a prefix, recovered or streamed with the '
-                         'layered formats --layers / --front-layers (versions {} and {}); an intact file decodes with '
-                         'decompress'.format(FORMAT_VERSION_DEPTH, what, FORMAT_VERSION_CHECKED, FORMAT_VERSION_WAVEFRONT,
-                                             FORMAT_VERSION_LAYERED, FORMAT_VERSION_FRONTS))
-
-
-def _refuse_rans(data, what):
-    """--salvage, --partial, --recover, stream and repair do not read format 12: one sentence, before anything else of the file is looked at"""
-    if len(data) >= 6 and data[:4] == MAGIC and struct.unpack('<H', data[4:6])[0] == FORMAT_VERSION_RANS:
-        raise ValueError('format version {} (lane-parallel rANS tiles) is not read by {}: a file to be salvaged is written with --tile '
-                         '--checked or --tile --wavefront (versions {} and {}), a file to be read from a prefix, recovered or streamed '
-                         'with the layered formats --layers / --front-layers (versions {} and {}); an intact file decodes with '
-                         'decompress'.format(FORMAT_VERSION_RANS, what, FORMAT_VERSION_CHECKED, FORMAT_VERSION_WAVEFRONT,
-                                             FORMAT_VERSION_LAYERED, FORMAT_VERSION_FRONTS))
+def _refuse(data, what):
+    """--salvage, --partial, --recover, stream and repair (`what`) do not read a format that carries the checksums they read by but
+    has none of them among its readers -- formats 10 and 12: one sentence, before anything else of the file is looked at.  The
+    formats without checksums and each other's formats they refuse in words of their own."""
+    row = FORMATS.get(_source_version(data))
+    if row is not None and row.checked and not row.readers:
+        raise ValueError('format version {} ({}) is not read by {}: a file to be salvaged is written with --tile --checked or --tile '
+                         '--wavefront (versions {} and {}), a file to be read from a prefix, recovered or streamed with the layered '
+                         'formats --layers / --front-layers (versions {} and {}); an intact file decodes with decompress'.format(
+                             row.version, row.name, what, FORMAT_VERSION_CHECKED, FORMAT_VERSION_WAVEFRONT, FORMAT_VERSION_LAYERED,
+                             FORMAT_VERSION_FRONTS))
 
 
 def _partial_open(data):
@@ -1438,8 +1425,7 @@ def _partial_open(data):
         raise ValueError('header damaged: truncated file: {} bytes, the smallest container has {}'.format(len(data), _MIN_SIZE))
     if data[:4] != MAGIC:
         raise ValueError('header damaged: wrong magic {!r}: not a codec file (expected {!r})'.format(data[:4], MAGIC))
-    _refuse_depth(data, '--partial / --recover / stream')
-    _refuse_rans(data, '--partial / --recover / stream')
+    _refuse(data, '--partial / --recover / stream')
     version, = struct.unpack('<H', data[4:6])
     if version not in _LAYERED_VERSIONS:
         raise ValueError('header damaged: format version {} is not the layered version {}: only a layered file (--tile --layers / '
@@ -1473,12 +1459,11 @@ def parse_recover(data):
     its byte range is not complete; 'crc': the bytes are there, their CRC differs).  The header must be whole and pass its own CRC, as
     for parse_partial, else ValueError('header damaged: ...'); behind it nothing raises.  Another format is a ValueError."""
     data = bytes(data)
-    if len(data) >= 6 and data[:4] == MAGIC:
-        version, = struct.unpack('<H', data[4:6])
-        if version in (FORMAT_VERSION, FORMAT_VERSION_TILED) + _WITH_CRCS:
-            raise ValueError('format version {} is not the layered version {}: --recover reads layered files (--tile --layers / --progressive); '
-                             'a damaged format-{} / format-{} file is read with --salvage, an intact file of any format with '
-                             'decompress'.format(version, FORMAT_VERSION_LAYERED, FORMAT_VERSION_CHECKED, FORMAT_VERSION_WAVEFRONT))
+    version = _source_version(data)
+    if version in (FORMAT_VERSION, FORMAT_VERSION_TILED) + _WITH_CRCS:
+        raise ValueError('format version {} is not the layered version {}: --recover reads layered files (--tile --layers / --progressive); '
+                         'a damaged format-{} / format-{} file is read with --salvage, an intact file of any format with '
+                         'decompress'.format(version, FORMAT_VERSION_LAYERED, FORMAT_VERSION_CHECKED, FORMAT_VERSION_WAVEFRONT))
     c, _, file_crc_ok = parse_partial(data)
     G, ntiles = len(c.layer_ends), len(c.first_syms)
     start = _prefix_from_bytes(data, 0)                    # the payload's first byte; in front of it: header CRC, payload length, table
@@ -1565,8 +1550,7 @@ def parse_salvage(data):
     if data[:4] != MAGIC:
         raise ValueError('wrong magic {!r}: not a codec file (expected {!r})'.format(data[:4], MAGIC))
     version, = struct.unpack('<H', data[4:6])
-    _refuse_depth(data, '--salvage')
-    _refuse_rans(data, '--salvage')
+    _refuse(data, '--salvage')
     if version in (FORMAT_VERSION, FORMAT_VERSION_TILED):
         raise ValueError('format version {} has nothing to salvage with: one CRC over the whole file, none per tile (only version {}, '
                          'written with --tile --checked, can be salvaged)'.format(version, FORMAT_VERSION_CHECKED))
@@ -1579,7 +1563,7 @@ def parse_salvage(data):
     r = _Reader(data)
     try:
         ae_name, pc_name, H, W, C, h, w = _parse_front(r)
-        L, resolution, fingerprint, th, tw, first_syms, lengths, crcs, n = _parse_tile_table(r, version, h, w)
+        L, resolution, fingerprint, th, tw, first_syms, lengths, crcs, n, _ = _parse_tile_table(r, version, h, w)
         end = r.pos
         stored, = r.unpack('<I', 'header CRC')
     except ValueError as e:
@@ -1604,8 +1588,8 @@ def parse_salvage(data):
         pos += n_t
     tail = data[start + n:start + n + 4]
     file_crc_ok = len(payload) == n and len(tail) == 4 and struct.unpack('<I', tail)[0] == zlib.crc32(data[:start + n]) & 0xffffffff
-    cls = WavefrontContainer if version == FORMAT_VERSION_WAVEFRONT else CheckedContainer
-    return cls(version, ae_name, pc_name, H, W, C, h, w, L, resolution, fingerprint, th, tw, first_syms, streams, payload, crcs), damage, file_crc_ok
+    c = FORMATS[version].container(version, ae_name, pc_name, H, W, C, h, w, L, resolution, fingerprint, th, tw, first_syms, streams, payload, crcs)
+    return c, damage, file_crc_ok
 
 
 def model_fingerprint(centers, pc_params):
@@ -1647,35 +1631,15 @@ class Codec(object):
 
     def __init__(self, ae_config, pc_config, weights, device='cuda', plan_flags=0, device_encode=True, tile=None, checked=False,
                  order='raster', layers=None, front_layers=None, depth_block=None, rans=None):
-        if rans is not None:
-            self._check_rans(rans, tile, checked, order, layers, front_layers, depth_block)
-        if depth_block is not None:
-            self._check_depth(depth_block, tile, order, layers, front_layers, ae_config.num_chan_bn)
         if tile is not None:
             tile = (int(tile[0]), int(tile[1]))
             if not (1 <= tile[0] <= 0xffff and 1 <= tile[1] <= 0xffff):
                 raise ValueError('tile extent {} x {} is outside 1 .. 65535'.format(*tile))
-        if checked and tile is None:
-            raise ValueError('checked=True needs a tile extent: the checksums of format 4 are per tile')
-        if order not in ('raster', 'wavefront'):
-            raise ValueError("order is 'raster' or 'wavefront', got {!r}".format(order))
-        if order == 'wavefront' and tile is None:
-            raise ValueError("order='wavefront' needs a tile extent: format 5 is a tiled format")
-        if front_layers is not None:
-            self._check_front_layers(front_layers, tile, order, layers)
-        if layers is not None:
-            if tile is None:
-                raise ValueError('layers needs a tile extent: format 6 is a tiled format')
-            if order == 'wavefront':
-                raise ValueError("layers does not go with order='wavefront': a layer is no prefix of a wavefront-ordered stream")
-            layers = layers if isinstance(layers, str) else check_layer_ends(layers, ae_config.num_chan_bn)
-            if isinstance(layers, str) and layers != 'default':
-                raise ValueError("layers is None, 'default' or a sequence of layer ends, got {!r}".format(layers))
-        if front_layers is not None:
-            front_layers = front_layers if isinstance(front_layers, str) else check_layer_ends(front_layers, ae_config.num_chan_bn)
         self.tile, self.checked, self.order, self.layers, self.front_layers = tile, bool(checked), order, layers, front_layers
-        self.depth_block = None if depth_block is None else int(depth_block)
-        self.rans = rans
+        self.depth_block, self.rans = depth_block, rans
+        self.C = getattr(ae_config, 'num_chan_bn', None)
+        self.wavefront_refusal = self.layered_refusal = self.depth_refusal = self.rans_refusal = None
+        self._target()                                               # the combinations: refused before any model is built
         import torch
         from . import autoencoder, probclass
         self.device = torch.device(device)
@@ -1687,25 +1651,16 @@ class Codec(object):
             self.wavefront_refusal = None
         except ValueError as e:
             self.wavefront_refusal = str(e)
-        if order == 'wavefront' and self.wavefront_refusal:
-            raise ValueError(self.wavefront_refusal)
         k = int(getattr(self.pc, '_k', None) or pc_config.arch_param__k)
         self.layered_refusal = None if k == 24 else ('layered tiles: the decoder that restarts at layer cuts covers context models of '
                                                      'width k = 24, this one has k = {}'.format(k))
-        if layers is not None and self.layered_refusal:
-            raise ValueError(self.layered_refusal)
-        if front_layers is not None and (self.wavefront_refusal or self.layered_refusal):
-            raise ValueError(self.wavefront_refusal or self.layered_refusal)
         self.depth_refusal = self.wavefront_refusal or (None if k == 24 else (
             'depth-mapped tiles: the front decoder that reads a depth plane covers context models of width k = 24, this one has '
             'k = {}'.format(k)))
-        if depth_block is not None and self.depth_refusal:
-            raise ValueError(self.depth_refusal)
         self.rans_refusal = self.wavefront_refusal or (None if k == 24 else (
             'lane-parallel rANS tiles: the front decoder that steps W coders at once covers context models of width k = 24, this one '
             'has k = {}'.format(k)))
-        if rans is not None and self.rans_refusal:
-            raise ValueError(self.rans_refusal)
+        self._target()                                               # the model's refusal of the format asked for
         self.pred =probclass.PredictionNetwork(self.pc, pc_config, self.ae.get_centers_variable())
         self.ae_name, self.pc_name = config_name(ae_config), config_name(pc_config)
         self.factor = int(self.ae.get_subsampling_factor())
@@ -1761,15 +1716,6 @@ class Codec(object):
                              'formats 6 and 8 cut a tile into several')
         check_depth_block(depth_block, C)
 
-    def _depth(self):
-        """the depth block of the format-10 file compress writes, or None (the attributes may have been set after construction, as main does)"""
-        if getattr(self, 'depth_block', None) is None:
-            return None
-        self._check_depth(self.depth_block, self.tile, self.order, self.layers, getattr(self, 'front_layers', None), self.C)
-        if self.depth_refusal:
-            raise ValueError(self.depth_refusal)
-        return int(self.depth_block)
-
     @staticmethod
     def _check_rans(rans, tile, checked, order, layers, front_layers, depth_block):
         if tile is None:
@@ -1788,24 +1734,58 @@ class Codec(object):
         if not (isinstance(rans, str) and rans == 'default'):
             check_rans_lanes(rans)
 
-    def _rans(self):
-        """the number of coders W of the format-12 file compress writes, or None (the attributes may have been set after construction, as main does)"""
-        if getattr(self, 'rans', None) is None:
-            return None
-        self._check_rans(self.rans, self.tile, self.checked, self.order, self.layers, getattr(self, 'front_layers', None),
-                         getattr(self, 'depth_block', None))
-        if self.rans_refusal:
-            raise ValueError(self.rans_refusal)
-        return DEFAULT_RANS_LANES if isinstance(self.rans, str) else int(self.rans)
+    def _target(self):
+        """the format this Codec writes -> (its row of FORMATS, the format's parameter: the coders W, the depth block B, the layer
+        ends, or None).  Resolved on every call from the attributes as they are now -- main and the timing tools set them after
+        construction -- with every refusal of a combination and of the model, in one order: rans, depth_block, front_layers, layers,
+        order, checked."""
+        tile, order, layers = self.tile, self.order, self.layers
+        checked, fronts = getattr(self, 'checked', False), getattr(self, 'front_layers', None)
+        depth, rans = getattr(self, 'depth_block', None), getattr(self, 'rans', None)
+        version, param = None, None                                  # (the checks leave at most one of the four options standing)
+
+        def allowed(refusal):
+            if refusal:
+                raise ValueError(refusal)
+
+        if rans is not None:
+            self._check_rans(rans, tile, checked, order, layers, fronts, depth)
+            allowed(self.rans_refusal)
+            version, param = FORMAT_VERSION_RANS, DEFAULT_RANS_LANES if isinstance(rans, str) else int(rans)
+        if depth is not None:
+            self._check_depth(depth, tile, order, layers, fronts, self.C)
+            allowed(self.depth_refusal)
+            version, param = FORMAT_VERSION_DEPTH, int(depth)
+        if fronts is not None:
+            self._check_front_layers(fronts, tile, order, layers)
+            allowed(self.wavefront_refusal or self.layered_refusal)
+            version, param = FORMAT_VERSION_FRONTS, default_layer_ends(self.C) if isinstance(fronts, str) else check_layer_ends(fronts, self.C)
+        if layers is not None:
+            if tile is None:
+                raise ValueError('layers needs a tile extent: format 6 is a tiled format')
+            if order == 'wavefront':
+                raise ValueError("layers does not go with order='wavefront': a layer is no prefix of a wavefront-ordered stream")
+            allowed(self.layered_refusal)
+            if isinstance(layers, str) and layers != 'default':
+                raise ValueError("layers is None, 'default' or a sequence of layer ends, got {!r}".format(layers))
+            version, param = FORMAT_VERSION_LAYERED, default_layer_ends(self.C) if isinstance(layers, str) else check_layer_ends(layers, self.C)
+        if order not in ('raster', 'wavefront'):
+            raise ValueError("order is 'raster' or 'wavefront', got {!r}".format(order))
+        if order == 'wavefront':
+            if tile is None:
+                raise ValueError("order='wavefront' needs a tile extent: format 5 is a tiled format")
+            allowed(self.wavefront_refusal)
+            version = FORMAT_VERSION_WAVEFRONT                       # (checked or not: format 5 always carries the checksums)
+        if checked and tile is None:
+            raise ValueError('checked=True needs a tile extent: the checksums of format 4 are per tile')
+        if version is None:
+            version = FORMAT_VERSION if tile is None else FORMAT_VERSION_CHECKED if checked else FORMAT_VERSION_TILED
+        return FORMATS[version], param
 
     def _front_ends(self):
-        """the layer ends of the format-8 file compress writes, or None (the attributes may have been set after construction, as main does)"""
-        if getattr(self, 'front_layers', None) is None:
-            return None
-        self._check_front_layers(self.front_layers, self.tile, self.order, self.layers)
-        if self.wavefront_refusal or self.layered_refusal:
-            raise ValueError(self.wavefront_refusal or self.layered_refusal)
-        return default_layer_ends(self.C) if isinstance(self.front_layers, str) else check_layer_ends(self.front_layers, self.C)
+        """the layer ends of the format-8 file compress writes, or None"""
+        row, param = self._target()
+        return param if row.version == FORMAT_VERSION_FRONTS else None
 
     def compress(self, img_hwc_uint8, cap=None, rois=None, background=None):
         """HWC uint8 -> container bytes.  cap: None, a level, or an (h, w) plane bounding the importance map (cap_plane; rois and
@@ -1908,37 +1888,10 @@ class Codec(object):
 
     def _container(self, sym, H, W):
         """the symbols (C, h, w) of an H x W image, on the device -> container bytes in this Codec's format"""
+        row, param = self._target()
+        if row.version != FORMAT_VERSION:
+            return self._pack(row, param, self.pred.encode_tiles(sym, self.tile[0], self.tile[1], **_coder_kw(row, param)), sym, H, W)
         C, h, w = (int(v) for v in sym.shape)
-        lanes = self._rans()
-        if lanes is not None:
-            th, tw = self.tile
-            coded = self.pred.encode_tiles(sym, th, tw, order='rans', lanes=lanes)
-            return build_rans_container(self.ae_name, self.pc_name, H, W, C, h, w, self.L, self.pred.freqs_resolution,
-                                        self.fingerprint, th, tw, lanes, [f for _, f in coded], [b for b, _ in coded])
-        B = self._depth()
-        if B is not None:
-            th, tw = self.tile
-            coded = self.pred.encode_tiles(sym, th, tw, order='wavefront', depth_block=B)
-            return build_depth_container(self.ae_name, self.pc_name, H, W, C, h, w, self.L, self.pred.freqs_resolution,
-                                         self.fingerprint, th, tw, B, [f for _, f in coded], [b for b, _ in coded])
-        fronts = self._front_ends()
-        if fronts is not None:
-            th, tw = self.tile
-            coded = self.pred.encode_tiles(sym, th, tw, front_ends=fronts)
-            return build_front_layered_container(self.ae_name, self.pc_name, H, W, C, h, w, self.L, self.pred.freqs_resolution,
-                                                 self.fingerprint, th, tw, [f for _, f in coded], fronts,
-                                                 [[segs[g] for segs, _ in coded] for g in range(len(fronts))])
-        ends = self._layer_ends()
-        if ends is not None:
-            th, tw = self.tile
-            coded = self.pred.encode_tiles(sym, th, tw, layer_ends=ends)
-            return build_layered_container(self.ae_name, self.pc_name, H, W, C, h, w, self.L, self.pred.freqs_resolution, self.fingerprint,
-                                           th, tw, [f for _, f in coded], ends, [[segs[g] for segs, _ in coded] for g in range(len(ends))])
-        if self.tile is not None:
-            th, tw = self.tile
-            coded = self.pred.encode_tiles(sym, th, tw, order=self._order())
-            return self._build_tiled(self.ae_name, self.pc_name, H, W, C, h, w, self.L, self.pred.freqs_resolution,
-                                         self.fingerprint, th, tw, [f for _, f in coded], [b for b, _ in coded])
         if self.device_encode:
             payload, first_sym = self.pred.encode_stream(sym)
         else:
@@ -1946,40 +1899,14 @@ class Codec(object):
         return build_container(self.ae_name, self.pc_name, H, W, C, h, w, self.L, first_sym, self.pred.freqs_resolution,
                                self.fingerprint, payload)
 
-    def _layer_ends(self):
-        """the layer ends compress writes, or None (the attributes may have been set after construction, as main does)"""
-        if self.layers is None:
-            return None
-        if self.tile is None:
-            raise ValueError('layers needs a tile extent: format 6 is a tiled format')
-        if self.order == 'wavefront':
-            raise ValueError("layers does not go with order='wavefront': a layer is no prefix of a wavefront-ordered stream")
-        if self.layered_refusal:
-            raise ValueError(self.layered_refusal)
-        if isinstance(self.layers, str):
-            if self.layers != 'default':
-                raise ValueError("layers is None, 'default' or a sequence of layer ends, got {!r}".format(self.layers))
-            return default_layer_ends(self.C)
-        return check_layer_ends(self.layers, self.C)
-
-    def _order(self):
-        """the order compress writes (the attributes may have been set after construction, as main does)"""
-        if self.order not in ('raster', 'wavefront'):
-            raise ValueError("order is 'raster' or 'wavefront', got {!r}".format(self.order))
-        if self.order == 'wavefront':
-            if self.tile is None:
-                raise ValueError("order='wavefront' needs a tile extent: format 5 is a tiled format")
-            if self.wavefront_refusal:
-                raise ValueError(self.wavefront_refusal)
-        return self.order
-
-    @property
-    def _build_tiled(self):
-        if self.checked and self.tile is None:
-            raise ValueError('checked=True needs a tile extent: the checksums of format 4 are per tile')
-        if self._order() == 'wavefront':
-            return build_wavefront_container                 # (checked or not: format 5 always carries the checksums)
-        return build_checked_container if self.checked else build_tiled_container
+    def _pack(self, row, param, coded, sym, H, W):
+        """the coded tiles of one volume, as encode_tiles gives them for the tiled format `row` -> its container bytes"""
+        C, h, w = (int(v) for v in sym.shape)
+        head = (self.ae_name, self.pc_name, H, W, C, h, w, self.L, self.pred.freqs_resolution, self.fingerprint) + tuple(self.tile)
+        if row.layered:
+            return build_layered_container(*(head + ([f for _, f in coded], param, [[segs[g] for segs, _ in coded] for g in range(len(param))])),
+                                           version=row.version)
+        return _build_tiled(row.version, *(head + ([f for _, f in coded], [b for b, _ in coded], param)))
 
     def check_container(self, c):
         """the header against the loaded model and against itself; the volume is bounded by the header's own image size only (a
@@ -1999,16 +1926,9 @@ class Codec(object):
         if (c.h, c.w) != (eh, ew):
             raise ValueError('header mismatch: symbol volume {} x {} does not belong to a {} x {} image (expected {} x {})'.format(
                 c.h, c.w, c.H, c.W, eh, ew))
-        if isinstance(c, WavefrontContainer) and self.wavefront_refusal:
-            raise ValueError('format 5 cannot be read with this model: {}'.format(self.wavefront_refusal))
-        if isinstance(c, DepthContainer) and self.depth_refusal:
-            raise ValueError('format {} cannot be read with this model: {}'.format(c.version, self.depth_refusal))
-        if isinstance(c, RansContainer) and self.rans_refusal:
-            raise ValueError('format {} cannot be read with this model: {}'.format(c.version, self.rans_refusal))
-        if isinstance(c, LayeredContainer) and self.layered_refusal:
-            raise ValueError('format {} cannot be read with this model: {}'.format(c.version, self.layered_refusal))
-        if isinstance(c, LayeredContainer) and c.version == FORMAT_VERSION_FRONTS and self.wavefront_refusal:
-            raise ValueError('format {} cannot be read with this model: {}'.format(c.version, self.wavefront_refusal))
+        for refusal in FORMATS[c.version].refusals:
+            if getattr(self, refusal):
+                raise ValueError('format {} cannot be read with this model: {}'.format(c.version, getattr(self, refusal)))
         for first_sym in (c.first_syms if isinstance(c, _TILED) else [c.first_sym]):
             if first_sym >= c.L:
                 raise ValueError('header mismatch: first symbol {} is not below L = {}'.format(first_sym, c.L))
@@ -2023,16 +1943,13 @@ class Codec(object):
         c = parse_container(data)
         self.check_container(c)
         try:
-            if isinstance(c, LayeredContainer):          # a batch of one: the layers are arguments of the batch entry
-                sym = self.pred.decode_tiles_batch([(c.streams, c.first_syms, (c.C, c.h, c.w))], c.th, c.tw, want='symbols',
-                                                   channels=channels, **_ends_kw(c))[0].cpu().numpy()
-            elif isinstance(c, (WavefrontContainer, DepthContainer, RansContainer)):    # a batch of one: the order and the depth block are flags of the batch entry
-                sym = self.pred.decode_tiles_batch([(c.streams, c.first_syms, (c.C, c.h, c.w))], c.th, c.tw, want='symbols',
-                                                   channels=channels, **_order_kw(c))[0].cpu().numpy()
-            elif isinstance(c, _TILED):
-                sym = self.pred.decode_tiles(c.streams, c.first_syms, (c.C, c.h, c.w), c.th, c.tw, channels=channels)
-            else:
+            if not isinstance(c, _TILED):
                 sym = self.pred.decode_stream(c.payload, (c.C, c.h, c.w), c.first_sym, channels=channels)
+            elif FORMATS[c.version].order == 'raster':   # formats 2 and 4: the entry of one volume
+                sym = self.pred.decode_tiles(c.streams, c.first_syms, (c.C, c.h, c.w), c.th, c.tw, channels=channels)
+            else:                                        # a batch of one: the order, the ends and the extra field are arguments of the batch entry
+                sym = self.pred.decode_tiles_batch([(c.streams, c.first_syms, (c.C, c.h, c.w))], c.th, c.tw, want='symbols',
+                                                   channels=channels, **_decode_kw(c))[0].cpu().numpy()
         except ValueError as e:
             raise ValueError('decoder status is not 0: {}'.format(e))
         return sym, c
@@ -2048,7 +1965,7 @@ class Codec(object):
         channels = c.layer_ends[complete - 1]
         try:
             sym = self.pred.decode_tiles_batch([(c.streams, c.first_syms, (c.C, c.h, c.w))], c.th, c.tw, want='symbols',
-                                               channels=channels, **_ends_kw(c))[0].cpu().numpy()
+                                               channels=channels, **_decode_kw(c))[0].cpu().numpy()
         except ValueError as e:
             raise ValueError('decoder status is not 0: {}'.format(e))
         return self._image(sym, c), PartialReport(len(c.layer_ends), complete, channels, file_crc_ok)
@@ -2136,44 +2053,11 @@ class Codec(object):
         import torch
         if not self.device_encode:
             return [self._container(sym, H, W) for sym, (H, W) in zip(syms, sizes)]
+        row, param = self._target()
+        if row.version != FORMAT_VERSION:
+            coded = self.pred.encode_tiles_batch(syms, self.tile[0], self.tile[1], **_coder_kw(row, param))
+            return [self._pack(row, param, coded[i], syms[i], H, W) for i, (H, W) in enumerate(sizes)]
         out = [None] * len(syms)
-        lanes = self._rans()
-        if lanes is not None:
-            th, tw = self.tile
-            for i, coded in enumerate(self.pred.encode_tiles_batch(syms, th, tw, order='rans', lanes=lanes)):
-                C, h, w = (int(v) for v in syms[i].shape)
-                out[i] = build_rans_container(self.ae_name, self.pc_name, sizes[i][0], sizes[i][1], C, h, w, self.L,
-                                              self.pred.freqs_resolution, self.fingerprint, th, tw, lanes,
-                                              [f for _, f in coded], [b for b, _ in coded])
-            return out
-        B = self._depth()
-        if B is not None:
-            th, tw = self.tile
-            for i, coded in enumerate(self.pred.encode_tiles_batch(syms, th, tw, order='wavefront', depth_block=B)):
-                C, h, w = (int(v) for v in syms[i].shape)
-                out[i] = build_depth_container(self.ae_name, self.pc_name, sizes[i][0], sizes[i][1], C, h, w, self.L,
-                                               self.pred.freqs_resolution, self.fingerprint, th, tw, B,
-                                               [f for _, f in coded], [b for b, _ in coded])
-            return out
-        fronts = self._front_ends()
-        ends = fronts if fronts is not None else self._layer_ends()
-        if ends is not None:
-            th, tw = self.tile
-            build = build_layered_container if fronts is None else build_front_layered_container
-            for i, coded in enumerate(self.pred.encode_tiles_batch(syms, th, tw, **({'layer_ends': ends} if fronts is None else {'front_ends': ends}))):
-                C, h, w = (int(v) for v in syms[i].shape)
-                out[i] = build(self.ae_name, self.pc_name, sizes[i][0], sizes[i][1], C, h, w, self.L,
-                               self.pred.freqs_resolution, self.fingerprint, th, tw, [f for _, f in coded], ends,
-                               [[segs[g] for segs, _ in coded] for g in range(len(ends))])
-            return out
-        if self.tile is not None:
-            th, tw = self.tile
-            for i, coded in enumerate(self.pred.encode_tiles_batch(syms, th, tw, order=self._order())):
-                C, h, w = (int(v) for v in syms[i].shape)
-                out[i] = self._build_tiled(self.ae_name, self.pc_name, sizes[i][0], sizes[i][1], C, h, w, self.L,
-                                               self.pred.freqs_resolution, self.fingerprint, th, tw,
-                                               [f for _, f in coded], [b for b, _ in coded])
-            return out
         by_shape = {}
         for i, sym in enumerate(syms):
             by_shape.setdefault(tuple(sym.shape), []).append(i)
@@ -2194,14 +2078,10 @@ class Codec(object):
         """the batched part of decompress_many / transcode_many over parsed and checked containers: per kind (raster, wavefront,
         layered, front-layered) the tiled files of the most frequent tile extent (and layer ends) in one decode_tiles_batch call ->
         yields (their indices, per file q or symbols on the device); the other files are the caller's, one by one"""
-        kind = lambda c: (('fronts' if c.version == FORMAT_VERSION_FRONTS else 'layered') if isinstance(c, LayeredContainer)
-                          else 'depth' if isinstance(c, DepthContainer) else 'rans' if isinstance(c, RansContainer)
-                          else 'wavefront' if isinstance(c, WavefrontContainer) else 'raster')
-        for order in ('raster', 'wavefront', 'layered', 'fronts', 'depth', 'rans'):
-            mine = [i for i, c in enumerate(heads) if isinstance(c, _TILED) and kind(c) == order]
-            extents = [(heads[i].th, heads[i].tw) + (tuple(heads[i].layer_ends) if order in ('layered', 'fronts') else
-                                                     (heads[i].depth_block,) if order == 'depth' else
-                                                     (heads[i].lanes,) if order == 'rans' else ()) for i in mine]
+        keys = [_batch_key(c) if isinstance(c, _TILED) else None for c in heads]
+        for kind in dict.fromkeys((row.order, row.param_kw) for row in FORMATS.values() if row.container in _TILED):
+            mine = [i for i, key in enumerate(keys) if key is not None and key[2:4] == kind]
+            extents = [keys[i] for i in mine]
             major = max(sorted(set(extents)), key=extents.count) if extents else None
             together = [i for i, e in zip(mine, extents) if e == major]
             if not together:
@@ -2210,10 +2090,7 @@ class Codec(object):
                 got = self.pred.decode_tiles_batch([(heads[i].streams, heads[i].first_syms, (heads[i].C, heads[i].h, heads[i].w))
                                                     for i in together], major[0], major[1], want=want,
                                                    max_workspace_bytes=max_workspace_bytes, channels=channels,
-                                                   **({'layer_ends': list(major[2:])} if order == 'layered' else
-                                                      {'front_ends': list(major[2:])} if order == 'fronts' else
-                                                      {'order': 'wavefront', 'depth_block': major[2]} if order == 'depth' else
-                                                      {'order': 'rans', 'lanes': major[2]} if order == 'rans' else {'order': order}))
+                                                   **_decode_kw(heads[together[0]]))
             except ValueError as e:
                 m = re.search(r'volume (\d+)', str(e))
                 where = 'file {}: '.format(together[int(m.group(1))]) if m else ''
@@ -2323,7 +2200,7 @@ class Codec(object):
             return self._region_crop(self.decompress(data, channels=channels), plan)
         try:
             q = self.pred.decode_tiles_batch([(win.streams, win.first_syms, (win.C, win.h, win.w))], win.th, win.tw, want='q', channels=channels,
-                                             **(_ends_kw(win) if isinstance(win, LayeredContainer) else _order_kw(win)))[0]
+                                             **_decode_kw(win))[0]
         except ValueError as e:
             raise ValueError('decoder status is not 0: {}'.format(e))
         return np.transpose(self._window_pixels(self.ae, q, plan, bits).cpu().numpy(), (1, 2, 0)).copy()
@@ -2395,7 +2272,7 @@ class Codec(object):
         import torch
         c, reasons, file_crc_ok = self._salvage_head(data)
         qs, damage = self.pred.decode_tiles_batch([(c.streams, c.first_syms, (c.C, c.h, c.w))], c.th, c.tw, want='q', conceal=True,
-                                                  order='wavefront' if isinstance(c, WavefrontContainer) else 'raster')
+                                                  **_decode_kw(c))
         x_out = self.ae.decode(qs[0][None], is_training=False).to(torch.uint8)   # tf.cast truncates (val.py)
         return self._crop(x_out[0], c), self._report(c, reasons, damage[0], file_crc_ok)
 
@@ -2412,12 +2289,11 @@ class Codec(object):
             except ValueError as e:
                 raise ValueError('file {}: {}'.format(i, e))
         out = [None] * len(datas)
-        kind = lambda c: (c.th, c.tw, 'wavefront' if isinstance(c, WavefrontContainer) else 'raster')
-        for extent in sorted(set(kind(c) for c, _, _ in heads)):
-            members = [i for i, (c, _, _) in enumerate(heads) if kind(c) == extent]
+        for extent in sorted(set(_batch_key(c) for c, _, _ in heads)):
+            members = [i for i, (c, _, _) in enumerate(heads) if _batch_key(c) == extent]
             qs, damage = self.pred.decode_tiles_batch([(heads[i][0].streams, heads[i][0].first_syms, (heads[i][0].C, heads[i][0].h, heads[i][0].w))
                                                        for i in members], extent[0], extent[1], want='q', conceal=True,
-                                                      max_workspace_bytes=max_workspace_bytes, order=extent[2])
+                                                      max_workspace_bytes=max_workspace_bytes, **_decode_kw(heads[members[0]][0]))
             imgs = self._in_flight(qs, lambda ae, q: ae.decode(q[None], is_training=False).to(torch.uint8)[0])    # tf.cast truncates (val.py)
             for i, x, dmg in zip(members, imgs, damage):
                 c, reasons, file_crc_ok = heads[i]
@@ -2438,7 +2314,7 @@ class Codec(object):
         c0 = heads[0][0]
         return self.pred.decode_tiles_batch([(c.streams, c.first_syms, (c.C, c.h, c.w)) for c, _, _, _ in heads], c0.th, c0.tw, want=want,
                                             max_workspace_bytes=max_workspace_bytes,
-                                            tile_layers=[layers for _, layers, _, _ in heads], **_ends_kw(c0))
+                                            tile_layers=[layers for _, layers, _, _ in heads], **_decode_kw(c0))
 
     def _recover_report(self, head, held):
         """held: [(tile, layers_read, channels, reason)] of decode_tiles_batch(tile_layers=...); the reader's reason where it has one"""
@@ -2494,16 +2370,6 @@ class Codec(object):
 
     # -- a file to a file: another format, a lower rate, no image and no autoencoder --
 
-    def _check_target(self):
-        """the refusals of the format this Codec writes, before anything is decoded"""
-        self._rans()
-        self._depth()
-        self._front_ends()
-        self._layer_ends()
-        self._order()
-        if self.checked and self.tile is None:
-            raise ValueError('checked=True needs a tile extent: the checksums of format 4 are per tile')
-
     def _keep_plane(self, c, cap=None, rois=None, background=None):
         """transcode's cap arguments for the file of container c -> None (no cap) or the (h, w) int64 plane of channels kept per
         cell (cap_plane on the header's H, W, then cap_channels: integer levels only)"""
@@ -2524,10 +2390,8 @@ class Codec(object):
         """a parsed and checked container -> its (C, h, w) int64 symbols, left on the device"""
         shape = (c.C, c.h, c.w)
         try:
-            if isinstance(c, LayeredContainer):
-                return self.pred.decode_tiles_batch([(c.streams, c.first_syms, shape)], c.th, c.tw, want='symbols', **_ends_kw(c))[0]
             if isinstance(c, _TILED):
-                return self.pred.decode_tiles_batch([(c.streams, c.first_syms, shape)], c.th, c.tw, want='symbols', **_order_kw(c))[0]
+                return self.pred.decode_tiles_batch([(c.streams, c.first_syms, shape)], c.th, c.tw, want='symbols', **_decode_kw(c))[0]
             return self.pred.decode_stream(c.payload, shape, c.first_sym, on_device=True)
         except ValueError as e:
             raise ValueError('decoder status is not 0: {}'.format(str(e).replace('(volume 0, tile ', '(tile ')))
@@ -2539,7 +2403,7 @@ class Codec(object):
         but at integer levels only (cap_channels: a fractional cap needs the bottleneck) -- cell p keeps the channels below its level,
         the others get the fill symbol (cap_symbols), which is compress(img, cap=...) of the same levels.  The file is parsed and
         checked as decompress does it; every refusal, the target format's included, comes before any device work."""
-        self._check_target()
+        self._target()
         c = parse_container(data)
         self.check_container(c)
         keep = self._keep_plane(c, cap, rois, background)
@@ -2556,7 +2420,7 @@ class Codec(object):
         caps = [None] * len(datas) if caps is None else list(caps)
         if len(caps) != len(datas):
             raise ValueError('caps: {} entries for {} files'.format(len(caps), len(datas)))
-        self._check_target()
+        self._target()
         heads, keeps = [], []
         for i, (data, cap) in enumerate(zip(datas, caps)):
             try:
@@ -2588,7 +2452,7 @@ class Codec(object):
         import torch
         from ._lib import lib, check, ptr, current_stream
         max_bytes = int(max_bytes)
-        self._check_target()
+        self._target()
         c = parse_container(data)
         self.check_container(c)
         C = self.C
@@ -2639,11 +2503,10 @@ class Codec(object):
         report: recover's RecoverReport); the symbols stay on the device and are coded again, under `cap` if one is given (as
         transcode's).  decompress(out) is salvage's / recover's picture; an intact file gives transcode(data) and an empty list.
         Formats 1 and 2 carry no checksums to read a damaged file by: refused in salvage's words."""
-        self._check_target()
+        self._target()
         raw = bytes(data)
-        _refuse_depth(raw, 'repair')
-        _refuse_rans(raw, 'repair')
-        if len(raw) >= 6 and raw[:4] == MAGIC and struct.unpack('<H', raw[4:6])[0] in _LAYERED_VERSIONS:
+        _refuse(raw, 'repair')
+        if _source_version(raw) in _LAYERED_VERSIONS:
             head = self._recover_head(raw)
             c = head[0]
             keep = self._keep_plane(c, cap)
@@ -2653,7 +2516,7 @@ class Codec(object):
             c, reasons, file_crc_ok = self._salvage_head(raw)
             keep = self._keep_plane(c, cap)
             syms, damage = self.pred.decode_tiles_batch([(c.streams, c.first_syms, (c.C, c.h, c.w))], c.th, c.tw, want='symbols', conceal=True,
-                                                        order='wavefront' if isinstance(c, WavefrontContainer) else 'raster')
+                                                        **_decode_kw(c))
             report = self._report(c, reasons, damage[0], file_crc_ok)
         return self._container(self._capped(syms[0], keep), c.H, c.W), report
 
@@ -2677,19 +2540,8 @@ class Codec(object):
         return torch.cat([scales, mse.reshape(1)])
 
     def written_version(self):
-        """the format version of the files this Codec writes (its refusals are _check_target's)"""
-        self._check_target()
-        if self._rans() is not None:
-            return FORMAT_VERSION_RANS
-        if self._depth() is not None:
-            return FORMAT_VERSION_DEPTH
-        if self._front_ends() is not None:
-            return FORMAT_VERSION_FRONTS
-        if self._layer_ends() is not None:
-            return FORMAT_VERSION_LAYERED
-        if self.tile is None:
-            return FORMAT_VERSION
-        return FORMAT_VERSION_WAVEFRONT if self._order() == 'wavefront' else FORMAT_VERSION_CHECKED if self.checked else FORMAT_VERSION_TILED
+        """the format version of the files this Codec writes (its refusals are _target's)"""
+        return self._target()[0].version
 
     def measure(self, img_hwc_uint8, data, channels=None, rect=None):
         """how good is this file?  -> Measure(bytes, bpp, mse, psnr, ms_ssim) of decompress(data, channels=channels) against its
@@ -2715,7 +2567,7 @@ class Codec(object):
     def _quality_inputs(self, img_hwc_uint8):
         """the part of rd_curve and compress_to_quality that runs once per image -> (bottleneck, original on the device, (H, W))"""
         x, (H, W) = self._image_tensor(img_hwc_uint8)
-        self._check_target()
+        self._target()
         _, bott = self.ae.encode_capped(x, None, keep_bottleneck=True)
         return bott, self._original(np.asarray(img_hwc_uint8)[:, :, :3]), (H, W)
 
@@ -2774,7 +2626,7 @@ class Codec(object):
         one batch-1 decode and one metrics call; the encoder is never run.  Level C is the file's own picture (psnr inf, ms_ssim 1)
         and meets every target, so probes <= 1 + 2 + ceil(log2 C)."""
         name, target = quality_target(psnr, ms_ssim)
-        self._check_target()
+        self._target()
         c = parse_container(data)
         self.check_container(c)
         sym = self._decode_device(c)
@@ -2813,18 +2665,32 @@ class Codec(object):
         return img
 
 
-def _order_kw(c):
-    """what decode_tiles_batch is told about the streams of an unlayered tiled container"""
-    if isinstance(c, DepthContainer):
-        return {'order': 'wavefront', 'depth_block': c.depth_block}
-    if isinstance(c, RansContainer):
-        return {'order': 'rans', 'lanes': c.lanes}
-    return {'order': 'wavefront' if isinstance(c, WavefrontContainer) else 'raster'}
+def _coder_kw(row, param):
+    """what encode_tiles* and decode_tiles_batch are told for the tiled format `row` with its parameter (the layer ends or the extra field)"""
+    kw = {} if row.order is None else {'order': row.order}
+    if row.param_kw is not None:
+        kw[row.param_kw] = param
+    return kw
 
 
-def _ends_kw(c):
-    """the keyword decode_tiles_batch takes a LayeredContainer's layer ends through: plane cuts of format 6, front cuts of format 8"""
-    return {'front_ends': c.layer_ends} if c.version == FORMAT_VERSION_FRONTS else {'layer_ends': c.layer_ends}
+def _param(c):
+    """the parameter of a parsed tiled container's format: its layer ends, its extra field, or None"""
+    row = FORMATS[c.version]
+    return c.layer_ends if row.layered else getattr(c, row.extra) if row.extra else None
+
+
+def _decode_kw(c):
+    """what decode_tiles_batch is told about the streams of a parsed tiled container"""
+    return _coder_kw(FORMATS[c.version], _param(c))
+
+
+_ends_kw = _decode_kw                                                # the name tests/test_gpu_codec_golden.py and tools/codec_fronts_timing.py call it by
+
+def _batch_key(c):
+    """tiled containers with one key decode in one decode_tiles_batch call: the tile extent, what the decoder is told (formats 2 and 4
+    are one kind of stream) and the format's parameter"""
+    row, param = FORMATS[c.version], _param(c)
+    return (c.th, c.tw, row.order, row.param_kw, tuple(param) if row.layered else param)
 
 
 class StreamDecoder(object):
@@ -2884,7 +2750,7 @@ class StreamDecoder(object):
         codec = self.codec
         if self._last is None or self._last[0] != layers:
             if self._session is None:
-                self._session = codec.pred.open_layers([(c.C, c.h, c.w)], c.th, c.tw, max_workspace_bytes=self.max_workspace_bytes, **_ends_kw(c))
+                self._session = codec.pred.open_layers([(c.C, c.h, c.w)], c.th, c.tw, max_workspace_bytes=self.max_workspace_bytes, **_decode_kw(c))
             qs, held = self._session.advance([(c.streams, c.first_syms)], [layers], want='q')
             x_out = codec.ae.decode(qs[0][None], is_training=False).to(torch.uint8)      # tf.cast truncates (val.py)
             self._last = (layers, codec._crop(x_out[0], c), held[0])
@@ -3328,7 +3194,7 @@ def _main_dir(flags, ae_config, pc_config):
 
 
 def _source_version(data):
-    """the format version a file names, for a printed line (the readers decide what it is worth); None without one"""
+    """the format version a file names, before anything else of it is looked at (the readers decide what it is worth); None without one"""
     return struct.unpack('<H', data[4:6])[0] if len(data) >= 6 and data[:4] == MAGIC else None
 
 
@@ -3539,7 +3405,7 @@ def verify_file(data):
             return True, 'ok (format {}, {} bytes, W = {} coders per tile)'.format(c.version, len(data), c.lanes)
         return True, 'ok (format {}, {} bytes)'.format(c.version, len(data))
     except ValueError as strict:
-        if len(data) >= 6 and data[:4] == MAGIC and struct.unpack('<H', data[4:6])[0] in _LAYERED_VERSIONS:
+        if _source_version(data) in _LAYERED_VERSIONS:
             try:
                 c, complete, _ = parse_partial(data)
             except ValueError as e:
@@ -3548,7 +3414,7 @@ def verify_file(data):
         try:
             c, damage, file_crc_ok = parse_salvage(data)
         except ValueError as e:
-            if len(data) >= 6 and data[:4] == MAGIC and struct.unpack('<H', data[4:6])[0] in _WITH_CRCS:
+            if _source_version(data) in _WITH_CRCS:
                 return False, str(e)
             return False, str(strict)
         if not damage:

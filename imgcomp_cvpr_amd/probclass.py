@@ -570,25 +570,8 @@ class PredictionNetwork(object):
         tile's corner, then the coder's bytes of its live positions (encode_stream).
         order='rans', lanes=W (container format 12; not with layer_ends, front_ends or depth_block): every tile's stream is that of W
         interleaved rANS coders over the rounds of its own extent (encode_stream)."""
-        from .codec import tile_grid
-        self._check_front_ends(front_ends, order, layer_ends)
-        self._check_depth_block(depth_block, order, layer_ends, front_ends)
-        sym = symbols if torch.is_tensor(symbols) else torch.as_tensor(np.ascontiguousarray(symbols))
-        assert sym.dim() == 3, 'Expected CHW symbols'
-        sym = sym.to(self.centers.device).long()
-        grid = tile_grid(int(sym.shape[1]), int(sym.shape[2]), th, tw)
-        by_shape = OrderedDict()
-        for t, (y0, x0, a, b) in enumerate(grid):
-            by_shape.setdefault((a, b), []).append(t)
-        res = [None] * len(grid)
-        for (a, b), members in by_shape.items():
-            batch = torch.stack([sym[:, grid[t][0]:grid[t][0] + a, grid[t][1]:grid[t][1] + b] for t in members])
-            seg_ends = None if layer_ends is None else [int(e) * a * b for e in layer_ends]
-            coded = (self._encode_fronts(batch, front_ends) if front_ends is not None else
-                     self.encode_stream(batch, order=order, seg_ends=seg_ends, depth_block=depth_block, lanes=lanes))
-            for t, r in zip(members, coded):
-                res[t] = r
-        return res
+        return self.encode_tiles_batch([symbols], th, tw, order=order, layer_ends=layer_ends, front_ends=front_ends, depth_block=depth_block,
+                                       lanes=lanes)[0]
 
     @staticmethod
     def _check_front_ends(front_ends, order, layer_ends):

@@ -327,12 +327,12 @@ def test_other_readers_refuse_in_one_sentence():
             call(data)
     for what in ('--salvage', '--partial / --recover / stream', 'repair'):
         with pytest.raises(ValueError) as e:
-            codec._refuse_rans(data, what)
+            codec._refuse(data, what)
         assert str(e.value) == ('format version 12 (lane-parallel rANS tiles) is not read by {}: a file to be salvaged is written with --tile '
                                 '--checked or --tile --wavefront (versions 4 and 5), a file to be read from a prefix, recovered or streamed '
                                 'with the layered formats --layers / --front-layers (versions 6 and 8); an intact file decodes with '
                                 'decompress'.format(what))
-    codec._refuse_rans(codec.build_wavefront_container('a', 'p', 8, 8, 1, 1, 1, 6, 1e9, 0, 1, 1, [0], [b'\x80']), 'repair')     # another format: not its business
+    codec._refuse(codec.build_wavefront_container('a', 'p', 8, 8, 1, 1, 1, 6, 1e9, 0, 1, 1, [0], [b'\x80']), 'repair')     # another format: not its business
 
 
 def _flags(command, **kw):
