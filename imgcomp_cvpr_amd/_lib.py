@@ -42,6 +42,7 @@ PC_DECODE_PER_LAYER = 0x01
 PC_DECODE_RECOMPUTE = 0x02
 PC_DECODE_WAVEFRONT = 0x04           # ic_pc_decode_tiles_batch_f32: streams in wavefront order (format 5)
 PC_ENCODE_SKIP = -1                  # ic_pc_encode_f32 / _segments_f32: a symbol that is stepped over (IC_PC_ENCODE_SKIP)
+PC_DECODE_RDO = 0x1000000            # ic_pc_decode_tiles_batch_channels_f32, alone in the flags: the sweep chooses symbols (IC_PC_DECODE_RDO)
 
 
 def PC_DECODE_DEPTH(b):

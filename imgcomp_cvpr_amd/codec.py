@@ -5,11 +5,11 @@
                                                                                 --front-layers a,b,.. | --front-progressive |
                                                                                 --depth [--depth-block B] | --rans [--lanes W]]]
                                                                 [--cap T | --max-bytes N | --bpp B | --min-psnr D | --min-ms-ssim S]
-                                                                [--roi X,Y,W,H ... [--background T]]
+                                                                [--roi X,Y,W,H ... [--background T]] [--rdo LAMBDA]
     python -m imgcomp_cvpr_amd.codec decompress IN.icf  OUT.png [same options] [--salvage | --channels K | --partial | --recover]
     python -m imgcomp_cvpr_amd.codec decompress IN.icf  OUT.png [same options] --region X,Y,W,H [--channels K]    a rectangle, from the tiles it needs
     python -m imgcomp_cvpr_amd.codec info PATH [PATH ...] [--region X,Y,W,H]    what the files hold and what a region would decode, without model or device
-    python -m imgcomp_cvpr_amd.codec compress-dir   IN_DIR OUT_DIR [--tile PIXELS [same choices]] [--batch N] [--cap T | --max-bytes N | --bpp B]   every *.png / *.jpg -> OUT_DIR/<stem>.icf
+    python -m imgcomp_cvpr_amd.codec compress-dir   IN_DIR OUT_DIR [--tile PIXELS [same choices]] [--batch N] [--cap T | --max-bytes N | --bpp B] [--rdo LAMBDA]   every *.png / *.jpg -> OUT_DIR/<stem>.icf
     python -m imgcomp_cvpr_amd.codec decompress-dir IN_DIR OUT_DIR [--batch N] [--salvage | --channels K | --partial | --recover]    every *.icf -> OUT_DIR/<stem>.png
     python -m imgcomp_cvpr_amd.codec verify PATH [PATH ...]         files or directories of *.icf: the checksums, without model or device
     python -m imgcomp_cvpr_amd.codec stream IN.icf OUT_DIR [model options] [--chunk BYTES]    a format-6 file fed chunk by chunk, a picture per gained layer
@@ -21,6 +21,8 @@
     python -m imgcomp_cvpr_amd.codec measure IN.png IN.icf [model options] [--channels K] [--region X,Y,W,H]    bytes, bpp, PSNR, MS-SSIM of the file
     python -m imgcomp_cvpr_amd.codec rd IN.png OUT.json [model options] [--tile PIXELS [the choices of compress]] [--levels N] [--roi X,Y,W,H ...]
                                                               the rate-distortion table of the cap levels k C / N as JSON, a line per level
+    python -m imgcomp_cvpr_amd.codec rd IN.png OUT.json [model options] [--tile PIXELS [the choices of compress]] --rdo-levels a,b,..
+                                                              the same table over lambdas of --rdo in place of cap levels
 
 compress:   pad to a multiple of the subsampling factor (val.add_padding) -> ae.encode -> PredictionNetwork.encode_stream (the
             range coder on the device, ic_pc_encode_f32) -> container.
@@ -204,6 +206,15 @@ entropy-coded until the level is found.  Quality need not be monotone in the lev
 quality_search -- budget_search on the mirrored index -- establishes both halves of its contract by calls: the level meets the target,
 the next one down does not.  transcode_to_quality does the same for a file over the integer levels 0 .. C against the picture the file
 decodes to now, without the encoder.  No new kernel, entry point or format.  With synthetic weights the numbers mean nothing.
+--rdo LAMBDA (Codec.compress(rdo=), compress_many(rdos=), choose_symbols, rdo_curve; ilog2_q16, rdo_choose, rdo_record): rate-aware symbol
+choice at encode.  The knobs above cut channels; this one asks the context model what a symbol costs.  After the encoder pass every
+tile of the Codec's grid (the whole volume for format 1) is swept front by front -- the sweep of the wavefront decoder, on the device:
+PredictionNetwork.choose_tiles_batch, IC_PC_DECODE_RDO -- and every position takes the first symbol that attains the minimum of
+float64(k_j) + Lambda * float64(R_j): k_j the hard quantiser's own float32 key of centre j, R_j = ilog2_q16(T) - ilog2_q16(f_j) the rate
+in 2^-16 bits over the coder's own integer table of the position given the symbols already chosen, Lambda = lambda 1e7 / 65536.  A chosen
+symbol is final (the greedy rule).  rdo_choose states the rule of one position on the host; the device equals it exactly.  lambda = 0 is
+the quantiser, and the file of compress byte for byte.  The symbols are coded in whatever format the Codec writes and read by every
+reader as ever: no new format, no new entry point.  A search over lambda for a budget or a quality is not offered.
 """
 import argparse
 import io
@@ -987,6 +998,107 @@ def rans_decode(data, rounds, W, freqs_of, out, full=True, stop=None):
     return status
 
 
+# ---- rate-aware symbol choice at encode (compress(rdo=...), IC_PC_DECODE_RDO): the rule of one position, the host's statement ----
+
+def ilog2_q16(v):
+    """log2 v in 2^-16 units for an integer 1 <= v < 2^32, computed in integers only: e = the position of the top bit,
+    m = v << (31 - e), r = e, then 16 times m = (m m) >> 31, r = 2 r, and if m >= 2^32: m >>= 1, r |= 1.  Every intermediate fits
+    64 unsigned bits; exact on powers of two; what the device computes bit for bit."""
+    v = int(v)
+    if not 1 <= v < (1 << 32):
+        raise ValueError('ilog2_q16: {} is outside 1 .. 2^32 - 1'.format(v))
+    e = v.bit_length() - 1
+    m, r = v << (31 - e), e
+    for _ in range(16):
+        m, r = (m * m) >> 31, r << 1
+        if m >> 32:
+            m, r = m >> 1, r | 1
+    return r
+
+
+def check_rdo(rdo):
+    """a lambda of compress(rdo=...): a number with 0 <= lambda < inf; else a ValueError -> float"""
+    if isinstance(rdo, (bool, np.bool_)) or not isinstance(rdo, (int, float, np.integer, np.floating)) or not 0.0 <= float(rdo) < float('inf'):
+        raise ValueError('rdo = {!r}: lambda is a number with 0 <= lambda < inf (0: the quantiser\'s own symbols)'.format(rdo))
+    return float(rdo)
+
+
+def rdo_lambda_q(lam):
+    """lambda, in units of the quantiser's key per bit -> Lambda = lambda * 1e7 / 65536 (float64): the factor on a rate in 2^-16
+    bits beside the key k = fl32(1e7 fl32(t t))"""
+    return check_rdo(lam) * 1e7 / 65536.0
+
+
+def rdo_choose(z, freqs_row, centers, lam_q, rated=True):
+    """the symbol of one position -> (symbol, status): the first j that attains min_j cost_j under `<`,
+    cost_j = float64(k_j) + lam_q * float64(R_j) (one rounded multiply, one rounded add), k_j = fl32(1e7 fl32(t t)) with
+    t = fl32(|z - c_j|), R_j = ilog2_q16(T) - ilog2_q16(f_j) over the coder's table row f, T = sum f.  rated=False (a tile's first
+    position, which every format stores raw) and a row whose total exceeds RANS_MAX_TOTAL (status 1): all R_j = 0.  lam_q = 0 is the
+    hard quantiser's symbol; a NaN cost never wins."""
+    c = np.asarray(centers, dtype=np.float32).reshape(-1)
+    L, status = len(c), 0
+    R = [0] * L
+    if rated:
+        f = [int(v) for v in np.asarray(freqs_row).reshape(-1)]
+        if len(f) != L:
+            raise ValueError('rdo_choose: a table row of {} entries for {} centres'.format(len(f), L))
+        T = sum(f)
+        if T > RANS_MAX_TOTAL:
+            status = 1
+        else:
+            lT = ilog2_q16(T)
+            R = [lT - ilog2_q16(fj) for fj in f]
+    with np.errstate(over='ignore', invalid='ignore'):
+        t = np.abs(np.float32(z) - c)
+        k = (np.float32(1e7) * (t * t).astype(np.float32)).astype(np.float32).astype(np.float64)
+        cost = k + np.float64(lam_q) * np.asarray(R, dtype=np.float64)
+    best, sym = float('inf'), 0
+    for j in range(L):
+        if float(cost[j]) < best:
+            best, sym = float(cost[j]), j
+    return sym, status
+
+
+def rdo_record_bytes(C, th, tw):
+    """the length of a tile's record: Lambda, then C th tw float32"""
+    return 8 + 4 * int(C) * int(th) * int(tw)
+
+
+def rdo_record(lam_q, z_chw):
+    """a tile's record as the chooser reads it: Lambda as a little-endian f64, then the tile's z as float32 in (c, y, x) order.
+    The host's statement of the layout, for callers of the C ABI and for the tests: no path of this package builds records on the
+    host (PredictionNetwork.choose_tiles_batch gathers them on the device)"""
+    z = np.ascontiguousarray(z_chw, dtype='<f4')
+    if z.ndim != 3:
+        raise ValueError('rdo_record: z is a (C, th, tw) array, got shape {}'.format(z.shape))
+    return struct.pack('<d', float(lam_q)) + z.tobytes()
+
+
+def check_rdo_record(off, nbytes, C, th, tw):
+    """what the entry asks of a record's place in the buffer: an offset that is a multiple of 8, the exact length.  The host's
+    statement of the entry's own argument checks (IC_ERR_ARG), like rdo_record for callers of the C ABI and for the tests"""
+    if int(off) % 8 != 0:
+        raise ValueError('record at offset {}: not a multiple of 8'.format(off))
+    if int(nbytes) != rdo_record_bytes(C, th, tw):
+        raise ValueError('record of {} bytes for a {} x {} x {} tile: expected {}'.format(nbytes, C, th, tw, rdo_record_bytes(C, th, tw)))
+
+
+def rdo_is_sequence(rdo):
+    """is this rdo argument one lambda per tile (a list, a tuple, an array of at least one dimension) and not one number?"""
+    return isinstance(rdo, (list, tuple)) or (isinstance(rdo, np.ndarray) and rdo.ndim > 0)
+
+
+def rdo_tile_lambdas(rdo, ntiles):
+    """compress's rdo argument for a volume of ntiles tiles -> [lambda per tile in tile_grid order]: a number serves every tile, a
+    sequence has one entry per tile"""
+    if not rdo_is_sequence(rdo):
+        return [check_rdo(rdo.item() if isinstance(rdo, np.ndarray) else rdo)] * int(ntiles)
+    lams = [check_rdo(v) for v in list(rdo)]
+    if len(lams) != int(ntiles):
+        raise ValueError('rdo: {} lambdas for {} tiles'.format(len(lams), ntiles))
+    return lams
+
+
 def chunk_tiles(tile_shapes, need, budget):
     """cut a list of tiles [(th, tw)] into consecutive chunks [(start, stop)] for a decoder whose workspace grows with the number of
     tiles of a call: need(th_max, tw_max, ntiles) -> bytes for a chunk of ntiles tiles, the largest th x tw.  Greedy, order kept:
@@ -1638,7 +1750,7 @@ class Codec(object):
         self.tile, self.checked, self.order, self.layers, self.front_layers = tile, bool(checked), order, layers, front_layers
         self.depth_block, self.rans = depth_block, rans
         self.C = getattr(ae_config, 'num_chan_bn', None)
-        self.wavefront_refusal = self.layered_refusal = self.depth_refusal = self.rans_refusal = None
+        self.wavefront_refusal = self.layered_refusal = self.depth_refusal = self.rans_refusal = self.rdo_refusal = None
         self._target()                                               # the combinations: refused before any model is built
         import torch
         from . import autoencoder, probclass
@@ -1660,6 +1772,8 @@ class Codec(object):
         self.rans_refusal = self.wavefront_refusal or (None if k == 24 else (
             'lane-parallel rANS tiles: the front decoder that steps W coders at once covers context models of width k = 24, this one '
             'has k = {}'.format(k)))
+        self.rdo_refusal = ('rate-aware symbol choice: the front sweep that chooses symbols covers context models of width k = 24, this '
+                            'one has k = {}'.format(k)) if k != 24 else self.wavefront_refusal      # (no format's: raised only when rdo is asked for)
         self._target()                                               # the model's refusal of the format asked for
         self.pred =probclass.PredictionNetwork(self.pc, pc_config, self.ae.get_centers_variable())
         self.ae_name, self.pc_name = config_name(ae_config), config_name(pc_config)
@@ -1787,14 +1901,41 @@ class Codec(object):
         row, param = self._target()
         return param if row.version == FORMAT_VERSION_FRONTS else None
 
-    def compress(self, img_hwc_uint8, cap=None, rois=None, background=None):
+    def compress(self, img_hwc_uint8, cap=None, rois=None, background=None, rdo=None):
         """HWC uint8 -> container bytes.  cap: None, a level, or an (h, w) plane bounding the importance map (cap_plane; rois and
-        background as there, the level inside the rectangles); without any of them the encoder's own operating point."""
+        background as there, the level inside the rectangles); without any of them the encoder's own operating point.
+        rdo: None, or lambda >= 0 -- a number, or one per tile of this Codec's grid in tile_grid order (format 1: one): the symbols
+        are those of choose_symbols, chosen by distortion + lambda * rate under the context model, in place of the quantiser's;
+        the file's format and every reader are what they are without it, and rdo=0 is the file of rdo=None byte for byte."""
+        if rdo is not None:
+            sym, _, (H, W) = self.choose_symbols(img_hwc_uint8, rdo, cap=cap, rois=rois, background=background)
+            return self._container(sym, H, W)
         if cap is None and not rois and background is None:
             enc, (H, W) = self.encode_symbols(img_hwc_uint8)
         else:
             enc, _, (H, W) = self.encode_symbols_capped(img_hwc_uint8, cap, rois, background)
         return self._container(enc.symbols[0], H, W)
+
+    def _rdo_tile(self, h, w):
+        """the coded volumes a sweep runs over: this Codec's tiles, or the whole (h, w) volume for format 1"""
+        return self.tile if self.tile is not None else (int(h), int(w))
+
+    def choose_symbols(self, img_hwc_uint8, rdo, cap=None, rois=None, background=None):
+        """compress's symbols under rdo -> ((C, h, w) int64 device tensor, EncoderOutput, (H, W)).  z is the masked bottleneck of
+        the encoder pass that compress runs, capped or not; every tile of this Codec's grid (the whole volume for format 1) is
+        swept front by front, each position taking the first symbol that attains min_j k_j + Lambda R_j (rdo_choose) given the
+        symbols already chosen (PredictionNetwork.choose_tiles_batch).  A ValueError (rdo_refusal) for a context model of another
+        width than k = 24."""
+        if self.rdo_refusal:
+            raise ValueError(self.rdo_refusal)
+        self._target()
+        if cap is None and not rois and background is None:
+            enc, (H, W) = self.encode_symbols(img_hwc_uint8)
+        else:
+            enc, _, (H, W) = self.encode_symbols_capped(img_hwc_uint8, cap, rois, background)
+        z = enc.z[0].contiguous()
+        th, tw = self._rdo_tile(z.shape[1], z.shape[2])
+        return self.pred.choose_tiles_batch([z], th, tw, [rdo])[0], enc, (H, W)
 
     def _image_tensor(self, img_hwc_uint8, what=''):
         """HWC uint8 -> ((1, 3, H', W') float32 device tensor of the padded image, (H, W))"""
@@ -2025,23 +2166,46 @@ class Codec(object):
             cur.wait_stream(st)
         return outs
 
-    def compress_many(self, images, caps=None):
+    def compress_many(self, images, caps=None, rdos=None):
         """[HWC uint8] of any mix of shapes -> [container bytes], element i byte for byte compress(images[i]).  Every image goes
         through the encoder on its own (batch 1, the plan flags of compress: the kernel form of a layer depends on the batch size,
         the bytes must not), up to IN_FLIGHT at a time; then the tiles of all images are coded by one launch per tile shape.
-        caps: None, or one entry per image -- None, a level or a plane, as compress's cap: element i is compress(images[i], cap=caps[i])."""
+        caps: None, or one entry per image -- None, a level or a plane, as compress's cap: element i is compress(images[i], cap=caps[i]).
+        rdos: None, or one entry per image -- None, a lambda or one per tile, as compress's rdo: element i is
+        compress(images[i], cap=caps[i], rdo=rdos[i]); the images that have one are swept by one chooser launch per chunk."""
         import torch
         images = list(images)
         caps = [None] * len(images) if caps is None else list(caps)
         if len(caps) != len(images):
             raise ValueError('caps: {} entries for {} images'.format(len(caps), len(images)))
+        rdos = [None] * len(images) if rdos is None else list(rdos)
+        if len(rdos) != len(images):
+            raise ValueError('rdos: {} entries for {} images'.format(len(rdos), len(images)))
+        if any(r is not None for r in rdos) and self.rdo_refusal:
+            raise ValueError(self.rdo_refusal)
         if not self.device_encode:
-            return [self.compress(img, cap=cap) for img, cap in zip(images, caps)]
+            return [self.compress(img, cap=cap, rdo=rdo) for img, cap, rdo in zip(images, caps, rdos)]
         xs, sizes = [], []
         for i, (img, cap) in enumerate(zip(images, caps)):
             x, size = self._image_tensor(img, 'image {}: '.format(i))
             sizes.append(size)
             xs.append((x, None if cap is None else torch.as_tensor(self.cap_plane(size[0], size[1], cap)[None]).to(self.device)))
+        chosen = [i for i, r in enumerate(rdos) if r is not None]
+        if chosen:
+            # an image with a lambda hands its z over in place of the quantiser's symbols: the sweep gives it its symbols
+            def half(ae, item):
+                (x, plane), rdo = item
+                enc = ae.encode(x, is_training=False) if plane is None else ae.encode_capped(x, plane)[0]
+                return enc.symbols[0] if rdo is None else enc.z[0].contiguous()
+            syms = self._in_flight(list(zip(xs, rdos)), half)
+            by_tile = {}
+            for i in chosen:                                          # format 1: a sweep's tile is the volume, one launch per shape
+                by_tile.setdefault(self._rdo_tile(syms[i].shape[1], syms[i].shape[2]), []).append(i)
+            for (th, tw), members in by_tile.items():
+                picked = self.pred.choose_tiles_batch([syms[i] for i in members], th, tw, [rdos[i] for i in members])
+                for i, sym in zip(members, picked):
+                    syms[i] = sym
+            return self._containers(syms, sizes)
         syms = self._in_flight(xs, lambda ae, xc: (ae.encode(xc[0], is_training=False) if xc[1] is None else
                                                    ae.encode_capped(xc[0], xc[1])[0]).symbols[0])
         return self._containers(syms, sizes)
@@ -2571,6 +2735,36 @@ class Codec(object):
         _, bott = self.ae.encode_capped(x, None, keep_bottleneck=True)
         return bott, self._original(np.asarray(img_hwc_uint8)[:, :, :3]), (H, W)
 
+    def compress_counting(self, img_hwc_uint8, rdo, cap=None, rois=None, background=None):
+        """compress(img, rdo=rdo, ...) -> (data, the number of symbols that differ from the quantiser's, the number of symbols)"""
+        sym, enc, (H, W) = self.choose_symbols(img_hwc_uint8, rdo, cap=cap, rois=rois, background=background)
+        return self._container(sym, H, W), int((sym != enc.symbols[0]).sum()), int(sym.numel())
+
+    def rdo_curve(self, img_hwc_uint8, lambdas):
+        """what does a lambda cost in quality, and save in bytes, on this picture?  -> [(lambda, Measure)], row i equal in every field
+        to measure(img, compress(img, rdo=lambdas[i])).  lambdas: a non-empty sequence of numbers, 0 <= lambda < inf.  The encoder
+        runs once, as compress runs it; all lambdas are swept by one chooser launch per chunk, each coded to a real file in this
+        Codec's format, and each decoded by a batch-1 pass of its own, as rd_curve does."""
+        import torch
+        lambdas = [check_rdo(v) for v in list(lambdas)]
+        if not lambdas:
+            raise ValueError('rdo_curve: no lambda given')
+        if self.rdo_refusal:
+            raise ValueError(self.rdo_refusal)
+        self._target()
+        enc, (H, W) = self.encode_symbols(img_hwc_uint8)
+        orig = self._original(np.asarray(img_hwc_uint8)[:, :, :3])
+        z = enc.z[0].contiguous()
+        th, tw = self._rdo_tile(z.shape[1], z.shape[2])
+        sizes, values = [], []
+        for start in range(0, len(lambdas), 16):
+            part = lambdas[start:start + 16]
+            syms = self.pred.choose_tiles_batch([z] * len(part), th, tw, part)
+            sizes += [len(d) for d in self._containers(syms, [(H, W)] * len(part))]
+            pics = self._in_flight(syms, lambda ae, s: self._picture(s, H, W, ae))
+            values += [self._values(orig, pic) for pic in pics]
+        return [(lm, measure_from_values(v, n, H * W)) for lm, n, v in zip(lambdas, sizes, torch.stack(values).tolist())]
+
     def rd_curve(self, img_hwc_uint8, levels=None, rois=None):
         """what does a cap level cost in quality on this picture?  -> [(level, Measure)], row i equal in every field to
         measure(img, compress(img, cap=levels[i])) -- with rois to measure(img, compress(img, rois=rois, background=levels[i])), the
@@ -2808,7 +3002,7 @@ WRITING_COMMANDS = ('compress', 'compress-dir', 'rd') + TRANSCODE_COMMANDS      
 def check_option_args(flags):
     """--checked / --wavefront / --salvage / --channels / --layers / --progressive / --front-layers / --front-progressive / --partial /
     --recover / --chunk / --fronts / --cap / --roi / --background / --max-bytes / --bpp / --region / --min-psnr / --min-ms-ssim /
-    --levels against the command, --tile and each other: decided before any model is built"""
+    --levels / --rdo / --rdo-levels against the command, --tile and each other: decided before any model is built"""
     cap, background, rois = getattr(flags, 'cap', None), getattr(flags, 'background', None), getattr(flags, 'roi', None) or []
     max_bytes, bpp = getattr(flags, 'max_bytes', None), getattr(flags, 'bpp', None)
     transcoding = flags.command in TRANSCODE_COMMANDS
@@ -2833,6 +3027,25 @@ def check_option_args(flags):
             if getattr(flags, name, False):
                 raise ValueError('{} does not go with --{}: a repaired file takes --cap alone'.format(quality, name))
         quality_target(min_psnr, min_ms_ssim)
+    rdo, rdo_levels = getattr(flags, 'rdo', None), getattr(flags, 'rdo_levels', None)
+    if rdo is not None:
+        if transcoding:
+            raise ValueError('--rdo does not go with {}: the choice weighs a symbol against the bottleneck value z, and a file has '
+                             'no z'.format(flags.command))
+        if flags.command not in ('compress', 'compress-dir'):
+            raise ValueError('--rdo belongs to compress / compress-dir: the rate-aware choice of symbols is the encoder\'s, a file is '
+                             'read without it')
+        for name, value in (('--max-bytes', max_bytes), ('--bpp', bpp), ('--min-psnr', min_psnr), ('--min-ms-ssim', min_ms_ssim)):
+            if value is not None:
+                raise ValueError('--rdo does not go with {}: a search over lambda for a budget or a quality is not offered, the '
+                                 'searches run over cap levels'.format(name))
+        check_rdo(rdo)
+    if rdo_levels is not None:
+        if flags.command != 'rd':
+            raise ValueError('--rdo-levels belongs to rd: the lambdas of the rate-distortion table\'s rows')
+        if getattr(flags, 'levels', None) is not None or rois:
+            raise ValueError('--rdo-levels does not go with --levels or --roi: its rows run over lambda in place of cap levels')
+        parse_rdo_levels_arg(rdo_levels)
     if getattr(flags, 'levels', None) is not None:
         if flags.command != 'rd':
             raise ValueError('--levels belongs to rd: the number of steps of the rate-distortion table')
@@ -3030,6 +3243,10 @@ def _budget_of(flags, H, W):
     return None
 
 
+def _rdo_note(lam, changed, count):
+    return ', lambda {:g}: {} of {} symbols differ from the quantiser\'s'.format(lam, changed, count)
+
+
 def _budget_note(level, probes):
     return ', cap level {:g} after {} codings'.format(level, probes)
 
@@ -3058,16 +3275,28 @@ def _measure_line(path, m, channels=None, C=None, rect=None):
     return line if channels is None else '{}, preview from {} of {} channels'.format(line, channels, C)
 
 
-def _rd_line(level, m):
-    return 'level {:g}: {} bytes = {:.4f} bpp, {}'.format(level, m.bytes, m.bpp, _measure_text(m))
+def _rd_line(level, m, key='level'):
+    return '{} {:g}: {} bytes = {:.4f} bpp, {}'.format(key, level, m.bytes, m.bpp, _measure_text(m))
 
 
-def rd_table(codec, rows, image, H, W, rois=None):
-    """what the rd command writes as JSON: the rows of Codec.rd_curve with the format and the configs they were measured under"""
+def rd_table(codec, rows, image, H, W, rois=None, key='level'):
+    """what the rd command writes as JSON: the rows of Codec.rd_curve -- or, with key='rdo', of Codec.rdo_curve, a lambda per row in
+    place of a cap level -- with the format and the configs they were measured under"""
     return {'image': image, 'H': int(H), 'W': int(W), 'ae_config': codec.ae_name, 'pc_config': codec.pc_name,
             'format': codec.written_version(), 'tile': None if codec.tile is None else [v * codec.factor for v in codec.tile],
             'rois': [list(r) for r in rois or []],
-            'rows': [dict(m._asdict(), level=level) for level, m in rows]}
+            'rows': [dict(m._asdict(), **{key: level}) for level, m in rows]}
+
+
+def parse_rdo_levels_arg(text, option='--rdo-levels'):
+    """'0,0.01,0.1' -> [0.0, 0.01, 0.1]; a ValueError for anything but comma-separated numbers with 0 <= lambda < inf"""
+    try:
+        lams = [float(v) for v in str(text).split(',')]
+    except ValueError:
+        raise ValueError('{} {!r} is not a comma-separated list of numbers'.format(option, text))
+    if not lams or not all(0.0 <= v < float('inf') for v in lams):
+        raise ValueError('{} {!r}: every lambda is a number with 0 <= lambda < inf'.format(option, text))
+    return lams
 
 
 def parse_layers_arg(text, option='--layers'):
@@ -3166,7 +3395,8 @@ def _main_dir(flags, ae_config, pc_config):
                 found = [codec.compress_to_quality(img, **_quality_of(flags)) for img in imgs]
                 datas, notes = [d for d, _, _, _ in found], [_quality_note(level, m, probes) for _, level, m, probes in found]
             else:
-                datas = codec.compress_many(imgs, caps=None if getattr(flags, 'cap', None) is None else [flags.cap] * len(imgs))
+                datas = codec.compress_many(imgs, caps=None if getattr(flags, 'cap', None) is None else [flags.cap] * len(imgs),
+                                            rdos=None if getattr(flags, 'rdo', None) is None else [flags.rdo] * len(imgs))
             for (src, dst), img, data, note in zip(part, imgs, datas, notes):
                 with open(dst, 'wb') as f:
                     f.write(data)
@@ -3666,6 +3896,13 @@ def main(argv=None):
                         'stays within D dB of the picture the file decodes to now; not with --cap, --max-bytes, --bpp or --background')
     p.add_argument('--min-ms-ssim', dest='min_ms_ssim', type=float, default=None, metavar='S', help='the same with an MS-SSIM of S in 0 .. 1')
     p.add_argument('--levels', type=int, default=None, metavar='N', help='rd: the N + 1 levels k C / N of the table, 1 <= N <= 256 (default 16)')
+    p.add_argument('--rdo', type=float, default=None, metavar='LAMBDA',
+                   help='compress / compress-dir: rate-aware symbol choice -- every symbol minimises distortion + LAMBDA * rate under the '
+                        'context model, given the symbols before it (0: the quantiser\'s own symbols); any format, the file is read as '
+                        'ever; goes with --cap / --roi / --background, not with --max-bytes, --bpp, --min-psnr or --min-ms-ssim; with '
+                        '--depth expect a LARGER file: the choice moves fill symbols, which format 10 would have left uncoded')
+    p.add_argument('--rdo-levels', dest='rdo_levels', default=None, metavar='a,b,..',
+                   help='rd: rows over these lambdas of --rdo in place of cap levels; not with --levels or --roi')
     flags = p.parse_args(argv)
     from . import config_parser, val, weights as _weights
     try:
@@ -3712,6 +3949,13 @@ def main(argv=None):
                 with open(flags.output, 'wb') as f:
                     f.write(data)
                 print(_compress_line(flags.output, data, img.shape[0] * img.shape[1]) + _quality_note(level, m, probes))
+            elif flags.rdo is not None:
+                from PIL import Image
+                img = np.asarray(Image.open(flags.input).convert('RGB'), dtype=np.uint8)     # as compress_file reads it
+                data, changed, count = codec.compress_counting(img, flags.rdo, cap=flags.cap, rois=rois or None, background=flags.background)
+                with open(flags.output, 'wb') as f:
+                    f.write(data)
+                print(_compress_line(flags.output, data, img.shape[0] * img.shape[1]) + _rdo_note(flags.rdo, changed, count))
             elif flags.cap is not None or rois:
                 data, pixels = codec.compress_file(flags.input, flags.output, cap=flags.cap, rois=rois or None, background=flags.background)
                 print(_compress_line(flags.output, data, pixels))
@@ -3732,12 +3976,16 @@ def main(argv=None):
         elif flags.command == 'rd':
             from PIL import Image
             img = np.asarray(Image.open(flags.input).convert('RGB'), dtype=np.uint8)         # as compress_file reads it
-            rows = codec.rd_curve(img, levels=rd_levels(codec.C, 16 if flags.levels is None else flags.levels), rois=rois or None)
+            key = 'level' if flags.rdo_levels is None else 'rdo'
+            if flags.rdo_levels is not None:
+                rows = codec.rdo_curve(img, parse_rdo_levels_arg(flags.rdo_levels))
+            else:
+                rows = codec.rd_curve(img, levels=rd_levels(codec.C, 16 if flags.levels is None else flags.levels), rois=rois or None)
             with open(flags.output, 'w') as f:
-                json.dump(rd_table(codec, rows, flags.input, img.shape[0], img.shape[1], rois), f, indent=1)
+                json.dump(rd_table(codec, rows, flags.input, img.shape[0], img.shape[1], rois, key=key), f, indent=1)
                 f.write('\n')
             for level, m in rows:
-                print(_rd_line(level, m))
+                print(_rd_line(level, m, 'lambda' if key == 'rdo' else key))
         elif flags.partial:
             from PIL import Image
             with open(flags.input, 'rb') as f:

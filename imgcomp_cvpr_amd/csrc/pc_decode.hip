@@ -10,6 +10,8 @@
 // ic_pc_decode_tiles_batch_fronts_f32 and ic_pc_decode_tiles_batch_fronts_pertile_f32 read every tile's wavefront-ordered stream as
 // segments cut at fronts (container format 8), with one channel limit or one per tile;
 // ic_pc_decode_tiles_batch_fronts_resume_f32 continues every tile's front sweep at the layer end where an earlier call stopped.
+// ic_pc_decode_tiles_batch_channels_f32 with IC_PC_DECODE_RDO is the encoder's: the front sweep over records of (lambda, z) CHOOSES
+// every tile's symbols by distortion + lambda * rate where the decoder reads them from a stream (pc_rdo_tiles_batch_kernel).
 #include "common.h"
 #include "pc_table.h"
 #include "pc_internal.h"
@@ -832,6 +834,15 @@ __device__ __forceinline__ void pc_wave_chain(const float* __restrict__ in, int 
 // Every trip count is fixed by the tile's geometry and W; nothing waits on anything; a symbol is < L whatever the bytes are, because
 // the table's sums end at M.  At the end of a full decode (cdec == C) the states must all be 2^16 and the words taken must end the
 // stream: else status 4, OR-ed with status 1 of a table whose total was too large.
+// RDO = true (IC_PC_DECODE_RDO; only with LIM and cdec == C, without SEG, FROM, DEPTH and RANS): not a decoder but the encoder's
+// rate-aware symbol CHOOSER, the same sweep with nothing to read symbols from.  bits / nbytes are the tile's record (imgcomp_hip.h):
+// lam as an f64, then the tile's masked bottleneck values z, f32 in (c, y, x) order; the caller has checked its length and its
+// alignment.  Phases 1 - 3 and the logits of a chunk are the decoder's as before; behind the chunk's barrier lane k < nc of wave 0
+// decides slot k by pc_rdo_pick -- the slot's table row, the integer log2 of its entries, z, the first minimum of distortion +
+// lam * rate -- and stores its symbol through out and its centre into V, where the later fronts' contexts find it.  The positions
+// of a front do not see each other (a context holds smaller T only), so the lanes of a chunk and the chunks of a front are
+// independent: no serial part, no coder state, no pc_dec_symbol_wave, no read outside the record.  Every trip count is fixed by the
+// tile's geometry.  first_sym is not read.  status: 1 if a table's total was too large (that position is decided by distortion alone).
 template <int LC>
 __device__ __forceinline__ bool pc_dec_rans_build(float (*row)[16], int slot, float resolution) {
     float l[LC];
@@ -845,7 +856,7 @@ __device__ __forceinline__ bool pc_dec_rans_build(float (*row)[16], int slot, fl
     return ok;
 }
 
-template <bool SYMS, bool LIM = false, bool SEG = false, bool FROM = false, bool DEPTH = false, bool RANS = false>
+template <bool SYMS, bool LIM = false, bool SEG = false, bool FROM = false, bool DEPTH = false, bool RANS = false, bool RDO = false>
 __device__ __forceinline__ void pc_dec_wave_body(const PcCachedArgs& f, const unsigned char* bits, long long nbytes, int h, int w, int first_sym,
                                                  float* vol, float* c0, float* c1, float* c2, int* status,
                                                  long long* __restrict__ out, long long out_cs, int out_rs, int cdec = 0,
@@ -857,6 +868,7 @@ __device__ __forceinline__ void pc_dec_wave_body(const PcCachedArgs& f, const un
     static_assert(!FROM || (LIM && SEG), "a sweep continues at a layer cut of a limited sweep");
     static_assert(!DEPTH || (LIM && !SEG), "the depth plane belongs to the unsegmented limited sweep");
     static_assert(!RANS || (LIM && !SEG && !FROM && !DEPTH), "the interleaved coders belong to the unsegmented limited sweep");
+    static_assert(!RDO || (LIM && !SEG && !FROM && !DEPTH && !RANS), "the symbol chooser is the unsegmented limited sweep without a coder");
     constexpr int K = 24, G = K / 4, CH = 64;             // CH: candidates of a front whose logits are in LDS at once
     __shared__ float s_logits[CH + (DEPTH ? 1 : 0)][16];  // DEPTH: one more row, CH bytes: s_live
     __shared__ float s_centers[16];
@@ -877,6 +889,14 @@ __device__ __forceinline__ void pc_dec_wave_body(const PcCachedArgs& f, const un
     unsigned rx = 0;
     long long rtaken = 0;
     int rerr = 0;
+    // RDO: the record's lam and z (uniform addresses; lam is a scalar load)
+    double rlam = 0.0;
+    const float* rz = nullptr;
+    if constexpr (RDO) {
+        s.error = 0;
+        rlam = *reinterpret_cast<const double*>(bits);
+        rz = reinterpret_cast<const float*>(bits + 8);
+    } else
     if constexpr (RANS) {
         s.error = 0;
         if (wave == 0 && lane < rlanes) {
@@ -1003,6 +1023,27 @@ __device__ __forceinline__ void pc_dec_wave_body(const PcCachedArgs& f, const un
                 s_logits[slot][co] = fmaxf(v[0] + f.b3[co], 0.f);
             }
             __syncthreads();
+            if constexpr (RDO) {
+                if (wave == 0) {                          // lane k decides slot k
+                    int c, y, x;
+                    if (lane < nc && pc_front_voxel(fr, cb + lane, c, y, x)) {
+                        const float z = rz[(c * h + y) * w + x];
+                        const bool rated = (c | y | x) != 0;                      // the first position is stored raw: no rate
+                        bool ok = true;
+                        int sym = 0;
+                        switch (L) {
+#define PC_RDO_CASE(l) case l: sym = pc_rdo_pick<l>(s_logits[lane], rated, a.resolution, z, s_centers, rlam, ok); break;
+                            PC_RDO_CASE(1) PC_RDO_CASE(2) PC_RDO_CASE(3) PC_RDO_CASE(4) PC_RDO_CASE(5) PC_RDO_CASE(6)
+                            PC_RDO_CASE(7) PC_RDO_CASE(8) PC_RDO_CASE(9) PC_RDO_CASE(10) PC_RDO_CASE(11) PC_RDO_CASE(12)
+                            PC_RDO_CASE(13) PC_RDO_CASE(14) PC_RDO_CASE(15) PC_RDO_CASE(16)
+#undef PC_RDO_CASE
+                        }
+                        if (!ok) rerr |= 1;
+                        if (SYMS) out[(long long)c * out_cs + (long long)y * out_rs + x] = sym;
+                        vol[((size_t)(c + 4) * PH + y + 4) * PW + x + 4] = s_centers[sym];
+                    }
+                }
+            } else
             if constexpr (RANS) {
                 if (wave == 0) {
                     {   // the tables of the chunk's slots, one per lane
@@ -1082,6 +1123,12 @@ __device__ __forceinline__ void pc_dec_wave_body(const PcCachedArgs& f, const un
             __syncthreads();                              // V of this front before the next step's conv0; s_logits free again
         }
     }
+    if constexpr (RDO) {
+        if (wave == 0) {
+            const int st = __ballot(rerr != 0) ? 1 : 0;
+            if (lane == 0) *status = st;
+        }
+    } else
     if constexpr (RANS) {
         if (wave == 0) {                                  // the end check of a full decode; status 1 and 4 OR-ed over the lanes
             const bool bad4 = cdec == a.C && ((lane < rlanes && rx != PC_RANS_M) || 4ll * rlanes + 2 * rtaken != nbytes);
@@ -1285,6 +1332,30 @@ __global__ __launch_bounds__(256) void pc_dec_tiles_batch_kernel(const PcTilesBa
     }
 }
 
+// The rate-aware symbol chooser over tiles (ic_pc_decode_tiles_batch_channels_f32 with IC_PC_DECODE_RDO; pc_dec_wave_body, RDO): the
+// launch shape, the tables and the slot of the wavefront decoder -- one work-group per tile, nothing passing between work-groups --,
+// the tile's "stream" being its record.  A kernel of its own beside pc_dec_tiles_batch_kernel, whose forms stay what they were.
+template <bool SYMS>
+__global__ __launch_bounds__(256) void pc_rdo_tiles_batch_kernel(const PcTilesBatchArgs t) {
+    const ic_pc_tile_t tl = t.tiles[blockIdx.x];
+    const ic_pc_volume_t v = t.volumes[tl.volume];        // (the batch entry: there is always a volume table)
+    char* slot = t.slots + (size_t)blockIdx.x * t.slot_bytes;
+    const long long corner = (long long)tl.y0 * v.w + tl.x0, plane = (long long)v.h * v.w;
+    const int C = t.f.d.C;
+    pc_dec_wave_body<SYMS, true, false, false, false, false, true>(t.f, t.bits + tl.stream_off, tl.stream_bytes, tl.th, tl.tw, 0, (float*)slot,
+                                                                   (float*)(slot + t.off_c0), (float*)(slot + t.off_c1), (float*)(slot + t.off_c2), t.status + blockIdx.x,
+                                                                   SYMS ? t.symbols + v.symbols_off + corner : nullptr, plane, v.w, C);
+    if (t.q == nullptr) return;
+    __syncthreads();                  // the volume's last stores (wave 0) are visible to the whole work-group
+    const float* vol = (const float*)slot;
+    float* q = t.q + v.q_off + corner;
+    const int PH = tl.th + 8, PW = tl.tw + 8, n = C * tl.th * tl.tw;
+    for (int i = threadIdx.x; i < n; i += 256) {
+        const int x = i % tl.tw, y = (i / tl.tw) % tl.th, c = i / (tl.tw * tl.th);
+        q[(long long)c * plane + (long long)y * v.w + x] = vol[((size_t)(c + 4) * PH + y + 4) * PW + x + 4];
+    }
+}
+
 // symbol 0 in every tile's padded volume: grid (ceil(n / 256), ntiles)
 __global__ __launch_bounds__(256) void pc_dec_fill_slots_kernel(char* __restrict__ slots, size_t slot_bytes, long long n,
                                                                 const float* __restrict__ centers) {
@@ -1463,7 +1534,7 @@ extern "C" int ic_pc_decode_f32(const uint8_t* bitstream, long long nbytes, int 
                                 int C, int h, int w, void* workspace, size_t workspace_bytes, int flags, ic_stream_t stream) {
     IC_CHECK_ARG(bitstream && wtab_host && centers && symbols && status && workspace);
     IC_CHECK_ARG(nbytes >= 0 && C > 0 && h > 0 && w > 0 && k > 0 && L > 0 && first_sym >= 0 && first_sym < L);
-    if (L > 16 || (flags & (IC_PC_DECODE_WAVEFRONT | IC_PC_DECODE_DEPTH(0xff) | IC_PC_DECODE_RANS(0xff)))) return IC_ERR_UNSUPPORTED;      // (the wavefront order: the batch entry only; the depth plane and the rANS coders: its channels form only)
+    if (L > 16 || (flags & (IC_PC_DECODE_WAVEFRONT | IC_PC_DECODE_DEPTH(0xff) | IC_PC_DECODE_RANS(0xff) | IC_PC_DECODE_RDO))) return IC_ERR_UNSUPPORTED;      // (the wavefront order: the batch entry only; the depth plane, the rANS coders and the symbol chooser: its channels form only)
     if (workspace_bytes < ic_pc_decode_workspace_bytes(C, h, w, k)) return IC_ERR_WORKSPACE;
     return pc_decode_impl(bitstream, nbytes, first_sym, wtab_host, centers, k, L, resolution, symbols, status, C, h, w, workspace,
                           flags, C, 0, stream);
@@ -1564,6 +1635,7 @@ struct PcTilesRequest {
     int th_max, tw_max;                               // the largest tile: pc_tiles_check fills them in
     int depth_block;                                  // IC_PC_DECODE_DEPTH(b) of the caller's flags, 0 without: pc_tiles_check fills it in
     int rans_lanes;                                   // IC_PC_DECODE_RANS(W) of the caller's flags, 0 without: pc_tiles_check fills it in
+    bool rdo;                                         // IC_PC_DECODE_RDO, accepted: the streams are records, the sweep chooses symbols: pc_tiles_check fills it in
 };
 
 // the arguments that all entries but the single-volume one begin with, and the values of a full decode of unsegmented streams
@@ -1608,9 +1680,15 @@ static int pc_tiles_check(PcTilesRequest& r, PcTilesLayout& l) {
         const ic_pc_volume_t& v = r.volumes[n];
         IC_CHECK_ARG(v.h >= 1 && v.w >= 1 && v.symbols_off >= 0 && v.q_off >= 0);
     }
+    // the symbol chooser's flag where it can be accepted at all (the channels entry, alone in the flags): its tiles are records,
+    // whose faults are faults of an argument like any other; everywhere else the flag is refused as unsupported further down
+    const bool rdo_asked = (r.flags & IC_PC_DECODE_RDO) != 0;
+    const bool records = r.takes_channels && batch && !segmented && r.flags == IC_PC_DECODE_RDO;
+    IC_CHECK_ARG(!records || (uintptr_t)r.bitstreams % 8 == 0);
     r.th_max = r.tw_max = 0;
     for (int t = 0; t < r.ntiles; ++t) {
         ic_pc_tile_t d = r.tiles[t];
+        if (rdo_asked) d.first_sym = 0;                   // ignored on input
         const int from = resume ? r.tile_from[t] : 0, limit = pertile ? r.tile_channels[t] : r.channels;
         IC_CHECK_ARG(from >= 0 && from <= r.nlayers);     // (from == nlayers: the tile is whole, its limit can only be C)
         IC_CHECK_ARG(limit >= 1 && limit <= r.C && (from ? r.ends[from - 1] : 0) <= limit);
@@ -1618,6 +1696,7 @@ static int pc_tiles_check(PcTilesRequest& r, PcTilesLayout& l) {
         if (segmented) { d.stream_off = 0; d.stream_bytes = 0; }             // not read: the segments stand for them
         const ic_pc_volume_t& v = batch ? r.volumes[d.volume] : r.one;
         IC_CHECK_ARG(pc_tile_ok(d, v.h, v.w, r.total_bytes, r.L));
+        IC_CHECK_ARG(!records || (d.stream_off % 8 == 0 && d.stream_bytes == 8 + 4ll * r.C * d.th * d.tw));
         // the segments THIS call reads: from `from` on (segment 0 only for a tile that starts afresh), of the layers that begin below
         // the limit, the launch's or the tile's own
         for (int g = from; g < r.nlayers && (g == 0 || r.ends[g - 1] < limit); ++g) {
@@ -1633,6 +1712,13 @@ static int pc_tiles_check(PcTilesRequest& r, PcTilesLayout& l) {
     // are what they are without it.
     // the interleaved rANS coders (bits 16 - 23 of the flags) likewise: the channels entry's alone, k = 24, and there ALONE in the flags --
     // the order is implied; beside IC_PC_DECODE_WAVEFRONT, a depth block or a slow-path flag, with another W, in any other entry: unsupported
+    // the symbol chooser (bit 24) likewise: the channels entry's alone, k = 24, alone in the flags, and over all channels
+    r.rdo = false;
+    if (rdo_asked) {
+        if (!records || r.k != 24 || r.channels != r.C) return IC_ERR_UNSUPPORTED;
+        r.rdo = true;
+        r.flags = r.order = IC_PC_DECODE_WAVEFRONT;
+    }
     r.rans_lanes = (r.flags >> 16) & 0xff;
     if (r.rans_lanes) {
         const int W = r.rans_lanes;
@@ -1729,6 +1815,10 @@ static int pc_decode_tiles_impl(const PcTilesRequest& r, const PcTilesLayout& l)
         a.cdec = r.channels; a.fill = r.fill_sym; a.depth_block = r.depth_block; a.rans_lanes = r.rans_lanes;
         const PcTilesKernel kernel = pc_tiles_kernel(wavefront, r.symbols != nullptr, r.tile_channels || r.channels < C || r.rans_lanes, r.nlayers != 0,
                                                      r.tile_channels != nullptr, r.tile_from != nullptr, r.depth_block != 0, r.rans_lanes != 0);
+        if (r.rdo) {
+            if (r.symbols) hipLaunchKernelGGL(pc_rdo_tiles_batch_kernel<true>, dim3((unsigned)ntiles), dim3(256), 0, st, a);
+            else hipLaunchKernelGGL(pc_rdo_tiles_batch_kernel<false>, dim3((unsigned)ntiles), dim3(256), 0, st, a);
+        } else
         hipLaunchKernelGGL(kernel, dim3((unsigned)ntiles), dim3(256), 0, st, a);
         IC_LAUNCH_CHECK();
         return IC_OK;

@@ -10,9 +10,9 @@
 // result is the FIRST index attaining max_j fl(-1e7f * fl((z - c_j)^2)) -- which is what is computed
 // here, with the products kept un-fused so that the fp32 roundings are the reference's.
 #include "common.h"
+#include "quant_key.h"
 
 #define IC_MAX_L 16
-#define HARD_SIGMA 1e7f
 
 __device__ __forceinline__ void quantize_one(float z, const float* c, int L, float sigma,
                                              float& qsoft, float& qhard, int& sym) {
@@ -104,8 +104,7 @@ __device__ __forceinline__ void quantize_hard(float z, const float* c, int L, fl
 #pragma unroll
     for (int j = 0; j < IC_MAX_L; ++j) {
         if (j < L) {
-            const float t = fabsf(z - c[j]);
-            const float lh = __fmul_rn(-HARD_SIGMA, __fmul_rn(t, t));
+            const float lh = ic_hard_logit(z, c[j]);
             if (lh > lmax_hard) { lmax_hard = lh; best = j; }
         }
     }

@@ -861,6 +861,77 @@ class PredictionNetwork(object):
         res = _cut(q, sym, shapes, offs, want)
         return (res, damage) if conceal else res
 
+    def choose_tiles_batch(self, zs, th, tw, lam, want='symbols', max_workspace_bytes=1 << 31):
+        """Rate-aware symbol choice at encode: the symbols of every th x tw tile of every volume, chosen front by front by the
+        rule of codec.rdo_choose over the context model's own tables -- ONE launch per chunk of ic_pc_decode_tiles_batch_channels_f32
+        with PC_DECODE_RDO, one work-group per tile, the sweep of the wavefront decoder with a chooser in place of a coder.
+        zs: [(C, h, w) float32 DEVICE tensors], the masked bottleneck values (EncoderOutput.z), one C throughout.  lam: a float (in
+        key units per bit, codec.rdo_lambda_q), or per volume a sequence with one lambda per tile in codec.tile_grid order.
+        want: 'symbols' -> per volume the (C, h, w) int64 device tensor, 'q' -> centers[symbols] as float32, 'both' -> (q, symbols).
+        The records (Lambda, then the tile's z) are gathered on the device; nothing visits the host but the status words.
+        The workspace is one slot per tile: the tile list is cut into chunks within max_workspace_bytes as decode_tiles_batch does.
+        A context model of another width than k = 24 is a ValueError; a table whose total is too large (status 1) too."""
+        from .codec import tile_grid, chunk_tiles, rdo_is_sequence, rdo_lambda_q, rdo_tile_lambdas, rdo_record_bytes
+        if want not in ('q', 'symbols', 'both'):
+            raise ValueError("want is 'q', 'symbols' or 'both', got {!r}".format(want))
+        if self.pc._k != 24:
+            raise ValueError('rate-aware symbol choice needs a context model of width k = 24, this one has k = {}'.format(self.pc._k))
+        zs = list(zs)
+        if not zs:
+            return []
+        dev = self.centers.device
+        per_volume = rdo_is_sequence(lam)
+        if per_volume and len(lam) != len(zs):
+            raise ValueError('lam: {} entries for {} volumes'.format(len(lam), len(zs)))
+        shapes, tiles, rows, lams, pos = [], [], [], [], 0
+        for n, z in enumerate(zs):
+            if z.dim() != 3 or z.dtype != torch.float32:
+                raise ValueError('volume {}: z is a (C, h, w) float32 tensor, got {} {}'.format(n, tuple(z.shape), z.dtype))
+            _lib.require_cuda(z, 'z of volume {}'.format(n))
+            C, h, w = (int(v) for v in z.shape)
+            if C != int(zs[0].shape[0]):
+                raise ValueError('volume {} has {} channels, volume 0 has {}'.format(n, C, int(zs[0].shape[0])))
+            shapes.append((C, h, w))
+            grid = tile_grid(h, w, th, tw)
+            for (y0, x0, a, b), lm in zip(grid, rdo_tile_lambdas(lam[n] if per_volume else lam, len(grid))):
+                nb = rdo_record_bytes(C, a, b)
+                tiles.append((y0, x0, a, b))
+                rows.append((y0, x0, a, b, pos, nb, 0, n))
+                lams.append(rdo_lambda_q(lm))
+                pos += (nb + 7) & ~7                                 # every record starts at a multiple of 8
+        C, k = shapes[0][0], self.pc._k
+        # the records, gathered on the device: Lambda of every tile by one upload and one indexed store, z by one strided copy per tile
+        data = torch.zeros(pos, dtype=torch.uint8, device=dev)
+        lam_dev = torch.as_tensor(np.asarray(lams, dtype='<f8')).to(dev)
+        at = torch.as_tensor(np.asarray([r[4] // 8 for r in rows], dtype=np.int64)).to(dev)
+        data.view(torch.float64)[at] = lam_dev                       # (every record starts at a multiple of 8: one indexed store)
+        for y0, x0, a, b, off, nb, _, n in rows:
+            data[off + 8:off + nb].view(torch.float32).view(C, a, b).copy_(zs[n][:, y0:y0 + a, x0:x0 + b])
+        table = _lib.tile_table(rows)
+        vtable, offs, total = _lib.packed_volume_table(shapes)
+
+        def need(th_max, tw_max, ntiles):
+            return int(lib.ic_pc_decode_tiles_batch_workspace_bytes(C, th_max, tw_max, ntiles, len(shapes), k))
+
+        chunks = chunk_tiles([(a, b) for _, _, a, b in tiles], need, int(max_workspace_bytes))
+        q = torch.empty(total, dtype=torch.float32, device=dev) if want in ('q', 'both') else None
+        sym = torch.empty(total, dtype=torch.int64, device=dev) if want in ('symbols', 'both') else None
+        status = torch.zeros(len(tiles), dtype=torch.int32, device=dev)
+        centers = self.centers.contiguous().float()
+        ws_bytes = max(need(max(tiles[i][2] for i in range(a, b)), max(tiles[i][3] for i in range(a, b)), b - a) for a, b in chunks)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        step = ctypes.sizeof(_lib.PcTile)
+        for a, b in chunks:
+            check(lib.ic_pc_decode_tiles_batch_channels_f32(
+                ptr(data), pos, ctypes.c_void_p(ctypes.addressof(table) + a * step), b - a, vtable, len(shapes), self.pc._tab,
+                ptr(centers), k, self.pc.L, self.freqs_resolution, ptr(sym), ptr(q), ptr(status[a:b]), C, ptr(ws), ws_bytes,
+                _lib.PC_DECODE_RDO, _lib.current_stream(dev), C, 0), 'ic_pc_decode_tiles_batch_channels_f32')
+        for i, st in enumerate(status.tolist()):            # (the host waits here: the tables and the records are done with)
+            if st != 0:
+                y0, x0, _, _, _, _, _, n = rows[i]
+                raise ValueError('Cannot choose symbol because total is too large (volume {}, tile at ({}, {}))'.format(n, y0, x0))
+        return _cut(q, sym, shapes, offs, want)
+
     def open_layers(self, volumes_geometry, th, tw, layer_ends=None, max_workspace_bytes=1 << 31, front_ends=None):
         """a LayerSession over the volumes [(C,h,w)] cut into th x tw tiles of layered streams (container format 6): the decoder's
         workspace, symbols and q stay on the device between its advance() calls, so that every layer of every tile is decoded once

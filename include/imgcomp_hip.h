@@ -132,6 +132,26 @@ int ic_build_has_tuning_forms(void);
  * IC_PC_ENCODE_RANS(W) as `nsegs` of ic_pc_encode_segments_f32: see there. */
 #define IC_PC_DECODE_RANS(w)      (((w) & 0xff) << 16)
 #define IC_PC_ENCODE_RANS(w)      (-(w))
+/* Rate-aware symbol choice at ENCODE (no new format: the decoder needs nothing).  IC_PC_DECODE_RDO: ic_pc_decode_tiles_batch_channels_f32
+ * with k = 24, L <= 16 and channels == C only, alone in `flags`.  The entry then decodes nothing: its sweep -- the wavefront decoder's
+ * launch shape, tables, workspace and outputs, one work-group per tile -- CHOOSES every tile's symbols front by front, each position
+ * by the rule
+ *     symbol = the first j that attains min_j  (double)k_j + Lambda * (double)R_j   under `<`  (one rounded multiply, one rounded add),
+ *     k_j = fl(1e7 fl(t t)), t = fl(|z - c_j|)            the hard quantiser's own key (float32),
+ *     R_j = ilog2_q16(T) - ilog2_q16(f_j)                  the rate in 2^-16 bits over the coder's table row f of the position
+ *                                                          (what ic_pc_logits_to_freqs_f32 gives for the symbols chosen so far), T = sum f,
+ *     ilog2_q16(v), 1 <= v < 2^32: e = the top bit of v, m = v << (31 - e), r = e, then 16 times m = (m m) >> 31, r = 2 r,
+ *                                  if m >= 2^32 { m >>= 1, r |= 1 }   -- integers only.
+ * A chosen symbol is final and enters the context of the later fronts as its centre (the greedy rule).  The tile's first position,
+ * which every format stores raw, has all R_j = 0; so has a position whose table's total exceeds 2^30 + 2, which sets status 1.
+ * Lambda = 0 is ic_quantize_f32's symbol at every position.
+ * A tile's "stream" is its RECORD: 8 bytes Lambda as a little-endian f64 (per tile: it may vary over the picture), then the tile's
+ * masked bottleneck values z, C th tw float32 in (c, y, x) order.  bitstreams 8-byte aligned, stream_off % 8 == 0 and stream_bytes ==
+ * 8 + 4 C th tw, else IC_ERR_ARG, checked on the host; first_sym is ignored.  No byte outside the record is read.  symbols / q: the
+ * chosen symbols and their centres, as the decoder writes them.  status: 0, or 1 as above.
+ * Every other entry, every other flag beside it, channels < C and every other k: IC_ERR_UNSUPPORTED, decided on the host, nothing
+ * written. */
+#define IC_PC_DECODE_RDO          0x1000000
 
 int ic_abi_version(void);
 /* static string for a return code of this library (hipGetErrorString for codes > 0) */
