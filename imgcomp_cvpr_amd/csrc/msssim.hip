@@ -29,6 +29,12 @@
 #define MS_TC 64                   // tile columns
 #define MS_RMAX (MS_TR + 10)       // rows of the intermediate a tile can need: window length <= 11
 #define MS_MAXPART 4096            // partial sums per level the finishing kernel accepts per pass (it loops beyond)
+// The moments are taken of a - MS_CENTRE and b - MS_CENTRE (max_val / 2).  Variances and the covariance do not depend on the
+// shift, but E[bb] - mu_b^2 in float32 cancels two numbers of up to 255^2 against each other: an absolute error of ~4e-3 in a
+// variance that is added to c2 = 58.5, which at a coarse scale with a handful of positions put 2e-5 on the scale's mean (the
+// tests' bound is 1e-5).  Centred, the squares are 4x smaller at worst and 100x on mid-grey content; measured on the means: <= 8.4e-8.
+// The same expressions hold in the centred variables (the backward kernel multiplies the partials by b - MS_CENTRE, a - MS_CENTRE).
+#define MS_CENTRE 127.5f
 
 static const double MS_WEIGHTS[MS_LEVELS] = {0.0448, 0.2856, 0.3001, 0.2363, 0.1333};
 
@@ -160,7 +166,7 @@ __global__ __launch_bounds__(256) void msssim_level_fwd_kernel(const MsFwdArgs g
         const float* __restrict__ rb = b + (size_t)(y0 + r) * g.W;
         float sa = 0.f, sb = 0.f, saa = 0.f, sbb = 0.f, sab = 0.f;
         for (int x = x0; x <= x1; ++x) {
-            const float w = aw[x], va = ra[x], vb = rb[x];
+            const float w = aw[x], va = ra[x] - MS_CENTRE, vb = rb[x] - MS_CENTRE;
             sa = fmaf(w, va, sa); sb = fmaf(w, vb, sb);
             saa = fmaf(w, va * va, saa); sbb = fmaf(w, vb * vb, sbb); sab = fmaf(w, va * vb, sab);
         }
@@ -183,7 +189,8 @@ __global__ __launch_bounds__(256) void msssim_level_fwd_kernel(const MsFwdArgs g
         const float va = eaa - ma * ma, vb = ebb - mb * mb, cov = eab - ma * mb;
         const float v1 = 2.f * cov + g.c2, v2 = va + vb + g.c2;
         const float cs = v1 / v2;
-        const float l1 = 2.f * ma * mb + g.c1, l2 = ma * ma + mb * mb + g.c1;
+        const float ua = ma + MS_CENTRE, ub = mb + MS_CENTRE;          // the luminance term takes the means themselves
+        const float l1 = 2.f * ua * ub + g.c1, l2 = ua * ua + ub * ub + g.c1;
         const float lum = l1 / l2;
         s_cs += (double)cs;
         s_ssim += (double)(lum * cs);
@@ -193,7 +200,7 @@ __global__ __launch_bounds__(256) void msssim_level_fwd_kernel(const MsFwdArgs g
         float dbb = -v1 * iv2 * iv2;
         float dmu = -2.f * ma * iv2 + 2.f * mb * v1 * iv2 * iv2;
         if (g.last) {                                               // ssim = lum * cs
-            const float dl = 2.f * ma / l2 - l1 * 2.f * mb / (l2 * l2);
+            const float dl = 2.f * ua / l2 - l1 * 2.f * ub / (l2 * l2);
             dmu = cs * dl + lum * dmu;
             dab *= lum;
             dbb *= lum;
@@ -321,7 +328,7 @@ __global__ __launch_bounds__(256) void msssim_level_bwd_kernel(const MsBwdArgs g
             s0 = fmaf(w, tq[0][r][xx], s0); s1 = fmaf(w, tq[1][r][xx], s1); s2 = fmaf(w, tq[2][r][xx], s2);
         }
         const size_t o = ((size_t)plane * g.H + y) * g.W + x;
-        float v = sc * (s0 + 2.f * g.b[o] * s1 + g.a[o] * s2);
+        float v = sc * (s0 + 2.f * (g.b[o] - MS_CENTRE) * s1 + (g.a[o] - MS_CENTRE) * s2);      // the partials are those of the centred moments
         if (g.gnext) {
             // transpose of the 2x2 box behind the (0,1) REFLECT pad: pixel y feeds output row y / 2, and on an odd-sized axis
             // the pixel before the last is also the reflection read by the last output row

@@ -31,7 +31,7 @@ from collections import OrderedDict, namedtuple
 import numpy as np
 import torch
 
-from tests.util import _boundary_margin, rel_err
+from tests.util import _boundary_margin, rel_err, true_rel_err
 
 GTOL = 2e-4                       # every gradient of a small step, relative to the tensor scale (tests/test_gpu_training.py)
 MAX_DIFFERING = 1e-5              # share of all decisions that may differ from the float64 oracle's own (CPU runs: <= 2 of 3.6 M)
@@ -171,9 +171,9 @@ def unforced(case):
 
 
 def worst_gradient_error(got, ref):
-    """-> (name, error relative to the tensor scale) of the worst of ALL gradients"""
+    """-> (name, error relative to the reference gradient's own scale max|ref|, no clamp at 1) of the worst of ALL gradients"""
     assert set(got) == set(ref), set(got) ^ set(ref)
-    return max(((n, rel_err(got[n], ref[n])) for n in ref), key=lambda t: t[1])
+    return max(((n, true_rel_err(got[n], ref[n])) for n in ref), key=lambda t: t[1])
 
 
 # ---- one evaluation's decisions and the values they were taken on ("a side") ----------------------------------------------------

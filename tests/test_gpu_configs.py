@@ -185,6 +185,10 @@ CFG3_GRAD_RTOL = {   # measured (gpurun_out/r3d/cfg3.log): 2.3e-3, 1.6e-3, 9.7e-
     'autoencoder/decoder/res_block_dec_0/dec_0_1/conv1/weights': 1.5e-3, 'autoencoder/decoder/dec_after_res/conv2/weights': 3.5e-4,
     'autoencoder/decoder/h12/weights': 3e-3}
 CFG3_GRAD_RTOL_FLIPS = 5e-2
+# The same bounds are asserted of max|ref| itself (no clamp at 1).  One of the fifteen tensors is small enough for that to bite: the
+# encoder's last beta has max|ref| = 1.5e-2 and sits behind the same depth of backward as to_bn's filter (3e-3); measured 2.06e-5
+# absolute = 1.39e-3 of max|ref| in the F(2x2)-forward run, bound twice that.  Every other tensor keeps its bound above.
+CFG3_GRAD_TRUE_RTOL = {'autoencoder/encoder/res_block_enc_final/conv2/BatchNorm/beta': 2.8e-3}
 
 
 _CFG3_ORACLE = {}
@@ -252,9 +256,13 @@ def test_cfg3_training_step_full_size(cuda, mode):
     for n in names:
         tol = CFG3_GRAD_RTOL_FLIPS if flips.any() else grad_factor * CFG3_GRAD_RTOL.get(n, CFG3_GRAD_RTOL_DEFAULT)
         e, a_ = rel_err(g.grads[n], p[n].grad), util.abs_err(g.grads[n], p[n].grad)
-        util.REPORT.append(('{} grad {}{}'.format(label, n.replace('autoencoder/', 'ae/').replace('probclass3d/logits/', 'pc/'), tag), a_, e, tol))
-        if e > tol:
-            bad.append('{}: {:.3e} > {:.1e}'.format(n, e, tol))
+        te = util.true_rel_err(g.grads[n], p[n].grad)          # of max|ref| itself: the same bound, no clamp at 1 (tests/util.py)
+        what = '{} grad {}{}'.format(label, n.replace('autoencoder/', 'ae/').replace('probclass3d/logits/', 'pc/'), tag)
+        util.REPORT.append((what, a_, e, tol))
+        util.SCALES.append((what, util.ref_scale(p[n].grad)))
+        ttol = tol if flips.any() or n not in CFG3_GRAD_TRUE_RTOL else grad_factor * CFG3_GRAD_TRUE_RTOL[n]
+        if e > tol or te > ttol:
+            bad.append('{}: {:.3e} > {:.1e} or {:.3e} of max|ref| > {:.1e}'.format(n, e, tol, te, ttol))
     assert not bad, label + ' gradients outside their bounds (relative to the tensor scale): ' + '; '.join(bad)
 
 

@@ -1284,7 +1284,7 @@ def test_batchnorm_from_the_conv_epilogue_sums(cuda):
 @pytest.mark.parametrize('shape', [(1, 3, 33, 47), (1, 2, 17, 19)], ids=lambda s: 'x'.join(map(str, s)))
 def test_msssim_loss_and_gradient(cuda, shape):
     """ic_msssim_plan_fill + ic_msssim_loss_grad_f32 as test_hip_ms_ssim_distortion_value_and_gradient checks them (the oracle's float64
-    MS-SSIM under autograd: 1e-5 on the value, 1e-3 on the gradient); the plan is uploaded into a fenced input"""
+    MS-SSIM under autograd: 1e-5 on the value, 2e-4 of max|ref| on the gradient); the plan is uploaded into a fenced input"""
     from imgcomp_cvpr_amd import config_parser as cp, weights as W
     from oracle import train_oracle as T
     L, B = _L(), Bufs(cuda)
@@ -1317,7 +1317,7 @@ def test_msssim_loss_and_gradient(cuda, shape):
     _written(scal[used], 'scalars')
     assert abs(float(scal[0]) - (1.0 - float(ref) / K)) < 1e-5
     assert abs(float(scal[1]) - float(ref)) < 1e-5 * K
-    _close(grad, tb.grad, 'MS-SSIM distortion gradient {}x{}'.format(H, Wd), 1e-3)
+    _close(grad, tb.grad, 'MS-SSIM distortion gradient {}x{}'.format(H, Wd), 2e-4)
     run.again()
     _one_byte_short(B, lambda: launch(grad, need - 1), 'msssim')
     value = scal.clone()

@@ -7,7 +7,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from tests.util import assert_close, dev, rel_err
+from tests.util import assert_close, dev, true_rel_err
 
 pytestmark = pytest.mark.gpu
 GTOL = 2e-4        # gradients: relative to the tensor scale, vs the float64 autograd of the oracle
@@ -143,7 +143,9 @@ def test_fused_adam_matches_the_multi_tensor_form(cuda):
     for i, (p, rp) in enumerate(zip(ps, ref_p)):
         assert_close(p, rp.double(), 'fused Adam, variable {}'.format(i), 1e-6)
         assert_close(fused.m[i], plain.m[i].double(), 'fused Adam m {}'.format(i), 1e-6)
-        assert_close(fused.v[i], plain.v[i].double(), 'fused Adam v {}'.format(i), 1e-6)
+        # true_rtol: the kernel forms 1.f - beta2 in float32 as TensorFlow's does (0.00099998713, -1.29e-5 of the multi-tensor form's
+        # 0.001), so every element of v differs by that share of itself: measured 1.305e-5 of max|v| (1.3e-2), bound twice that
+        assert_close(fused.v[i], plain.v[i].double(), 'fused Adam v {}'.format(i), 1e-6, true_rtol=2.7e-5)
     assert float(fp[offs[1] + 33:offs[2]].abs().max()) == 0.0          # the padding between tensors stays zero
 
 
@@ -287,10 +289,10 @@ def test_training_step_matches_oracle(cuda):
     for name, ref in p.items():
         if ref.grad is None:
             continue
-        e = rel_err(g.grads[name], ref.grad)
+        e = true_rel_err(g.grads[name], ref.grad)          # of max|ref| itself, no clamp at 1: 73 of the 219 are below 1
         if e > worst[1]:
             worst = (name, e)
-        assert e <= GTOL, 'gradient of {}: relative error {:.3e}'.format(name, e)
+        assert e <= GTOL, 'gradient of {}: error {:.3e} of max|ref|'.format(name, e)
     assert len([n for n in p if p[n].grad is not None]) == len(g.grads) == 219
     print('worst gradient error', worst)
 
@@ -355,7 +357,8 @@ def test_ms_ssim_loss_module(cuda):
     v = ms_ssim.multiscale_ssim(dev(a, cuda), gb)
     v.backward()
     assert abs(float(v) - float(ref)) < 1e-5
-    assert rel_err(gb.grad, tb.grad) < 1e-3
+    # max|ref| is 4.9e-7 here (no K; measured 7.3e-5 of it): GTOL of that, where 1e-3 of max(1, max|ref|) would have passed a gradient of zero
+    assert_close(gb.grad, tb.grad, 'torch MS-SSIM module gradient', GTOL)
 
 
 @pytest.mark.parametrize('shape', [(2, 3, 128, 128), (3, 3, 64, 64), (1, 3, 160, 160), (2, 3, 72, 136), (1, 3, 33, 47), (1, 2, 17, 19), (1, 3, 320, 160), (2, 3, 40, 20)])
@@ -385,7 +388,8 @@ def test_hip_ms_ssim_distortion_value_and_gradient(cuda, shape):
     assert 0.0 < float(d.ms_ssim) <= 1.0
     assert abs(float(d.ms_ssim) - (1.0 - float(ref) / K)) < 1e-5, (float(d.ms_ssim), 1.0 - float(ref) / K)
     assert abs(float(d.d_loss_scaled) - float(ref)) < 1e-5 * K
-    assert_close(d.grad, tb.grad, 'MS-SSIM distortion gradient {}x{}'.format(shape[2], shape[3]), 1e-3)
+    # GTOL of max|ref| (1e-3 .. 1.4e-1 on these shapes; tests/test_gpu_msssim_grad.py has the per-scale checks)
+    assert_close(d.grad, tb.grad, 'MS-SSIM distortion gradient {}x{}'.format(shape[2], shape[3]), GTOL)
     # the autograd form the plugin call sites use
     xo = dev(b, cuda).requires_grad_(True)
     dd = hd(dev(a, cuda), xo)
@@ -857,17 +861,17 @@ def test_two_rank_training_step_equals_single_rank(cuda):
             p_.join(timeout=120)
             assert p_.exitcode == 0
     grads, out2, mv = results[True]
-    worst = max(rel_err(torch.as_tensor(grads[k]), torch.as_tensor(ref[k]).double()) for k in ref)
+    worst = max(true_rel_err(torch.as_tensor(grads[k]), torch.as_tensor(ref[k]).double()) for k in ref)
     assert worst < 5e-5, 'sync BatchNorm: 2 x 2 != 1 x 4, worst bucket error {:.3e}'.format(worst)
     assert np.allclose(mv, ref_mv, rtol=1e-5, atol=1e-7)               # the moving averages see the whole batch too
     assert abs(out2['pc_loss'] - out1['pc_loss']) < 5e-2 * abs(out1['pc_loss']) + 1e-3      # (losses are per-rank means over half the batch)
     # the hand-written exchange over peer-mapped memory (peer.py) sums the same float64 moments in rank order: same result
     grads_p, _, mv_p = results['p2p']
-    worst_p = max(rel_err(torch.as_tensor(grads_p[k]), torch.as_tensor(ref[k]).double()) for k in ref)
+    worst_p = max(true_rel_err(torch.as_tensor(grads_p[k]), torch.as_tensor(ref[k]).double()) for k in ref)
     assert worst_p < 5e-5 and np.allclose(mv_p, ref_mv, rtol=1e-5, atol=1e-7), 'p2p sync BatchNorm: worst bucket error {:.3e}'.format(worst_p)
     assert all(np.array_equal(grads_p[k], grads[k]) for k in ref), 'p2p exchange and all-reduce disagree (both sum in rank order)'
     grads_l, _, mv_l = results[False]
-    worst_l = max(rel_err(torch.as_tensor(grads_l[k]), torch.as_tensor(ref[k]).double()) for k in ref)
+    worst_l = max(true_rel_err(torch.as_tensor(grads_l[k]), torch.as_tensor(ref[k]).double()) for k in ref)
     assert worst_l > 10 * worst and not np.allclose(mv_l, ref_mv, rtol=1e-5), 'local statistics reproduce the full batch?'
 
 
@@ -1116,5 +1120,5 @@ def test_sync_bn_over_rccl_and_p2p_between_gpus(cuda):
         for p_ in procs:
             p_.join(timeout=120)
             assert p_.exitcode == 0
-        worst = max(rel_err(torch.as_tensor(grads[k]), torch.as_tensor(ref[k]).double()) for k in ref)
+        worst = max(true_rel_err(torch.as_tensor(grads[k]), torch.as_tensor(ref[k]).double()) for k in ref)
         assert worst < 5e-5, 'sync_bn={!r} over {} GPUs: worst bucket error {:.3e}'.format(mode, 2, worst)

@@ -14,6 +14,10 @@ HEATMAP_RTOL = 1e-4         # heatmap = clip(sigmoid(z0) * C - c, 0, 1): amplifi
 NORTH_STAR_RTOL = 1e-4
 REPORT = []          # (label, max abs error, relative error, bound)
 FLIPS = []           # (label, flipped symbols, total symbols)
+# The clamp in max(1, max|ref|) turns the bound into an ABSOLUTE one for a tensor whose reference is much smaller than 1 (a
+# gradient of order 1e-3 passes 1e-3 "relative" when half of it is missing), so assert_close asserts a second time against the
+# reference's own scale: max|got - ref| <= true_rtol * max|ref| ("Parity scale").  SCALES keeps that yardstick per call.
+SCALES = []          # (label, yardstick = max|ref64|, or the call's scale=)
 
 
 def rel_err(got, ref64):
@@ -30,11 +34,39 @@ def abs_err(got, ref64):
     return float((got - ref64).abs().max())
 
 
-def assert_close(got, ref64, what, rtol=RTOL):
+def ref_scale(ref64):
+    """max|ref64|: the scale-true yardstick of a comparison (0.0 for a reference that is identically zero)."""
+    ref64 = ref64.detach().double().cpu() if torch.is_tensor(ref64) else torch.as_tensor(ref64).double()
+    return float(ref64.abs().max()) if ref64.numel() else 0.0
+
+
+def true_rel_err(got, ref64):
+    """max|got - ref64| / max|ref64|: rel_err without the clamp at 1.  A reference that is identically zero has no scale of its
+    own; the absolute error is returned for it, as rel_err does."""
+    y = ref_scale(ref64)
+    e = rel_err(got, ref64)            # checks the shapes
+    return abs_err(got, ref64) / y if y > 0.0 else e
+
+
+def assert_close(got, ref64, what, rtol=RTOL, true_rtol=None, scale=None):
+    """two assertions: max|got - ref| <= rtol * max(1, max|ref|), the bar the report prints, and max|got - ref| <= true_rtol *
+    yardstick with yardstick = max|ref| (skipped when the reference is identically zero: the first check is absolute there).
+    true_rtol defaults to rtol.  scale= replaces max|ref| where another quantity sets the rounding error (a displacement p_new -
+    p_old rounds like |p|): it comes from the operation's inputs or the reference, never from `got`, and may not exceed
+    max(1, max|ref|), so the second check is never looser than the first at the same tolerance."""
     e = rel_err(got, ref64)
-    REPORT.append((what, abs_err(got, ref64), e, rtol))
-    assert e <= rtol, '{}: max error {:.3e} (relative to tensor scale; absolute {:.3e}) exceeds {:.1e}'.format(
-        what, e, REPORT[-1][1], rtol)
+    a = abs_err(got, ref64)
+    REPORT.append((what, a, e, rtol))
+    y = ref_scale(ref64)
+    if scale is not None:
+        scale = float(scale)
+        assert 0.0 < scale <= max(1.0, y), '{}: scale={:.3e} exceeds max(1, max|ref|) = {:.3e}'.format(what, scale, max(1.0, y))
+        y = scale
+    SCALES.append((what, y))
+    t = rtol if true_rtol is None else true_rtol
+    te = a / y if y > 0.0 else 0.0
+    assert e <= rtol and te <= t, ('{}: max error {:.3e} absolute; {:.3e} of max(1, max|ref|), bound {:.1e}; {:.3e} of the yardstick '
+                                   '{:.3e}, bound {:.1e}').format(what, a, e, rtol, te, y, t)
     return e
 
 
