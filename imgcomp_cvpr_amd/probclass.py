@@ -11,7 +11,7 @@ variable names/layouts (unmasked conv3d filters [2,3,3,cin,cout] + biases).
 """
 import ctypes
 import itertools
-from collections import OrderedDict
+from collections import OrderedDict, namedtuple
 
 import numpy as np
 import torch
@@ -374,11 +374,8 @@ class PredictionNetwork(object):
         assert sym.dim() == 4, 'Expected CHW or NCHW symbols'
         sym = sym.to(dev).long().contiguous()
         N, C, h, w = (int(v) for v in sym.shape)
-        pad = self.pc_class.get_context_size(self.config) // 2
-        q = self.centers[torch.nn.functional.pad(sym, (pad, pad, pad, pad, pad, 0))].contiguous()    # (N,C+4,h+8,w+8), symbol 0 around
-        logits = self.pc.logits(q, is_training=False)                  # (N,C,h,w,L)
+        logits = self._symbol_logits(sym)
         count = C * h * w
-        coded = sym
         if order == 'rans':
             if seg_ends is not None or depth_block is not None:
                 raise ValueError("order='rans' is one interleaved stream per volume: not with seg_ends or depth_block")
@@ -386,14 +383,9 @@ class PredictionNetwork(object):
             return res if batched else res[0]
         if lanes is not None:
             raise ValueError("lanes is the number of coders of order='rans', order is {!r}".format(order))
-        if order == 'wavefront':
-            from .codec import wavefront_order
-            perm = torch.as_tensor(np.array(wavefront_order(C, h, w))).to(dev)       # (a copy: the cached order is read-only)
-            logits = logits.view(N, count, self.pc.L).index_select(1, perm).contiguous()
-            coded = sym.view(N, count).index_select(1, perm).contiguous()
-        elif order != 'raster':
+        if order not in ('raster', 'wavefront'):
             raise ValueError("order is 'raster' or 'wavefront' -- or 'rans' --, got {!r}".format(order))
-        planes = None
+        coded, planes = sym, None
         if depth_block is not None:
             from .codec import check_depth_block
             B = check_depth_block(depth_block, C)
@@ -401,31 +393,62 @@ class PredictionNetwork(object):
                 raise ValueError("depth_block leaves positions out of the wavefront order: order is {!r}{}".format(
                     order, '' if seg_ends is None else ', with seg_ends'))
             planes, keep = self._depth_plane(sym, B)
-            coded = torch.where(keep, sym, torch.full_like(sym, _lib.PC_ENCODE_SKIP)).view(N, count).index_select(1, perm).contiguous()
-            planes = planes.to(torch.uint8).cpu().numpy()
+            coded = torch.where(keep, sym, torch.full_like(sym, _lib.PC_ENCODE_SKIP))
+        if order == 'wavefront':
+            logits, coded = self._in_wavefront_order(logits, coded)
+        if planes is not None:
+            planes = planes.to(torch.uint8).cpu().numpy()       # (the host waits here, behind the gather)
         if seg_ends is not None:
             if order != 'raster':
                 raise ValueError("seg_ends cuts a raster stream: order is {!r}".format(order))
             res = self._encode_segments(logits, sym, N, count, [int(e) for e in seg_ends], capacity)
             return res if batched else res[0]
-        cap = int(lib.ic_pc_encode_capacity_bytes(count)) if capacity is None else int(capacity)
-        out = torch.empty((N, max(cap, 1)), dtype=torch.uint8, device=dev)
-        info = torch.zeros((2, N), dtype=torch.int64, device=dev)       # row 0: nbytes; row 1: status (int32 in the low words)
-        status = info[1].view(torch.int32)[:N]
-        check(lib.ic_pc_encode_f32(ptr(logits), ptr(coded), N, count, self.pc.L, self.freqs_resolution, ptr(out), cap,
-                                   ptr(info[0]), ptr(status), _lib.current_stream(dev)), 'ic_pc_encode_f32')
-        nbytes = info[0].tolist()
-        status = status.tolist()
-        res = []
-        for n in range(N):
-            if status[n] == 1:
-                raise ValueError('Cannot code symbol because total is too large')
-            if status[n] != 0:
-                raise ValueError('device range encoder: {} (status {})'.format(
-                    {2: 'stream capacity too small', 3: 'symbol outside [0, L)'}.get(status[n], 'error'), status[n]))
-            head = b'' if planes is None else planes[n].tobytes()
-            res.append((head + bytes(out[n, :nbytes[n]].cpu().numpy()), int(sym[n, 0, 0, 0])))
+        streams = self._encode_launch(logits, coded, N, count, count, capacity, None, 'rows')
+        res = [((b'' if planes is None else planes[n].tobytes()) + streams[n], int(sym[n, 0, 0, 0])) for n in range(N)]
         return res if batched else res[0]
+
+    def _symbol_logits(self, sym):
+        """the logits (N,C,h,w,L) of a batch (N,C,h,w) of symbol volumes on the device: padded with symbol 0, the centres gathered,
+        pc.logits on the padded volume, as _tables does"""
+        pad = self.pc_class.get_context_size(self.config) // 2
+        q = self.centers[torch.nn.functional.pad(sym, (pad, pad, pad, pad, pad, 0))].contiguous()    # (N,C+4,h+8,w+8), symbol 0 around
+        return self.pc.logits(q, is_training=False)
+
+    def _in_wavefront_order(self, logits, coded):
+        """logits (N,C,h,w,L) and what is coded (N,C,h,w), gathered through the permutation of the volume's wavefront order on the device
+        -> ((N,count,L), (N,count))"""
+        from .codec import wavefront_order
+        N, C, h, w = (int(v) for v in coded.shape)
+        perm = torch.as_tensor(np.array(wavefront_order(C, h, w))).to(coded.device)       # (a copy: the cached order is read-only)
+        return (logits.view(N, C * h * w, self.pc.L).index_select(1, perm).contiguous(),
+                coded.reshape(N, C * h * w).index_select(1, perm).contiguous())
+
+    def _encode_launch(self, logits, coded, N, count, longest, capacity, segments, take):
+        """ONE launch of the coding side and what comes back: segments=None -> ic_pc_encode_f32, a coder per volume; (ends, nsegs) ->
+        ic_pc_encode_segments_f32 with these.  Every coder has `capacity` bytes, by default what `longest` symbols can take; -> the bytes
+        of every coder in the launch's order, or the ValueError of _encode_status.  take says how they come back, the one thing that
+        differs between the callers: 'rows' copies every coder's bytes by themselves, 'head' and 'tail' copy the whole buffer once and
+        cut the first / the LAST nbytes of every capacity."""
+        dev = self.centers.device
+        cap = int(lib.ic_pc_encode_capacity_bytes(longest)) if capacity is None else int(capacity)
+        units = N * (segments[1] if segments is not None and segments[1] > 0 else 1)
+        out = torch.empty((units, max(cap, 1)), dtype=torch.uint8, device=dev)
+        info = torch.zeros((2, units), dtype=torch.int64, device=dev)   # row 0: nbytes; row 1: status (int32 in the low words)
+        status = info[1].view(torch.int32)[:units]
+        if segments is None:
+            check(lib.ic_pc_encode_f32(ptr(logits), ptr(coded), N, count, self.pc.L, self.freqs_resolution, ptr(out), cap,
+                                       ptr(info[0]), ptr(status), _lib.current_stream(dev)), 'ic_pc_encode_f32')
+        else:
+            host_ends = (ctypes.c_longlong * len(segments[0]))(*segments[0])
+            check(lib.ic_pc_encode_segments_f32(ptr(logits), ptr(coded), N, count, self.pc.L, self.freqs_resolution, host_ends, segments[1],
+                                                ptr(out), cap, ptr(info[0]), ptr(status), _lib.current_stream(dev)), 'ic_pc_encode_segments_f32')
+        nbytes = info[0].tolist()
+        for st in status.tolist():
+            self._encode_status(st)
+        if take == 'rows':
+            return [bytes(out[u, :nbytes[u]].cpu().numpy()) for u in range(units)]
+        host = out.cpu().numpy()
+        return [bytes(host[u, cap - nbytes[u]:cap] if take == 'tail' else host[u, :nbytes[u]]) for u in range(units)]
 
     def _encode_rans(self, logits, sym, lanes, capacity):
         """encode_stream(order='rans') behind the logits: (N,C,h,w,L) logits and (N,C,h,w) symbols -> [(stream, first_sym)]"""
@@ -442,19 +465,7 @@ class PredictionNetwork(object):
         glog = logits.view(N, C * h * w, self.pc.L).index_select(1, at).contiguous()
         coded = torch.where(rounds >= 0, sym.view(N, C * h * w).index_select(1, at),
                             torch.full((), _lib.PC_ENCODE_SKIP, dtype=torch.int64, device=dev)).contiguous()
-        cap = int(lib.ic_pc_encode_capacity_bytes(count)) if capacity is None else int(capacity)
-        out = torch.empty((N, max(cap, 1)), dtype=torch.uint8, device=dev)
-        info = torch.zeros((2, N), dtype=torch.int64, device=dev)       # row 0: nbytes; row 1: status (int32 in the low words)
-        status = info[1].view(torch.int32)[:N]
-        host_ends = (ctypes.c_longlong * 1)(count)
-        check(lib.ic_pc_encode_segments_f32(ptr(glog), ptr(coded), N, count, self.pc.L, self.freqs_resolution, host_ends, _lib.PC_ENCODE_RANS(W),
-                                            ptr(out), cap, ptr(info[0]), ptr(status), _lib.current_stream(dev)), 'ic_pc_encode_segments_f32')
-        nbytes, status, host = info[0].tolist(), status.tolist(), out.cpu().numpy()
-        res = []
-        for n in range(N):
-            self._encode_status(status[n])
-            res.append((bytes(host[n, cap - nbytes[n]:cap]), firsts[n]))       # the stream is the LAST nbytes of the volume's capacity
-        return res
+        return list(zip(self._encode_launch(glog, coded, N, count, count, capacity, ([count], _lib.PC_ENCODE_RANS(W)), 'tail'), firsts))
 
     def _depth_plane(self, sym, B):
         """codec.depth_plane and the live positions of a batch (N,C,h,w) of symbol volumes on their device -> ((N, ceil(h/B), ceil(w/B))
@@ -479,44 +490,24 @@ class PredictionNetwork(object):
 
     def _encode_segments(self, logits, sym, N, count, ends, capacity):
         """encode_stream(seg_ends=ends) behind the logits: one launch of N * len(ends) work-groups"""
-        dev = self.centers.device
         G = len(ends)
         if not 1 <= G <= 16 or ends[0] < 1 or ends[-1] != count or any(b <= a for a, b in zip(ends, ends[1:])):
             raise ValueError('segment ends {} are not 1 to 16 increasing symbol counts from at least 1 to {}'.format(ends, count))
         longest = max(b - max(1, a) for a, b in zip([0] + ends, ends))
-        cap = int(lib.ic_pc_encode_capacity_bytes(longest + 1)) if capacity is None else int(capacity)
-        out = torch.empty((N, G, max(cap, 1)), dtype=torch.uint8, device=dev)
-        info = torch.zeros((2, N * G), dtype=torch.int64, device=dev)   # row 0: nbytes; row 1: status (int32 in the low words)
-        status = info[1].view(torch.int32)[:N * G]
-        host_ends = (ctypes.c_longlong * G)(*ends)
-        check(lib.ic_pc_encode_segments_f32(ptr(logits), ptr(sym), N, count, self.pc.L, self.freqs_resolution, host_ends, G, ptr(out), cap,
-                                            ptr(info[0]), ptr(status), _lib.current_stream(dev)), 'ic_pc_encode_segments_f32')
-        nbytes, status, host = info[0].tolist(), status.tolist(), out.cpu().numpy()
-        res = []
-        for n in range(N):
-            for g in range(G):
-                self._encode_status(status[n * G + g])
-            res.append(([bytes(host[n, g, :nbytes[n * G + g]]) for g in range(G)], int(sym[n, 0, 0, 0])))
-        return res
+        segs = self._encode_launch(logits, sym, N, count, longest + 1, capacity, (ends, G), 'head')
+        return [(segs[n * G:(n + 1) * G], int(sym[n, 0, 0, 0])) for n in range(N)]
 
     def _encode_fronts(self, symbols, layer_ends, capacity=None):
         """a batch (N,C,h,w) of volumes of one shape, each coded in wavefront order and cut at fronts (container format 8): logits and
         symbols gathered through codec.wavefront_order(C, h, w) on the device, as encode_stream(order='wavefront') does it, then ONE
         ic_pc_encode_segments_f32 launch with the cuts codec.front_layer_cuts(C, h, w, layer_ends) -> [([segment bytes per layer],
         first_sym)].  Segment g is arithmetic_coding.encode_sequence over the permuted symbols and tables [max(1, n_{g-1}), n_g)."""
-        from .codec import wavefront_order, front_layer_cuts
-        dev = self.centers.device
-        sym = symbols.to(dev).long().contiguous()
+        from .codec import front_layer_cuts
+        sym = symbols.to(self.centers.device).long().contiguous()
         N, C, h, w = (int(v) for v in sym.shape)
         cuts = front_layer_cuts(C, h, w, layer_ends)
-        pad = self.pc_class.get_context_size(self.config) // 2
-        q = self.centers[torch.nn.functional.pad(sym, (pad, pad, pad, pad, pad, 0))].contiguous()    # (N,C+4,h+8,w+8), symbol 0 around
-        logits = self.pc.logits(q, is_training=False)                  # (N,C,h,w,L)
-        count = C * h * w
-        perm = torch.as_tensor(np.array(wavefront_order(C, h, w))).to(dev)           # (a copy: the cached order is read-only)
-        logits = logits.view(N, count, self.pc.L).index_select(1, perm).contiguous()
-        coded = sym.view(N, count).index_select(1, perm).contiguous()
-        return self._encode_segments(logits, coded.view(N, count, 1, 1), N, count, cuts, capacity)
+        logits, coded = self._in_wavefront_order(self._symbol_logits(sym), sym)
+        return self._encode_segments(logits, coded.view(N, C * h * w, 1, 1), N, C * h * w, cuts, capacity)
 
     def _preview(self, channels, C):
         """channels=None -> None (the full decode, the old entries); else (channels, fill symbol) for the *_channels entries, which
@@ -595,30 +586,27 @@ class PredictionNetwork(object):
         C, h, w = (int(v) for v in symbols_shape)
         if order not in ('raster', 'rans'):
             raise ValueError("decode_tiles reads raster streams or, with order='rans', rANS streams; order {!r} is decode_tiles_batch's".format(order))
-        if channels is not None or order == 'rans':
-            try:
+        try:
+            if channels is not None or order == 'rans':
                 return self.decode_tiles_batch([(streams, first_syms, (C, h, w))], th, tw, want='symbols', flags=flags,
                                                channels=channels, order=order, lanes=lanes)[0].cpu().numpy()
-            except ValueError as e:
-                raise ValueError(str(e).replace('(volume 0, tile ', '(tile '))
-        grid = tile_grid(h, w, th, tw)
-        if len(streams) != len(grid) or len(first_syms) != len(grid):
-            raise ValueError('{} streams and {} first symbols for a grid of {} tiles'.format(len(streams), len(first_syms), len(grid)))
-        dev = self.centers.device
-        table, _, blob, pos, _ = _tile_tables([(0, t, cell, first_syms[t], streams[t], None) for t, cell in enumerate(grid)])
-        data = torch.frombuffer(blob, dtype=torch.uint8).to(dev)
-        out = torch.empty((C, h, w), dtype=torch.int64, device=dev)
-        status = torch.zeros(len(grid), dtype=torch.int32, device=dev)
-        need = lib.ic_pc_decode_tiles_workspace_bytes(C, min(th, h), min(tw, w), len(grid), self.pc._k)
-        ws = torch.empty(need, dtype=torch.uint8, device=dev)
-        centers = self.centers.contiguous().float()
-        check(lib.ic_pc_decode_tiles_f32(ptr(data), pos, table, len(grid), self.pc._tab, ptr(centers), self.pc._k, self.pc.L,
-                                         self.freqs_resolution, ptr(out), ptr(status), C, h, w, ptr(ws), need, int(flags),
-                                         _lib.current_stream(dev)), 'ic_pc_decode_tiles_f32')
-        for t, st in enumerate(status.tolist()):            # (the host waits here: the table and the streams are done with)
-            if st != 0:
-                raise ValueError('Cannot decode symbol because total is too large (tile {} at ({}, {}))'.format(t, grid[t][0], grid[t][1]))
-        return out.cpu().numpy()
+            grid = tile_grid(h, w, th, tw)
+            if len(streams) != len(grid) or len(first_syms) != len(grid):
+                raise ValueError('{} streams and {} first symbols for a grid of {} tiles'.format(len(streams), len(first_syms), len(grid)))
+            dev = self.centers.device
+            (table, _, data, pos), where = _tile_tables([(0, t, cell, first_syms[t], streams[t], None) for t, cell in enumerate(grid)], dev)
+            out = torch.empty((C, h, w), dtype=torch.int64, device=dev)
+            status = torch.zeros(len(grid), dtype=torch.int32, device=dev)
+            need = lib.ic_pc_decode_tiles_workspace_bytes(C, min(th, h), min(tw, w), len(grid), self.pc._k)
+            ws = torch.empty(need, dtype=torch.uint8, device=dev)
+            centers = self.centers.contiguous().float()
+            check(lib.ic_pc_decode_tiles_f32(ptr(data), pos, table, len(grid), self.pc._tab, ptr(centers), self.pc._k, self.pc.L,
+                                             self.freqs_resolution, ptr(out), ptr(status), C, h, w, ptr(ws), need, int(flags),
+                                             _lib.current_stream(dev)), 'ic_pc_decode_tiles_f32')
+            _failed_tiles(status, where)                                        # (no report: the first tile that failed is a ValueError)
+            return out.cpu().numpy()
+        except ValueError as e:
+            raise ValueError(str(e).replace('(volume 0, tile ', '(tile '))
 
     def encode_tiles_batch(self, volumes, th, tw, order='raster', layer_ends=None, front_ends=None, depth_block=None, lanes=None):
         """encode_tiles for a list of un-padded (C,h,w) symbol volumes of any mix of (h, w): -> per volume the list encode_tiles
@@ -694,7 +682,100 @@ class PredictionNetwork(object):
         sets PC_DECODE_RANS(W) on ic_pc_decode_tiles_batch_channels_f32, whose `channels` is C unless channels=K asks for a preview.
         A full decode checks the stream's end: a ValueError that names the tile tells a stream that does not end where the coders'
         run ends (status 4) from a table whose total is too large (status 1)."""
-        from .codec import tile_grid, chunk_tiles, check_channels, check_layer_ends, check_depth_block, check_rans_lanes, DEFAULT_RANS_LANES
+        mode = self._decode_mode(want, int(volumes[0][2][0]) if volumes else None, conceal, order, channels, layer_ends, tile_layers,
+                                 front_ends, depth_block, lanes, flags)
+        if not volumes:
+            return ([], []) if conceal or tile_layers is not None else []
+        dev = self.centers.device
+        shapes, grids, listed, missing, limits = _list_tiles(volumes, th, tw, mode, tile_layers)
+        chunks, ws, ws_bytes = self._chunk_plan(mode, [cell for _, _, cell, _, _, _ in listed], len(shapes), max_workspace_bytes)
+        tables, where = _tile_tables(listed, dev)
+        vtable, offs, total = _lib.packed_volume_table(shapes)
+        alloc = torch.zeros if missing else torch.empty
+        q = alloc(total, dtype=torch.float32, device=dev) if want in ('q', 'both') else None
+        sym = alloc(total, dtype=torch.int64, device=dev) if want in ('symbols', 'both') or mode.report is not None else None    # the rules read symbols
+        status = torch.zeros(len(listed), dtype=torch.int32, device=dev)
+        centers = self.centers.contiguous().float()
+        per_tile = () if tile_layers is None else ((ctypes.c_int * max(len(limits), 1))(*limits),)
+        for a, b in chunks:
+            self._launch_tiles(mode, tables, vtable, len(shapes), sym, q, status, ws, ws_bytes, centers, a, b, per_tile)
+        failed = _failed_tiles(status, where, mode.report, mode.coder)
+        if mode.report is None:
+            return _cut(q, sym, shapes, offs, want)
+        if mode.report == 'held':
+            held = self._conceal_held(sym, q, shapes, grids, vtable, tile_layers, set(failed), mode.ends, th, tw, centers)
+            return _cut(q, sym, shapes, offs, want), held
+        marked = [(n, t, 'missing') for n, t in missing] + [(n, t, 'decoder') for n, t in failed]
+        damage = [sorted((t, why) for m, t, why in marked if m == n) for n in range(len(shapes))]
+        if any(damage):
+            self._conceal(sym, q, shapes, grids, vtable, damage, th, tw, centers)
+        return _cut(q, sym, shapes, offs, want), damage
+
+    def choose_tiles_batch(self, zs, th, tw, lam, want='symbols', max_workspace_bytes=1 << 31):
+        """Rate-aware symbol choice at encode: the symbols of every th x tw tile of every volume, chosen front by front by the
+        rule of codec.rdo_choose over the context model's own tables -- ONE launch per chunk of ic_pc_decode_tiles_batch_channels_f32
+        with PC_DECODE_RDO, one work-group per tile, the sweep of the wavefront decoder with a chooser in place of a coder.
+        zs: [(C, h, w) float32 DEVICE tensors], the masked bottleneck values (EncoderOutput.z), one C throughout.  lam: a float (in
+        key units per bit, codec.rdo_lambda_q), or per volume a sequence with one lambda per tile in codec.tile_grid order.
+        want: 'symbols' -> per volume the (C, h, w) int64 device tensor, 'q' -> centers[symbols] as float32, 'both' -> (q, symbols).
+        The records (Lambda, then the tile's z) are gathered on the device; nothing visits the host but the status words.
+        The workspace is one slot per tile: the tile list is cut into chunks within max_workspace_bytes as decode_tiles_batch does.
+        A context model of another width than k = 24 is a ValueError; a table whose total is too large (status 1) too."""
+        from .codec import tile_grid, rdo_is_sequence, rdo_lambda_q, rdo_tile_lambdas, rdo_record_bytes
+        if want not in ('q', 'symbols', 'both'):
+            raise ValueError("want is 'q', 'symbols' or 'both', got {!r}".format(want))
+        if self.pc._k != 24:
+            raise ValueError('rate-aware symbol choice needs a context model of width k = 24, this one has k = {}'.format(self.pc._k))
+        zs = list(zs)
+        if not zs:
+            return []
+        dev = self.centers.device
+        per_volume = rdo_is_sequence(lam)
+        if per_volume and len(lam) != len(zs):
+            raise ValueError('lam: {} entries for {} volumes'.format(len(lam), len(zs)))
+        shapes, rows, lams, pos = [], [], [], 0
+        for n, z in enumerate(zs):
+            if z.dim() != 3 or z.dtype != torch.float32:
+                raise ValueError('volume {}: z is a (C, h, w) float32 tensor, got {} {}'.format(n, tuple(z.shape), z.dtype))
+            _lib.require_cuda(z, 'z of volume {}'.format(n))
+            C, h, w = (int(v) for v in z.shape)
+            if C != int(zs[0].shape[0]):
+                raise ValueError('volume {} has {} channels, volume 0 has {}'.format(n, C, int(zs[0].shape[0])))
+            shapes.append((C, h, w))
+            grid = tile_grid(h, w, th, tw)
+            for (y0, x0, a, b), lm in zip(grid, rdo_tile_lambdas(lam[n] if per_volume else lam, len(grid))):
+                nb = rdo_record_bytes(C, a, b)
+                rows.append((y0, x0, a, b, pos, nb, 0, n))
+                lams.append(rdo_lambda_q(lm))
+                pos += (nb + 7) & ~7                                 # every record starts at a multiple of 8
+        C = shapes[0][0]
+        # the records, gathered on the device: Lambda of every tile by one upload and one indexed store, z by one strided copy per tile
+        data = torch.zeros(pos, dtype=torch.uint8, device=dev)
+        lam_dev = torch.as_tensor(np.asarray(lams, dtype='<f8')).to(dev)
+        at = torch.as_tensor(np.asarray([r[4] // 8 for r in rows], dtype=np.int64)).to(dev)
+        data.view(torch.float64)[at] = lam_dev                       # (every record starts at a multiple of 8: one indexed store)
+        for y0, x0, a, b, off, nb, _, n in rows:
+            data[off + 8:off + nb].view(torch.float32).view(C, a, b).copy_(zs[n][:, y0:y0 + a, x0:x0 + b])
+        # the sweep of the wavefront decoder with a chooser in place of a coder: the full decode's tail, no fill symbol
+        mode = _tiles_mode('_channels', C, _lib.PC_DECODE_RDO, (C, 0), coder='rdo')
+        vtable, offs, total = _lib.packed_volume_table(shapes)
+        chunks, ws, ws_bytes = self._chunk_plan(mode, [r[:4] for r in rows], len(shapes), max_workspace_bytes)
+        q = torch.empty(total, dtype=torch.float32, device=dev) if want in ('q', 'both') else None
+        sym = torch.empty(total, dtype=torch.int64, device=dev) if want in ('symbols', 'both') else None
+        status = torch.zeros(len(rows), dtype=torch.int32, device=dev)
+        centers = self.centers.contiguous().float()
+        tables = (_lib.tile_table(rows), None, data, pos)
+        for a, b in chunks:
+            self._launch_tiles(mode, tables, vtable, len(shapes), sym, q, status, ws, ws_bytes, centers, a, b)
+        _failed_tiles(status, [(n, None, y0, x0) for y0, x0, _, _, _, _, _, n in rows], coder='rdo')
+        return _cut(q, sym, shapes, offs, want)
+
+    def _decode_mode(self, want, C, conceal, order, channels, layer_ends, tile_layers, front_ends, depth_block, lanes, flags):
+        """THE decision of decode_tiles_batch, on the host alone: which keywords go together, and for those that do the _TilesMode
+        the call launches.  Every refusal of a combination is here, in this order.  C: the volumes' channels, which the ends, `channels`
+        and the depth block are checked against; None (no volumes) -> None once the keywords have been checked.  The context model's
+        width is read only where a check needs it."""
+        from .codec import check_channels, check_layer_ends, check_depth_block, check_rans_lanes, DEFAULT_RANS_LANES
         rans = None
         if order == 'rans':
             if conceal or layer_ends is not None or tile_layers is not None or front_ends is not None or depth_block is not None or int(flags) != 0:
@@ -711,17 +792,17 @@ class PredictionNetwork(object):
                 raise ValueError('depth_block does not go with conceal=True, tile_layers or flags ({})'.format(flags))
             if self.pc._k != 24:
                 raise ValueError('depth-mapped tiles need a context model of width k = 24, this one has k = {}'.format(self.pc._k))
-        fronts = front_ends is not None
-        if fronts:
+        kind = '_layers'
+        if front_ends is not None:
             self._check_front_ends(front_ends, order, layer_ends)
-            layer_ends = front_ends
+            kind, layer_ends = '_fronts', front_ends
         if layer_ends is not None:
             if conceal:
                 raise ValueError('layer_ends with conceal=True: salvage of layered tiles is not offered')
             if order != 'raster' or int(flags) != 0:
                 raise ValueError('layer_ends cuts raster streams for the k = 24 decoder: order {!r}, flags {}'.format(order, flags))
             if self.pc._k != 24:
-                raise ValueError('layered tiles need a context model of width k = 24, this one has k = {}'.format(self.pc._k))
+                raise ValueError(_NEEDS_K24.format(self.pc._k))
         if tile_layers is not None:
             if layer_ends is None:
                 raise ValueError('tile_layers counts layers per tile: it needs layer_ends')
@@ -734,203 +815,54 @@ class PredictionNetwork(object):
             raise ValueError("want is 'q', 'symbols' or 'both', got {!r}".format(want))
         if order not in ('raster', 'wavefront', 'rans'):
             raise ValueError("order is 'raster' or 'wavefront' -- or 'rans' --, got {!r}".format(order))
-        if order == 'wavefront':
-            flags = int(flags) | _lib.PC_DECODE_WAVEFRONT
-        if not volumes:
-            return ([], []) if conceal or tile_layers is not None else []
-        dev = self.centers.device
-        C0 = int(volumes[0][2][0])
+        if C is None:
+            return None
+        flags = int(flags) | (_lib.PC_DECODE_WAVEFRONT if order == 'wavefront' else 0)
+        ends, read = None, 0
         if layer_ends is not None:
-            ends = check_layer_ends(layer_ends, C0)
-            upto = C0 if channels is None else check_channels(channels, C0)
-            needed = [g for g in range(len(ends)) if g == 0 or ends[g - 1] < upto]     # the layers that begin below `channels`: 0 .. len - 1
-        shapes, grids, listed, missing, limits = [], [], [], [], []
-        if tile_layers is not None and len(tile_layers) != len(volumes):
-            raise ValueError('tile_layers has {} entries for {} volumes'.format(len(tile_layers), len(volumes)))
-        for n, (streams, first_syms, shape) in enumerate(volumes):
-            C, h, w = (int(v) for v in shape)
-            if C != int(volumes[0][2][0]):
-                raise ValueError('volume {} has {} channels, volume 0 has {}'.format(n, C, int(volumes[0][2][0])))
-            grid = tile_grid(h, w, th, tw)
-            if len(streams) != len(grid) or len(first_syms) != len(grid):
-                raise ValueError('volume {}: {} streams and {} first symbols for a grid of {} tiles'.format(
-                    n, len(streams), len(first_syms), len(grid)))
-            shapes.append((C, h, w))
-            grids.append(grid)
-            if tile_layers is not None and len(tile_layers[n]) != len(grid):
-                raise ValueError('volume {}: tile_layers has {} entries for a grid of {} tiles'.format(n, len(tile_layers[n]), len(grid)))
-            for t, cell in enumerate(grid):
-                if tile_layers is not None:
-                    g_t = int(tile_layers[n][t])
-                    if not 0 <= g_t <= len(ends):
-                        raise ValueError('volume {}, tile {}: {} layers to read of {}'.format(n, t, g_t, len(ends)))
-                    if g_t == 0:
-                        missing.append((n, t))
-                        continue
-                    if streams[t] is None or len(streams[t]) != len(ends) or any(streams[t][g] is None for g in range(g_t)):
-                        raise ValueError('volume {}, tile {}: {} layers to read need the segments 0 .. {} of {}'.format(n, t, g_t, g_t - 1, len(ends)))
-                    listed.append((n, t, cell, first_syms[t], streams[t], range(g_t)))
-                    limits.append(ends[g_t - 1])
-                elif streams[t] is None:
-                    missing.append((n, t))
-                elif layer_ends is not None:
-                    if len(streams[t]) != len(ends) or any(streams[t][g] is None for g in needed):
-                        raise ValueError('volume {}, tile {}: {} layers need the segments {} of {}'.format(n, t, len(ends), needed, len(ends)))
-                    listed.append((n, t, cell, first_syms[t], streams[t], range(len(needed))))
-                else:
-                    listed.append((n, t, cell, first_syms[t], streams[t], None))
-        table, seg_table, blob, pos, where = _tile_tables(listed)
-        tiles = [cell for _, _, cell, _, _, _ in listed]
-        C, k = shapes[0][0], self.pc._k
+            ends = check_layer_ends(layer_ends, C)
+            upto = C if channels is None else check_channels(channels, C)
+            read = len([g for g in range(len(ends)) if g == 0 or ends[g - 1] < upto])      # the layers that begin below `channels`: 0 .. read - 1
         preview = self._preview(channels, C)
         if depth_block is not None:
-            flags = int(flags) | _lib.PC_DECODE_DEPTH(check_depth_block(depth_block, C))
-            if preview is None:
-                preview = (C, self.conceal_fallback())            # the entry that takes the flag: channels == C is the full decode
+            flags |= _lib.PC_DECODE_DEPTH(check_depth_block(depth_block, C))
         if rans is not None:
             flags = _lib.PC_DECODE_RANS(rans)                     # alone in the flags: the order is implied
-            if preview is None:
-                preview = (C, self.conceal_fallback())
-        G = 0 if layer_ends is None else len(ends)
-        vtable, offs, total = _lib.packed_volume_table(shapes)
-
-        kind = 'fronts' if fronts else 'layers'
-        entry_name, entry_per_name = 'ic_pc_decode_tiles_batch_{}_f32'.format(kind), 'ic_pc_decode_tiles_batch_{}_pertile_f32'.format(kind)
-        entry, entry_per = getattr(lib, entry_name), getattr(lib, entry_per_name)
-        entry_ws = getattr(lib, 'ic_pc_decode_tiles_batch_{}_workspace_bytes'.format(kind))
-        entry_per_ws = getattr(lib, 'ic_pc_decode_tiles_batch_{}_pertile_workspace_bytes'.format(kind))
-
-        def need(th_max, tw_max, ntiles):
-            if tile_layers is not None:
-                return int(entry_per_ws(C, th_max, tw_max, ntiles, len(shapes), k, G))
-            if G:
-                return int(entry_ws(C, th_max, tw_max, ntiles, len(shapes), k, G))
-            return int(lib.ic_pc_decode_tiles_batch_workspace_bytes(C, th_max, tw_max, ntiles, len(shapes), k))
-
-        chunks = chunk_tiles([(a, b) for _, _, a, b in tiles], need, int(max_workspace_bytes))
-        data = torch.frombuffer(blob, dtype=torch.uint8).to(dev)
-        alloc = torch.zeros if missing else torch.empty
-        q = alloc(total, dtype=torch.float32, device=dev) if want in ('q', 'both') else None
-        sym = alloc(total, dtype=torch.int64, device=dev) if want in ('symbols', 'both') or conceal or tile_layers is not None else None    # the rules read symbols
-        status = torch.zeros(len(tiles), dtype=torch.int32, device=dev)
-        centers = self.centers.contiguous().float()
-        if chunks:
-            ws_bytes = max(need(max(tiles[i][2] for i in range(a, b)), max(tiles[i][3] for i in range(a, b)), b - a) for a, b in chunks)
-            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        step = ctypes.sizeof(_lib.PcTile)
-        if G:
-            host_ends = (ctypes.c_int * G)(*ends)
-            layers = (C, self.conceal_fallback()) if preview is None else preview
-            host_limits = (ctypes.c_int * max(len(limits), 1))(*limits)
-        for a, b in chunks:
-            args = (ptr(data), pos, ctypes.c_void_p(ctypes.addressof(table) + a * step), b - a, vtable, len(shapes), self.pc._tab,
-                    ptr(centers), k, self.pc.L, self.freqs_resolution, ptr(sym), ptr(q), ptr(status[a:b]), C, ptr(ws), ws_bytes,
-                    int(flags), _lib.current_stream(dev))
-            if G:
-                seg_ptr = ctypes.c_void_p(ctypes.addressof(seg_table) + a * G * ctypes.sizeof(_lib.PcSeg))
-            if tile_layers is not None:
-                lim_ptr = ctypes.c_void_p(ctypes.addressof(host_limits) + a * ctypes.sizeof(ctypes.c_int))
-                check(entry_per(*(args + (lim_ptr, self.conceal_fallback(), host_ends, G, seg_ptr))), entry_per_name)
-            elif G:
-                check(entry(*(args + layers + (host_ends, G, seg_ptr))), entry_name)
-            elif preview is None:
-                check(lib.ic_pc_decode_tiles_batch_f32(*args), 'ic_pc_decode_tiles_batch_f32')
-            else:
-                check(lib.ic_pc_decode_tiles_batch_channels_f32(*(args + preview)), 'ic_pc_decode_tiles_batch_channels_f32')
         if tile_layers is not None:
-            failed = set(where[i][:2] for i, st in enumerate(status.tolist()) if st != 0)      # (the host waits here, as below)
-            held = self._conceal_held(sym, q, shapes, grids, vtable, tile_layers, failed, ends, th, tw, centers)
-            return _cut(q, sym, shapes, offs, want), held
-        damage = [[] for _ in shapes]
-        for n, t in missing:
-            damage[n].append((t, 'missing'))
-        for i, st in enumerate(status.tolist()):            # (the host waits here: the tables and the streams are done with)
-            if st != 0:
-                n, t, y0, x0 = where[i]
-                if depth_block is not None and st == 2:
-                    raise ValueError('stream shorter than its depth plane (volume {}, tile {} at ({}, {}))'.format(n, t, y0, x0))
-                if rans is not None and st & 4 and not st & 1:            # (status 1 beside it: the total is the cause, said below)
-                    raise ValueError('the stream does not end where the coders\' run ends: a coder state is not 2^16 or bytes are missing '
-                                     'or left over (status {}; volume {}, tile {} at ({}, {}))'.format(st, n, t, y0, x0))
-                if not conceal:
-                    raise ValueError('Cannot decode symbol because total is too large (volume {}, tile {} at ({}, {}))'.format(n, t, y0, x0))
-                damage[n].append((t, 'decoder'))
-        damage = [sorted(d) for d in damage]
-        if conceal and any(damage):
-            self._conceal(sym, q, shapes, grids, vtable, damage, th, tw, centers)
-        res = _cut(q, sym, shapes, offs, want)
-        return (res, damage) if conceal else res
+            return _tiles_mode(kind + '_pertile', C, flags, (self.conceal_fallback(),), ends, read, 'held')
+        if ends is None and preview is None and depth_block is None and rans is None:
+            return _tiles_mode('', C, flags, (), report='damage' if conceal else None)
+        # the entries that take (channels, fill symbol): channels == C is the full decode
+        coder = 'depth' if depth_block is not None else 'rans' if rans is not None else None
+        return _tiles_mode(kind if ends is not None else '_channels', C, flags, preview or (C, self.conceal_fallback()), ends, read, coder=coder)
 
-    def choose_tiles_batch(self, zs, th, tw, lam, want='symbols', max_workspace_bytes=1 << 31):
-        """Rate-aware symbol choice at encode: the symbols of every th x tw tile of every volume, chosen front by front by the
-        rule of codec.rdo_choose over the context model's own tables -- ONE launch per chunk of ic_pc_decode_tiles_batch_channels_f32
-        with PC_DECODE_RDO, one work-group per tile, the sweep of the wavefront decoder with a chooser in place of a coder.
-        zs: [(C, h, w) float32 DEVICE tensors], the masked bottleneck values (EncoderOutput.z), one C throughout.  lam: a float (in
-        key units per bit, codec.rdo_lambda_q), or per volume a sequence with one lambda per tile in codec.tile_grid order.
-        want: 'symbols' -> per volume the (C, h, w) int64 device tensor, 'q' -> centers[symbols] as float32, 'both' -> (q, symbols).
-        The records (Lambda, then the tile's z) are gathered on the device; nothing visits the host but the status words.
-        The workspace is one slot per tile: the tile list is cut into chunks within max_workspace_bytes as decode_tiles_batch does.
-        A context model of another width than k = 24 is a ValueError; a table whose total is too large (status 1) too."""
-        from .codec import tile_grid, chunk_tiles, rdo_is_sequence, rdo_lambda_q, rdo_tile_lambdas, rdo_record_bytes
-        if want not in ('q', 'symbols', 'both'):
-            raise ValueError("want is 'q', 'symbols' or 'both', got {!r}".format(want))
-        if self.pc._k != 24:
-            raise ValueError('rate-aware symbol choice needs a context model of width k = 24, this one has k = {}'.format(self.pc._k))
-        zs = list(zs)
-        if not zs:
-            return []
-        dev = self.centers.device
-        per_volume = rdo_is_sequence(lam)
-        if per_volume and len(lam) != len(zs):
-            raise ValueError('lam: {} entries for {} volumes'.format(len(lam), len(zs)))
-        shapes, tiles, rows, lams, pos = [], [], [], [], 0
-        for n, z in enumerate(zs):
-            if z.dim() != 3 or z.dtype != torch.float32:
-                raise ValueError('volume {}: z is a (C, h, w) float32 tensor, got {} {}'.format(n, tuple(z.shape), z.dtype))
-            _lib.require_cuda(z, 'z of volume {}'.format(n))
-            C, h, w = (int(v) for v in z.shape)
-            if C != int(zs[0].shape[0]):
-                raise ValueError('volume {} has {} channels, volume 0 has {}'.format(n, C, int(zs[0].shape[0])))
-            shapes.append((C, h, w))
-            grid = tile_grid(h, w, th, tw)
-            for (y0, x0, a, b), lm in zip(grid, rdo_tile_lambdas(lam[n] if per_volume else lam, len(grid))):
-                nb = rdo_record_bytes(C, a, b)
-                tiles.append((y0, x0, a, b))
-                rows.append((y0, x0, a, b, pos, nb, 0, n))
-                lams.append(rdo_lambda_q(lm))
-                pos += (nb + 7) & ~7                                 # every record starts at a multiple of 8
-        C, k = shapes[0][0], self.pc._k
-        # the records, gathered on the device: Lambda of every tile by one upload and one indexed store, z by one strided copy per tile
-        data = torch.zeros(pos, dtype=torch.uint8, device=dev)
-        lam_dev = torch.as_tensor(np.asarray(lams, dtype='<f8')).to(dev)
-        at = torch.as_tensor(np.asarray([r[4] // 8 for r in rows], dtype=np.int64)).to(dev)
-        data.view(torch.float64)[at] = lam_dev                       # (every record starts at a multiple of 8: one indexed store)
-        for y0, x0, a, b, off, nb, _, n in rows:
-            data[off + 8:off + nb].view(torch.float32).view(C, a, b).copy_(zs[n][:, y0:y0 + a, x0:x0 + b])
-        table = _lib.tile_table(rows)
-        vtable, offs, total = _lib.packed_volume_table(shapes)
+    def _chunk_plan(self, mode, tiles, nvolumes, max_workspace_bytes):
+        """the tiles [(y0, x0, a, b)] of a call cut into chunks whose workspace stays within max_workspace_bytes (codec.chunk_tiles by
+        the mode's own size) -> ([(start, stop)], ONE workspace for the largest chunk, its bytes)"""
+        from .codec import chunk_tiles
 
         def need(th_max, tw_max, ntiles):
-            return int(lib.ic_pc_decode_tiles_batch_workspace_bytes(C, th_max, tw_max, ntiles, len(shapes), k))
-
+            return mode.size(mode.C, th_max, tw_max, ntiles, nvolumes, self.pc._k)
         chunks = chunk_tiles([(a, b) for _, _, a, b in tiles], need, int(max_workspace_bytes))
-        q = torch.empty(total, dtype=torch.float32, device=dev) if want in ('q', 'both') else None
-        sym = torch.empty(total, dtype=torch.int64, device=dev) if want in ('symbols', 'both') else None
-        status = torch.zeros(len(tiles), dtype=torch.int32, device=dev)
-        centers = self.centers.contiguous().float()
-        ws_bytes = max(need(max(tiles[i][2] for i in range(a, b)), max(tiles[i][3] for i in range(a, b)), b - a) for a, b in chunks)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        step = ctypes.sizeof(_lib.PcTile)
-        for a, b in chunks:
-            check(lib.ic_pc_decode_tiles_batch_channels_f32(
-                ptr(data), pos, ctypes.c_void_p(ctypes.addressof(table) + a * step), b - a, vtable, len(shapes), self.pc._tab,
-                ptr(centers), k, self.pc.L, self.freqs_resolution, ptr(sym), ptr(q), ptr(status[a:b]), C, ptr(ws), ws_bytes,
-                _lib.PC_DECODE_RDO, _lib.current_stream(dev), C, 0), 'ic_pc_decode_tiles_batch_channels_f32')
-        for i, st in enumerate(status.tolist()):            # (the host waits here: the tables and the records are done with)
-            if st != 0:
-                y0, x0, _, _, _, _, _, n = rows[i]
-                raise ValueError('Cannot choose symbol because total is too large (volume {}, tile at ({}, {}))'.format(n, y0, x0))
-        return _cut(q, sym, shapes, offs, want)
+        ws_bytes = max([need(max(tiles[i][2] for i in range(a, b)), max(tiles[i][3] for i in range(a, b)), b - a) for a, b in chunks], default=0)
+        return chunks, torch.empty(ws_bytes, dtype=torch.uint8, device=self.centers.device), ws_bytes
+
+    def _launch_tiles(self, mode, tables, vtable, nvolumes, sym, q, status, ws, ws_bytes, centers, a, b, per_tile=()):
+        """ONE launch of the mode's entry over the rows [a, b) of a call's tiles: the 19 arguments every entry takes, with the tile
+        table, the status words, the per-tile tables of the entry's own tail (limits; the session's from) and the segment table from
+        row a on, then the tail's scalars and, for the segmented entries, layer_ends, nlayers, segs.  tables: (tile table, segment
+        table, the bytes on the device, their number), as _tile_tables gives them."""
+        table, seg_table, data, pos = tables
+
+        def from_row(arr, per_row=1):
+            return ctypes.c_void_p(ctypes.addressof(arr) + a * per_row * ctypes.sizeof(arr._type_))
+        args = (ptr(data), pos, from_row(table), b - a, vtable, nvolumes, self.pc._tab, ptr(centers), self.pc._k, self.pc.L,
+                self.freqs_resolution, ptr(sym), ptr(q), ptr(status[a:b]), mode.C, ptr(ws), ws_bytes, mode.flags,
+                _lib.current_stream(self.centers.device))
+        args += tuple(from_row(arr) for arr in per_tile) + mode.tail
+        if mode.ends is not None:
+            args += ((ctypes.c_int * len(mode.ends))(*mode.ends), len(mode.ends), from_row(seg_table, len(mode.ends)))
+        check(mode.call(*args), mode.name)
 
     def open_layers(self, volumes_geometry, th, tw, layer_ends=None, max_workspace_bytes=1 << 31, front_ends=None):
         """a LayerSession over the volumes [(C,h,w)] cut into th x tw tiles of layered streams (container format 6): the decoder's
@@ -953,7 +885,6 @@ class PredictionNetwork(object):
     def _conceal(self, sym, q, shapes, grids, vtable, damage, th, tw, centers):
         """one ic_pc_conceal_tiles launch on the current stream for the damaged tiles of all volumes; sym / q as decode_tiles_batch
         lays them out (q may be None)"""
-        dev = self.centers.device
         marks, tiles = [], []
         for n, (grid, dmg) in enumerate(zip(grids, damage)):
             m = bytearray(len(grid))
@@ -962,27 +893,26 @@ class PredictionNetwork(object):
                 tiles.append(grid[t] + (0, 0, 0, n))
             marks.append(bytes(m))
         marks = b''.join(marks)
-        table, host_marks = _lib.tile_table(tiles), ctypes.create_string_buffer(marks, len(marks))
-        need = int(lib.ic_pc_conceal_tiles_workspace_bytes(len(tiles), len(shapes), len(marks)))
-        ws = torch.empty(need, dtype=torch.uint8, device=dev)
-        check(lib.ic_pc_conceal_tiles(ptr(sym), ptr(q), table, len(tiles), vtable, len(shapes), host_marks, ptr(centers), self.pc.L,
-                                      self.conceal_fallback(), shapes[0][0], int(th), int(tw), ptr(ws), need,
-                                      _lib.current_stream(dev)), 'ic_pc_conceal_tiles')
-        torch.cuda.current_stream(dev).synchronize()        # the three host tables and the workspace are done with
+        self._conceal_launch('ic_pc_conceal_tiles', sym, q, tiles, shapes, vtable, ctypes.create_string_buffer(marks, len(marks)), len(marks),
+                             th, tw, centers)
 
     def _conceal_channels(self, sym, q, shapes, grids, vtable, have, th, tw, centers):
         """one ic_pc_conceal_tiles_channels launch on the current stream: have[n][t] = the leading channels tile t of volume n holds;
         every (tile, channel) at or above it is filled.  sym / q as decode_tiles_batch lays them out (q may be None)"""
-        dev = self.centers.device
         C = shapes[0][0]
         tiles = [grid[t] + (0, 0, 0, n) for n, (grid, row) in enumerate(zip(grids, have)) for t in range(len(grid)) if row[t] < C]
         flat = [int(v) for row in have for v in row]
-        table, host_have = _lib.tile_table(tiles), (ctypes.c_uint16 * len(flat))(*flat)
-        need = int(lib.ic_pc_conceal_tiles_channels_workspace_bytes(len(tiles), len(shapes), len(flat)))
+        self._conceal_launch('ic_pc_conceal_tiles_channels', sym, q, tiles, shapes, vtable, (ctypes.c_uint16 * len(flat))(*flat), len(flat),
+                             th, tw, centers)
+
+    def _conceal_launch(self, name, sym, q, tiles, shapes, vtable, host_marks, nmarks, th, tw, centers):
+        """the launch of either conceal entry: `tiles` are filled by the rule over host_marks, one mark per tile of every volume"""
+        dev = self.centers.device
+        table = _lib.tile_table(tiles)
+        need = int(getattr(lib, name + '_workspace_bytes')(len(tiles), len(shapes), nmarks))
         ws = torch.empty(need, dtype=torch.uint8, device=dev)
-        check(lib.ic_pc_conceal_tiles_channels(ptr(sym), ptr(q), table, len(tiles), vtable, len(shapes), host_have, ptr(centers), self.pc.L,
-                                               self.conceal_fallback(), C, int(th), int(tw), ptr(ws), need,
-                                               _lib.current_stream(dev)), 'ic_pc_conceal_tiles_channels')
+        check(getattr(lib, name)(ptr(sym), ptr(q), table, len(tiles), vtable, len(shapes), host_marks, ptr(centers), self.pc.L,
+                                 self.conceal_fallback(), shapes[0][0], int(th), int(tw), ptr(ws), need, _lib.current_stream(dev)), name)
         torch.cuda.current_stream(dev).synchronize()        # the three host tables and the workspace are done with
 
     def _conceal_held(self, sym, q, shapes, grids, vtable, tile_layers, failed, ends, th, tw, centers):
@@ -1015,12 +945,108 @@ class PredictionNetwork(object):
         return f
 
 
-def _tile_tables(listed):
-    """The host tables of one decode over tiles.  listed: per tile (n, t, (y0, x0, a, b), first_sym, stream, None), or
+# How one call of the tile decoder goes to the library (PredictionNetwork._decode_mode; choose_tiles_batch and LayerSession build
+# theirs).  flags: the final ones.  name, call, size: the entry, and its workspace bytes as a function of (C, th_max, tw_max, ntiles,
+# nvolumes, k).  tail: the scalars of the entry's own tail, behind its per-tile tables and in front of layer_ends, nlayers, segs.
+# C: the volumes' channels.  ends: the checked layer ends of a segmented entry, else None; read: the leading layers a tile is read up
+# to unless tile_layers says otherwise.  report: what the call returns beside the result -- None (a status that is not 0 is a
+# ValueError, in the words of `coder`: None, 'depth', 'rans' or 'rdo'), 'damage' or 'held' (these read the symbols: always allocated).
+_TilesMode = namedtuple('_TilesMode', 'flags name call size tail C ends read report coder')
+_NEEDS_K24 = 'layered tiles need a context model of width k = 24, this one has k = {}'
+
+
+def _tiles_mode(kind, C, flags=0, tail=(), ends=None, read=0, report=None, coder=None):
+    """the _TilesMode of the entry ic_pc_decode_tiles_batch<kind>_f32, kind '' / '_channels' / '_layers' / '_fronts', the latter two
+    also with '_pertile' / '_resume': the one place where these names reach the library"""
+    name = 'ic_pc_decode_tiles_batch{}_f32'.format(kind)
+    size = getattr(lib, 'ic_pc_decode_tiles_batch{}_workspace_bytes'.format('' if kind == '_channels' else kind))
+    nlayers = () if ends is None else (len(ends),)
+    return _TilesMode(flags, name, getattr(lib, name), lambda *geometry: int(size(*(geometry + nlayers))), tail, C, ends, read, report, coder)
+
+
+def _list_tiles(volumes, th, tw, mode, tile_layers=None, opened=None):
+    """volumes [(streams, first_syms, (C,h,w))] -> (shapes, grids, listed, missing, limits): listed = the tiles that are read, as
+    _tile_tables takes them; missing = [(n, t)] of those that are not (no stream, or 0 layers); limits = per listed tile the channels
+    its layers hold, with tile_layers = [per volume [g_t per tile]].  Without it a tile of a segmented mode is read up to mode.read
+    layers.  opened = (shapes, grids) of a LayerSession: its volumes may come without a shape and are counted in its words."""
+    from .codec import tile_grid
+    ends = mode.ends
+    shapes, grids, listed, missing, limits = [], [], [], [], []
+    if opened is None and tile_layers is not None and len(tile_layers) != len(volumes):
+        raise ValueError('tile_layers has {} entries for {} volumes'.format(len(tile_layers), len(volumes)))
+    for n, volume in enumerate(volumes):
+        streams, first_syms = volume[0], volume[1]
+        if opened is None:
+            C, h, w = (int(v) for v in volume[2])
+            if C != mode.C:
+                raise ValueError('volume {} has {} channels, volume 0 has {}'.format(n, C, mode.C))
+            grid = tile_grid(h, w, th, tw)
+            if len(streams) != len(grid) or len(first_syms) != len(grid):
+                raise ValueError('volume {}: {} streams and {} first symbols for a grid of {} tiles'.format(
+                    n, len(streams), len(first_syms), len(grid)))
+            if tile_layers is not None and len(tile_layers[n]) != len(grid):
+                raise ValueError('volume {}: tile_layers has {} entries for a grid of {} tiles'.format(n, len(tile_layers[n]), len(grid)))
+        else:
+            (C, h, w), grid = opened[0][n], opened[1][n]
+            if len(volume) > 2 and tuple(int(v) for v in volume[2]) != (C, h, w):
+                raise ValueError('volume {} is {}, the session was opened for {}'.format(n, tuple(volume[2]), (C, h, w)))
+            if len(streams) != len(grid) or len(first_syms) != len(grid) or len(tile_layers[n]) != len(grid):
+                raise ValueError('volume {}: {} streams, {} first symbols and {} entries of tile_layers for a grid of {} tiles'.format(
+                    n, len(streams), len(first_syms), len(tile_layers[n]), len(grid)))
+        shapes.append((C, h, w))
+        grids.append(grid)
+        for t, cell in enumerate(grid):
+            if tile_layers is not None:
+                g_t = int(tile_layers[n][t])
+                if not 0 <= g_t <= len(ends):
+                    raise ValueError('volume {}, tile {}: {} layers to read of {}'.format(n, t, g_t, len(ends)))
+                if g_t == 0:
+                    missing.append((n, t))
+                    continue
+                if streams[t] is None or len(streams[t]) != len(ends) or any(streams[t][g] is None for g in range(g_t)):
+                    raise ValueError('volume {}, tile {}: {} layers to read need the segments 0 .. {} of {}'.format(n, t, g_t, g_t - 1, len(ends)))
+                listed.append((n, t, cell, first_syms[t], streams[t], range(g_t)))
+                limits.append(ends[g_t - 1])
+            elif streams[t] is None:
+                missing.append((n, t))
+            elif ends is not None:
+                if len(streams[t]) != len(ends) or any(streams[t][g] is None for g in range(mode.read)):
+                    raise ValueError('volume {}, tile {}: {} layers need the segments {} of {}'.format(
+                        n, t, len(ends), list(range(mode.read)), len(ends)))
+                listed.append((n, t, cell, first_syms[t], streams[t], range(mode.read)))
+            else:
+                listed.append((n, t, cell, first_syms[t], streams[t], None))
+    return shapes, grids, listed, missing, limits
+
+
+def _failed_tiles(status, where, report=None, coder=None):
+    """the status words of a call's launches, row for row with where = [(n, t, y0, x0)]: THE host wait of the call, after which the
+    tables and the streams are done with.  -> [(n, t)] of the rows whose status is not 0, for a call that reports them (_TilesMode.report);
+    else the first of them is the ValueError, in the coder's words."""
+    failed = []
+    for (n, t, y0, x0), st in zip(where, status.tolist()):
+        if st == 0:
+            continue
+        if report is not None:
+            failed.append((n, t))
+            continue
+        if coder == 'rdo':
+            raise ValueError('Cannot choose symbol because total is too large (volume {}, tile at ({}, {}))'.format(n, y0, x0))
+        if coder == 'depth' and st == 2:
+            raise ValueError('stream shorter than its depth plane (volume {}, tile {} at ({}, {}))'.format(n, t, y0, x0))
+        if coder == 'rans' and st & 4 and not st & 1:                # (status 1 beside it: the total is the cause, said below)
+            raise ValueError('the stream does not end where the coders\' run ends: a coder state is not 2^16 or bytes are missing '
+                             'or left over (status {}; volume {}, tile {} at ({}, {}))'.format(st, n, t, y0, x0))
+        raise ValueError('Cannot decode symbol because total is too large (volume {}, tile {} at ({}, {}))'.format(n, t, y0, x0))
+    return failed
+
+
+def _tile_tables(listed, dev):
+    """The tables of one decode over tiles.  listed: per tile (n, t, (y0, x0, a, b), first_sym, stream, None), or
     (n, t, (y0, x0, a, b), first_sym, segments, layers) where `layers` is the range of the tile's segments to read.
-    -> (tile table, segment table, blob, its length, where): the blob is everything that is read, joined (one byte if that is nothing);
-    a stream's place in it stands in its tile's row; a tile of segments has zeros there and len(segments) rows of the segment table,
-    (0, 0) for those outside `layers`; where = [(n, t, y0, x0)] per row of the tile table."""
+    -> ((tile table, segment table, blob on the device `dev`, its length), where): the blob is everything that is read, joined (one
+    byte if that is nothing) and uploaded; a stream's place in it stands in its tile's row; a tile of segments has zeros there and
+    len(segments) rows of the segment table, (0, 0) for those outside `layers`; where = [(n, t, y0, x0)] per row of the tile table."""
     tiles, segs, blobs, pos, where = [], [], [], 0, []
     for n, t, (y0, x0, a, b), first_sym, payload, layers in listed:
         where.append((n, t, y0, x0))
@@ -1037,7 +1063,8 @@ def _tile_tables(listed):
                 pos += len(seg)
             else:
                 segs.append((0, 0))
-    return _lib.tile_table(tiles), _lib.seg_table(segs), bytearray(b''.join(blobs)) or bytearray(1), pos, where
+    data = torch.frombuffer(bytearray(b''.join(blobs)) or bytearray(1), dtype=torch.uint8).to(dev)
+    return (_lib.tile_table(tiles), _lib.seg_table(segs), data, pos), where
 
 
 def _cut(q, sym, shapes, offs, want, copy=False):
@@ -1082,16 +1109,18 @@ class LayerSession(object):
             if shape[0] != C:
                 raise ValueError('volume {} has {} channels, volume 0 has {}'.format(n, shape[0], C))
         if pred.pc._k != 24:
-            raise ValueError('layered tiles need a context model of width k = 24, this one has k = {}'.format(pred.pc._k))
+            raise ValueError(_NEEDS_K24.format(pred.pc._k))
         self.ends = check_layer_ends(layer_ends, C)
         self.fronts = bool(fronts)
-        self.entry = 'ic_pc_decode_tiles_batch_fronts_resume_f32' if self.fronts else 'ic_pc_decode_tiles_batch_layers_resume_f32'
+        self.mode = _tiles_mode('_fronts_resume' if self.fronts else '_layers_resume', C, 0, (pred.conceal_fallback(),), self.ends,
+                                report='held')
+        self.entry = self.mode.name
         self.th, self.tw = int(th), int(tw)
         self.grids = [tile_grid(h, w, self.th, self.tw) for _, h, w in self.shapes]
         self.vtable, self.offs, self.total = _lib.packed_volume_table(self.shapes)
         dev = pred.centers.device
-        need = self._need(max(a for grid in self.grids for _, _, a, _ in grid), max(b for grid in self.grids for _, _, _, b in grid),
-                          sum(len(grid) for grid in self.grids))
+        need = self.mode.size(C, max(a for grid in self.grids for _, _, a, _ in grid), max(b for grid in self.grids for _, _, _, b in grid),
+                              sum(len(grid) for grid in self.grids), len(self.shapes), pred.pc._k)
         if need > int(max_workspace_bytes):
             raise ValueError('the session keeps one workspace slot per tile and cannot be chunked: {} tiles need {} bytes, '
                              'max_workspace_bytes is {}'.format(sum(len(grid) for grid in self.grids), need, int(max_workspace_bytes)))
@@ -1102,70 +1131,40 @@ class LayerSession(object):
         self.place = [[None] * len(grid) for grid in self.grids]               # (index in the launch, shape of the launch) of that slot
         self.launches = 0
 
-    def _need(self, th_max, tw_max, ntiles):
-        size = (lib.ic_pc_decode_tiles_batch_fronts_resume_workspace_bytes if self.fronts
-                else lib.ic_pc_decode_tiles_batch_layers_resume_workspace_bytes)
-        return int(size(self.shapes[0][0], th_max, tw_max, ntiles, len(self.shapes), self.pred.pc._k, len(self.ends)))
-
     def advance(self, volumes_segments, tile_layers, want='q'):
         from .codec import resume_plan
-        pred, ends, G, C = self.pred, self.ends, len(self.ends), self.shapes[0][0]
+        pred, mode = self.pred, self.mode
         if want not in ('q', 'symbols', 'both'):
             raise ValueError("want is 'q', 'symbols' or 'both', got {!r}".format(want))
         if len(volumes_segments) != len(self.shapes) or len(tile_layers) != len(self.shapes):
             raise ValueError('{} volumes and {} rows of tile_layers for a session of {} volumes'.format(
                 len(volumes_segments), len(tile_layers), len(self.shapes)))
-        listed = []
-        for n, (volume, grid) in enumerate(zip(volumes_segments, self.grids)):
-            streams, first_syms = volume[0], volume[1]
-            if len(volume) > 2 and tuple(int(v) for v in volume[2]) != self.shapes[n]:
-                raise ValueError('volume {} is {}, the session was opened for {}'.format(n, tuple(volume[2]), self.shapes[n]))
-            if len(streams) != len(grid) or len(first_syms) != len(grid) or len(tile_layers[n]) != len(grid):
-                raise ValueError('volume {}: {} streams, {} first symbols and {} entries of tile_layers for a grid of {} tiles'.format(
-                    n, len(streams), len(first_syms), len(tile_layers[n]), len(grid)))
-            for t, cell in enumerate(grid):
-                g_t = int(tile_layers[n][t])
-                if not 0 <= g_t <= G:
-                    raise ValueError('volume {}, tile {}: {} layers to read of {}'.format(n, t, g_t, G))
-                if g_t == 0:
-                    continue
-                if streams[t] is None or len(streams[t]) != G or any(streams[t][g] is None for g in range(g_t)):
-                    raise ValueError('volume {}, tile {}: {} layers to read need the segments 0 .. {} of {}'.format(n, t, g_t, g_t - 1, G))
-                listed.append((n, t, cell, int(first_syms[t]), streams[t], g_t))
+        _, _, listed, missing, _ = _list_tiles(volumes_segments, self.th, self.tw, mode, tile_layers, (self.shapes, self.grids))
         dev = pred.centers.device
         centers = pred.centers.contiguous().float()
-        for n, grid in enumerate(self.grids):                                  # a tile that holds nothing now has no slot to continue in
-            for t in range(len(grid)):
-                if int(tile_layers[n][t]) == 0:
-                    self.done[n][t], self.place[n][t] = 0, None
+        for n, t in missing:                                                   # a tile that holds nothing now has no slot to continue in
+            self.done[n][t], self.place[n][t] = 0, None
         failed = set()
         if listed:
             shape = (len(listed), max(cell[2] for _, _, cell, _, _, _ in listed), max(cell[3] for _, _, cell, _, _, _ in listed))
             reads, froms, limits = [], [], []
-            for i, (n, t, cell, first, streams, g_t) in enumerate(listed):
+            for i, (n, t, cell, first, streams, layers) in enumerate(listed):
                 have = self.done[n][t] if self.place[n][t] == (i, shape) else 0
-                g_from, channels = resume_plan(have, g_t, ends)
-                reads.append((n, t, cell, first, streams, range(g_from, g_t)))
+                g_from, channels = resume_plan(have, len(layers), self.ends)
+                reads.append((n, t, cell, first, streams, range(g_from, len(layers))))
                 froms.append(g_from)
                 limits.append(channels)
-            need = self._need(shape[1], shape[2], shape[0])
+            need = mode.size(mode.C, shape[1], shape[2], shape[0], len(self.shapes), pred.pc._k)
             assert need <= self.ws.numel()
-            table, seg_table, blob, pos, _ = _tile_tables(reads)
-            host_ends, host_from, host_limits = (ctypes.c_int * G)(*ends), (ctypes.c_int * len(froms))(*froms), (ctypes.c_int * len(limits))(*limits)
-            data = torch.frombuffer(blob, dtype=torch.uint8).to(dev)
+            tables, where = _tile_tables(reads, dev)
             status = torch.zeros(len(reads), dtype=torch.int32, device=dev)
-            check(getattr(lib, self.entry)(
-                ptr(data), pos, table, len(reads), self.vtable, len(self.shapes), pred.pc._tab, ptr(centers), pred.pc._k, pred.pc.L,
-                pred.freqs_resolution, ptr(self.sym), ptr(self.q), ptr(status), C, ptr(self.ws), need, 0, _lib.current_stream(dev),
-                host_from, host_limits, pred.conceal_fallback(), host_ends, G, seg_table), self.entry)
+            pred._launch_tiles(mode, tables, self.vtable, len(self.shapes), self.sym, self.q, status, self.ws, need, centers, 0, len(reads),
+                               ((ctypes.c_int * len(froms))(*froms), (ctypes.c_int * len(limits))(*limits)))
             self.launches += 1
-            for (n, t, _, _, _, g_t), i, st in zip(listed, range(len(listed)), status.tolist()):      # (the host waits here)
-                if st != 0:
-                    failed.add((n, t))
-                    self.done[n][t], self.place[n][t] = 0, None
-                else:
-                    self.done[n][t], self.place[n][t] = g_t, (i, shape)
-        held = pred._conceal_held(self.sym, self.q, self.shapes, self.grids, self.vtable, tile_layers, failed, ends, self.th, self.tw, centers)
+            failed = set(_failed_tiles(status, where, mode.report))
+            for i, (n, t, _, _, _, layers) in enumerate(listed):
+                self.done[n][t], self.place[n][t] = (0, None) if (n, t) in failed else (len(layers), (i, shape))
+        held = pred._conceal_held(self.sym, self.q, self.shapes, self.grids, self.vtable, tile_layers, failed, self.ends, self.th, self.tw, centers)
         return _cut(self.q, self.sym, self.shapes, self.offs, want, copy=True), held
 
 
